@@ -24,10 +24,19 @@ time / K), the number `rocprofv3 --kernel-trace --stats` of the same command rep
 streams overlap, so `value` is the wall clock and the kernel duration for the roofline object comes from one more pass of K
 launches on ONE stream).
 
+Plain run and `--full`. `python bench.py --gpus 1 --steps K --warmup W` does only what its headline needs: set up, the clock ramp,
+W warm-up steps, the K timed steps, the outputs of the last step when `--dump-outputs DIR` is given, and the result line. Everything
+else -- the world-1 communicator and its gather, the check of the timed outputs against the goldens, the observed shader clock, the CPU
+baselines and the secondary legs below -- runs only with `--full` (`--no-cpu-baseline` / `--no-secondary` still drop parts of it).
+Under a process group (torchrun, N > 1) the final gather is part of `value` and always runs.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller, rank 0's batch, as float32 `DIR/<name>.npy` (decode:
+`verts3d`, `proj`, `lmk_px`; render: `image`); the inputs are seeded, so the same arguments give the same inputs every run.
+
 Multi-GPU: images shard over ranks (weak scaling, 64 per GPU per step, no data-path collective); the timed
 region ends with the job's single RCCL all-gather of the last step's landmarks (north_star: "RCCL/xGMI
-only for the final gather"). EVERY line -- the plain N = 1 run included, through a communicator of one rank -- executes that
-collective behind its K steps and prints two per-step times from device events on the launch stream, MAX over ranks:
+only for the final gather"). EVERY `--full` line and every process-group line -- the N = 1 run included, through a communicator of
+one rank -- executes that collective behind its K steps and prints two per-step times from device events on the launch stream, MAX over ranks:
 `ms_per_step_compute` ([first launch ... last launch]) and `ms_per_step_with_gather` ([first launch ... end of the all-gather]).
 `value` is images / the COMPUTE time for the plain N = 1 run (the metric as BASELINE.json defines it: decode + landmark
 projection; there is nobody to gather from) and images / the time WITH the gather under a process group (any N, N = 1 under
@@ -35,8 +44,8 @@ torchrun included); `config.value_definition` says which, and BOTH rates are pri
 gather's built-in share of the region in `config.scaling_note` -- read a scaling curve on one of them. `config.toolchain` = the compiler / HIP headers
 the library was built with and the runtime it runs on. Rank 0 prints ONE JSON line.
 
-Secondary legs (plain N = 1 decode run only, AFTER the contract region, none of them touches `value` / `ms_per_step` / `roofline`;
-`--no-secondary` skips them): `long_region` = 2000 more launches of the same step between two hipEvents (the driver's K = 20 region
+Secondary legs (`--full` N = 1 decode run without a process group only, AFTER the contract region, none of them touches `value` /
+`ms_per_step` / `roofline`; `--no-secondary` skips them): `long_region` = 2000 more launches of the same step between two hipEvents (the driver's K = 20 region
 is 0.26 ms -- too short to mean much on its own); `secondary.decode_b256` = BASELINE configs[2] (batch 256, head_mesh path:
 3d_vertices + 3-component projection + landmarks, 125 764 B per image) with its own MFMA / HBM fractions, every row checked against
 reference-HeadMesh goldens, with `landmarks_only` (configs[3]'s per-GPU share and all 2048 rows: bit-equal to the whole-mesh launch);
@@ -56,6 +65,7 @@ import ctypes as C
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -163,8 +173,9 @@ def pmc_json(name, key):
 
 
 def self_launch(args) -> None:
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a child
+    and exit with its status."""
     visible = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if visible < args.gpus:
         raise SystemExit(f"bench.py: {args.gpus} GPUs requested, {visible} visible on this node -- nothing was run "
@@ -176,7 +187,8 @@ def self_launch(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    # a child process, not exec: this process has already opened the HIP runtime (device_count above)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main() -> None:
@@ -189,8 +201,12 @@ def main() -> None:
     ap.add_argument("--workload", choices=("decode", "render"), default="decode")
     ap.add_argument("--gather", choices=("root", "all"), default="root",
                     help="render workload: the finished images go to rank 0 only (grouped ncclSend/ncclRecv) or to every rank (ncclAllGather)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: world-1 gather, golden check, shader clock, CPU baselines, secondary legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip long_region / secondary.* (plain N = 1 decode run only)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip long_region / secondary.* (--full N = 1 decode run only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as float32 DIR/<name>.npy")
     args = ap.parse_args()
 
     under_launcher = "RANK" in os.environ and "MASTER_ADDR" in os.environ and "WORLD_SIZE" in os.environ
@@ -345,6 +361,14 @@ def observed_shader_clock_mhz(lib, handle, call, dev):
         return float(np.median(cyc[ok] / wall[ok])) if ok.any() else None
     except Exception:
         return None
+
+
+def dump_outputs(path, arrays) -> None:
+    """`--dump-outputs`: what the last timed step returned to its caller as float32 `path/<name>.npy` (int32 landmark pixels and uint8
+    image bytes are exact in float32)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def fence(dist, dev):
@@ -816,7 +840,9 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
                      "call": (meshes[i].flame._handle, params.data_ptr(), BATCH, flags, verts3d.data_ptr(), proj.data_ptr(),
                               None, lmk_px.data_ptr(), streams[i].cuda_stream)})
     decode = lib.dad3d_flame_decode
-    direct = make_direct_gather(dist)  # RCCL's C API on the launch stream (rccl.py); None under the shared-GPU test hook
+    # RCCL's C API on the launch stream (rccl.py); None under the shared-GPU test hook. Without a process group (a world of one) the
+    # collective does not enter `value`: it runs with --full only
+    direct = make_direct_gather(dist) if (dist is not None or args.full) else None
     have_gather = dist is not None or direct is not None
     gathered = torch.empty((world * BATCH, N_LMK, 2), dtype=torch.int32, device=dev) if have_gather else None
     torch.cuda.synchronize(dev)
@@ -870,6 +896,8 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
         region1.record(s_gather)  # behind the collective: the region's device time, host latency aside
     fence(dist, dev)
     wall = max_over_ranks(dist, dev, time.perf_counter() - t0)
+    last = sets[(args.steps - 1) % n_streams]
+    dumped = {k: last[k].cpu().numpy() for k in ("verts3d", "proj", "lmk_px")} if (args.dump_outputs and rank == 0) else None
     gather_us = time_gather(lambda: gather_last(args.steps - 1), dev) if have_gather else None
     # the two device-side definitions of the job's time, each MAX over ranks: [first launch .. last launch] and [.. end of the all-gather]
     compute_s = max_over_ranks(dist, dev, region0.elapsed_time(pre_gather) * 1e-3) if n_streams == 1 else None
@@ -892,22 +920,24 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
         kern_s = tot.value / max(cnt.value, 1) * 1e-3
     else:
         kern_s = region0.elapsed_time(pre_gather) * 1e-3 / args.steps  # this rank's K launches on its stream
-    clock_mhz = observed_shader_clock_mhz(lib, handle, sets[0]["call"], dev) if rank == 0 else None
+    clock_mhz = observed_shader_clock_mhz(lib, handle, sets[0]["call"], dev) if (rank == 0 and args.full) else None
     events_s = compute_s if compute_s is not None else max_over_ranks(dist, dev, tot.value * 1e-3)  # MAX over ranks
 
-    # long_region: the same launch 2000 more times between two hipEvents (plain N = 1 run; the contract region above is untouched)
-    secondary_on = world == 1 and dist is None and n_streams == 1 and not args.no_secondary
+    # long_region: the same launch 2000 more times between two hipEvents (--full N = 1 run; the contract region above is untouched)
+    secondary_on = args.full and world == 1 and dist is None and n_streams == 1 and not args.no_secondary
     long_s = events_per_step(lambda: step(0), 2000, streams[0], dev)[0] if secondary_on else None
 
     timeouts = C.c_uint()
     _lib.check(lib.dad3d_flame_handoff_timeouts(handle, C.byref(timeouts)))
-    check = verify_against_golden(sets[0], lmk_idx, dev) if rank == 0 else None  # after EVERY launch of this process on these buffers
+    check = verify_against_golden(sets[0], lmk_idx, dev) if (rank == 0 and args.full) else None  # after EVERY launch of this process on these buffers
     ok_gather = True
     if have_gather:  # this rank's slice of the gathered landmarks is what its last timed step wrote
         mine = sets[(args.steps - 1) % n_streams]["lmk_px"]
         ok_gather = bool(torch.equal(gathered[rank * BATCH:(rank + 1) * BATCH], mine))
     if rank != 0:
         return None
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     images = world * BATCH * args.steps
     flops = FLOP_PER_IMAGE * BATCH
     alg_bytes = CONST_BYTES + BATCH * BYTES_PER_IMAGE
@@ -937,8 +967,9 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
         "data": "synthetic",
         "config": {
             "value_definition": ("images / ms_per_step_with_gather (process group: the job ends behind its one all-gather)" if region_s is not None
-                                 else "images / compute time (plain N = 1 run: the metric as BASELINE.json defines it; the same collective ran "
-                                      "behind the K steps and is reported as ms_per_step_with_gather)") if from_events
+                                 else "images / compute time (N = 1 run: the metric as BASELINE.json defines it"
+                                      + ("; the same collective ran behind the K steps and is reported as ms_per_step_with_gather)" if have_gather
+                                         else "; no collective in this run)")) if from_events
                                 else "wall clock (several streams)",
             "scaling_note": (None if not (have_gather and n_streams == 1 and with_gather_s) else
                              f"built-in gather share of the timed region: gather_in_region_us / region = {gather_region_us / (with_gather_s * 1e6):.3f} "
@@ -954,7 +985,8 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
             "parallelism": f"image-sharded x{world}, one final RCCL all-gather of landmarks"
                            + ((" (TEST HOOK: ranks share one GPU, gloo with host-staged gathers -- not a multi-GPU measurement)"
                                if getattr(dist, "_dad3d_shared_gpu", False) else " (process group: nccl)")
-                              if dist is not None else " (no process group: plain N=1 run, communicator of one rank)"),
+                              if dist is not None else (" (no process group: N=1 run, communicator of one rank)" if direct is not None
+                                                        else " (no process group: N=1 run, no collective)")),
             "streams": n_streams,
             "prewarm_ms": prewarm_ms,
             "value_from": ("device events around the K timed launches AND the final all-gather (MAX over ranks)" if region_s is not None
@@ -995,7 +1027,7 @@ def run_decode(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
         },
     }
     e2e_warm = E2EWarmup(model, lmk_idx, dev) if secondary_on else None  # (after every timed decode region; the GPU idles during the next leg)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, lmk_idx)
         out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     if e2e_warm is not None:
@@ -1089,12 +1121,16 @@ def run_render(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
     e1.record(s_end)
     fence(dist, dev)
     wall = max_over_ranks(dist, dev, time.perf_counter() - t0)
+    last = lanes[(args.steps - 1) % n_streams]["renderer"]
+    dumped = {"image": last._img.cpu().numpy()} if (args.dump_outputs and rank == 0) else None  # what render_local returns
     ev_s = max_over_ranks(dist, dev, e0.elapsed_time(e1) * 1e-3)
     gather_us = time_gather(gather_last, dev, n=5) if dist is not None else None
     steps_s = e0.elapsed_time(e_steps) * 1e-3  # one stream: this rank's K steps alone, the per-step duration behind `roofline`
     start_skew = align.skew_us(e0)
     if rank != 0:
         return None
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     img = lanes[(args.steps - 1) % n_streams]["renderer"]._img
     covered = min(float((ln["renderer"]._img.reshape(BATCH, -1).max(dim=1).values > 0).float().mean().item()) for ln in lanes)
     ok_gather = True if dist is None else bool(torch.equal(gathered[:BATCH], img))
@@ -1124,7 +1160,7 @@ def run_render(args, dist, dev, rank, world, hm, lib, static, model, lmk_idx):
                      "bound": "hbm", "achieved": alg / per_step / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                      "frac": alg / per_step / 1e9 / PEAK_HBM_GBS, "traffic": None, "algorithmic_bytes_per_step": alg},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         timed = [(np.ascontiguousarray(ln["renderer"]._dec["proj"][0].cpu().numpy()), np.ascontiguousarray(ln["renderer"]._light_buf[0].cpu().numpy()),
                   ln["renderer"]._img[0].cpu().numpy()) for ln in lanes]
         out["cpu_baseline"] = cpu_baseline_render(timed[0][0], faces, timed)

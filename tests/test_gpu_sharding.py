@@ -175,7 +175,7 @@ def test_bench_plain_and_torchrun_lines_agree_and_two_gpus_are_refused():
     """The driver's contract: `python bench.py --gpus 1` and the same under torch.distributed.run (N = 1: RCCL process group,
     warm-up gather, timed all_gather_into_tensor) print one JSON line each that agree within noise; a 20-step run agrees
     with a 2000-step run within 5 %; `--gpus 2` on this 1-GPU box says what is wrong."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary"]
     plain = _run_bench(base + ["--gpus", "1", "--steps", "2000", "--warmup", "100"])
     assert plain.returncode == 0, plain.stderr[-800:]
     a = json.loads(plain.stdout.strip().splitlines()[-1])
@@ -183,7 +183,7 @@ def test_bench_plain_and_torchrun_lines_agree_and_two_gpus_are_refused():
     assert short.returncode == 0, short.stderr[-800:]
     s = json.loads(short.stdout.strip().splitlines()[-1])
     tr = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-                     "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--gpus", "1",
+                     "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--gpus", "1",
                      "--steps", "2000", "--warmup", "100"])
     assert tr.returncode == 0, tr.stderr[-800:]
     lines = [ln for ln in tr.stdout.strip().splitlines() if ln.startswith("{")]
@@ -207,7 +207,7 @@ def test_bench_plain_and_torchrun_lines_agree_and_two_gpus_are_refused():
     # the device-side aligned start (a 4-byte ncclAllGather in front of the opening event) costs the region nothing: the driver's
     # own 20-step command under torchrun against the plain 20-step line, compute time to compute time
     tr20 = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-                       "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--gpus", "1",
+                       "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--gpus", "1",
                        "--steps", "20", "--warmup", "5"])
     assert tr20.returncode == 0, tr20.stderr[-800:]
     c = json.loads([ln for ln in tr20.stdout.strip().splitlines() if ln.startswith("{")][0])
@@ -226,7 +226,7 @@ def test_bench_eight_ranks_code_path_on_one_gpu():
     8 x 64 rows and its check, the two per-step times, clean teardown. Not a multi-GPU measurement, and the line says so."""
     for workload, steps, extra in (("decode", "100", []), ("render", "20", []), ("render", "20", ["--gather", "all"])):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--gpus", "8", "--steps", steps,
+               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--gpus", "8", "--steps", steps,
                "--warmup", "10", "--workload", workload] + extra
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_RANK")}
         env["DAD3D_BENCH_SHARE_GPU"] = "1"
@@ -259,7 +259,7 @@ def test_bench_two_ranks_code_path_on_one_gpu():
     env_extra = {"DAD3D_BENCH_SHARE_GPU": "1"}
     for workload, steps in (("decode", "300"), ("render", "60")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--gpus", "2", "--steps", steps,
+               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--gpus", "2", "--steps", steps,
                "--warmup", "20", "--workload", workload]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_RANK")}
         env.update(env_extra)
@@ -280,14 +280,14 @@ def test_bench_two_ranks_code_path_on_one_gpu():
 
 
 def test_driver_command_carries_the_secondary_legs():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (what the driver runs): the contract fields as before, plus -- measured in the
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: the contract fields as before, plus -- measured in the
     same process after the contract region -- long_region, secondary.decode_b256 (BASELINE configs[2], every row held to
     reference-HeadMesh goldens), secondary.render_b64 (configs[4] per-GPU share, timed images re-rasterised by the reference's own
     C++) and cpu_baseline_render; the whole run inside the driver's budget."""
     import time
 
     t0 = time.time()
-    p = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    p = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
     took = time.time() - t0
     assert p.returncode == 0, p.stderr[-800:]
     lines = [ln for ln in p.stdout.strip().splitlines() if ln.strip()]
@@ -323,3 +323,31 @@ def test_driver_command_carries_the_secondary_legs():
     print(f"driver command took {took:.0f} s; long {lr['ms_per_step'] * 1e3:.2f} us, b256 {b256['ms_per_step'] * 1e3:.2f} us frac {b256['frac']:.3f}, "
           f"render {rnd['us_per_batch']:.1f} us")
     assert took < 150  # the driver's run was 32 s in round 4; the secondary legs add ~20 s (two CPU baselines dominate)
+
+
+def test_plain_bench_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path, static):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR`: the headline fields and none of the legs that `--full`
+    adds (CPU baselines, secondary legs, the world-1 gather, the golden check); the dumped arrays are float32 and are the last timed
+    step's outputs -- rows of the golden's seeded batch within the bars bench.py's own check holds them to, landmark pixels = the
+    truncated projection at the 445 indices."""
+    from dad_3dheads_amd import landmarks
+
+    p = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                    "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-800:]
+    lines = [ln for ln in p.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 20
+    assert d["metric"].startswith("images/sec (FLAME decode + 445-lmk projection)")
+    assert d["value"] == d["value_compute"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 64) < 1e-6
+    for leg in ("cpu_baseline", "cpu_baseline_render", "long_region", "secondary"):
+        assert leg not in d, leg
+    assert d["config"]["gather_via"] is None and d["config"]["verification"] is None and d["roofline"]["shader_clock_mhz"] is None
+    v, pr, lm = (np.load(tmp_path / f"{k}.npy") for k in ("verts3d", "proj", "lmk_px"))
+    assert [a.dtype for a in (v, pr, lm)] == [np.float32] * 3 and v.shape == (64, 5023, 3) and pr.shape == (64, 5023, 2) and lm.shape == (64, 445, 2)
+    with np.load(os.path.join(ROOT, "tests", "golden", "decode_golden.npz")) as g:
+        sub = g["b64_subset"]
+        assert np.abs(v[:, sub] - g["b64_v3d_sub"]).max() < 5e-6 and np.abs(pr[:, sub] - g["b64_proj_sub"]).max() < 1e-3
+    idx = landmarks.canonical("445", static)
+    assert np.array_equal(lm, pr[:, idx].astype(np.int32).astype(np.float32))

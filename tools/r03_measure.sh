@@ -3,11 +3,11 @@
 #   bash tools/r03_measure.sh [fast]      fast: skip the end-to-end CNN and the PMC passes
 export TMPDIR=/tmp; root="${GRAFT_REPO_ROOT:-/root/repo}"; out="$root/gpurun_out/r03rec"; mkdir -p "$out"; cd "$root"
 tr() { python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port $1 bench.py --gpus 1 "${@:3}" 2> "$out/$2.err" | grep '^{' > "$out/$2.json"; }
-python bench.py --steps 20 --warmup 5 > "$out/bench_driver_args.json" 2> "$out/bench_driver_args.err"
-python bench.py > "$out/bench.json" 2> "$out/bench.err"
+python bench.py --full --steps 20 --warmup 5 > "$out/bench_driver_args.json" 2> "$out/bench_driver_args.err"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 tr 29531 bench_torchrun_n1 --steps 20 --warmup 5 --no-cpu-baseline
 tr 29532 bench_torchrun_n1_2000 --no-cpu-baseline
-python bench.py --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2> "$out/bench_render.err"
+python bench.py --full --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2> "$out/bench_render.err"
 tr 29533 bench_render_torchrun_n1 --workload render --steps 500 --warmup 50 --no-cpu-baseline
 (cd /tmp && rm -rf /tmp/prof_r03 && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r03 -- python $root/bench.py --no-cpu-baseline > /dev/null 2> "$out/rocprof.err"; f=$(find /tmp/prof_r03 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/bench_kernel_stats.csv")
 (cd /tmp && rm -rf /tmp/prof_r03r && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r03r -- python $root/bench.py --workload render --steps 500 --warmup 50 --no-cpu-baseline > /dev/null 2>> "$out/rocprof.err"; f=$(find /tmp/prof_r03r -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/bench_render_kernel_stats.csv")

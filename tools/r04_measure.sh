@@ -3,12 +3,12 @@
 #   bash tools/r04_measure.sh [fast]      fast: skip the PMC passes
 export TMPDIR=/tmp; root="${GRAFT_REPO_ROOT:-/root/repo}"; out="$root/gpurun_out/r04rec"; mkdir -p "$out"; cd "$root"
 tr() { python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port $1 bench.py --gpus 1 "${@:3}" 2> "$out/$2.err" > "$out/$2.json"; }
-python bench.py --steps 20 --warmup 5 > "$out/bench_driver_args.json" 2> "$out/bench_driver_args.err"
-python bench.py > "$out/bench.json" 2> "$out/bench.err"
+python bench.py --full --steps 20 --warmup 5 > "$out/bench_driver_args.json" 2> "$out/bench_driver_args.err"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 tr 29531 bench_torchrun_n1 --steps 20 --warmup 5 --no-cpu-baseline
 tr 29532 bench_torchrun_n1_2000 --no-cpu-baseline
-python bench.py --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2> "$out/bench_render.err"
-python bench.py --workload render --streams 2 --steps 500 --warmup 50 > "$out/bench_render_s2.json" 2> "$out/bench_render_s2.err"
+python bench.py --full --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2> "$out/bench_render.err"
+python bench.py --full --workload render --streams 2 --steps 500 --warmup 50 > "$out/bench_render_s2.json" 2> "$out/bench_render_s2.err"
 (cd /tmp && rm -rf /tmp/prof_r04 && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r04 -- python $root/bench.py --no-cpu-baseline > /dev/null 2> "$out/rocprof.err"; f=$(find /tmp/prof_r04 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/bench_kernel_stats.csv")
 (cd /tmp && rm -rf /tmp/prof_r04r && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r04r -- python $root/bench.py --workload render --steps 500 --warmup 50 --no-cpu-baseline > /dev/null 2>> "$out/rocprof.err"; f=$(find /tmp/prof_r04r -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/bench_render_kernel_stats.csv")
 S="1 16 17 32 33 48 64 65 96 128 192 256 512 1024 2048"

@@ -7,7 +7,7 @@ tr() { python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-ad
 python bench.py --no-cpu-baseline --no-secondary > "$out/bench_2000.json" 2>/dev/null
 tr --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_torchrun_n1.json" 2>/dev/null
 tr --gpus 1 --steps 2000 --warmup 100 --no-cpu-baseline > "$out/bench_torchrun_n1_2000.json" 2>/dev/null
-python bench.py --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2>/dev/null
+python bench.py --full --workload render --steps 500 --warmup 50 > "$out/bench_render.json" 2>/dev/null
 tr --gpus 1 --workload render --steps 500 --warmup 50 --no-cpu-baseline > "$out/bench_render_torchrun_n1.json" 2>/dev/null
 tr --gpus 1 --workload render --steps 500 --warmup 50 --no-cpu-baseline --gather all > "$out/bench_render_torchrun_n1_allgather.json" 2>/dev/null
 python - "$out" <<'PY'

@@ -2,7 +2,7 @@
 # Round 6: the driver's bench command, timed, with the new legs printed.
 export TMPDIR=/tmp
 root="${GRAFT_REPO_ROOT:-/root/repo}"; out="$root/gpurun_out/r06"; mkdir -p "$out"; cd "$root"
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"
 tail -4 "$out/bench_driver_command.err"
 python - <<'PY'
 import json

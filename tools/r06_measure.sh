@@ -3,7 +3,7 @@
 # split kernel and the fp32 kernel at B = 256 (separate --pmc runs, --kernel-trace only), the headline kernel's PMC refresh.
 export TMPDIR=/tmp
 root="${GRAFT_REPO_ROOT:-/root/repo}"; out="$root/gpurun_out/r06"; mkdir -p "$out"; cd "$root"
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"
 tail -3 "$out/bench_driver_command.err"
 cd /tmp; rm -rf /tmp/prof_bench
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python "$root/bench.py" --gpus 1 --steps 20 --warmup 5 > "$out/bench_profiled.json" 2> "$out/bench_profiled.err"
