@@ -37,7 +37,13 @@ using namespace dad3d;
 // =================================================================================================
 // FLAME
 // =================================================================================================
-// Read-only model constants on the device, shared by a handle and its forks (dad3d_flame_fork)
+static void free_device(int device, std::initializer_list<void*> ptrs) {
+    DeviceGuard guard(device);
+    for (void* p : ptrs) (void)hipFree(p);
+}
+
+// Read-only model constants on the device, shared by a handle and its forks (dad3d_flame_fork). A landmark sub-model keeps its pipelined
+// pack in one of these too (d_bpack_pipe, n_tiles_pipe, split_b_scale and the fp16 planes only).
 struct FlameConsts {
     int device = 0;
     float *d_bpack = nullptr, *d_jdirs = nullptr, *d_j0 = nullptr, *d_w8 = nullptr;
@@ -48,14 +54,27 @@ struct FlameConsts {
     int n_tiles_pipe = 0;
     float* d_gpack = nullptr;  // basis^T in MFMA fragment order for dad3d_flame_grad_inputs: built by the first training forward
     std::mutex gpack_mutex;
-    ~FlameConsts() {
-        DeviceGuard guard(device);
-        for (void* p : {(void*)d_bpack, (void*)d_jdirs, (void*)d_j0, (void*)d_w8, (void*)d_gpack, (void*)d_bpack_pipe, (void*)d_bpack_f16})
-            if (p) (void)hipFree(p);
-    }
+    ~FlameConsts() { free_device(device, {d_bpack, d_jdirs, d_j0, d_w8, d_gpack, d_bpack_pipe, d_bpack_f16}); }
 };
 
-struct dad3d_flame {
+// A landmark list on the device. Immutable once built -- dad3d_flame_set_landmarks builds a new one -- except for the sub-model's fp16
+// planes (built under their mutex), so a handle and its forks share it until one of them installs another list.
+struct LandmarkList {
+    int device = 0;
+    int n = 0;
+    int *d_head = nullptr, *d_next = nullptr;  // [V][2] {first slot of the vertex, the slot after it}, [n] the slot after each slot
+    float4* d_vtab = nullptr;  // [V] {W, w_jaw, first landmark slot, slot chained after it}: the pipelined kernel's; null when it does not cover the model
+    // Landmark-only launches on the pipelined and split kernels (SURVEY 7.1 "landmark-only fast path"; BASELINE configs[3]'s per-GPU work):
+    // the SUB-MODEL of the distinct vertices the list names (445 of 5023: 23 tiles instead of 252). Same per-vertex arithmetic, ~11x less
+    // of it. Its slot chains are the list's own (d_next): renumbering the vertices does not change which slot follows which.
+    std::unique_ptr<FlameConsts> sub;  // its pipelined pack (build_landmark_sub); null: no sub-model
+    int sub_verts = 0;
+    float4* d_sub_vtab = nullptr;  // [sub_verts] the rows of d_vtab of its vertices
+    ~LandmarkList() { free_device(device, {d_head, d_next, d_vtab, d_sub_vtab}); }
+};
+
+// What a fork copies from its parent: the model's dimensions and parameter layout
+struct FlameShape {
     int device = 0;
     int n_verts = 0, n_betas = 0;
     ParamLayout lay{};
@@ -65,15 +84,17 @@ struct dad3d_flame {
     int n_tiles = 0, n_tiles_pad8 = 0;
     int max_shape = 300;
     float image_size = 256.f;
-    std::shared_ptr<FlameConsts> c;
-    int *d_lmk_head = nullptr, *d_lmk_next = nullptr;
-    float4* d_vtab = nullptr;  // [V] {W, w_jaw, first landmark slot, slot chained after it}: per handle (the landmark list is)
+};
+
+struct dad3d_flame : FlameShape {
+    std::shared_ptr<FlameConsts> c;     // shared with forks
+    std::shared_ptr<LandmarkList> lmk;  // shared with forks until either calls dad3d_flame_set_landmarks; never null
     int kernel_choice = -1;    // dad3d_flame_select_kernel; -1 = the process default (DAD3D_DECODE_KERNEL)
+    // ---- per handle, freed by the destructor
     float* d_bwd_partials = nullptr;  // [cap][kBackwardMaxSplit][72] scratch of dad3d_flame_decode_backward
     int bwd_cap = 0;
     float* d_grad_partials = nullptr;  // [slices][padded batch][kGradRows] scratch of dad3d_flame_grad_inputs
     size_t grad_cap = 0;               // its capacity in rows of kGradRows floats
-    int n_lmk = 0;
     float* d_imgc = nullptr;
     unsigned* d_sync = nullptr;   // [0] arrival counter, [1] time-out counter; [4], [5], [last]: device-epoch launches
     unsigned arrive_total = 0;    // host mirror of sync[0] after the last launch
@@ -86,10 +107,13 @@ struct dad3d_flame {
     std::vector<char*> split_retired;  // smaller scratches it outgrew: kept until destroy -- a graph captured at a smaller batch still points there
     hipEvent_t ev_first = nullptr, ev_last = nullptr;  // bracket a run of back-to-back launches
     int prof_launches = 0;
-    // Landmark-only launches (SURVEY 7.1 "landmark-only fast path"; BASELINE configs[3]'s per-GPU work): a second handle over the
-    // SUB-MODEL of the vertices the landmark list names (445 of 5023: 22 tiles instead of 240), built by dad3d_flame_set_landmarks
-    // from the packed basis; a decode that asks for landmark outputs only runs there. Same per-vertex arithmetic, ~11x less of it.
-    dad3d_flame* lmk_sub = nullptr;
+    ~dad3d_flame() {
+        DeviceGuard guard(device);
+        for (void* p : {(void*)d_sync, (void*)d_imgc, (void*)d_bwd_partials, (void*)d_grad_partials, (void*)d_split_a}) (void)hipFree(p);
+        for (char* p : split_retired) (void)hipFree(p);
+        if (ev_first) (void)hipEventDestroy(ev_first);
+        if (ev_last) (void)hipEventDestroy(ev_last);
+    }
 };
 
 // Process-wide default of dad3d_flame_select_kernel: DAD3D_DECODE_KERNEL=v1 forces the two-role kernel of rounds 1-3 (A/B timing).
@@ -105,22 +129,18 @@ static int decode_kernel_choice() {
     return choice;
 }
 
-// the per-vertex table of the pipelined kernel: skinning weights from the model, landmark slots from the handle's list
-static dad3d_status upload_vtab(dad3d_flame* h, const std::vector<int>& head2) {
-    if (!h->c->d_bpack_pipe) return DAD3D_OK;
-    std::vector<float> w8((size_t)h->n_verts * 8);
-    DAD3D_HIP_TRY(hipMemcpy(w8.data(), h->c->d_w8, w8.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<float4> vt(h->n_verts);
-    for (int v = 0; v < h->n_verts; ++v) {
-        const float* w = &w8[(size_t)v * 8];
-        int hd = head2[(size_t)v * 2], nx = head2[(size_t)v * 2 + 1];
-        float fh, fn;
-        memcpy(&fh, &hd, 4), memcpy(&fn, &nx, 4);
-        vt[v] = float4{w[5] + w[2], w[2], fh, fn};  // W = (w0 + w1 + w3 + w4) + w_jaw
-    }
-    if (!h->d_vtab) DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_vtab), vt.size() * sizeof(float4)));
-    DAD3D_HIP_TRY(hipMemcpy(h->d_vtab, vt.data(), vt.size() * sizeof(float4), hipMemcpyHostToDevice));
-    return DAD3D_OK;
+// Every fragment of a basis pack in MFMA B-fragment order, [tile][group of 16 k][wave][lane][4 MFMA steps]: MFMA step s of group g has
+// lane (q = lane >> 4, n = lane & 15) of wave w supply basis row k = 16 g + 4 q + s of column 16 w + n (the k order inside a group is
+// permuted so the A operand can be read row-major with one 16-byte LDS load). frag_offset places the four floats of (tile, g, col, q).
+static size_t frag_offset(int tile, int kgroups, int g, int col, int q) {
+    return ((((size_t)tile * kgroups + g) * 4 + col / 16) * 64 + (col % 16) + 16 * q) * 4;
+}
+template <typename F>
+static void for_each_fragment(std::vector<float>& pack, int n_tiles, int kgroups, F&& f) {  // f(tile, g, col, q, float* four)
+    for (int t = 0; t < n_tiles; ++t)
+        for (int g = 0; g < kgroups; ++g)
+            for (int col = 0; col < kTileCols; ++col)
+                for (int q = 0; q < 4; ++q) f(t, g, col, q, &pack[frag_offset(t, kgroups, g, col, q)]);
 }
 
 static int grad_chunks(const dad3d_flame* h) { return (h->n_verts * 3 + kGradChunk - 1) / kGradChunk; }
@@ -177,6 +197,82 @@ static dad3d_status flame_reserve(dad3d_flame* h, int nbb) {
     h->cap_nbb = 0;
     DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_imgc), (size_t)nbb * kBlockImages * kImgConsts * sizeof(float)));
     h->cap_nbb = nbb;
+    return DAD3D_OK;
+}
+
+static bool landmark_subset_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("DAD3D_LANDMARK_SUBSET");  // =0: landmark-only launches decode the whole mesh like any other (A/B timing)
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
+// The sub-model of list L (idx[0..n)): the model's pipelined pack restricted to the distinct vertices the list names, in ascending vertex
+// order, copied out fragment by fragment. A column's 416 values do not depend on which tile holds it (the jaw-joint columns are the same in
+// every tile), so the sub-model multiplies the same numbers in the same order: a landmark-only launch returns the bits a full-output launch
+// of the same handle returns for those vertices (tests/test_gpu_landmark_subset.py). None when the list names more than a third of the mesh.
+static dad3d_status build_landmark_sub(const dad3d_flame* h, const int64_t* idx, int n, const std::vector<float4>& vtab, LandmarkList* L) {
+    std::vector<char> named(h->n_verts, 0);
+    for (int s = 0; s < n; ++s) named[idx[s]] = 1;
+    std::vector<int> uniq;
+    for (int v = 0; v < h->n_verts; ++v)
+        if (named[v]) uniq.push_back(v);
+    const int nu = (int)uniq.size(), nt = (nu + kPipeTileVerts - 1) / kPipeTileVerts;
+    if ((size_t)nu * 3 > (size_t)h->n_verts) return DAD3D_OK;
+    std::vector<float> full((size_t)h->c->n_tiles_pipe * kPipeKGroups * 4 * 64 * 4), pack((size_t)nt * kPipeKGroups * 4 * 64 * 4, 0.0f);
+    DAD3D_HIP_TRY(hipMemcpy(full.data(), h->c->d_bpack_pipe, full.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for_each_fragment(pack, nt, kPipeKGroups, [&](int t, int g, int col, int q, float* dst) {
+        int src_tile = 0, src_col = col;  // the jaw-joint columns (and the zero pad) are the same in every tile
+        if (col < 3 * kPipeTileVerts) {
+            const int u = t * kPipeTileVerts + col / 3;
+            if (u >= nu) return;
+            src_tile = uniq[u] / kPipeTileVerts, src_col = (uniq[u] % kPipeTileVerts) * 3 + col % 3;
+        }
+        std::copy_n(&full[frag_offset(src_tile, kPipeKGroups, g, src_col, q)], 4, dst);
+    });
+    std::vector<float4> sub_vtab(nu);
+    for (int u = 0; u < nu; ++u) sub_vtab[u] = vtab[uniq[u]];
+    L->sub.reset(new FlameConsts);
+    L->sub->device = h->device;
+    L->sub->n_tiles_pipe = nt;
+    L->sub->split_b_scale = h->c->split_b_scale;  // a subset of the model's entries: its scale holds
+    L->sub_verts = nu;
+    const dad3d_status st = upload(&L->sub->d_bpack_pipe, pack);
+    return st ? st : upload(&L->d_sub_vtab, sub_vtab);
+}
+
+// A new landmark list for h's model: the per-vertex slot chains, the pipelined kernel's per-vertex table (skinning weights from the model,
+// landmark slots from the list) and the sub-model, the last two for models the pipelined kernel covers only.
+static dad3d_status build_landmarks(const dad3d_flame* h, const int64_t* idx, int n, std::shared_ptr<LandmarkList>* out) {
+    const int V = h->n_verts;
+    std::vector<int> head(V, -1), next(n, -1);
+    for (int s = n - 1; s >= 0; --s) {  // reverse walk: each vertex's chain comes out in ascending slot order
+        next[s] = head[idx[s]];
+        head[idx[s]] = s;
+    }
+    std::vector<int> head2((size_t)V * 2, -1);  // what the kernels stage per tile: {head, next[head]}
+    for (int v = 0; v < V; ++v)
+        if (head[v] >= 0) head2[(size_t)v * 2] = head[v], head2[(size_t)v * 2 + 1] = next[head[v]];
+    auto L = std::make_shared<LandmarkList>();
+    L->device = h->device;
+    L->n = n;
+    dad3d_status st;
+    if ((st = upload(&L->d_head, head2)) || (st = upload(&L->d_next, next))) return st;
+    if (h->c->d_bpack_pipe) {
+        std::vector<float> w8((size_t)V * 8);
+        DAD3D_HIP_TRY(hipMemcpy(w8.data(), h->c->d_w8, w8.size() * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<float4> vtab(V);
+        for (int v = 0; v < V; ++v) {
+            const float* w = &w8[(size_t)v * 8];
+            float fh, fn;
+            memcpy(&fh, &head2[(size_t)v * 2], 4), memcpy(&fn, &head2[(size_t)v * 2 + 1], 4);
+            vtab[v] = float4{w[5] + w[2], w[2], fh, fn};  // W = (w0 + w1 + w3 + w4) + w_jaw
+        }
+        if ((st = upload(&L->d_vtab, vtab))) return st;
+        if (landmark_subset_enabled() && n > 0 && (st = build_landmark_sub(h, idx, n, vtab, L.get()))) return st;
+    }
+    *out = std::move(L);
     return DAD3D_OK;
 }
 
@@ -260,9 +356,7 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
     h->n_tiles = (V + kTileVerts - 1) / kTileVerts;
     h->n_tiles_pad8 = (h->n_tiles + 7) / 8 * 8;
 
-    // ---- pack the basis in MFMA B-fragment order: [tile][group of 16 k][wave][lane][4 MFMA steps] -------
-    // MFMA step s of group G: lane (q = lane>>4, n = lane&15) supplies basis row k = 16G + 4q + s (the k
-    // order inside a group is permuted so the A operand can be read row-major with one 16-byte LDS load).
+    // ---- pack the basis in MFMA B-fragment order (for_each_fragment), 21 vertices = 63 columns per tile -------
     auto basis = [&](int k, int v, int comp) -> float {
         if (k < NB) return m->shapedirs[((size_t)v * 3 + comp) * NB + k];
         if (k < NB + h->n_pose_feats) {
@@ -272,37 +366,14 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
         return m->v_template[(size_t)v * 3 + comp];  // k == NB + n_pose_feats: the row multiplied by 1
     };
     std::vector<float> bpack((size_t)h->n_tiles * h->kgroups * 4 * 64 * 4, 0.0f);
-#if defined(DAD3D_MFMA32) && DAD3D_MFMA32
-    // 32x32x2 tiling of flame_decode.hip: [tile][group][column half wc][lane][8]: lane (hh = lane >> 5, n = lane & 31) supplies
-    // basis rows k = 16 g + 8 hh + i, i = 0..7, of column 32 wc + n
-    for (int t = 0; t < h->n_tiles; ++t)
-        for (int g = 0; g < h->kgroups; ++g)
-            for (int wc = 0; wc < 2; ++wc)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int col = wc * 32 + (lane & 31);
-                    const int v = t * kTileVerts + col / 3, comp = col % 3;
-                    if (col >= kTileVerts * 3 || v >= V) continue;
-                    float* dst = &bpack[((((size_t)t * h->kgroups + g) * 2 + wc) * 64 + lane) * 8];
-                    for (int i = 0; i < 8; ++i) {
-                        const int k = 16 * g + 8 * (lane >> 5) + i;
-                        if (k < k_used) dst[i] = basis(k, v, comp);
-                    }
-                }
-    if (false)
-#endif
-    for (int t = 0; t < h->n_tiles; ++t)
-        for (int g = 0; g < h->kgroups; ++g)
-            for (int w = 0; w < 4; ++w)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int col = w * 16 + (lane & 15);
-                    const int v = t * kTileVerts + col / 3, comp = col % 3;
-                    if (col >= kTileVerts * 3 || v >= V) continue;
-                    float* dst = &bpack[((((size_t)t * h->kgroups + g) * 4 + w) * 64 + lane) * 4];
-                    for (int i = 0; i < 4; ++i) {
-                        const int k = 16 * g + 4 * (lane >> 4) + i;
-                        if (k < k_used) dst[i] = basis(k, v, comp);
-                    }
-                }
+    for_each_fragment(bpack, h->n_tiles, h->kgroups, [&](int t, int g, int col, int q, float* dst) {
+        const int v = t * kTileVerts + col / 3;
+        if (col >= kTileVerts * 3 || v >= V) return;
+        for (int i = 0; i < 4; ++i) {
+            const int k = 16 * g + 4 * q + i;
+            if (k < k_used) dst[i] = basis(k, v, col % 3);
+        }
+    });
 
     // ---- joints are linear in betas: J = J_regressor.v_template + (J_regressor.shapedirs).betas ----
     std::vector<float> j0(3 * kNumJoints), jdirs((size_t)3 * kNumJoints * NB);
@@ -330,8 +401,6 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
         for (int j = 0; j < kNumJoints; ++j) w8[(size_t)v * 8 + j] = w[j];
         w8[(size_t)v * 8 + 5] = ((w[0] + w[1]) + w[3]) + w[4];  // weight of the joints that cannot rotate (jaw-only mode)
     }
-    std::vector<int> head((size_t)V * 2, -1);  // [V][2]: first landmark slot of the vertex, the slot after it
-
     // ---- the pipelined single-role kernel (flame_decode_pipe.hip): jaw-only models with the dad_3dnet.yaml params layout.
     // Tiles of 20 vertices; columns 60..62 of every tile carry the jaw joint J_jaw = J0_jaw + Jdirs_jaw . betas (rows of the pose
     // feature contribute nothing to a joint: smplx regresses the joints from v_shaped), column 63 is zero.
@@ -341,27 +410,21 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
     const int n_tiles_pipe = (V + kPipeTileVerts - 1) / kPipeTileVerts;
     if (pipe_ok) {
         bpack_pipe.assign((size_t)n_tiles_pipe * kPipeKGroups * 4 * 64 * 4, 0.0f);
-        for (int t = 0; t < n_tiles_pipe; ++t)
-            for (int g = 0; g < kPipeKGroups; ++g)
-                for (int w = 0; w < 4; ++w)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int col = w * 16 + (lane & 15);
-                        float* dst = &bpack_pipe[((((size_t)t * kPipeKGroups + g) * 4 + w) * 64 + lane) * 4];
-                        for (int i = 0; i < 4; ++i) {
-                            const int k = 16 * g + 4 * (lane >> 4) + i;
-                            if (k >= k_used) continue;
-                            if (col < 3 * kPipeTileVerts) {
-                                const int v = t * kPipeTileVerts + col / 3;
-                                if (v < V) dst[i] = basis(k, v, col % 3);
-                            } else if (col < 3 * kPipeTileVerts + 3) {
-                                const int o = 2 * 3 + (col - 3 * kPipeTileVerts);  // joint 2 = jaw
-                                dst[i] = k < NB ? jdirs[(size_t)o * NB + k] : (k == NB + h->n_pose_feats ? j0[o] : 0.0f);
-                            }
-                        }
-                    }
+        for_each_fragment(bpack_pipe, n_tiles_pipe, kPipeKGroups, [&](int t, int g, int col, int q, float* dst) {
+            for (int i = 0; i < 4; ++i) {
+                const int k = 16 * g + 4 * q + i;
+                if (k >= k_used) continue;
+                if (col < 3 * kPipeTileVerts) {
+                    const int v = t * kPipeTileVerts + col / 3;
+                    if (v < V) dst[i] = basis(k, v, col % 3);
+                } else if (col < 3 * kPipeTileVerts + 3) {
+                    const int o = 2 * 3 + (col - 3 * kPipeTileVerts);  // joint 2 = jaw
+                    dst[i] = k < NB ? jdirs[(size_t)o * NB + k] : (k == NB + h->n_pose_feats ? j0[o] : 0.0f);
+                }
+            }
+        });
     }
 
-    dad3d_status st;
     h->c = std::make_shared<FlameConsts>();
     h->c->device = device;
     h->c->n_tiles_pipe = n_tiles_pipe;
@@ -370,250 +433,50 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
         for (float v : bpack_pipe) max_abs = std::max(max_abs, std::fabs(v));
         h->c->split_b_scale = split_basis_scale(max_abs);
     }
-    if (pipe_ok && (st = upload(&h->c->d_bpack_pipe, bpack_pipe))) {
-        dad3d_flame_destroy(h.release());
+    dad3d_status st;
+    if ((pipe_ok && (st = upload(&h->c->d_bpack_pipe, bpack_pipe))) || (st = upload(&h->c->d_bpack, bpack)) ||
+        (st = upload(&h->c->d_jdirs, jdirs)) || (st = upload(&h->c->d_j0, j0)) || (st = upload(&h->c->d_w8, w8)) ||
+        (st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) || (st = flame_reserve(h.get(), 1)) ||
+        (st = build_landmarks(h.get(), nullptr, 0, &h->lmk)))
         return st;
-    }
-    if ((st = upload(&h->c->d_bpack, bpack)) || (st = upload(&h->c->d_jdirs, jdirs)) || (st = upload(&h->c->d_j0, j0)) ||
-        (st = upload(&h->c->d_w8, w8)) || (st = upload(&h->d_lmk_head, head)) ||
-        (st = upload(&h->d_lmk_next, std::vector<int>())) || (st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) ||
-        (st = flame_reserve(h.get(), 1)) || (st = upload_vtab(h.get(), head))) {
-        dad3d_flame_destroy(h.release());
-        return st;
-    }
     *out = h.release();
     return DAD3D_OK;
 }
 
-void dad3d_flame_destroy(dad3d_flame* h) {
-    if (!h) return;
-    if (h->lmk_sub) dad3d_flame_destroy(h->lmk_sub);
-    h->lmk_sub = nullptr;
-    DeviceGuard guard(h->device);
-    for (void* p : {(void*)h->d_lmk_head, (void*)h->d_lmk_next, (void*)h->d_sync, (void*)h->d_imgc, (void*)h->d_bwd_partials,
-                    (void*)h->d_grad_partials, (void*)h->d_vtab, (void*)h->d_split_a})
-        if (p) (void)hipFree(p);
-    for (char* p : h->split_retired) (void)hipFree(p);
-    if (h->ev_first) (void)hipEventDestroy(h->ev_first);
-    if (h->ev_last) (void)hipEventDestroy(h->ev_last);
-    delete h;
-}
+void dad3d_flame_destroy(dad3d_flame* h) { delete h; }
 
 dad3d_status dad3d_flame_fork(dad3d_flame* parent, dad3d_flame** out) {
     DAD3D_REQUIRE(parent && out, "dad3d_flame_fork: bad argument");
     *out = nullptr;
     DeviceGuard guard(parent->device);
     DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", parent->device);
-    std::unique_ptr<dad3d_flame> h(new dad3d_flame(*parent));  // layout, tiling, shared constants
-    h->lmk_sub = nullptr;  // forked below: the sub-model's constants are shared like the model's
-    h->d_lmk_head = h->d_lmk_next = nullptr;
-    h->d_vtab = nullptr;
-    h->d_imgc = nullptr;
-    h->d_sync = nullptr;
-    h->d_bwd_partials = nullptr;
-    h->bwd_cap = 0;
-    h->d_grad_partials = nullptr;
-    h->grad_cap = 0;
-    h->arrive_total = 0;
-    h->cap_nbb = 0;
-    h->d_split_a = nullptr, h->split_cap = 0;
-    h->split_retired.clear();
-    h->profiling = false;
-    h->d_trace = nullptr;
-    h->ev_first = h->ev_last = nullptr;
-    h->prof_launches = 0;
-    dad3d_status st = DAD3D_OK;
-    const size_t nv = (size_t)parent->n_verts, nl = (size_t)std::max(parent->n_lmk, 0);
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_lmk_head), std::max<size_t>(nv, 1) * 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->d_lmk_next), std::max<size_t>(nl, 1) * sizeof(int)) != hipSuccess ||
-        hipMemcpy(h->d_lmk_head, parent->d_lmk_head, nv * 2 * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess ||
-        (nl && hipMemcpy(h->d_lmk_next, parent->d_lmk_next, nl * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess) ||
-        (st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) != DAD3D_OK) {
-        if (st == DAD3D_OK) set_error("dad3d_flame_fork: device allocation or copy failed");
-        dad3d_flame_destroy(h.release());
-        return st == DAD3D_OK ? DAD3D_E_HIP : st;
-    }
-    if (parent->d_vtab) {
-        if (hipMalloc(reinterpret_cast<void**>(&h->d_vtab), nv * sizeof(float4)) != hipSuccess ||
-            hipMemcpy(h->d_vtab, parent->d_vtab, nv * sizeof(float4), hipMemcpyDeviceToDevice) != hipSuccess) {
-            set_error("dad3d_flame_fork: device allocation or copy failed");
-            dad3d_flame_destroy(h.release());
-            return DAD3D_E_HIP;
-        }
-    }
-    if (parent->lmk_sub) {
-        dad3d_status st2 = dad3d_flame_fork(parent->lmk_sub, &h->lmk_sub);
-        if (st2) {
-            dad3d_flame_destroy(h.release());
-            return st2;
-        }
-    }
-    // the device-to-device copies above are ordered on the NULL stream and may return before they ran: a first launch of the fork on a
-    // non-blocking stream must not overtake them
-    if (hipStreamSynchronize(nullptr) != hipSuccess) {
-        set_error("dad3d_flame_fork: hipStreamSynchronize failed");
-        dad3d_flame_destroy(h.release());
-        return DAD3D_E_HIP;
-    }
+    std::unique_ptr<dad3d_flame> h(new dad3d_flame);
+    static_cast<FlameShape&>(*h) = *parent;
+    h->c = parent->c;
+    h->lmk = parent->lmk;
+    h->kernel_choice = parent->kernel_choice;
+    dad3d_status st;
+    if ((st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) || (st = flame_reserve(h.get(), 1))) return st;
     *out = h.release();
     return DAD3D_OK;
 }
 
 int dad3d_flame_num_params(const dad3d_flame* h) { return h ? h->lay.n_params : -1; }
 int dad3d_flame_num_verts(const dad3d_flame* h) { return h ? h->n_verts : -1; }
-int dad3d_flame_num_landmarks(const dad3d_flame* h) { return h ? h->n_lmk : -1; }
-int dad3d_flame_num_landmark_vertices(const dad3d_flame* h) { return (h && h->lmk_sub) ? h->lmk_sub->n_verts : 0; }
-
-// the per-vertex slot chains of a landmark list: head2[v] = {first slot of vertex v, the slot after it}, next[s] = the slot after s
-static void landmark_chains(const int64_t* idx, int n, int n_verts, std::vector<int>& head2, std::vector<int>& next) {
-    std::vector<int> head(n_verts, -1);
-    next.assign(n, -1);
-    for (int s = n - 1; s >= 0; --s) {  // reverse walk: each vertex's chain comes out in ascending slot order
-        next[s] = head[idx[s]];
-        head[idx[s]] = s;
-    }
-    head2.assign((size_t)n_verts * 2, -1);  // what the kernel stages per tile: {head, next[head]}
-    for (int v = 0; v < n_verts; ++v)
-        if (head[v] >= 0) head2[(size_t)v * 2] = head[v], head2[(size_t)v * 2 + 1] = next[head[v]];
-}
-
-static dad3d_status install_landmark_lists(dad3d_flame* h, const std::vector<int>& head2, const std::vector<int>& next, int n) {
-    int* d_next = nullptr;
-    dad3d_status st = upload(&d_next, next);
-    if (st) return st;
-    DAD3D_HIP_TRY(hipDeviceSynchronize());  // no decode may still be walking the old lists
-    DAD3D_HIP_TRY(hipMemcpy(h->d_lmk_head, head2.data(), head2.size() * sizeof(int), hipMemcpyHostToDevice));
-    (void)hipFree(h->d_lmk_next);
-    h->d_lmk_next = d_next;
-    h->n_lmk = n;
-    return upload_vtab(h, head2);
-}
-
-static bool landmark_subset_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DAD3D_LANDMARK_SUBSET");  // =0: landmark-only launches decode the whole mesh like any other (A/B timing)
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// (Re)build h->lmk_sub for the list just installed: the model restricted to the distinct vertices the list names, in ascending
-// vertex order, with the list remapped onto it. The basis fragments are copied out of the parent's packs -- both of them: the
-// pipelined kernel's (20-vertex tiles + the jaw-joint columns) and the two-role kernel's -- and a column's 416 values do not depend
-// on which tile holds it, so the sub-model multiplies the same numbers in the same order on whichever kernel the parent would have
-// taken: a landmark-only launch returns the bits a full-output launch of the same handle returns for those vertices
-// (tests/test_gpu_landmark_subset.py). No sub-model when the list names more than a third of the mesh.
-static dad3d_status build_landmark_subset(dad3d_flame* h, const int64_t* idx, int n) {
-    if (h->lmk_sub) dad3d_flame_destroy(h->lmk_sub);
-    h->lmk_sub = nullptr;
-#if defined(DAD3D_MFMA32) && DAD3D_MFMA32
-    return DAD3D_OK;  // diagnostics build with the 32x32x2 fragment order: not mirrored here
-#endif
-    if (!landmark_subset_enabled() || n <= 0) return DAD3D_OK;
-    std::vector<int> where(h->n_verts, -1), uniq;
-    for (int s = 0; s < n; ++s) where[idx[s]] = 0;
-    for (int v = 0; v < h->n_verts; ++v)
-        if (where[v] == 0) where[v] = (int)uniq.size(), uniq.push_back(v);
-    const int nu = (int)uniq.size();
-    if ((size_t)nu * 3 > (size_t)h->n_verts) return DAD3D_OK;
-    const int KG = h->kgroups, nt_sub = (nu + kTileVerts - 1) / kTileVerts;
-    std::vector<float> full((size_t)h->n_tiles * KG * 4 * 64 * 4), w8((size_t)h->n_verts * 8);
-    std::vector<float> jdirs((size_t)3 * kNumJoints * h->n_betas), j0(3 * kNumJoints);
-    DAD3D_HIP_TRY(hipMemcpy(full.data(), h->c->d_bpack, full.size() * sizeof(float), hipMemcpyDeviceToHost));
-    DAD3D_HIP_TRY(hipMemcpy(w8.data(), h->c->d_w8, w8.size() * sizeof(float), hipMemcpyDeviceToHost));
-    DAD3D_HIP_TRY(hipMemcpy(jdirs.data(), h->c->d_jdirs, jdirs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    DAD3D_HIP_TRY(hipMemcpy(j0.data(), h->c->d_j0, j0.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<float> sub((size_t)nt_sub * KG * 4 * 64 * 4, 0.0f), w8s((size_t)nu * 8);
-    for (int t = 0; t < nt_sub; ++t)
-        for (int g = 0; g < KG; ++g)
-            for (int w = 0; w < 4; ++w)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int col = w * 16 + (lane & 15), u = t * kTileVerts + col / 3;
-                    if (col >= kTileVerts * 3 || u >= nu) continue;
-                    const int v = uniq[u], scol = (v % kTileVerts) * 3 + col % 3;  // the column's place in the parent's tile
-                    const float* src = &full[((((size_t)(v / kTileVerts) * KG + g) * 4 + scol / 16) * 64 + (scol % 16) + 16 * (lane >> 4)) * 4];
-                    float* dst = &sub[((((size_t)t * KG + g) * 4 + w) * 64 + lane) * 4];
-                    dst[0] = src[0], dst[1] = src[1], dst[2] = src[2], dst[3] = src[3];
-                }
-    for (int u = 0; u < nu; ++u) std::copy(&w8[(size_t)uniq[u] * 8], &w8[(size_t)uniq[u] * 8 + 8], &w8s[(size_t)u * 8]);
-    // the pipelined kernel's pack of the sub-model: [tile][26][4 waves][64 lanes][4], columns 0..59 = 20 vertices, 60..62 = the jaw joint
-    std::vector<float> sub_pipe;
-    const int nt_pipe = (nu + kPipeTileVerts - 1) / kPipeTileVerts;
-    if (h->c->d_bpack_pipe) {
-        std::vector<float> full_pipe((size_t)h->c->n_tiles_pipe * kPipeKGroups * 4 * 64 * 4);
-        DAD3D_HIP_TRY(hipMemcpy(full_pipe.data(), h->c->d_bpack_pipe, full_pipe.size() * sizeof(float), hipMemcpyDeviceToHost));
-        sub_pipe.assign((size_t)nt_pipe * kPipeKGroups * 4 * 64 * 4, 0.0f);
-        for (int t = 0; t < nt_pipe; ++t)
-            for (int g = 0; g < kPipeKGroups; ++g)
-                for (int w = 0; w < 4; ++w)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int col = w * 16 + (lane & 15), u = t * kPipeTileVerts + col / 3;
-                        int st = 0, scol = col;  // the jaw-joint columns (and the zero pad) are the same in every tile
-                        if (col < 3 * kPipeTileVerts) {
-                            if (u >= nu) continue;
-                            st = uniq[u] / kPipeTileVerts, scol = (uniq[u] % kPipeTileVerts) * 3 + col % 3;
-                        }
-                        const float* src = &full_pipe[((((size_t)st * kPipeKGroups + g) * 4 + scol / 16) * 64 + (scol % 16) + 16 * (lane >> 4)) * 4];
-                        float* dst = &sub_pipe[((((size_t)t * kPipeKGroups + g) * 4 + w) * 64 + lane) * 4];
-                        dst[0] = src[0], dst[1] = src[1], dst[2] = src[2], dst[3] = src[3];
-                    }
-    }
-    std::vector<int64_t> remapped(n);
-    for (int s = 0; s < n; ++s) remapped[s] = where[idx[s]];
-    std::vector<int> head2, next;
-    landmark_chains(remapped.data(), n, nu, head2, next);
-
-    std::unique_ptr<dad3d_flame> q(new dad3d_flame(*h));  // layout, K depth, image size
-    q->lmk_sub = nullptr;
-    q->d_lmk_head = q->d_lmk_next = nullptr;
-    q->d_vtab = nullptr;
-    q->d_imgc = nullptr;
-    q->d_sync = nullptr;
-    q->d_bwd_partials = q->d_grad_partials = nullptr;
-    q->bwd_cap = 0, q->grad_cap = 0, q->arrive_total = 0, q->cap_nbb = 0;
-    q->d_split_a = nullptr, q->split_cap = 0;
-    q->split_retired.clear();
-    q->profiling = false;
-    q->d_trace = nullptr, q->trace_capacity = 0;
-    q->ev_first = q->ev_last = nullptr;
-    q->prof_launches = 0;
-    q->kernel_choice = h->c->d_bpack_pipe ? DAD3D_KERNEL_AUTO : DAD3D_KERNEL_TWO_ROLE;  // the kernel the parent's full launches take
-    q->n_verts = nu;
-    q->n_tiles = nt_sub;
-    q->n_tiles_pad8 = (nt_sub + 7) / 8 * 8;
-    q->n_lmk = n;
-    q->c = std::make_shared<FlameConsts>();
-    q->c->device = h->device;
-    q->c->n_tiles_pipe = nt_pipe;
-    q->c->split_b_scale = h->c->split_b_scale;  // a subset of the parent's entries: its scale holds
-    dad3d_status st;
-    if ((st = upload(&q->c->d_bpack, sub)) || (st = upload(&q->c->d_jdirs, jdirs)) || (st = upload(&q->c->d_j0, j0)) ||
-        (st = upload(&q->c->d_w8, w8s)) || (st = upload(&q->d_lmk_head, head2)) || (st = upload(&q->d_lmk_next, next)) ||
-        (!sub_pipe.empty() && (st = upload(&q->c->d_bpack_pipe, sub_pipe))) || (st = upload_vtab(q.get(), head2)) ||
-        (st = upload(&q->d_sync, std::vector<unsigned>(kSyncWords, 0u))) || (st = flame_reserve(q.get(), std::max(1, h->cap_nbb)))) {
-        dad3d_flame_destroy(q.release());
-        return st;
-    }
-    h->lmk_sub = q.release();
-    return DAD3D_OK;
-}
+int dad3d_flame_num_landmarks(const dad3d_flame* h) { return h ? h->lmk->n : -1; }
+int dad3d_flame_num_landmark_vertices(const dad3d_flame* h) { return h ? h->lmk->sub_verts : 0; }
 
 dad3d_status dad3d_flame_set_landmarks(dad3d_flame* h, const int64_t* idx, int n) {
     DAD3D_REQUIRE(h && n >= 0 && (idx || n == 0), "dad3d_flame_set_landmarks: bad argument");
     for (int s = 0; s < n; ++s)
         DAD3D_REQUIRE(idx[s] >= 0 && idx[s] < h->n_verts, "landmark index %lld out of range [0,%d)", (long long)idx[s], h->n_verts);
-    std::vector<int> head2, next;
-    landmark_chains(idx, n, h->n_verts, head2, next);
     DeviceGuard guard(h->device);
-    // the old list's sub-model goes first: if anything below fails, no launch can return (or overrun with) the old list's landmarks
-    if (h->lmk_sub) {
-        DAD3D_HIP_TRY(hipDeviceSynchronize());
-        dad3d_flame_destroy(h->lmk_sub);
-        h->lmk_sub = nullptr;
-    }
-    dad3d_status st = install_landmark_lists(h, head2, next, n);
-    if (st) return st;
-    return build_landmark_subset(h, idx, n);
+    std::shared_ptr<LandmarkList> list;
+    dad3d_status st = build_landmarks(h, idx, n, &list);
+    if (st) return st;  // the handle keeps its old list
+    DAD3D_HIP_TRY(hipDeviceSynchronize());  // no decode of this handle may still be walking the old list when it is freed
+    h->lmk = std::move(list);
+    return DAD3D_OK;
 }
 
 // entries of a dad3d_flame_debug_trace buffer one launch stamps (the two kernels lay it out differently, include/dad3d.h)
@@ -626,8 +489,7 @@ static uint64_t trace_entries_pipe(const dad3d_flame* h) { return (uint64_t)h->c
 // DAD3D_KERNEL_SPLIT_F16: the model's basis pack as two fp16 planes, built on the device by the first decode in that form (26.7 MB for the whole
 // mesh: not spent on models that never use the form), shared by forks. The builder waits for its kernel before publishing the pointer: a fork
 // on another stream must not read a pack still being written.
-static dad3d_status ensure_basis_f16(dad3d_flame* h, hipStream_t s) {
-    FlameConsts* c = h->c.get();
+static dad3d_status ensure_basis_f16(FlameConsts* c, hipStream_t s) {
     std::lock_guard<std::mutex> lock(c->f16_mu);
     if (c->d_bpack_f16) return DAD3D_OK;
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
@@ -666,6 +528,23 @@ static dad3d_status ensure_split_scratch(dad3d_flame* h, int n_phase, hipStream_
     return DAD3D_OK;
 }
 
+// The kernel a decode launch of h takes: DAD3D_KERNEL_TWO_ROLE, _PIPELINED, _SPLIT_BF16 or _SPLIT_F16; -1 (error set) when the pinned one
+// does not cover it. The pipelined single-role kernel (flame_decode_pipe.hip) takes EVERY inference launch it covers (jaw-only model, the
+// dad_3dnet.yaml params layout, no DAD3D_ZERO_ROTATION / DAD3D_COMPAT_CROSS_B3, outputs below 2 GB); the two-role kernel of rounds 1-3 keeps
+// the rest and the training forward. Round 4 also sent 1..3 and 33..40 images to the two-role kernel for 0.3-0.6 us measured on one box
+// (profiles/r04_ab_decode.txt: 6.8 against 7.4 us at B = 1, 11.63 against 11.90 at 33); that crossover table is gone -- inside box-to-box
+// spread at 33..40, irrelevant next to a 4 ms network at B = 1, and it made the jaw sine/cosine (flame_math.hpp against OCML) depend on the
+// batch size. DAD3D_DECODE_KERNEL=v1 / dad3d_flame_select_kernel remain the escape hatch. The split forms are never chosen automatically.
+static int resolve_kernel(const dad3d_flame* h, int pinned, int batch, unsigned flags, bool posed) {
+    const bool pipe_covers = h->c->d_bpack_pipe && !posed && !(flags & (DAD3D_COMPAT_CROSS_B3 | DAD3D_ZERO_ROTATION)) &&
+                             (size_t)batch * h->n_verts * 12 < ((size_t)1 << 31) && (size_t)batch * std::max(h->lmk->n, 1) * 8 < ((size_t)1 << 31);
+    if (pinned == DAD3D_KERNEL_TWO_ROLE || (pinned == DAD3D_KERNEL_AUTO && !pipe_covers)) return DAD3D_KERNEL_TWO_ROLE;
+    if (pipe_covers) return pinned == DAD3D_KERNEL_AUTO ? DAD3D_KERNEL_PIPELINED : pinned;
+    set_error("dad3d_flame_decode: the %s kernel does not cover this launch (model, flags or output size)",
+              pinned == DAD3D_KERNEL_PIPELINED ? "pipelined" : "split");
+    return -1;
+}
+
 static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsigned flags, float* verts3d, float* proj,
                                 float* lmk_xy, int32_t* lmk_px, float* posed, void* stream) {
     DAD3D_REQUIRE(h, "dad3d_flame_decode: null handle");
@@ -678,97 +557,65 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
     DAD3D_REQUIRE(!(posed && (flags & DAD3D_COMPAT_CROSS_B3)), "DAD3D_COMPAT_CROSS_B3 is inference-only (dad3d_flame_decode_posed refuses it)");
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // Landmark outputs only (BASELINE configs[3]'s per-GPU work; sharding.ShardedLandmarkDecoder): the sub-model of the listed vertices,
-    // 23 column tiles instead of 252 with the batch cut into chunks across workgroups (pipe_chunking / split_chunking) -- same kernel, same
-    // bits as the landmark rows of a full-output launch of the handle, default or split form -- unless the caller pinned the two-role or the
-    // pipelined kernel (A/B timing, diagnostics: the whole mesh then).
     const int pinned = h->kernel_choice >= 0 ? h->kernel_choice : decode_kernel_choice();
-    const bool pinned_split = pinned == DAD3D_KERNEL_SPLIT_BF16 || pinned == DAD3D_KERNEL_SPLIT_F16;
-    if (h->lmk_sub && !verts3d && !proj && !posed && (lmk_xy || lmk_px) && !(flags & DAD3D_COMPAT_CROSS_B3) && !h->d_trace &&
-        (pinned == DAD3D_KERNEL_AUTO || (pinned_split && h->lmk_sub->c->d_bpack_pipe && h->lmk_sub->d_vtab))) {
-        // a handle on a split form keeps ITS arithmetic: the sub-model runs the same form (its phases dealt over workgroups: split_chunking)
-        // on the PARENT's scratch -- one stream per handle, and a landmark-only launch captured behind a full-output warm-up must not allocate
-        h->lmk_sub->kernel_choice = pinned_split ? pinned : (h->lmk_sub->c->d_bpack_pipe ? DAD3D_KERNEL_AUTO : DAD3D_KERNEL_TWO_ROLE);
-        if (pinned_split) {
-            dad3d_status sst = ensure_split_scratch(h, (batch + kSplitRows - 1) / kSplitRows, s);
-            if (sst) return sst;
-            h->lmk_sub->d_split_a = h->d_split_a, h->lmk_sub->split_cap = h->split_cap;
-        }
-        dad3d_status st = decode_impl(h->lmk_sub, params, batch, flags, nullptr, nullptr, lmk_xy, lmk_px, nullptr, stream);
-        if (pinned_split) h->lmk_sub->d_split_a = nullptr, h->lmk_sub->split_cap = 0;  // (lent, not owned)
-        if (!st && h->profiling) ++h->prof_launches;
-        return st;
-    }
-    // A training forward: what its backward pass needs exists before any of it can be captured into a graph -- for the batches
-    // the host mirror sends to dad3d_flame_grad_inputs (up to DAD3D_GRAD_INPUTS_MAX_BATCH; above it takes the library GEMM and
-    // the split-K scratch, tens to hundreds of MB, would never be used) and for models the kernel covers (otherwise the
-    // forward must not fail for a backward path that will not be taken: dad3d_flame_grad_inputs reports it when called).
-    if (posed && batch <= DAD3D_GRAD_INPUTS_MAX_BATCH && h->n_betas + 36 <= kGradRows) {
-        dad3d_status st = grad_inputs_prepare(h, batch, s);
-        if (st) return st;
-    }
-    // The pipelined single-role kernel (flame_decode_pipe.hip) takes EVERY inference launch it covers (jaw-only model, the
-    // dad_3dnet.yaml params layout, no DAD3D_ZERO_ROTATION / DAD3D_COMPAT_CROSS_B3, outputs below 2 GB); the two-role kernel of
-    // rounds 1-3 keeps the rest and the training forward. Round 4 also sent 1..3 and 33..40 images to the two-role kernel for
-    // 0.3-0.6 us measured on one box (profiles/r04_ab_decode.txt: 6.8 against 7.4 us at B = 1, 11.63 against 11.90 at 33); that
-    // crossover table is gone -- inside box-to-box spread at 33..40, irrelevant next to a 4 ms network at B = 1, and it made the
-    // jaw sine/cosine (flame_math.hpp against OCML) depend on the batch size. DAD3D_DECODE_KERNEL=v1 / dad3d_flame_select_kernel
-    // remain the escape hatch.
-    const int choice = h->kernel_choice >= 0 ? h->kernel_choice : decode_kernel_choice();
-    const bool pipe_covers = h->c->d_bpack_pipe && h->d_vtab && !posed && !(flags & (DAD3D_COMPAT_CROSS_B3 | DAD3D_ZERO_ROTATION)) &&
-                             (size_t)batch * h->n_verts * 12 < ((size_t)1 << 31) && (size_t)batch * std::max(h->n_lmk, 1) * 8 < ((size_t)1 << 31);
-    const bool split = choice == DAD3D_KERNEL_SPLIT_BF16 || choice == DAD3D_KERNEL_SPLIT_F16;
-    if ((choice == DAD3D_KERNEL_PIPELINED || split) && !pipe_covers) {
-        set_error("dad3d_flame_decode: the %s kernel does not cover this launch (model, flags or output size)",
-                  choice == DAD3D_KERNEL_PIPELINED ? "pipelined" : "split");
-        return DAD3D_E_UNSUPPORTED;
-    }
-    if (split) {
+    const int kernel = resolve_kernel(h, pinned, batch, flags, posed != nullptr);
+    if (kernel < 0) return DAD3D_E_UNSUPPORTED;
+    const LandmarkList& L = *h->lmk;
+    const int n_lmk = (lmk_xy || lmk_px) ? L.n : 0;
+
+    // Geometry of the pipelined and split kernels. Landmark outputs only (BASELINE configs[3]'s per-GPU work;
+    // sharding.ShardedLandmarkDecoder): the sub-model of the listed vertices, 23 column tiles instead of 252 with the batch cut into chunks
+    // across workgroups (pipe_chunking / split_chunking) -- same kernel, same bits as the landmark rows of a full-output launch -- unless the
+    // caller pinned the pipelined kernel or traces the launch (A/B timing, diagnostics: the whole mesh then). The launch covers no posed
+    // output and no DAD3D_COMPAT_CROSS_B3 here: resolve_kernel sent those to the two-role kernel, which always decodes the whole mesh.
+    const bool on_sub = L.sub && !verts3d && !proj && n_lmk && !h->d_trace && pinned != DAD3D_KERNEL_PIPELINED;
+    FlameConsts* c = on_sub ? L.sub.get() : h->c.get();
+    const float4* vtab = on_sub ? L.d_sub_vtab : L.d_vtab;
+    const int n_verts = on_sub ? L.sub_verts : h->n_verts;
+
+    dad3d_status st;
+    if (kernel == DAD3D_KERNEL_SPLIT_BF16 || kernel == DAD3D_KERNEL_SPLIT_F16) {
         // The gated exact-product splits (flame_decode_split.hip; bf16 x 3 planes x 6 products, or fp16 x 2 planes x 3 products): same
         // model coverage, same pack, same epilogue as the pipelined kernel; the contraction differs (and is more accurate than the
-        // fp32 MFMA chain in both forms: profiles/r06_split_error.md). Two launches.
+        // fp32 MFMA chain in both forms: profiles/r06_split_error.md). Two launches, the handle's own scratch in between.
         DAD3D_REQUIRE(!h->d_trace, "dad3d_flame_decode: the split kernels have no trace stamps");
         const int n_phase = (batch + kSplitRows - 1) / kSplitRows;
-        dad3d_status sst = ensure_split_scratch(h, n_phase, s);
-        if (!sst && choice == DAD3D_KERNEL_SPLIT_F16) sst = ensure_basis_f16(h, s);
-        // (and the landmark sub-model's, so that a landmark-only launch captured behind a full-output warm-up builds nothing)
-        if (!sst && choice == DAD3D_KERNEL_SPLIT_F16 && h->lmk_sub && h->lmk_sub->c->d_bpack_pipe) sst = ensure_basis_f16(h->lmk_sub, s);
-        if (sst) return sst;
+        st = ensure_split_scratch(h, n_phase, s);
+        if (!st && kernel == DAD3D_KERNEL_SPLIT_F16) st = ensure_basis_f16(c, s);
+        // (and the sub-model's, so that a landmark-only launch captured behind a full-output warm-up builds nothing)
+        if (!st && kernel == DAD3D_KERNEL_SPLIT_F16 && L.sub) st = ensure_basis_f16(L.sub.get(), s);
+        if (st) return st;
         SplitArgs sa{};
         sa.params = params;
-        sa.bpack = h->c->d_bpack_pipe;
-        sa.bpack_f16 = h->c->d_bpack_f16;
-        sa.vtab = h->d_vtab;
-        sa.lmk_next = h->d_lmk_next;
+        sa.bpack = c->d_bpack_pipe;
+        sa.bpack_f16 = c->d_bpack_f16;
+        sa.vtab = vtab;
+        sa.lmk_next = L.d_next;
         sa.verts3d = verts3d;
         sa.proj = proj;
         sa.lmk_xy = lmk_xy;
         sa.lmk_px = lmk_px;
         sa.aplanes = h->d_split_a;
-        sa.b_scale = h->c->split_b_scale;
+        sa.b_scale = c->split_b_scale;
         sa.n_params = h->lay.n_params;
         sa.batch = batch;
         sa.n_phase = n_phase;
-        sa.n_tiles = h->c->n_tiles_pipe;
+        sa.n_tiles = c->n_tiles_pipe;
         split_chunking(sa.n_tiles, n_phase, &sa.n_chunks, &sa.phases_per_chunk);
-        sa.n_verts = h->n_verts;
-        sa.n_lmk = (lmk_xy || lmk_px) ? h->n_lmk : 0;
+        sa.n_verts = n_verts;
+        sa.n_lmk = n_lmk;
         sa.image_size = h->image_size;
         sa.flags = flags & 0xFFu;
-        dad3d_status st = launch_flame_decode_split(sa, choice, s);
-        if (st) return st;
-        if (h->profiling) ++h->prof_launches;
-        return DAD3D_OK;
-    }
-    if (pipe_covers && choice != DAD3D_KERNEL_TWO_ROLE) {
+        st = launch_flame_decode_split(sa, kernel, s);
+    } else if (kernel == DAD3D_KERNEL_PIPELINED) {
         DAD3D_REQUIRE(!h->d_trace || h->trace_capacity >= trace_entries_pipe(h), "dad3d_flame_decode: the trace buffer holds %llu entries, "
                       "this launch stamps %llu (dad3d_flame_debug_trace_entries)", (unsigned long long)h->trace_capacity,
                       (unsigned long long)trace_entries_pipe(h));
         PipeArgs pa{};
         pa.params = params;
-        pa.bpack = h->c->d_bpack_pipe;
-        pa.vtab = h->d_vtab;
-        pa.lmk_next = h->d_lmk_next;
+        pa.bpack = c->d_bpack_pipe;
+        pa.vtab = vtab;
+        pa.lmk_next = L.d_next;
         pa.verts3d = verts3d;
         pa.proj = proj;
         pa.lmk_xy = lmk_xy;
@@ -777,78 +624,74 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
         pa.n_params = h->lay.n_params;
         pa.batch = batch;
         pa.n_half = (batch + kPipeHalf - 1) / kPipeHalf;
-        pa.n_tiles = h->c->n_tiles_pipe;
-        pa.n_verts = h->n_verts;
-        pa.n_lmk = (lmk_xy || lmk_px) ? h->n_lmk : 0;
+        pa.n_tiles = c->n_tiles_pipe;
+        pa.n_verts = n_verts;
+        pa.n_lmk = n_lmk;
         pa.image_size = h->image_size;
         pa.flags = flags & 0xFFu;
         pa.n_chunks = 1;
         if (!h->d_trace && (!proj || (flags & DAD3D_TO_2D))) pipe_chunking(pa.n_tiles, pa.n_half, &pa.chunk_half, &pa.n_chunks, &pa.wg_per_xcd);
-        dad3d_status st = launch_flame_decode_pipe(pa, s);
-        if (st) return st;
-        if (h->profiling) ++h->prof_launches;
-        return DAD3D_OK;
-    }
-    DAD3D_REQUIRE(!h->d_trace || h->trace_capacity >= trace_entries_two_role(h, batch), "dad3d_flame_decode: the trace buffer holds %llu "
-                  "entries, this launch stamps %llu (dad3d_flame_debug_trace_entries)", (unsigned long long)h->trace_capacity,
-                  (unsigned long long)trace_entries_two_role(h, batch));
-    const int nbb = (batch + kBlockImages - 1) / kBlockImages;
-    if (nbb > h->cap_nbb) {
-        DAD3D_HIP_TRY(hipDeviceSynchronize());
-        dad3d_status st = flame_reserve(h, nbb);
-        // a two-role sub-model grows with its parent: a landmark-only launch captured into a graph after a full-output warm-up of the
-        // same batch must not find its scratch too small (it could not allocate there)
-        if (!st && h->lmk_sub && h->lmk_sub->kernel_choice == DAD3D_KERNEL_TWO_ROLE && nbb > h->lmk_sub->cap_nbb) st = flame_reserve(h->lmk_sub, nbb);
-        if (st) return st;
-    }
-    DecodeArgs da{};
-    da.params = params;
-    da.bpack = h->c->d_bpack;
-    da.jdirs = h->c->d_jdirs;
-    da.j0 = h->c->d_j0;
-    da.weights8 = h->c->d_w8;
-    da.lmk_head = h->d_lmk_head;
-    da.lmk_next = h->d_lmk_next;
-    da.imgc = h->d_imgc;
-    da.sync = h->d_sync;
-    da.verts3d = verts3d;
-    da.proj = proj;
-    da.lmk_xy = lmk_xy;
-    da.lmk_px = lmk_px;
-    da.posed = posed;
-    da.trace = h->d_trace;
-    da.lay = h->lay;
-    std::copy(h->parents, h->parents + kNumJoints, da.parents);
-    da.batch = batch;
-    da.nbb = nbb;
-    da.n_tiles = h->n_tiles;
-    da.n_tiles_pad8 = h->n_tiles_pad8;
-    da.n_verts = h->n_verts;
-    da.n_lmk = (lmk_xy || lmk_px) ? h->n_lmk : 0;
-    da.n_pose_blocks = (batch + 3) / 4;  // one wave per image, four per workgroup
-    da.n_pose_blocks_pad8 = (da.n_pose_blocks + 7) / 8 * 8;
-    da.n_betas = h->n_betas;
-    da.max_shape = h->max_shape;
-    da.betas_contiguous = (h->lay.shape_n == 300 && h->lay.expr_n == 100 && h->lay.shape_off == 0 && h->lay.expr_off == 300);
-    da.kgroups = h->kgroups;
-    // a launch that is being captured into a graph cannot carry a per-launch target: the epoch then lives on the device
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (s != nullptr) (void)hipStreamIsCapturing(s, &capture);
-    const bool device_epoch = capture != hipStreamCaptureStatusNone;
-    da.arrive_target = h->arrive_total + (unsigned)da.n_pose_blocks;  // every pose workgroup arrives once per launch
-    da.spin_limit = 1u << 20;
+        st = launch_flame_decode_pipe(pa, s);
+    } else {
+        DAD3D_REQUIRE(!h->d_trace || h->trace_capacity >= trace_entries_two_role(h, batch), "dad3d_flame_decode: the trace buffer holds %llu "
+                      "entries, this launch stamps %llu (dad3d_flame_debug_trace_entries)", (unsigned long long)h->trace_capacity,
+                      (unsigned long long)trace_entries_two_role(h, batch));
+        // A training forward: what its backward pass needs exists before any of it can be captured into a graph -- for the batches
+        // the host mirror sends to dad3d_flame_grad_inputs (up to DAD3D_GRAD_INPUTS_MAX_BATCH; above it takes the library GEMM and
+        // the split-K scratch, tens to hundreds of MB, would never be used) and for models the kernel covers (otherwise the
+        // forward must not fail for a backward path that will not be taken: dad3d_flame_grad_inputs reports it when called).
+        if (posed && batch <= DAD3D_GRAD_INPUTS_MAX_BATCH && h->n_betas + 36 <= kGradRows && (st = grad_inputs_prepare(h, batch, s))) return st;
+        const int nbb = (batch + kBlockImages - 1) / kBlockImages;
+        if (nbb > h->cap_nbb) {
+            DAD3D_HIP_TRY(hipDeviceSynchronize());
+            if ((st = flame_reserve(h, nbb))) return st;
+        }
+        DecodeArgs da{};
+        da.params = params;
+        da.bpack = h->c->d_bpack;
+        da.jdirs = h->c->d_jdirs;
+        da.j0 = h->c->d_j0;
+        da.weights8 = h->c->d_w8;
+        da.lmk_head = L.d_head;
+        da.lmk_next = L.d_next;
+        da.imgc = h->d_imgc;
+        da.sync = h->d_sync;
+        da.verts3d = verts3d;
+        da.proj = proj;
+        da.lmk_xy = lmk_xy;
+        da.lmk_px = lmk_px;
+        da.posed = posed;
+        da.trace = h->d_trace;
+        da.lay = h->lay;
+        std::copy(h->parents, h->parents + kNumJoints, da.parents);
+        da.batch = batch;
+        da.nbb = nbb;
+        da.n_tiles = h->n_tiles;
+        da.n_tiles_pad8 = h->n_tiles_pad8;
+        da.n_verts = h->n_verts;
+        da.n_lmk = n_lmk;
+        da.n_pose_blocks = (batch + 3) / 4;  // one wave per image, four per workgroup
+        da.n_pose_blocks_pad8 = (da.n_pose_blocks + 7) / 8 * 8;
+        da.n_betas = h->n_betas;
+        da.max_shape = h->max_shape;
+        da.betas_contiguous = (h->lay.shape_n == 300 && h->lay.expr_n == 100 && h->lay.shape_off == 0 && h->lay.expr_off == 300);
+        da.kgroups = h->kgroups;
+        // a launch that is being captured into a graph cannot carry a per-launch target: the epoch then lives on the device
+        hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+        if (s != nullptr) (void)hipStreamIsCapturing(s, &capture);
+        const bool device_epoch = capture != hipStreamCaptureStatusNone;
+        da.arrive_target = h->arrive_total + (unsigned)da.n_pose_blocks;  // every pose workgroup arrives once per launch
+        da.spin_limit = 1u << 20;
 #ifdef DAD3D_DIAG_SPIN_ENV  // diagnostics builds only (tools/build_variant.sh): hand-off spin limit from the environment
-    if (const char* e = getenv("DAD3D_SPIN_LIMIT")) da.spin_limit = (unsigned)atoi(e);
+        if (const char* e = getenv("DAD3D_SPIN_LIMIT")) da.spin_limit = (unsigned)atoi(e);
 #endif
-    da.image_size = h->image_size;
-    da.flags = (flags & 0xFFu) | (device_epoch ? kDeviceEpoch : 0u);
-    dad3d_status st;
-
-    st = launch_flame_decode(da, s);
-    if (st) return st;
-    if (!device_epoch) h->arrive_total = da.arrive_target;  // committed only once the launch was accepted
-    if (h->profiling) ++h->prof_launches;
-    return DAD3D_OK;
+        da.image_size = h->image_size;
+        da.flags = (flags & 0xFFu) | (device_epoch ? kDeviceEpoch : 0u);
+        st = launch_flame_decode(da, s);
+        if (!st && !device_epoch) h->arrive_total = da.arrive_target;  // committed only once the launch was accepted
+    }
+    if (!st && h->profiling) ++h->prof_launches;
+    return st;
 }
 
 dad3d_status dad3d_flame_decode(dad3d_flame* h, float* params, int batch, unsigned flags, float* verts3d, float* proj,
@@ -868,7 +711,7 @@ dad3d_status dad3d_flame_decode_host(dad3d_flame* h, float* params, int batch, u
     if (batch == 0) return DAD3D_OK;
     DAD3D_REQUIRE(params, "dad3d_flame_decode_host: null params");
     DeviceGuard guard(h->device);
-    const size_t B = batch, V = h->n_verts, P = h->lay.n_params, NL = h->n_lmk;
+    const size_t B = batch, V = h->n_verts, P = h->lay.n_params, NL = h->lmk->n;
     const size_t pc = (flags & DAD3D_TO_2D) ? 2 : 3;
     const size_t n_par = B * P, n_v = verts3d ? B * V * 3 : 0, n_p = proj ? B * V * pc : 0;
     const size_t n_lx = lmk_xy ? B * NL * 2 : 0, n_lp = lmk_px ? B * NL * 2 : 0;
@@ -919,11 +762,6 @@ dad3d_status dad3d_flame_handoff_timeouts(dad3d_flame* h, unsigned* count) {
     DeviceGuard guard(h->device);
     DAD3D_HIP_TRY(hipDeviceSynchronize());
     DAD3D_HIP_TRY(hipMemcpy(count, h->d_sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (h->lmk_sub) {  // landmark-only launches of a model the pipelined kernel does not cover run the two-role kernel there
-        unsigned sub = 0;
-        DAD3D_HIP_TRY(hipMemcpy(&sub, h->lmk_sub->d_sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-        *count += sub;
-    }
     return DAD3D_OK;
 }
 

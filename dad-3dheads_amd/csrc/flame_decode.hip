@@ -34,14 +34,10 @@
 #ifndef DAD3D_ABLATE  // diagnostics builds only (tools/ablate.sh); 0 in the product
 #define DAD3D_ABLATE 0
 #endif
-#ifndef DAD3D_MFMA32  // 1: the four multiplying waves tile the 64 x 64 block 2 x 2 with v_mfma_f32_32x32x2_f32 (half the MFMA
-#define DAD3D_MFMA32 0  // issues and half the A-fragment reads per MAC); needs the matching basis pack of capi.cpp
-#endif
 
 namespace dad3d {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));  // 16 B load from a 4-byte aligned row
@@ -339,9 +335,9 @@ __device__ void image_constants(const DecodeArgs& a, const float* p, float* dst,
 template <int KG>
 struct DecodeLds {
     static constexpr int K = KG * 16;
-    // row stride: ds_read_b128 of the A operand conflict-free (16x16x4: lanes (row i, k 4q); 32x32x2: lanes (row i, k 8h):
-    // the 16 lanes the LDS serves together hold 16 different rows, so LD / 4 must be odd)
-    static constexpr int LD = DAD3D_MFMA32 ? ((KG == 26) ? 420 : 452) : ((KG == 26) ? 424 : 456);
+    // row stride: ds_read_b128 of the A operand conflict-free (16x16x4: lanes (row i, k 4q): the 16 lanes the LDS serves together
+    // hold 16 different rows, so LD / 4 must be odd)
+    static constexpr int LD = (KG == 26) ? 424 : 456;
     static constexpr int a_off = 0;                    // [64 images][LD]
     static constexpr int imgc_off = kBlockImages * LD;                   // [64][kImgConsts]
     static constexpr int vc_off = imgc_off + kBlockImages * kImgConsts;  // [21][8] skinning weights
@@ -583,54 +579,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_kernel(DecodeArgs a) {
         if (lane == 0) __hip_atomic_fetch_add(part_ready + p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
 
-    if (wave < 4 && DAD3D_MFMA32 && RB == 4) {
-        // =============================== mma waves, 32x32x2 tiling ==============================
-        // wave = (row half wr, column half wc): images [32 wr, 32 wr + 32) x columns [32 wc, 32 wc + 32), ONE 32x32
-        // accumulator. MFMA step (G, s), s = 0..7: lane (h = lane >> 5, i = lane & 31) contributes basis row
-        // k = 16 G + 8 h + s: its A operands of a group are the two float4 at a_lds[32 wr + i][16 G + 8 h], its B operands
-        // the two float4 the host packed for (G, wc, lane). 208 MFMAs of 64 cycles instead of 416 of 32, two ds_read_b128
-        // per eight MFMAs instead of four per sixteen.
-        const int wc = wave & 1, wr = wave >> 1;
-        const float4* bsrc = reinterpret_cast<const float4*>(a.bpack) + ((size_t)tile * KG * 2 + wc) * 128 + lane * 2;
-        constexpr int kBAhead = 6;
-        float4 bq0[KG], bq1[KG];
-#pragma unroll
-        for (int G = 0; G < kBAhead && G < KG; ++G) bq0[G] = bsrc[(size_t)G * 256], bq1[G] = bsrc[(size_t)G * 256 + 1];
-        f32x16 acc32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc32[r] = 0.0f;
-        const float* afrag = a_lds + (32 * wr + (lane & 31)) * LD + 8 * (lane >> 5);
-        float4 af0, af1, an0 = {}, an1 = {};
-        stamp(1);
-        wait_part(0);
-        stamp(2);
-        af0 = *reinterpret_cast<const float4*>(afrag), af1 = *reinterpret_cast<const float4*>(afrag + 4);
-#pragma unroll
-        for (int G = 0; G < KG; ++G) {
-            if (G + 1 == PT::begin(1) || G + 1 == PT::begin(2)) wait_part(G + 1 == PT::begin(1) ? 1 : 2);
-            if (G + 1 < KG) {
-                an0 = *reinterpret_cast<const float4*>(afrag + 16 * (G + 1));
-                an1 = *reinterpret_cast<const float4*>(afrag + 16 * (G + 1) + 4);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int sst = 0; sst < 8; ++sst) {
-                const float4 aq = sst < 4 ? af0 : af1, bb4 = sst < 4 ? bq0[G] : bq1[G];
-                const int e = sst & 3;
-                const float av = e == 0 ? aq.x : e == 1 ? aq.y : e == 2 ? aq.z : aq.w;
-                const float bv = e == 0 ? bb4.x : e == 1 ? bb4.y : e == 2 ? bb4.z : bb4.w;
-                acc32 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc32, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            af0 = an0, af1 = an1;
-            if (G + kBAhead < KG) bq0[G + kBAhead] = bsrc[(size_t)(G + kBAhead) * 256], bq1[G + kBAhead] = bsrc[(size_t)(G + kBAhead) * 256 + 1];
-        }
-        stamp(3);
-        // D layout of the 32x32 accumulator: register r of lane (h, i) = row 8 (r / 4) + 4 h + r % 4, column i
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            otile[(32 * wr + 8 * (r / 4) + 4 * (lane >> 5) + (r & 3)) * kOutStride + 32 * wc + (lane & 31)] = acc32[r];
-    } else if (wave < 4) {
+    if (wave < 4) {
         // =============================== mma waves ===============================================
         // acc[m] = images [16m,16m+16) x columns [16*wave,16*wave+16). MFMA step (G, s): lane group
         // q = lane>>4 contributes basis row k = 16G + 4q + s, so the A operand of lane (q, i) for s = 0..3 is
@@ -1014,14 +963,6 @@ static dad3d_status launch_decode_t(const DecodeArgs& a, hipStream_t s) {
 }
 
 dad3d_status launch_flame_decode(const DecodeArgs& a, hipStream_t s) {
-#if DAD3D_MFMA32
-    // diagnostics variant: capi.cpp packs the basis for the 32x32x2 tiling ONLY; the quarter-size instantiation (<= 16 images), the
-    // training forward and the backward pass's basis^T pack all read the 16x16x4 layout
-    if (a.posed || a.batch <= 16) {
-        set_error("DAD3D_MFMA32 build: only inference launches of more than 16 images");
-        return DAD3D_E_UNSUPPORTED;
-    }
-#endif
     switch (a.kgroups) {
         case 26:  // K = 400 + 9 (jaw only) + 1 -> 416
             return a.betas_contiguous ? launch_decode_t<26, true, true>(a, s) : launch_decode_t<26, true, false>(a, s);

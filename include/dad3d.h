@@ -90,9 +90,10 @@ DAD3D_EXPORT dad3d_status dad3d_flame_create(const dad3d_flame_model* model, con
                                 int device, dad3d_flame** out);
 DAD3D_EXPORT void dad3d_flame_destroy(dad3d_flame* h);
 /* A second handle on the same device that SHARES the model constants of `parent` (26 MB, reference counted: either may
- * be destroyed first) and owns its hand-off buffers and landmark list (copied from the parent's current one). A handle
- * serves one stream at a time -- its pose-role -> decode-role hand-off block is per handle -- so a serving loop that
- * keeps several batches in flight uses one fork per stream (bench.py does, with two). */
+ * be destroyed first) and its current landmark list (until either handle calls dad3d_flame_set_landmarks, which changes that
+ * handle's list only), and owns its hand-off buffers and scratch. A handle serves one stream at a time -- its pose-role ->
+ * decode-role hand-off block and its split-kernel scratch, which landmark-only launches use too, are per handle -- so a serving
+ * loop that keeps several batches in flight uses one fork per stream (bench.py does, with two). */
 DAD3D_EXPORT dad3d_status dad3d_flame_fork(dad3d_flame* parent, dad3d_flame** out);
 
 /* Number of floats per params row (sum of the consts; 413 for dad_3dnet.yaml). */
@@ -104,12 +105,14 @@ DAD3D_EXPORT int dad3d_flame_num_verts(const dad3d_flame* h);
 DAD3D_EXPORT dad3d_status dad3d_flame_set_landmarks(dad3d_flame* h, const int64_t* indices, int n);
 DAD3D_EXPORT int dad3d_flame_num_landmarks(const dad3d_flame* h);
 /* Landmark-only launches (every vertex output NULL, a landmark output given -- BASELINE configs[3]'s per-GPU work, the landmark-only fast
- * path of SURVEY 7.1) run on the SUB-MODEL of the distinct vertices the list names, built by dad3d_flame_set_landmarks: 445 of 5023 vertices
- * = 23 column tiles instead of 252, with the batch cut into chunks across workgroups so that the launch still fills the GPU. Same kernel,
- * same basis values in the same order: lmk_xy / lmk_px of such a launch are BIT-IDENTICAL to those of a full-output launch of the same
- * handle, at every batch size (tests/test_gpu_landmark_subset.py). This returns the number of vertices of that sub-model, 0 when there is
- * none (empty list, a list naming more than a third of the mesh, DAD3D_LANDMARK_SUBSET=0). A handle pinned with
- * dad3d_flame_select_kernel(TWO_ROLE / PIPELINED) or tracing decodes the whole mesh for such a launch like for any other. */
+ * path of SURVEY 7.1) on the pipelined or a split kernel run on the SUB-MODEL of the distinct vertices the list names, built by
+ * dad3d_flame_set_landmarks: 445 of 5023 vertices = 23 column tiles instead of 252, with the batch cut into chunks across workgroups so that
+ * the launch still fills the GPU. Same kernel, same basis values in the same order: lmk_xy / lmk_px of such a launch are BIT-IDENTICAL to
+ * those of a full-output launch of the same handle, at every batch size (tests/test_gpu_landmark_subset.py). This returns the number of
+ * vertices of that sub-model, 0 when there is none (empty list, a list naming more than a third of the mesh, a model the pipelined kernel
+ * does not cover, DAD3D_LANDMARK_SUBSET=0). A launch that takes the two-role kernel (DAD3D_ZERO_ROTATION, outputs of the whole mesh past
+ * 2 GB, an uncovered model), a handle pinned with dad3d_flame_select_kernel(TWO_ROLE / PIPELINED) and a tracing handle decode the whole
+ * mesh for such a launch like for any other. */
 DAD3D_EXPORT int dad3d_flame_num_landmark_vertices(const dad3d_flame* h);
 
 /* One fused decode of B parameter rows. Any output pointer may be NULL (not produced).

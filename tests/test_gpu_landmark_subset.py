@@ -1,4 +1,4 @@
-"""GPU: landmark-only launches run on the sub-model of the listed vertices (csrc/capi.cpp: build_landmark_subset; SURVEY 7.1's
+"""GPU: landmark-only launches run on the sub-model of the listed vertices (csrc/capi.cpp: build_landmark_sub; SURVEY 7.1's
 landmark-only fast path, BASELINE configs[3]'s per-GPU work) -- on the SAME kernel a full-output launch of the handle takes, with the
 batch cut into chunks across workgroups. Held to: the landmark rows of a full-output launch of the same handle -- bit for bit, at every
 batch size --, a whole-mesh launch of a pinned handle (same kernel, no sub-model) -- bit for bit --, the two-role kernel to fp32
@@ -68,12 +68,41 @@ def test_landmark_only_launch_against_the_two_role_kernel(flame_model, static, b
     assert bool(((d == 0) | ((d == 1) & (frac < TOL_PX))).all())
 
 
+def test_landmark_only_launch_past_the_pipelined_output_limit_is_the_two_role_launch(flame_model, static):
+    """35 700 rows: the whole mesh's outputs would pass 2 GB, so the handle resolves to the two-role kernel -- and its landmark-only launch
+    decodes the whole mesh there too, the bits of a handle pinned to that kernel."""
+    idx = landmarks.canonical("445", static)
+    auto, two = _pair(flame_model, static, idx, pin="two_role")
+    params = synthetic.synthetic_params(35700, seed=8170)
+    a = auto.decode(torch.from_numpy(params.copy()).cuda(), verts3d=False, proj=False, landmarks=True, landmarks_px=True)
+    t = two.decode(torch.from_numpy(params.copy()).cuda(), verts3d=False, proj=False, landmarks=True, landmarks_px=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a["lmk_xy"], t["lmk_xy"]) and torch.equal(a["lmk_px"], t["lmk_px"])
+
+
+def test_model_the_pipelined_kernel_does_not_cover_has_no_sub_model(flame_model, static):
+    """Neck + eyeball poses (test_gpu_decode.py::test_full_pose_config_neck_and_eyeballs): the two-role kernel, whole mesh, for every launch
+    -- the landmark-only one returns the landmark rows of the full-output one bit for bit."""
+    consts = {"shape": 300, "expression": 100, "jaw": 3, "rotation": 6, "eyeballs": 6, "neck": 3, "translation": 3, "scale": 1}
+    idx = landmarks.canonical("445", static)
+    hm = HeadMesh(flame_config=consts, flame_model=flame_model, landmarks=idx, static=static, device=0)
+    assert _n_sub(hm) == 0
+    base = synthetic.synthetic_params(70, seed=8180)
+    rng = np.random.default_rng(8180)
+    p = np.concatenate([base[:, :409], 0.2 * rng.standard_normal((70, 9)).astype(np.float32), base[:, 409:]], axis=1)
+    whole = hm.decode(torch.from_numpy(p.copy()).cuda(), landmarks=True, landmarks_px=True)
+    only = hm.decode(torch.from_numpy(p.copy()).cuda(), verts3d=False, proj=False, landmarks=True, landmarks_px=True)
+    torch.cuda.synchronize()
+    assert torch.equal(whole["lmk_xy"], whole["proj"][:, torch.from_numpy(idx).cuda()])
+    assert torch.equal(only["lmk_xy"], whole["lmk_xy"]) and torch.equal(only["lmk_px"], whole["lmk_px"])
+
+
 def test_subset_follows_the_list_forks_and_pins(flame_model, static):
     idx = landmarks.canonical("445", static)
     hm = HeadMesh(flame_model=flame_model, landmarks=idx, static=static, device=0)
     p = torch.from_numpy(synthetic.synthetic_params(70, seed=8200)).cuda()
     first = hm.decode(p.clone(), verts3d=False, proj=False, landmarks=True)["lmk_xy"].clone()
-    twin = hm.fork()  # shares the sub-model's constants, owns its lists and hand-off buffers
+    twin = hm.fork()  # shares the landmark list and its sub-model until either installs another, owns its hand-off buffers
     assert _n_sub(twin) == _n_sub(hm) == len(np.unique(idx))
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -107,20 +136,22 @@ def test_full_output_launches_are_untouched_and_agree_with_the_landmark_only_one
     assert torch.equal(only["lmk_xy"], whole["lmk_xy"]) and torch.equal(only["lmk_px"], whole["lmk_px"])  # one arithmetic
 
 
-def test_landmark_only_launch_is_capturable_after_a_full_output_warm_up(flame_model, static):
-    """the sub-model needs no scratch on the pipelined kernel, so a graph may capture a landmark-only launch whose warm-up
-    was a full-output launch of the same batch."""
+@pytest.mark.parametrize("zero_rotation", [False, True])
+def test_landmark_only_launch_is_capturable_after_a_full_output_warm_up(flame_model, static, zero_rotation):
+    """a graph may capture a landmark-only launch whose warm-up was a full-output launch of the same batch -- the sub-model
+    needs no scratch on the pipelined kernel, and with DAD3D_ZERO_ROTATION both launches take the two-role kernel on the whole mesh, whose
+    scratch the warm-up grew."""
     idx = landmarks.canonical("445", static)
     hm = HeadMesh(flame_model=flame_model, landmarks=idx, static=static, device=0)
     p = torch.from_numpy(synthetic.synthetic_params(192, seed=8400)).cuda()
-    want = hm.decode(p.clone(), landmarks=True)["lmk_xy"].clone()  # warm-up: every output
+    want = hm.decode(p.clone(), landmarks=True, zero_rotation=zero_rotation)["lmk_xy"].clone()  # warm-up: every output
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
     static_in = p.clone()
     with torch.cuda.stream(s):
         with torch.cuda.graph(g, stream=s):
-            out = hm.decode(static_in, verts3d=False, proj=False, landmarks=True)
+            out = hm.decode(static_in, verts3d=False, proj=False, landmarks=True, zero_rotation=zero_rotation)
     g.replay()
     torch.cuda.synchronize()
     assert torch.equal(out["lmk_xy"], want)
