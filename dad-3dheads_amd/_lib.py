@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("DAD3D_LIB_PATH") or os.path.join(_HERE, "libdad3d_hip
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = range(5)
 ZERO_ROTATION, TO_2D, MUTATE_PARAMS, FLIP_Z, COMPAT_CROSS_B3 = 0x1, 0x2, 0x4, 0x8, 0x10
 NORMAL_ACCUMULATE = 0x1
+EVAL_SELF_EXCLUDE, EVAL_MAX_K, EVAL_MAX_HEAD, EVAL_MAX_ANCHORS = 0x1, 8, 4096, 8
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -107,6 +108,8 @@ SIGNATURES = {
     "dad3d_cube_region_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "dad3d_point_loss_terms": (_I, [_I]),
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),
+    "dad3d_eval_nearest": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "dad3d_eval_z5_ranks": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _I, _P]),
     "dad3d_sim3dr_get_tri_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_ver_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_normal": (None, [_P, _P, _P, _I, _I]),

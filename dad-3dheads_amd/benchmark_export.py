@@ -5,8 +5,8 @@ A submission is one JSON object `{item_id: {"68_landmarks_2d": [[x, y]] * 68, "N
 are points ON the mesh: barycentric combinations of the corners of 68 fixed faces -- 17 contour points (row 0 of the
 "dynamic" table: the reference always evaluates it at a zero pose) followed by 51 static points
 (`get_68_landmarks`, dad_3dheads_benchmark/utils.py:29-117 == model_training/data/utils.py:120-206); the 7 alignment
-landmarks are rows 36, 39, 42, 45, 33, 48, 54 of them (utils.py:143-151). Batched and device-resident here; the evaluation
-itself (chamfer distance, Procrustes, kaolin) is out of scope.
+landmarks are rows 36, 39, 42, 45, 33, 48, 54 of them (utils.py:143-151). Batched and device-resident here; the scoring side
+(pose error, NME, Z5, Chamfer after Procrustes) is `evaluation.py`.
 """
 from __future__ import annotations
 

@@ -1243,6 +1243,43 @@ dad3d_status dad3d_weighted_point_loss(const float* pred, const float* target, i
     return launch_point_loss(a, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_eval_nearest(const float* query, const float* points, const int32_t* counts, const float* similarity,
+                                int batch, int n_query, int n_points, int k, int flags, float* min_dist2, int32_t* knn_index,
+                                float* knn_dist2, int device, void* stream) {
+    DAD3D_REQUIRE(batch > 0 && n_query > 0 && n_points > 0, "dad3d_eval_nearest: sizes must be positive (B %d, Q %d, N %d)", batch,
+                  n_query, n_points);
+    DAD3D_REQUIRE(k >= 1 && k <= kEvalMaxK, "dad3d_eval_nearest: k = %d outside 1..%d", k, kEvalMaxK);
+    DAD3D_REQUIRE((flags & ~DAD3D_EVAL_SELF_EXCLUDE) == 0, "dad3d_eval_nearest: unknown flags 0x%x", flags);
+    DAD3D_REQUIRE(query && points && min_dist2, "dad3d_eval_nearest: null argument");
+    DAD3D_REQUIRE(batch <= 65535, "dad3d_eval_nearest: batch beyond the launch grid");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    EvalNearestArgs a{query, points, counts, similarity, min_dist2, knn_index, knn_dist2, batch, n_query, n_points, k,
+                      (flags & DAD3D_EVAL_SELF_EXCLUDE) ? 1 : 0};
+    return launch_eval_nearest(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_eval_z5_ranks(const float* gt_head, const float* pred_head, int batch, int n_head, const int32_t* anchors,
+                                 int n_anchors, int32_t* counts, int32_t* order, int device, void* stream) {
+    DAD3D_REQUIRE(batch > 0 && n_head > 0, "dad3d_eval_z5_ranks: sizes must be positive (B %d, K %d)", batch, n_head);
+    DAD3D_REQUIRE(n_head <= kEvalMaxHead, "dad3d_eval_z5_ranks: K = %d head vertices exceed the %d the LDS sort holds", n_head,
+                  kEvalMaxHead);
+    DAD3D_REQUIRE(n_anchors >= 1 && n_anchors <= kEvalMaxAnchors, "dad3d_eval_z5_ranks: %d anchors outside 1..%d", n_anchors,
+                  kEvalMaxAnchors);
+    DAD3D_REQUIRE(gt_head && pred_head && anchors && counts, "dad3d_eval_z5_ranks: null argument");
+    DAD3D_REQUIRE(batch <= 65535, "dad3d_eval_z5_ranks: batch beyond the launch grid");
+    EvalZ5Args a{gt_head, pred_head, counts, order, {}, batch, n_head, 1, n_anchors};
+    for (int i = 0; i < n_anchors; ++i) {
+        DAD3D_REQUIRE(anchors[i] >= 0 && anchors[i] < n_head, "dad3d_eval_z5_ranks: anchor %d = %d outside 0..%d", i, anchors[i],
+                      n_head - 1);
+        a.anchors[i] = anchors[i];
+    }
+    while (a.sort_len < n_head) a.sort_len <<= 1;
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    return launch_eval_z5(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_mesh_debug_trace(dad3d_mesh* m, unsigned long long* device_buffer) {
     DAD3D_REQUIRE(m, "null handle");
     m->d_trace = device_buffer;

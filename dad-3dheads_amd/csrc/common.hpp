@@ -337,6 +337,31 @@ int point_loss_blocks(int n_points);
 dad3d_status launch_cube_loss(const CubeLossArgs& a, hipStream_t s);
 dad3d_status launch_point_loss(const PointLossArgs& a, hipStream_t s);
 
+// the benchmark scorer's point-set steps (mesh_eval.hip)
+constexpr int kEvalMaxK = 8;        // nearest neighbours kept per query
+constexpr int kEvalMaxHead = 4096;  // head-subset size the Z5 sort holds in LDS (8-byte keys: 32 KB)
+constexpr int kEvalMaxAnchors = 8;
+struct EvalNearestArgs {
+    const float* query;       // [B,Q,3]
+    const float* points;      // [B,N,3]; rows of item b past counts[b] are never read
+    const int* counts;        // [B] or null (every item has N points)
+    const float* similarity;  // [B][13] = s, R (3x3 row-major), t: p' = s * p . R + t; or null (identity)
+    float* min_dist2;         // [B,Q]
+    int* knn_index;           // [B,Q,k] or null; -1 where fewer than k points exist
+    float* knn_dist2;         // [B,Q,k] or null; +inf there
+    int batch, n_query, n_points, k, self_exclude;
+};
+struct EvalZ5Args {
+    const float* gt_head;    // [B,K,3] (the GT head subset, already negated as the scorer does)
+    const float* pred_head;  // [B,K,3]
+    int* counts;             // [B][n_anchors]
+    int* order;              // [B][n_anchors][K] or null
+    int anchors[kEvalMaxAnchors];
+    int batch, n_head, sort_len, n_anchors;
+};
+dad3d_status launch_eval_nearest(const EvalNearestArgs& a, hipStream_t s);
+dad3d_status launch_eval_z5(const EvalZ5Args& a, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -349,6 +349,37 @@ DAD3D_EXPORT dad3d_status dad3d_weighted_point_loss(const float* pred, const flo
                                        float* grad_pred, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The DAD-3DHeads benchmark scorer's two dense point-set steps (dad_3dheads_benchmark/benchmark.py `DADEvaluator`, utils.py).
+ * All pointers are DEVICE pointers unless noted; nothing is allocated, both calls can be captured into a graph. Distances are
+ * squared, fp32, in the direct-difference form (qx-px)^2 + (qy-py)^2 + (qz-pz)^2 (no |q|^2 + |p|^2 - 2 q.p expansion).
+ * Sizes are validated before any device work: B, Q, N, K <= 0, k outside 1..8, K > 4096 or a NULL pointer -> DAD3D_E_INVALID.
+ *
+ * dad3d_eval_nearest  one-sided nearest neighbours (utils.py:119-133 `calc_ch_dist`: kaolin's `chamfer_distance(gt, pred,
+ *   1.0, 0.0)` = mean over the GT points of min_dist2, its alignment loop utils.py:154-171 `align_pred_to_gt` fused):
+ *     query [B,Q,3]; points [B,N,3]; counts [B] int32 or NULL: item b uses points[b, :counts[b]] (clamped to 0..N)
+ *     similarity [B][13] = (s, R row-major 3x3, t) or NULL: every point is mapped to s * p . R + t (row vector) first
+ *     flags: DAD3D_EVAL_SELF_EXCLUDE = query and points are the same set in the same order: point q is not a neighbour of
+ *            query q
+ *     min_dist2 [B,Q] (required); knn_index [B,Q,k] int32, knn_dist2 [B,Q,k]: the k nearest in ascending distance, ties to
+ *     the lower index, -1 / +inf where fewer than k points exist (each optional, NULL)
+ * dad3d_eval_z5_ranks  benchmark.py:126-160 `calc_zn` / `zn` as the script computes it: for every anchor a (head-subset
+ *   positions, HOST array anchors[n_anchors], n_anchors <= 8), all K head vertices ordered by fp32 distance to gt_head[a]
+ *   (ties to the lower index, rank 0 included) = o_a, then
+ *     counts[b][a] = #{ i < K : (g_z[i] >= g_z[o_a[i]]) == (w_z[i] >= w_z[o_a[i]]) }
+ *     gt_head [B,K,3] (the GT world head subset TIMES -1, benchmark.py:155), pred_head [B,K,3], counts [B][n_anchors] int32,
+ *     order [B][n_anchors][K] int32 (o_a) or NULL
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_EVAL_SELF_EXCLUDE 0x1
+#define DAD3D_EVAL_MAX_K 8
+#define DAD3D_EVAL_MAX_HEAD 4096
+#define DAD3D_EVAL_MAX_ANCHORS 8
+DAD3D_EXPORT dad3d_status dad3d_eval_nearest(const float* query, const float* points, const int32_t* counts, const float* similarity,
+                                int batch, int n_query, int n_points, int k, int flags, float* min_dist2, int32_t* knn_index,
+                                float* knn_dist2, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_eval_z5_ranks(const float* gt_head, const float* pred_head, int batch, int n_head,
+                                 const int32_t* anchors, int n_anchors, int32_t* counts, int32_t* order, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
  * in one launch: LongestMaxSize (cv2.resize INTER_LINEAR, 8-bit fixed-point path) -> PadIfNeeded (centred, 0) -> Normalize
  * ((x - 255 mean) * (1 / (255 std)), float32) -> CHW. All DEVICE pointers:
