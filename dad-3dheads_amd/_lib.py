@@ -110,6 +110,11 @@ SIGNATURES = {
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),
     "dad3d_eval_nearest": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "dad3d_eval_z5_ranks": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _I, _P]),
+    "dad3d_uvmap_create": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, C.POINTER(_P)]),
+    "dad3d_uvmap_destroy": (None, [_P]),
+    "dad3d_uvmap_size": (_I, [_P]),
+    "dad3d_uvmap_vertex_normals": (_I, [_P, _P, _P, _I, _P]),
+    "dad3d_uvmap_bake": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dad3d_sim3dr_get_tri_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_ver_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_normal": (None, [_P, _P, _P, _I, _I]),

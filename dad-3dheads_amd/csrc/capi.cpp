@@ -1280,6 +1280,120 @@ dad3d_status dad3d_eval_z5_ranks(const float* gt_head, const float* pred_head, i
     return launch_eval_z5(a, static_cast<hipStream_t>(stream));
 }
 
+}  // extern "C"
+
+// =================================================================================================
+// UV-texture bake (uv_texture.hip)
+// =================================================================================================
+struct dad3d_uvmap {
+    int device = 0;
+    int nver = 0, size = 0, n_cand = 0;
+    int* d_adj_ptr = nullptr;  // vertex -> faces (UvNormalArgs)
+    int4* d_adj = nullptr;
+    int* d_texel_ptr = nullptr;  // texel -> candidates, descending (UvBakeArgs)
+    int* d_cand_verts = nullptr;
+    double* d_cand_bary = nullptr;
+};
+
+extern "C" {
+
+dad3d_status dad3d_uvmap_create(const int32_t* faces, int ntri, int nver, const int32_t* cand_texel, const int32_t* cand_verts,
+                                const double* cand_bary, int n, int img_size, int device, dad3d_uvmap** out) {
+    DAD3D_REQUIRE(out, "dad3d_uvmap_create: null output handle");
+    *out = nullptr;
+    DAD3D_REQUIRE(ntri >= 0 && nver >= 0 && n >= 0, "dad3d_uvmap_create: negative size (ntri %d, nver %d, n %d)", ntri, nver, n);
+    DAD3D_REQUIRE(img_size > 0 && img_size <= 46340, "dad3d_uvmap_create: texture size %d outside 1..46340", img_size);
+    DAD3D_REQUIRE((faces || ntri == 0) && ((cand_texel && cand_verts && cand_bary) || n == 0), "dad3d_uvmap_create: null argument");
+    for (size_t i = 0; i < 3 * (size_t)ntri; ++i)
+        DAD3D_REQUIRE(faces[i] >= 0 && faces[i] < nver, "dad3d_uvmap_create: face %zu names vertex %d outside [0,%d)", i / 3,
+                      faces[i], nver);
+    const int n_tex = img_size * img_size;
+    for (int i = 0; i < n; ++i) {
+        DAD3D_REQUIRE(cand_texel[i] >= 0 && cand_texel[i] < n_tex, "dad3d_uvmap_create: candidate %d on texel %d outside [0,%d)", i,
+                      cand_texel[i], n_tex);
+        for (int c = 0; c < 3; ++c)
+            DAD3D_REQUIRE(cand_verts[3 * (size_t)i + c] >= 0 && cand_verts[3 * (size_t)i + c] < nver,
+                          "dad3d_uvmap_create: candidate %d names vertex %d outside [0,%d)", i, cand_verts[3 * (size_t)i + c], nver);
+    }
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    // vertex -> faces in ascending face order, each face once with its multiplicity: the rows of psbody's faces_by_vertex
+    // CSR after scipy summed the duplicate (vertex, face) entries
+    std::vector<int> ptr(nver + 1, 0);
+    std::vector<int4> adj;
+    {
+        std::vector<std::vector<int4>> rows(nver);
+        for (int f = 0; f < ntri; ++f) {
+            const int* t = faces + 3 * (size_t)f;
+            for (int c = 0; c < 3; ++c) {
+                std::vector<int4>& r = rows[t[c]];
+                if ((c > 0 && t[c] == t[0]) || (c == 2 && t[c] == t[1])) {
+                    ++r.back().w;  // the same face names this vertex again
+                    continue;
+                }
+                r.push_back(make_int4(t[0], t[1], t[2], 1));
+            }
+        }
+        for (int v = 0; v < nver; ++v) ptr[v + 1] = ptr[v] + (int)rows[v].size();
+        adj.reserve(ptr[nver]);
+        for (int v = 0; v < nver; ++v) adj.insert(adj.end(), rows[v].begin(), rows[v].end());
+    }
+    // texel -> candidates, descending candidate index: the first that passes is the reference's last writer
+    std::vector<int> tptr(n_tex + 1, 0);
+    for (int i = 0; i < n; ++i) ++tptr[cand_texel[i] + 1];
+    for (int t = 0; t < n_tex; ++t) tptr[t + 1] += tptr[t];
+    std::vector<int> fill(tptr.begin(), tptr.end() - 1), verts(3 * (size_t)n);
+    std::vector<double> bary(3 * (size_t)n);
+    for (int i = n - 1; i >= 0; --i) {
+        const int j = fill[cand_texel[i]]++;
+        for (int c = 0; c < 3; ++c) verts[3 * (size_t)j + c] = cand_verts[3 * (size_t)i + c], bary[3 * (size_t)j + c] = cand_bary[3 * (size_t)i + c];
+    }
+    std::unique_ptr<dad3d_uvmap> m(new dad3d_uvmap);
+    m->device = device, m->nver = nver, m->size = img_size, m->n_cand = n;
+    dad3d_status st;
+    if ((st = upload(&m->d_adj_ptr, ptr)) || (st = upload(&m->d_adj, adj)) || (st = upload(&m->d_texel_ptr, tptr)) ||
+        (st = upload(&m->d_cand_verts, verts)) || (st = upload(&m->d_cand_bary, bary))) {
+        dad3d_uvmap_destroy(m.release());
+        return st;
+    }
+    *out = m.release();
+    return DAD3D_OK;
+}
+
+void dad3d_uvmap_destroy(dad3d_uvmap* m) {
+    if (!m) return;
+    DeviceGuard guard(m->device);
+    for (void* p : {(void*)m->d_adj_ptr, (void*)m->d_adj, (void*)m->d_texel_ptr, (void*)m->d_cand_verts, (void*)m->d_cand_bary})
+        if (p) (void)hipFree(p);
+    delete m;
+}
+
+int dad3d_uvmap_size(const dad3d_uvmap* m) { return m ? m->size : 0; }
+
+dad3d_status dad3d_uvmap_vertex_normals(dad3d_uvmap* m, double* normals, const float* vertices, int batch, void* stream) {
+    DAD3D_REQUIRE(m && batch >= 0, "dad3d_uvmap_vertex_normals: bad argument");
+    DAD3D_REQUIRE(batch <= 65535, "dad3d_uvmap_vertex_normals: batch beyond the launch grid");
+    if (batch == 0 || m->nver == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(normals && vertices, "dad3d_uvmap_vertex_normals: null argument");
+    DeviceGuard guard(m->device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", m->device);
+    UvNormalArgs a{m->d_adj_ptr, m->d_adj, vertices, normals, batch, m->nver};
+    return launch_uv_vertex_normals(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* vertices, const double* normals, const uint8_t* images,
+                              const int32_t* hw, int batch, int h, int w, void* stream) {
+    DAD3D_REQUIRE(m && batch >= 0 && h > 0 && w > 0, "dad3d_uvmap_bake: bad argument (batch %d, h %d, w %d)", batch, h, w);
+    DAD3D_REQUIRE(uv_bake_grid_y(batch, kUvBakeChunk) <= 65535, "dad3d_uvmap_bake: batch beyond the launch grid");
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(texture && images && ((vertices && normals) || m->n_cand == 0), "dad3d_uvmap_bake: null argument");
+    DeviceGuard guard(m->device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", m->device);
+    UvBakeArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, images, hw, texture,
+                 batch, m->nver, m->size, h, w, kUvBakeChunk};
+    return launch_uv_bake(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_mesh_debug_trace(dad3d_mesh* m, unsigned long long* device_buffer) {
     DAD3D_REQUIRE(m, "null handle");
     m->d_trace = device_buffer;

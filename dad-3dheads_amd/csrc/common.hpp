@@ -362,6 +362,30 @@ struct EvalZ5Args {
 dad3d_status launch_eval_nearest(const EvalNearestArgs& a, hipStream_t s);
 dad3d_status launch_eval_z5(const EvalZ5Args& a, hipStream_t s);
 
+// the reference demo's UV-texture bake (uv_texture.hip), float64 like its NumPy
+struct UvNormalArgs {
+    const int* adj_ptr;   // [V+1] CSR rows: the faces of a vertex, ascending face index, each face once
+    const int4* adj;      // [adj_ptr[V]] {corner 0, corner 1, corner 2, how often the face names the vertex}
+    const float* vertices;  // [B,V,3]
+    double* normals;        // [B,V,3]
+    int batch, n_verts;
+};
+struct UvBakeArgs {
+    const int* texel_ptr;     // [S*S+1] CSR rows: the candidates of a texel, DESCENDING candidate index
+    const int* cand_verts;    // [n,3] in texel-list order
+    const double* cand_bary;  // [n,3] in texel-list order
+    const float* vertices;    // [B,V,3]
+    const double* normals;    // [B,V,3]
+    const uint8_t* images;    // [B,h,w,3]
+    const int* hw;            // [B,2] per-item (height, width) inside the padded h x w, or null
+    uint8_t* texture;         // [B,S,S,3], every byte written
+    int batch, n_verts, size, h, w, chunk;
+};
+constexpr int kUvBakeChunk = 8;  // images per bake workgroup: the table is read once per chunk
+int uv_bake_grid_y(int batch, int chunk);
+dad3d_status launch_uv_vertex_normals(const UvNormalArgs& a, hipStream_t s);
+dad3d_status launch_uv_bake(const UvBakeArgs& a, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -121,3 +121,87 @@ def synthetic_params(batch: int, seed: int = 0, profile: str = "crop") -> np.nda
         raise ValueError(f"unknown profile {profile!r}")
     p[:, 411] = rng.standard_normal(batch)  # tz: zeroed by the path (head_mesh.py:41)
     return p.astype(np.float32)
+
+
+TEXTURE_DATA_KEYS = ("x_coords", "y_coords", "valid_pixel_ids", "valid_pixel_3d_faces", "valid_pixel_b_coords", "img_size")
+
+
+def _diamond_angle(x: np.ndarray, z: np.ndarray) -> np.ndarray:
+    """A monotonic stand-in for the angle of (x, z) about the vertical axis, in [0, 4), built from + - / alone (no
+    transcendental function: the atlas, and so its digest, is the same on every machine). Starts at +x, 1 at +z."""
+    ax, az = np.abs(x), np.abs(z)
+    d = np.where(ax + az == 0.0, 1.0, ax + az)
+    r = az / d
+    return np.where(z >= 0, np.where(x >= 0, r, 2.0 - r), np.where(x < 0, 2.0 + r, 4.0 - r)) % 4.0
+
+
+def synthetic_texture_data(img_size: int = 256, seed: int = 0, static: Optional[dict] = None, duplicates: int = 0) -> dict:
+    """Deterministic stand-in for the reference's `inference/texture_data.npy` (not redistributed), with its keys:
+
+        x_coords, y_coords      float64 [S*S]  column / row of every pixel id y*S + x (a meshgrid; the consumer truncates
+                                               them with astype(int))
+        valid_pixel_ids         int64 [n]      the pixel id of every candidate
+        valid_pixel_3d_faces    int64 [n,3]    the three vertex ids of the candidate's face
+        valid_pixel_b_coords    float64 [n,3]  its barycentrics in that face
+        img_size                int            S
+
+    The dtypes are an assumption (the real file is absent). The atlas: the template gets a cylindrical UV map (a rational
+    stand-in for the angle about the vertical axis, height), every face's UV triangle is rasterised into the S x S grid at the texel centres, and a
+    texel keeps the first face that covers it. Faces across the seam are left out. `duplicates = k` appends k further
+    candidates on texels already in use, each with another face and random barycentrics: the reference loop's last
+    writer then decides those texels."""
+    st = static if static is not None else load_static()
+    faces = st["faces"].astype(np.int64)
+    v = st["template_geo"].astype(np.float64)
+    s = int(img_size)
+    u = _diamond_angle(v[:, 0], v[:, 2]) / 4.0  # [0, 1): the face (+z) at 0.25, the seam behind the head
+    h = (v[:, 1] - v[:, 1].min()) / (v[:, 1].max() - v[:, 1].min())
+    uv = np.stack([u * (s - 1), (1.0 - h) * (s - 1)], 1)  # texel units, row 0 at the top of the head
+    owner = np.full(s * s, -1, np.int64)
+    bary = np.zeros((s * s, 3), np.float64)
+    for fi, (a, b, c) in enumerate(faces):
+        p0, p1, p2 = uv[a], uv[b], uv[c]
+        if max(p0[0], p1[0], p2[0]) - min(p0[0], p1[0], p2[0]) > 0.5 * s:
+            continue  # across the seam
+        det = (p1[0] - p0[0]) * (p2[1] - p0[1]) - (p2[0] - p0[0]) * (p1[1] - p0[1])
+        if det == 0.0:
+            continue
+        x0, x1 = int(np.ceil(min(p0[0], p1[0], p2[0]))), int(np.floor(max(p0[0], p1[0], p2[0])))
+        y0, y1 = int(np.ceil(min(p0[1], p1[1], p2[1]))), int(np.floor(max(p0[1], p1[1], p2[1])))
+        if x1 < x0 or y1 < y0:
+            continue
+        gx, gy = np.meshgrid(np.arange(x0, x1 + 1, dtype=np.float64), np.arange(y0, y1 + 1, dtype=np.float64))
+        w1 = ((gx - p0[0]) * (p2[1] - p0[1]) - (p2[0] - p0[0]) * (gy - p0[1])) / det
+        w2 = ((p1[0] - p0[0]) * (gy - p0[1]) - (gx - p0[0]) * (p1[1] - p0[1])) / det
+        w0 = 1.0 - w1 - w2
+        inside = (w0 >= 0) & (w1 >= 0) & (w2 >= 0)
+        pid = (gy[inside].astype(np.int64) * s + gx[inside].astype(np.int64))
+        fresh = owner[pid] < 0
+        pid = pid[fresh]
+        owner[pid] = fi
+        bary[pid] = np.stack([w0[inside][fresh], w1[inside][fresh], w2[inside][fresh]], 1)
+    ids = np.flatnonzero(owner >= 0).astype(np.int64)
+    verts = faces[owner[ids]]
+    b = bary[ids]
+    if duplicates:
+        rng = np.random.default_rng(seed)
+        extra_ids = ids[rng.integers(0, len(ids), duplicates)]
+        extra_faces = faces[rng.integers(0, len(faces), duplicates)]
+        r = rng.random((duplicates, 3)) + 0.05
+        extra_b = r / r.sum(1, keepdims=True)
+        ids = np.concatenate([ids, extra_ids])
+        verts = np.concatenate([verts, extra_faces])
+        b = np.concatenate([b, extra_b])
+    gy, gx = np.divmod(np.arange(s * s, dtype=np.int64), s)
+    return {"x_coords": gx.astype(np.float64), "y_coords": gy.astype(np.float64), "valid_pixel_ids": ids,
+            "valid_pixel_3d_faces": np.ascontiguousarray(verts, np.int64), "valid_pixel_b_coords": np.ascontiguousarray(b),
+            "img_size": s}
+
+
+def texture_data_digest(texture_data: dict) -> str:
+    """sha256 over the atlas' arrays in key order (dtype, shape and bytes): guards golden textures against drift."""
+    h = hashlib.sha256()
+    for k in TEXTURE_DATA_KEYS:
+        a = np.ascontiguousarray(np.asarray(texture_data[k]))
+        h.update(k.encode() + str(a.dtype).encode() + str(a.shape).encode() + a.tobytes())
+    return h.hexdigest()

@@ -1,0 +1,234 @@
+"""UV-texture bake (the reference demo's `uv_texture` output): a drop-in for `inference/uv_texture.py` `UVTextureCreator`.
+
+Same surface as the reference (`get_mesh`, `_compute_texture_map`, `__call__`, the `texture_data` dict), plus the batched
+device-resident entry `bake_batch`: ONE fused decode launch (`to_2d=False`, translation z := 0) followed by the float64 vertex
+normals and the texel bake (csrc/uv_texture.hip); vertices, normals, photos and textures never leave HBM.
+
+What the reference computes, per candidate i of the atlas (`_compute_texture_map`, uv_texture.py:21-46), in float64:
+    p = v[a] * b0 + v[b] * b1 + v[c] * b2,  the same with the vertex normals,  n_dot_view = -n.z
+    (x, y) = np.round(p[:2]).astype(int)      (half to even)
+    skip if n_dot_view < 0; write texture[y_coords[id], x_coords[id]] = image[y, x] if 0 < x < W and 0 < y < H
+in candidate order (the last writer wins), zeros elsewhere. The GPU bake gives every texel its candidates in descending order
+and takes the first that passes, which is the same texel.
+
+Parity labels: the vertex normals are psbody-mesh's `Mesh.estimate_vertex_normals`, restated from its published source (psbody
+is not installed: unpinned here); the faces are the packaged FLAME topology (`assets/flame_static.npz` `faces`), assumed equal
+to `generic_model.pkl['f']`, which is absent; the atlas (`texture_data.npy`) is not redistributed: pass its path or set
+`DAD3D_TEXTURE_DATA` (`synthetic.synthetic_texture_data` is a stand-in for tests and benchmarks only).
+
+One difference from the reference: a candidate whose texel lies outside the texture is refused when the creator is built
+(IndexError); the reference raises only when such a candidate passes both tests on some image.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from types import SimpleNamespace
+from typing import Dict, Optional, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from .head_mesh import HeadMesh
+from .synthetic import load_static
+
+
+def load_texture_data(path: str) -> dict:
+    """uv_texture.py:17: the atlas dict of `texture_data.npy`."""
+    return np.load(path, allow_pickle=True, encoding="latin1").item()
+
+
+def _resolve_texture_data(texture_data: Union[str, dict, None]) -> dict:
+    if isinstance(texture_data, dict):
+        return texture_data
+    path = texture_data if texture_data is not None else os.environ.get("DAD3D_TEXTURE_DATA")
+    if not path or not os.path.isfile(path):
+        raise FileNotFoundError(
+            "UV texture atlas not found. The reference ships without `inference/texture_data.npy`; pass texture_data=<path or "
+            "dict> or set DAD3D_TEXTURE_DATA.")
+    return load_texture_data(path)
+
+
+def texel_table(texture_data: dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """The candidate table the handle is built from, in candidate order: texel y * S + x (int32; `astype(int)` truncation,
+    NumPy's negative indices wrapped), vertex ids int32 [n,3], barycentrics float64 [n,3], and S. IndexError for a texel
+    outside the texture."""
+    s = int(texture_data["img_size"])
+    ids = np.asarray(texture_data["valid_pixel_ids"]).astype(np.int64)
+    ty = np.asarray(texture_data["y_coords"])[ids].astype(int)
+    tx = np.asarray(texture_data["x_coords"])[ids].astype(int)
+    bad = (ty < -s) | (ty >= s) | (tx < -s) | (tx >= s)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise IndexError(f"texture_data candidate {i}: texel (y {int(ty[i])}, x {int(tx[i])}) is outside the {s} x {s} texture")
+    texel = ((ty % s) * s + (tx % s)).astype(np.int32)
+    verts = np.ascontiguousarray(np.asarray(texture_data["valid_pixel_3d_faces"]), dtype=np.int32).reshape(-1, 3)
+    bary = np.ascontiguousarray(np.asarray(texture_data["valid_pixel_b_coords"]), dtype=np.float64).reshape(-1, 3)
+    if not (len(texel) == len(verts) == len(bary)):
+        raise ValueError(f"texture_data: {len(texel)} pixel ids, {len(verts)} vertex triples, {len(bary)} barycentric rows")
+    return np.ascontiguousarray(texel), verts, bary, s
+
+
+def _check_image(image) -> np.ndarray:
+    # as strict as the Sim3DR wrapper: the bake reads 3-channel uint8 pixels and nothing else
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("image must be a uint8 numpy array [H,W,3], got "
+                         f"{getattr(image, 'dtype', type(image))} {getattr(image, 'shape', '')}")
+    return np.ascontiguousarray(image)
+
+
+class UVMap:
+    """The device handle (dad3d_uvmap): a mesh's vertex -> face lists and an atlas' texel -> candidate table in HBM."""
+
+    def __init__(self, faces: np.ndarray, n_verts: int, texture_data: dict, device: Optional[int] = None):
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        texel, verts, bary, s = texel_table(texture_data)
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        handle = C.c_void_p()
+        _lib.check(self._lib.dad3d_uvmap_create(f.ctypes.data, len(f), int(n_verts), texel.ctypes.data, verts.ctypes.data,
+                                                bary.ctypes.data, len(texel), s, self.device, C.byref(handle)))
+        self._handle = handle
+        self.size = s
+        self.n_verts = int(n_verts)
+
+    def __del__(self):
+        h = self.__dict__.get("_handle")
+        self.__dict__["_handle"] = None
+        if h:
+            try:
+                self._lib.dad3d_uvmap_destroy(h)
+            except Exception:
+                pass
+
+    def _check(self, t: Tensor, name: str, dtype, shape) -> None:
+        if t.device != torch.device("cuda", self.device) or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected a contiguous {dtype} tensor {shape} on cuda:{self.device}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def vertex_normals(self, vertices: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        b = vertices.shape[0]
+        self._check(vertices, "vertices", torch.float32, (b, self.n_verts, 3))
+        if out is None:
+            out = torch.empty((b, self.n_verts, 3), dtype=torch.float64, device=vertices.device)
+        self._check(out, "normals", torch.float64, (b, self.n_verts, 3))
+        stream = torch.cuda.current_stream(vertices.device).cuda_stream
+        _lib.check(self._lib.dad3d_uvmap_vertex_normals(self._handle, out.data_ptr(), vertices.data_ptr(), b, stream))
+        return out
+
+    def bake(self, vertices: Tensor, normals: Tensor, images: Tensor, hw: Optional[Tensor] = None,
+             out: Optional[Tensor] = None) -> Tensor:
+        b = vertices.shape[0]
+        self._check(vertices, "vertices", torch.float32, (b, self.n_verts, 3))
+        self._check(normals, "normals", torch.float64, (b, self.n_verts, 3))
+        if images.ndim != 4 or images.shape[0] != b or images.shape[3] != 3:
+            raise ValueError(f"images: expected [B={b},H,W,3], got {tuple(images.shape)}")
+        _, h, w, _ = images.shape
+        self._check(images, "images", torch.uint8, (b, h, w, 3))
+        if hw is not None:
+            self._check(hw, "hw", torch.int32, (b, 2))
+        s = self.size
+        if out is None:
+            out = torch.empty((b, s, s, 3), dtype=torch.uint8, device=images.device)
+        self._check(out, "out", torch.uint8, (b, s, s, 3))
+        stream = torch.cuda.current_stream(images.device).cuda_stream
+        _lib.check(self._lib.dad3d_uvmap_bake(self._handle, out.data_ptr(), vertices.data_ptr(), normals.data_ptr(),
+                                              images.data_ptr(), hw.data_ptr() if hw is not None else None, b, h, w, stream))
+        return out
+
+
+class UVTextureCreator:
+    """`UVTextureCreator(texture_data=path | dict | None, head_mesh=None, static=None, **head_mesh_kwargs)`.
+
+    `texture_data` None reads the path in DAD3D_TEXTURE_DATA. `head_mesh_kwargs` go to `HeadMesh` (e.g. `flame_model`,
+    `device`) when no `head_mesh` is given, as in `pncc.PNCCEstimator`."""
+
+    def __init__(self, texture_data: Union[str, dict, None] = None, head_mesh: Optional[HeadMesh] = None,
+                 static: Optional[dict] = None, **head_mesh_kwargs):
+        self.texture_data = _resolve_texture_data(texture_data)
+        texel_table(self.texture_data)  # refuse an out-of-range texel before any device work
+        st = static if static is not None else load_static()
+        self.head_mesh = head_mesh if head_mesh is not None else HeadMesh(static=st, **head_mesh_kwargs)
+        # generic_model.pkl is absent: its faces are taken to be the packaged FLAME topology
+        self.flame_model = {"f": np.asarray(st["faces"]).astype(np.uint32)}
+        self.img_size = int(self.texture_data["img_size"])
+        self._maps: Dict[Tuple[int, bytes], UVMap] = {}
+        self._normals: Optional[Tensor] = None
+
+    # -- handles ------------------------------------------------------------------------------------------
+    def _map(self, faces: np.ndarray, n_verts: int) -> UVMap:
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        key = (n_verts, f.tobytes())
+        m = self._maps.get(key)
+        if m is None:
+            m = UVMap(f, n_verts, self.texture_data, device=self.head_mesh.flame.device_index)
+            self._maps[key] = m
+        return m
+
+    @property
+    def uv_map(self) -> UVMap:
+        """The handle of the head mesh's topology (the one `bake_batch` uses), built on first use."""
+        m = self.__dict__.get("_head_map")
+        if m is None:
+            m = self._map(self.flame_model["f"], int(self.head_mesh.flame.n_verts))
+            self._head_map = m
+        return m
+
+    def reserve(self, batch: int) -> None:
+        """Size the normals buffer of `bake_batch` for `batch` images, so that a later call can be captured in a graph."""
+        m = self.uv_map
+        if self._normals is None or self._normals.shape[0] < batch:
+            self._normals = torch.empty((batch, m.n_verts, 3), dtype=torch.float64, device=self.head_mesh.flame.torch_device)
+
+    # -- reference surface (single image, host arrays) ----------------------------------------------------
+    def get_mesh(self, predicted_mesh: Dict[str, Tensor]) -> SimpleNamespace:
+        """uv_texture.py:51-53: `Mesh(v, f)` with `v` float64 [V,3] (psbody's dtype) and `f` the faces. Sets translation z := 0
+        in `predicted_mesh["3dmm_params"]`, like the reference."""
+        with torch.no_grad():
+            v = self.head_mesh.reprojected_vertices(params_3dmm=predicted_mesh["3dmm_params"], to_2d=False)[0]
+        return SimpleNamespace(v=v.detach().cpu().numpy().astype(np.float64), f=self.flame_model["f"])
+
+    def _compute_texture_map(self, source_img: np.ndarray, target_mesh) -> np.ndarray:
+        """uv_texture.py:21-46 on the GPU -> uint8 [S,S,3]. `target_mesh.v` must hold float32 values (the decode's): the
+        kernels read fp32 vertices and widen them exactly."""
+        img = _check_image(source_img)
+        v64 = np.asarray(target_mesh.v, dtype=np.float64)
+        v32 = v64.astype(np.float32)
+        if not np.array_equal(v32.astype(np.float64), v64, equal_nan=True):
+            raise ValueError("target_mesh.v must hold float32 values (the GPU bake widens fp32 vertices to float64 exactly)")
+        m = self._map(np.asarray(target_mesh.f), v64.shape[0])
+        dev = torch.device("cuda", m.device)
+        vert = torch.from_numpy(v32[None]).to(dev)
+        normals = m.vertex_normals(vert)
+        tex = m.bake(vert, normals, torch.from_numpy(img[None]).to(dev))
+        return tex[0].cpu().numpy()
+
+    def __call__(self, image: np.ndarray, mesh: Dict[str, Tensor], *args, **kwargs) -> np.ndarray:
+        return self._compute_texture_map(image, self.get_mesh(mesh))
+
+    # -- MI355X-native batched entries ---------------------------------------------------------------------
+    def vertex_normals(self, vertices: Tensor) -> Tensor:
+        """`vertices [B,V,3]` fp32 on the GPU -> psbody's vertex normals `[B,V,3]` float64 (see the module docstring)."""
+        return self.uv_map.vertex_normals(vertices)
+
+    def bake_batch(self, params: Tensor, images: Tensor, hw: Optional[Tensor] = None, mutate: bool = True,
+                   out: Optional[Tensor] = None) -> Tensor:
+        """`params [B,413]` fp32 and `images [B,H,W,3]` uint8 on the GPU -> UV textures `[B,S,S,3]` uint8 on the GPU.
+
+        Three launches on the current stream, no host sync: the fused decode (`proj=True, to_2d=False`; `mutate` writes
+        translation z := 0 into `params` like `HeadMesh.reprojected_vertices`), the float64 normals and the bake. `hw [B,2]`
+        int32: each photo's own (height, width) inside a padded batch. Capturable in a graph after one call of the same
+        batch size or after `reserve(batch)`. Composes with the predictor:
+
+            params = FaceMeshPredictor(...).predict_tensor(images)["3dmm_params"]   # [B,413] on the GPU
+            textures = creator.bake_batch(params, photos)                          # photos [B,H,W,3] uint8 on the GPU
+        """
+        m = self.uv_map
+        b = params.shape[0]
+        self.reserve(b)
+        verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, mutate=mutate)["proj"]
+        normals = m.vertex_normals(verts, out=self._normals[:b])
+        return m.bake(verts, normals, images, hw=hw, out=out)

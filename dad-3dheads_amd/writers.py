@@ -20,6 +20,12 @@ def get_mesh(predictions: Dict[str, torch.Tensor], faces: np.ndarray) -> Tuple[n
     return predictions["3d_vertices"].detach().cpu().numpy(), np.asarray(faces) + 1.0
 
 
+def get_uv_texture(predictions: Dict[str, torch.Tensor], image: np.ndarray, creator) -> np.ndarray:
+    """demo_utils.py:97-100 with the creator passed in (the reference builds a `UVTextureCreator()` per call, which loads its
+    atlas and model files): uint8 [S,S,3]; zeroes translation z in `predictions["3dmm_params"]` like the reference."""
+    return creator(image, predictions)
+
+
 def get_flame_params(predictions: Dict[str, torch.Tensor], constants: Dict[str, int] = FLAME_CONSTS) -> Dict[str, List[float]]:
     """demo_utils.py:112-116: {"shape": [...], "expression": [...], ...} of the first row."""
     fp = FlameParams.from_3dmm(predictions["3dmm_params"].detach().cpu(), constants)

@@ -380,6 +380,36 @@ DAD3D_EXPORT dad3d_status dad3d_eval_z5_ranks(const float* gt_head, const float*
                                  const int32_t* anchors, int n_anchors, int32_t* counts, int32_t* order, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The reference demo's UV-texture bake (inference/uv_texture.py `UVTextureCreator._compute_texture_map`), float64 like its
+ * NumPy. A dad3d_uvmap holds, in HBM, the vertex -> face lists of the mesh's normals and the texel -> candidate table of a
+ * texture atlas. Candidate i (the atlas' valid pixel i) has three vertex ids, three float64 barycentrics and its texel
+ * y * S + x (wrapped into [0, S*S) by the caller, as NumPy's negative indices wrap).
+ *   dad3d_uvmap_create          HOST arrays: faces [ntri,3], cand_texel [n], cand_verts [n,3], cand_bary [n,3]. An index
+ *                               outside [0,nver), a texel outside [0,S*S) or S <= 0 -> DAD3D_E_INVALID.
+ *   dad3d_uvmap_vertex_normals  psbody-mesh's `Mesh.estimate_vertex_normals` of fp32 vertices widened to float64: the
+ *                               unnormalised face normals cross(v1 - v0, v2 - v0) summed in ascending face order (a face that
+ *                               names a vertex twice counts twice), divided by sqrt((x*x + y*y) + z*z), a zero norm read as 1.
+ *                               DEVICE normals [B,nver,3] float64, vertices [B,nver,3] float32.
+ *   dad3d_uvmap_bake            for every texel the LAST candidate (the reference loop's last writer) whose interpolated normal
+ *                               has -n.z >= 0 (or NaN) and whose interpolated point rounds half to even to 0 < x < w,
+ *                               0 < y < h takes images[b, y, x]; texels no candidate reaches are 0. DEVICE texture [B,S,S,3]
+ *                               (every byte written), vertices [B,nver,3] float32, normals [B,nver,3] float64 (from
+ *                               dad3d_uvmap_vertex_normals), images [B,h,w,3] uint8, hw [B,2] int32 = per-item (height,
+ *                               width) bounds inside the padded h x w (clamped to it), or NULL for (h, w).
+ * Neither launch allocates; both are stream-ordered and can be captured into a graph. One handle may serve several streams.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct dad3d_uvmap dad3d_uvmap; /* opaque: face CSR + texel -> candidate CSR (vertex ids, float64 barycentrics) */
+DAD3D_EXPORT dad3d_status dad3d_uvmap_create(const int32_t* faces, int ntri, int nver, const int32_t* cand_texel,
+                                const int32_t* cand_verts, const double* cand_bary, int n, int img_size, int device,
+                                dad3d_uvmap** out);
+DAD3D_EXPORT void dad3d_uvmap_destroy(dad3d_uvmap* m);
+DAD3D_EXPORT int dad3d_uvmap_size(const dad3d_uvmap* m);
+DAD3D_EXPORT dad3d_status dad3d_uvmap_vertex_normals(dad3d_uvmap* m, double* normals, const float* vertices, int batch,
+                                        void* stream);
+DAD3D_EXPORT dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* vertices, const double* normals,
+                              const uint8_t* images, const int32_t* hw, int batch, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
  * in one launch: LongestMaxSize (cv2.resize INTER_LINEAR, 8-bit fixed-point path) -> PadIfNeeded (centred, 0) -> Normalize
  * ((x - 255 mean) * (1 / (255 std)), float32) -> CHW. All DEVICE pointers:
