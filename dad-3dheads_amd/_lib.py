@@ -15,6 +15,7 @@ OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = range(5)
 ZERO_ROTATION, TO_2D, MUTATE_PARAMS, FLIP_Z, COMPAT_CROSS_B3 = 0x1, 0x2, 0x4, 0x8, 0x10
 NORMAL_ACCUMULATE = 0x1
 EVAL_SELF_EXCLUDE, EVAL_MAX_K, EVAL_MAX_HEAD, EVAL_MAX_ANCHORS = 0x1, 8, 4096, 8
+HEATMAP_RAW, HEATMAP_UINT8, HEATMAP_FLOAT = 0, 1, 2
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -110,6 +111,11 @@ SIGNATURES = {
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),
     "dad3d_eval_nearest": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "dad3d_eval_z5_ranks": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _I, _P]),
+    "dad3d_heatmap_encode": (_I, [_P, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P]),
+    "dad3d_heatmap_iou": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "dad3d_heatmap_iou_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "dad3d_visibility_point_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    "dad3d_keypoint_errors": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _F, _F, _I, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P, _I, _P]),
     "dad3d_uvmap_create": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, C.POINTER(_P)]),
     "dad3d_uvmap_destroy": (None, [_P]),
     "dad3d_uvmap_size": (_I, [_P]),

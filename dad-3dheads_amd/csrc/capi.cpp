@@ -1243,6 +1243,104 @@ dad3d_status dad3d_weighted_point_loss(const float* pred, const float* target, i
     return launch_point_loss(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- the rest of the training objective (train_objective.hip) ----------------------------------------------------------
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+dad3d_status dad3d_heatmap_encode(void* out, int form, const float* keypoints, const uint8_t* presence, int batch,
+                                  int n_classes, float stride, int size, int radius, const void* table, int32_t* invalid,
+                                  int device, void* stream) {
+    DAD3D_REQUIRE(form >= DAD3D_HEATMAP_RAW && form <= DAD3D_HEATMAP_FLOAT, "dad3d_heatmap_encode: unknown form %d", form);
+    DAD3D_REQUIRE(batch >= 0 && n_classes >= 0 && size >= 0, "dad3d_heatmap_encode: negative size");
+    DAD3D_REQUIRE(size <= 46340, "dad3d_heatmap_encode: heatmap size %d beyond 46340", size);
+    DAD3D_REQUIRE(radius >= 0 && radius <= 4096, "dad3d_heatmap_encode: radius %d outside 0..4096", radius);
+    DAD3D_REQUIRE(std::isfinite(stride) && stride > 0.0f, "dad3d_heatmap_encode: stride must be finite and positive");
+    if (batch == 0 || n_classes == 0 || size == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(out && keypoints && presence && table, "dad3d_heatmap_encode: null argument");
+    DAD3D_REQUIRE(aligned16(out), "dad3d_heatmap_encode: the output must be 16-byte aligned");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    HeatmapEncodeArgs a{out, keypoints, presence, table, invalid, (size_t)batch * n_classes, stride, size, radius, form};
+    return launch_heatmap_encode(a, static_cast<hipStream_t>(stream));
+}
+
+static dad3d_status iou_check(const char* who, const float* pred, const void* target, int target_u8, int batch, int channels,
+                              int hw) {
+    DAD3D_REQUIRE(batch >= 0 && channels >= 0 && hw >= 0, "%s: negative size", who);
+    DAD3D_REQUIRE(target_u8 == 0 || target_u8 == 1, "%s: target_u8 must be 0 or 1", who);
+    DAD3D_REQUIRE((long long)batch * channels <= 0x7fffffffLL, "%s: %d x %d channels beyond the launch grid", who, batch, channels);
+    DAD3D_REQUIRE(batch == 0 || channels == 0 || (pred && target), "%s: null argument", who);
+    return DAD3D_OK;
+}
+
+static bool iou_vec(const float* pred, const void* target, int target_u8, int hw) {
+    return hw % 4 == 0 && aligned16(pred) && (reinterpret_cast<uintptr_t>(target) & (target_u8 ? 3 : 15)) == 0;
+}
+
+dad3d_status dad3d_heatmap_iou(const float* pred, const void* target, int target_u8, int batch, int channels, int hw,
+                               int sigmoid, double* sums, float* iou, float* loss, float* accum, int device, void* stream) {
+    dad3d_status st = iou_check("dad3d_heatmap_iou", pred, target, target_u8, batch, channels, hw);
+    if (st) return st;
+    DAD3D_REQUIRE(batch > 0 && channels > 0, "dad3d_heatmap_iou: no channels (the reference's mean over none is NaN)");
+    DAD3D_REQUIRE(sums, "dad3d_heatmap_iou: null sums");
+    DAD3D_REQUIRE(!accum || loss, "dad3d_heatmap_iou: accum needs loss");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    IouArgs a{pred, target, sums, iou, loss, accum, nullptr, nullptr, (size_t)batch * channels, hw, target_u8 != 0};
+    return launch_heatmap_iou(a, sigmoid != 0, iou_vec(pred, target, target_u8, hw), static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_heatmap_iou_grad(const float* pred, const void* target, int target_u8, int batch, int channels, int hw,
+                                    const double* sums, const float* grad_out, float* grad, int device, void* stream) {
+    dad3d_status st = iou_check("dad3d_heatmap_iou_grad", pred, target, target_u8, batch, channels, hw);
+    if (st) return st;
+    if (batch == 0 || channels == 0 || hw == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(sums && grad_out && grad, "dad3d_heatmap_iou_grad: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    IouArgs a{pred, target, const_cast<double*>(sums), nullptr, nullptr, nullptr, grad_out, grad, (size_t)batch * channels, hw,
+              target_u8 != 0};
+    return launch_heatmap_iou_grad(a, iou_vec(pred, target, target_u8, hw) && aligned16(grad), static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_visibility_point_loss(const float* pred, const float* pred_presence, const float* target,
+                                         const float* target_presence, int batch, int n_points, int criterion, float* loss,
+                                         float* grad_pred, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 0 && n_points >= 0, "dad3d_visibility_point_loss: negative size");
+    DAD3D_REQUIRE(criterion >= DAD3D_LOSS_L1 && criterion <= DAD3D_LOSS_SMOOTH_L1, "dad3d_visibility_point_loss: unknown criterion %d",
+                  criterion);
+    DAD3D_REQUIRE(batch > 0 && n_points > 0, "dad3d_visibility_point_loss: no points (the reference's mean over none is NaN)");
+    DAD3D_REQUIRE(pred && pred_presence && target && target_presence && loss, "dad3d_visibility_point_loss: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    VisibilityLossArgs a{pred, pred_presence, target, target_presence, loss, grad_pred, batch, n_points, criterion};
+    return launch_visibility_loss(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_keypoint_errors(const float* pred, const float* target, int batch, int n_verts, int dims, const int32_t* index,
+                                   int n_points, const float* presence, float pred_scale, float target_scale, int cube,
+                                   const int32_t* bbox, const double* thresholds, int n_thresholds, int below, double* err,
+                                   float* out, float* accum, int device, void* stream) {
+    DAD3D_REQUIRE(batch > 0 && n_verts > 0 && n_points > 0, "dad3d_keypoint_errors: bad size (batch %d, n_verts %d, n_points %d)",
+                  batch, n_verts, n_points);
+    DAD3D_REQUIRE(batch <= 0x7fffffff && (dims == 2 || dims == 3), "dad3d_keypoint_errors: dims must be 2 or 3, not %d", dims);
+    DAD3D_REQUIRE(index || n_points <= n_verts, "dad3d_keypoint_errors: %d points of %d vertices", n_points, n_verts);
+    DAD3D_REQUIRE(n_thresholds >= 0 && n_thresholds <= kMaxThresholds, "dad3d_keypoint_errors: %d thresholds (at most %d)", n_thresholds,
+                  kMaxThresholds);
+    DAD3D_REQUIRE(!cube || dims == 3, "dad3d_keypoint_errors: normalize_to_cube needs 3-D points");
+    DAD3D_REQUIRE(pred && target && err && (n_thresholds == 0 || thresholds), "dad3d_keypoint_errors: null argument");
+    DAD3D_REQUIRE(!accum || out, "dad3d_keypoint_errors: accum needs out");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    KeypointErrArgs a{};
+    a.pred = pred, a.target = target, a.index = index, a.presence = presence, a.bbox = bbox, a.err = err, a.out = out,
+    a.accum = accum;
+    a.pred_scale = pred_scale, a.target_scale = target_scale;
+    for (int k = 0; k < n_thresholds; ++k) a.thresholds[k] = thresholds[k];  // HOST array
+    a.batch = batch, a.n_verts = n_verts, a.n_points = n_points, a.dims = dims, a.n_thresholds = n_thresholds;
+    a.cube = cube != 0, a.below = below != 0;
+    return launch_keypoint_errors(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_eval_nearest(const float* query, const float* points, const int32_t* counts, const float* similarity,
                                 int batch, int n_query, int n_points, int k, int flags, float* min_dist2, int32_t* knn_index,
                                 float* knn_dist2, int device, void* stream) {

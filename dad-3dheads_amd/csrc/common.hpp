@@ -386,6 +386,62 @@ int uv_bake_grid_y(int batch, int chunk);
 dad3d_status launch_uv_vertex_normals(const UvNormalArgs& a, hipStream_t s);
 dad3d_status launch_uv_bake(const UvBakeArgs& a, hipStream_t s);
 
+// the rest of the reference's training objective (train_objective.hip): heatmap target, heatmap IoU, visibility landmark
+// loss, keypoint metrics
+struct HeatmapEncodeArgs {
+    void* out;                // [channels][size][size] float32 or uint8 (form), 16-byte aligned, every element written
+    const float* keypoints;   // [channels][2] resized-image pixels
+    const uint8_t* presence;  // [channels] (bool / uint8, non-zero = present)
+    const void* table;        // [(2r+1)^2] the stamp in the output's form
+    int* invalid;             // [1] += present points whose centre is NaN / inf, or null
+    size_t channels;          // B * C
+    float stride;
+    int size, radius, form;
+};
+constexpr double kIouEps = 1e-6;  // keypoint_losses.py:12, metrics/iou.py:15
+struct IouArgs {
+    const float* pred;    // [channels][hw] logits (or probabilities: no sigmoid)
+    const void* target;   // [channels][hw] float32 or uint8 (/ 255 fused in)
+    double* sums;         // [channels][3] sum(t s), sum(t^2), sum(s^2)
+    float* iou;           // [channels] or null
+    float* loss;          // [2] = 1 - mean, mean; or null (terms only)
+    float* accum;         // [2] += mean, += 1 (SoftIoUMetric's ious / total), or null
+    const float* grad_out;  // [1] upstream gradient of the loss (backward)
+    float* grad;            // [channels][hw] (backward)
+    size_t channels;
+    int hw;
+    bool target_u8;
+};
+struct VisibilityLossArgs {
+    const float* pred;             // [B,N,2]
+    const float* pred_presence;    // [B,N]
+    const float* target;           // [B,N,2]
+    const float* target_presence;  // [B,N]
+    float* loss;                   // [1]
+    float* grad_pred;              // [B,N,2] dL/dpred for an upstream gradient of 1, or null
+    int batch, n_points, criterion;
+};
+constexpr int kMaxThresholds = 8;
+struct KeypointErrArgs {
+    const float* pred;       // [B,V,D]
+    const float* target;     // [B,V,D]
+    const int* index;        // [n_points] into V, or null (the first n_points)
+    const float* presence;   // [B,V] multiplies both, or null
+    const int* bbox;         // [B,4] (x, y, w, h): norm sqrt(w h); null: 2.0
+    double* err;             // [B][2] scratch: err, norm
+    float* out;              // [1 + n_thresholds] NME, failure fractions; or null (per-item errors only)
+    float* accum;            // [2 (1 + n_thresholds)] += (value, 1) pairs, or null
+    double pred_scale, target_scale;
+    double thresholds[kMaxThresholds];
+    int batch, n_verts, n_points, dims, n_thresholds;
+    bool cube, below;
+};
+dad3d_status launch_heatmap_encode(const HeatmapEncodeArgs& a, hipStream_t s);
+dad3d_status launch_heatmap_iou(const IouArgs& a, bool sigmoid, bool vec, hipStream_t s);
+dad3d_status launch_heatmap_iou_grad(const IouArgs& a, bool vec, hipStream_t s);
+dad3d_status launch_visibility_loss(const VisibilityLossArgs& a, hipStream_t s);
+dad3d_status launch_keypoint_errors(const KeypointErrArgs& a, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -9,7 +9,7 @@ FLAME material, so the tests build their own regions).
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, List, Sequence, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -18,7 +18,7 @@ from torch.autograd.function import once_differentiable
 
 from .head_mesh import HeadMesh
 
-__all__ = ["Vertices3DLoss", "ReprojectionLoss", "indices_reweighing", "normalize_to_cube"]
+__all__ = ["Vertices3DLoss", "ReprojectionLoss", "IoULoss", "LandmarksLossWVisibility", "indices_reweighing", "normalize_to_cube"]
 losses = {"l1": nn.L1Loss, "l2": nn.MSELoss, "smooth_l1": nn.SmoothL1Loss}
 
 
@@ -202,3 +202,141 @@ class ReprojectionLoss(_MeshLoss):
         projected_vertices = self.head_mesh.reprojected_vertices(params_3dmm=predicted, to_2d=True)
         full_target = target[0] if isinstance(target, list) else target
         return _WeightedPointLoss.apply(projected_vertices, full_target, self.tables, self.criterion_id)
+
+
+# ---- the heatmap and landmark terms (csrc/train_objective.hip) ---------------------------------------------------------
+def _on_gpu(t: Tensor, what: str) -> Tensor:
+    if t.device.type != "cuda":
+        raise ValueError(f"{what} must be a GPU tensor: the HIP kernels have no CPU path")
+    return t
+
+
+def _f32(t: Tensor, what: str) -> Tensor:
+    """fp32 and contiguous; other floating / bool / integer dtypes are converted explicitly (a copy), never a CPU path."""
+    _on_gpu(t, what)
+    if t.is_complex():
+        raise TypeError(f"{what}: complex tensors are not supported")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def heatmap_target(t: Tensor, like: Tensor) -> Tuple[Tensor, int]:
+    """A heatmap target as the IoU kernels read it: uint8 (the dataset's bytes, / 255 fused in) or fp32."""
+    _on_gpu(t, "the heatmap target")
+    if t.shape != like.shape:
+        raise ValueError(f"prediction {tuple(like.shape)} and target {tuple(t.shape)} differ in shape")
+    if t.device != like.device:
+        raise ValueError("prediction and target are on different devices")
+    if t.dtype == torch.uint8:
+        return t.detach().contiguous(), 1
+    return _f32(t, "the heatmap target"), 0
+
+
+def heatmap_iou_terms(pred: Tensor, target: Tensor, sigmoid: bool, accum: Optional[Tensor] = None):
+    """One pass over [B,C,H,W]: (sums [B*C,3] float64, out [2] = (1 - mean IoU, mean IoU)), on the current stream."""
+    from . import _lib
+
+    if pred.ndim < 3:
+        raise ValueError(f"expected [B,C,...] heatmaps, got {tuple(pred.shape)}")
+    p = _f32(pred, "the heatmap prediction")
+    t, u8 = heatmap_target(target, p)
+    b, c, hw = p.shape[0], p.shape[1], int(np.prod(p.shape[2:]))
+    sums = torch.empty((b * c, 3), dtype=torch.float64, device=p.device)
+    out = torch.empty(2, dtype=torch.float32, device=p.device)
+    _lib.check(_lib.load().dad3d_heatmap_iou(p.data_ptr(), t.data_ptr(), u8, b, c, hw, int(sigmoid), sums.data_ptr(), None,
+                                             out.data_ptr(), None if accum is None else accum.data_ptr(), p.device.index or 0,
+                                             torch.cuda.current_stream(p.device).cuda_stream))
+    return p, t, u8, sums, out
+
+
+class _HeatmapIoU(torch.autograd.Function):
+    """keypoint_losses.py:25-30: 1 - mean_{b,c} IoU(sigmoid(pred), target); one read of each channel, one more (and the
+    gradient written) backward."""
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor):
+        _first_order_pred_only(ctx)
+        p, t, u8, sums, out = heatmap_iou_terms(pred, target, sigmoid=True)
+        ctx.u8, ctx.shape = u8, p.shape
+        ctx.save_for_backward(p, t, sums)
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g: Tensor):
+        from . import _lib
+
+        p, t, sums = ctx.saved_tensors
+        gd = g.detach().to(p.device, torch.float32).reshape(1).contiguous()
+        grad = torch.empty_like(p)
+        b, c = ctx.shape[0], ctx.shape[1]
+        _lib.check(_lib.load().dad3d_heatmap_iou_grad(p.data_ptr(), t.data_ptr(), ctx.u8, b, c, p[0, 0].numel(), sums.data_ptr(),
+                                                      gd.data_ptr(), grad.data_ptr(), p.device.index or 0,
+                                                      torch.cuda.current_stream(p.device).cuda_stream))
+        return grad, None
+
+
+class IoULoss(nn.Module):
+    """losses/keypoint_losses.py:5-30 on the fused HIP kernels. The target may be the dataset's uint8 heatmap (read as
+    uint8 / 255.0, what `get_input` makes of it) or fp32."""
+
+    def __init__(self) -> None:
+        super().__init__()
+
+    @staticmethod
+    def iou_metric(y_pred: Tensor, y_true: Tensor) -> Tensor:
+        """The mean soft IoU of probabilities `y_pred` (no sigmoid), as keypoint_losses.py:11-23."""
+        return heatmap_iou_terms(y_pred, y_true, sigmoid=False)[4][1]
+
+    @torch.autocast("cuda", enabled=False)
+    def forward(self, y_pred: Tensor, y_true: Tensor) -> Tensor:
+        return _HeatmapIoU.apply(y_pred, y_true)
+
+
+class _VisibilityPointLoss(torch.autograd.Function):
+    """landmarks_loss_w_visibility.py:17-26: one HIP launch, value and dL/d(pred)."""
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, pred_presence: Tensor, target: Tensor, target_presence: Tensor, criterion: int):
+        from . import _lib
+
+        if any(ctx.needs_input_grad[1:4]):
+            raise RuntimeError("the HIP landmark loss differentiates with respect to the predicted landmarks only: detach the "
+                               "presence and the target (the reference's are dataset tensors)")
+        p, t = _f32(pred, "the predicted landmarks"), _f32(target, "the target landmarks")
+        pp, tp = _f32(pred_presence, "the predicted presence"), _f32(target_presence, "the target presence")
+        if p.ndim != 3 or p.shape[2] != 2 or t.shape != p.shape or pp.shape != p.shape[:2] or tp.shape != p.shape[:2]:
+            raise ValueError(f"expected [B,N,2] landmarks and [B,N] presences, got {tuple(p.shape)}, {tuple(pp.shape)}, "
+                             f"{tuple(t.shape)}, {tuple(tp.shape)}")
+        if len({p.device, t.device, pp.device, tp.device}) != 1:
+            raise ValueError("the landmark loss operands are on different devices")
+        need_grad = ctx.needs_input_grad[0]
+        grad = torch.empty_like(p) if need_grad else None
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        _lib.check(_lib.load().dad3d_visibility_point_loss(
+            p.data_ptr(), pp.data_ptr(), t.data_ptr(), tp.data_ptr(), p.shape[0], p.shape[1], criterion, loss.data_ptr(),
+            grad.data_ptr() if need_grad else None, p.device.index or 0, torch.cuda.current_stream(p.device).cuda_stream))
+        if need_grad:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g: Tensor):
+        (grad,) = ctx.saved_tensors
+        return grad * g.to(grad.device), None, None, None, None
+
+
+class LandmarksLossWVisibility(nn.Module):
+    """losses/landmarks_loss_w_visibility.py:10-26: criterion(pred * pred_presence, target * target_presence), mean over
+    B * N * 2, on one HIP launch. It multiplies (not selects): a NaN prediction under presence 0 stays NaN, as there."""
+
+    def __init__(self, criterion: str) -> None:
+        super().__init__()
+        if criterion not in losses:
+            raise ValueError(f"Unsupported discrepancy loss type {criterion}")
+        self.criterion = losses[criterion]()
+        self.criterion_id = _CRITERION_ID[criterion]
+
+    @torch.autocast("cuda", enabled=False)
+    def forward(self, predicted: List[Tensor], target: List[Tensor]) -> Tensor:
+        return _VisibilityPointLoss.apply(predicted[0], predicted[1], target[0], target[1], self.criterion_id)

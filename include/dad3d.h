@@ -349,6 +349,55 @@ DAD3D_EXPORT dad3d_status dad3d_weighted_point_loss(const float* pred, const flo
                                        float* grad_pred, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rest of the reference's training objective: the heatmap target, the heatmap IoU loss, the landmark loss with visibility
+ * and the keypoint metrics of a training step. All pointers are DEVICE pointers; nothing is allocated, no call waits for the
+ * device, every call can be captured into a graph. Sums run in a fixed order (no float atomics): two runs give the same bits.
+ * Bad sizes, an unknown form / criterion or a NULL pointer -> DAD3D_E_INVALID before any device work.
+ *
+ * dad3d_heatmap_encode  HeatmapCoder.__call__ (model_training/data/coder.py:17-24; draw_gaussian data/utils.py:48-71) for
+ *   B * C channels: keypoints [B*C,2] fp32 (resized-image pixels), presence [B*C] bool / uint8. A present point stamps the
+ *   (2r+1)^2 `table` around int(point // stride) (numpy's float32 floor_divide), clipped to the size x size channel; every
+ *   other element is 0. `table` holds the stamp in the output's form (DAD3D_HEATMAP_RAW float32 = the coder's return,
+ *   DAD3D_HEATMAP_UINT8 = flame_dataset.py:198 `np.uint8(255.0 * heatmap)`, DAD3D_HEATMAP_FLOAT = mixins.py:50
+ *   `uint8 / 255.0`). out [B*C,size,size] float32 / uint8, 16-byte aligned. A present point whose centre is NaN or inf (the
+ *   reference raises) leaves its channel zero and adds 1 to invalid[0] (invalid may be NULL).
+ * dad3d_heatmap_iou  IoULoss (losses/keypoint_losses.py:11-30), SoftIoUMetric / soft_iou (metrics/iou.py:15-72):
+ *   per channel N = sum(t s) + 1e-6, D = sum(t^2) + sum(s^2) - sum(t s) + 1e-6 over hw elements, s = sigmoid(pred) when
+ *   `sigmoid` (the loss) or pred itself (the metric), t = target (float32) or target / 255 (uint8, target_u8 = 1).
+ *   sums [channels,3] float64 (saved for the gradient); iou [channels] fp32 or NULL; loss [2] = (1 - mean N/D, mean N/D)
+ *   or NULL; accum [2] += (mean, 1) or NULL.
+ * dad3d_heatmap_iou_grad  dL/dpred of the loss for an upstream gradient grad_out [1] (read on the device):
+ *   -g / channels * (t D - N (2 s - t)) / D^2 * s (1 - s), with the sums of dad3d_heatmap_iou. grad [channels,hw] fp32.
+ * dad3d_visibility_point_loss  LandmarksLossWVisibility (losses/landmarks_loss_w_visibility.py:17-26):
+ *   criterion(pred * pred_presence[..., None], target * target_presence[..., None]), mean over B*N*2; pred, target [B,N,2],
+ *   presences [B,N] fp32. loss [1]; grad_pred [B,N,2] (for an upstream gradient of 1) or NULL.
+ * dad3d_keypoint_errors  metrics/keypoints.py:19-53 (`keypoints_nme`, `percentage_of_errors_below_IOD`): per item
+ *   err = mean_n |p_n - q_n|_2 over index [n_points] (NULL: the first n_points of n_verts) with p = pred * pred_scale * presence,
+ *   q = target * presence * target_scale (presence [B,n_verts] or NULL), both normalize_to_cube'd (model/utils.py:55-68)
+ *   when `cube`; norm = sqrt(w h) of bbox [B,4] int32 (x, y, w, h), or 2.0 when bbox is NULL. Float64 throughout. An index
+ *   outside [0,n_verts) reads as NaN. thresholds [n_thresholds] is a HOST float64 array.
+ *   err [B,2] float64 = (err, norm). out [1 + n_thresholds] = (mean(err / norm), count(err < thr_k norm) / B ...) (`below` = 0:
+ *   err > thr_k norm), or NULL; accum [2 (1 + n_thresholds)] += (value, 1) pairs, or NULL. n_thresholds <= 8, dims 2 or 3.
+ * --------------------------------------------------------------------------------------------- */
+enum { DAD3D_HEATMAP_RAW = 0, DAD3D_HEATMAP_UINT8 = 1, DAD3D_HEATMAP_FLOAT = 2 };
+DAD3D_EXPORT dad3d_status dad3d_heatmap_encode(void* out, int form, const float* keypoints, const uint8_t* presence, int batch,
+                                  int n_classes, float stride, int size, int radius, const void* table, int32_t* invalid,
+                                  int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_heatmap_iou(const float* pred, const void* target, int target_u8, int batch, int channels,
+                               int hw, int sigmoid, double* sums, float* iou, float* loss, float* accum, int device,
+                               void* stream);
+DAD3D_EXPORT dad3d_status dad3d_heatmap_iou_grad(const float* pred, const void* target, int target_u8, int batch, int channels,
+                                    int hw, const double* sums, const float* grad_out, float* grad, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_visibility_point_loss(const float* pred, const float* pred_presence, const float* target,
+                                         const float* target_presence, int batch, int n_points, int criterion, float* loss,
+                                         float* grad_pred, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_keypoint_errors(const float* pred, const float* target, int batch, int n_verts, int dims,
+                                   const int32_t* index, int n_points, const float* presence, float pred_scale,
+                                   float target_scale, int cube, const int32_t* bbox, const double* thresholds,
+                                   int n_thresholds, int below, double* err, float* out, float* accum, int device,
+                                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The DAD-3DHeads benchmark scorer's two dense point-set steps (dad_3dheads_benchmark/benchmark.py `DADEvaluator`, utils.py).
  * All pointers are DEVICE pointers unless noted; nothing is allocated, both calls can be captured into a graph. Distances are
  * squared, fp32, in the direct-difference form (qx-px)^2 + (qy-py)^2 + (qz-pz)^2 (no |q|^2 + |p|^2 - 2 q.p expansion).

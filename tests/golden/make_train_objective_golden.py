@@ -1,0 +1,214 @@
+#!/usr/bin/env python3
+"""tests/golden/train_objective_golden.npz: the reference's OWN heatmap coder (`HeatmapCoder`, `draw_gaussian`, the dataset's
+uint8 store and `uint8_to_float32`), `IoULoss`, `LandmarksLossWVisibility`, `soft_iou`, `keypoints_nme`,
+`percentage_of_errors_below_IOD` and `LossModule`, imported unmodified from the reference tree. The mesh terms of the
+LossModule case are the reference's `Vertices3DLoss` / `ReprojectionLoss` through oracle/reference_runner.py on the seeded
+synthetic FLAME model. Inputs come from seeds (tests/train_objective_restatement.py); only small gradients are stored.
+
+The data and metrics modules import packages that are not installed here (cv2, skimage.io, smplx.lbs, torchmetrics,
+hydra.utils): this script installs `sys.modules` stand-ins for them, none of which the code paths run here call.
+Authoring container only."""
+import importlib
+import os
+import sys
+import tempfile
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_objective_golden.npz")
+
+CODER_CASES = [  # (name, img_size, stride, radius)
+    ("s4_r5", 256, 4, 5), ("s3_r2", 96, 3, 2), ("s4_pw", 64, 4, "pointwise"), ("s3_r5", 120, 3, 5)]
+IOU_CASES = [("hw64", 71, 2, 5, 64, 64), ("hw37x41", 72, 2, 5, 37, 41)]  # (name, seed, B, C, H, W)
+VIS_SEED, VIS_B, VIS_N = 81, 3, 68
+KP_CASES = [("kp2d", 91, 16, 68, 2, 0.02), ("kp3d", 92, 16, 300, 3, 0.03)]  # (name, seed, B, N, dims, spread)
+LM_SEED, LM_B, LM_C, LM_EPOCH = 101, 2, 5, 3
+REGIONS = {"face": (1.0, np.arange(0, 5023, 5)), "face_w_ears": (0.75, np.arange(1000, 3000, 3)), "head": (0.5, np.arange(0, 5023, 11))}
+
+
+def _mod(name):
+    m = types.ModuleType(name)
+    sys.modules[name] = m
+    return m
+
+
+def load_reference(model):
+    from oracle import reference_runner as rr
+
+    v3d, rep = rr.load_reference_losses(model)  # stubs for hydra, smplx, pytorch_toolbelt, omegaconf, coloredlogs; sys.path
+    ref = rr.REFERENCE_ROOT
+    if "cv2" not in sys.modules:
+        _mod("cv2")
+    if "skimage" not in sys.modules:
+        sk = _mod("skimage")
+        sk.io = _mod("skimage.io")
+        sk.io.imread = None
+    sys.modules["smplx.lbs"].find_dynamic_lmk_idx_and_bcoords = None
+    if "torchmetrics" not in sys.modules:
+        tm = _mod("torchmetrics")
+        tm.Metric = type("Metric", (), {})
+        tm.MetricCollection = dict
+    if not hasattr(sys.modules["hydra.utils"], "instantiate"):
+        sys.modules["hydra.utils"].instantiate = None
+    for pkg in ("model_training.data", "model_training.metrics", "model_training.train"):
+        if pkg not in sys.modules:  # their __init__ pull in datasets / lightning: bypassed
+            m = _mod(pkg)
+            m.__path__ = [os.path.join(ref, *pkg.split("."))]
+    get = importlib.import_module
+    return types.SimpleNamespace(
+        coder=get("model_training.data.coder"), data_utils=get("model_training.data.utils"),
+        flame=get("model_training.model.flame"), model_utils=get("model_training.model.utils"),
+        keypoint_losses=get("model_training.losses.keypoint_losses"),
+        vis_loss=get("model_training.losses.landmarks_loss_w_visibility"),
+        iou=get("model_training.metrics.iou"), keypoints=get("model_training.metrics.keypoints"),
+        loss_module=get("model_training.train.loss_module"), Vertices3DLoss=v3d, ReprojectionLoss=rep)
+
+
+def main():
+    import train_objective_restatement as rs
+    from dad_3dheads_amd import synthetic
+    from dad_3dheads_amd.flame import FLAME_CONSTS
+    from oracle import flame_ref
+
+    st = synthetic.load_static()
+    model = synthetic.synthetic_flame_model(0, st)
+    R = load_reference(model)
+    out = {}
+
+    # ---- coder: the three forms, boundary centres, strides 4 / 3, radius 5 / 2 / pointwise -----------------------------
+    for i, (name, img, stride, radius) in enumerate(CODER_CASES):
+        size = img // stride
+        kp, pr = rs.boundary_keypoints(size, stride, radius, seed=200 + i)
+        coder = R.coder.HeatmapCoder({"img_size": img, "stride": stride, "radius": radius}, kp.shape[1])
+        raw = np.stack([coder(kp[b], pr[b]) for b in range(kp.shape[0])])
+        u8 = np.uint8(255.0 * raw)  # flame_dataset.py:198, per item there; elementwise, so the same bytes
+        f = R.flame.uint8_to_float32(torch.from_numpy(u8)).numpy()
+        out.update({f"coder_{name}_keypoints": kp, f"coder_{name}_presence": pr, f"coder_{name}_raw": raw,
+                    f"coder_{name}_uint8": u8, f"coder_{name}_float": f})
+        bad = kp[0].copy()
+        bad[0, 0] = np.nan
+        try:  # a present NaN raises in the reference
+            coder(bad, np.ones(len(bad), bool))
+            raise AssertionError("the reference coder accepted a NaN point")
+        except ValueError:
+            pass
+        bad[0, 0] = np.inf
+        try:
+            coder(bad, np.ones(len(bad), bool))
+            raise AssertionError("the reference coder accepted an inf point")
+        except ValueError:
+            pass
+    out["coder_cases"] = np.array([f"{n}:{i}:{s}:{r}" for n, i, s, r in CODER_CASES])
+
+    # ---- IoU loss: uint8 and float targets, saturated logits, an all-zero target channel --------------------------------
+    for name, seed, b, c, h, w in IOU_CASES:
+        logits, t8 = rs.iou_inputs(seed, b, c, h, w)
+        # the target as the training step reads it (mixins.py:50); the reference's own arithmetic on a raw uint8 tensor
+        # would square in uint8. The HIP loss reads either form.
+        tgt = R.flame.uint8_to_float32(torch.from_numpy(t8))
+        x = torch.from_numpy(logits).requires_grad_(True)
+        loss = R.keypoint_losses.IoULoss()(x, tgt)
+        (g,) = torch.autograd.grad(loss, x)
+        out[f"iou_{name}_loss"], out[f"iou_{name}_grad"] = np.float32(loss.detach()), g.numpy()
+        out[f"iou_{name}_soft_iou"] = np.float32(R.iou.soft_iou(torch.sigmoid(torch.from_numpy(logits)), tgt))
+    out["iou_cases"] = np.array([f"{n}:{s}:{b}:{c}:{h}:{w}" for n, s, b, c, h, w in IOU_CASES])
+
+    # ---- visibility landmark loss: three criteria, NaN under presence 0 -------------------------------------------------
+    pred, pp, tgt, tp = rs.visibility_inputs(VIS_SEED, VIS_B, VIS_N)
+    for crit in rs.CRITERIA:
+        x = torch.from_numpy(pred).requires_grad_(True)
+        loss = R.vis_loss.LandmarksLossWVisibility(crit)([x, torch.from_numpy(pp)], [torch.from_numpy(tgt), torch.from_numpy(tp)])
+        (g,) = torch.autograd.grad(loss, x)
+        out[f"vis_{crit}_loss"], out[f"vis_{crit}_grad"] = np.float32(loss.detach()), g.numpy()
+        # the same loss without the NaN point (a finite value the bars can measure)
+        clean = pred.copy()
+        clean[0, 0, 1] = 0.25
+        x = torch.from_numpy(clean).requires_grad_(True)
+        loss = R.vis_loss.LandmarksLossWVisibility(crit)([x, torch.from_numpy(pp)], [torch.from_numpy(tgt), torch.from_numpy(tp)])
+        (g,) = torch.autograd.grad(loss, x)
+        out[f"vis_clean_{crit}_loss"], out[f"vis_clean_{crit}_grad"] = np.float32(loss.detach()), g.numpy()
+
+    # ---- keypoint metrics: 2-D with bbox and presence, 3-D cube-normalised on an index subset -----------------------------
+    for name, seed, b, n, dims, spread in KP_CASES:
+        p, q, pres, bbox = rs.keypoint_inputs(seed, b, n, dims, spread)
+        if dims == 2:
+            pt = torch.from_numpy(p) * 256 * torch.from_numpy(pres)[..., None]
+            qt = torch.from_numpy(q) * torch.from_numpy(pres)[..., None] * 256
+            bb = torch.from_numpy(bbox)
+            err64, norm64 = rs.keypoint_errors(p, q, bbox, presence=pres, pred_scale=256, target_scale=256)
+        else:
+            idx = np.arange(3, n, 2)
+            pt = R.model_utils.normalize_to_cube(torch.from_numpy(p)[:, idx])
+            qt = R.model_utils.normalize_to_cube(torch.from_numpy(q)[:, idx])
+            bb = None
+            err64, norm64 = rs.keypoint_errors(p, q, None, index=idx, cube=True)
+            out[f"{name}_index"] = idx
+        ratio = err64 / norm64
+        for thr in (0.05, 0.1):  # the failure rates are exact only away from the thresholds
+            assert np.all(np.abs(ratio - thr) >= 1e-5 * thr), (name, thr, ratio)
+        out[f"{name}_nme"] = np.float32(R.keypoints.keypoints_nme(pt, qt, bb))
+        out[f"{name}_nme_items"] = R.keypoints.keypoints_nme(pt, qt, bb, reduce="none").numpy()
+        for thr in (0.05, 0.1):
+            out[f"{name}_fr_{thr}"] = np.float32(R.keypoints.percentage_of_errors_below_IOD(pt, qt, bb, threshold=thr))
+        out[f"{name}_bbox"] = bbox
+    out["kp_cases"] = np.array([f"{n}:{s}:{b}:{k}:{d}:{sp}" for n, s, b, k, d, sp in KP_CASES])
+
+    # ---- LossModule: the four criteria of train_loss.yaml, schedule gating, three reductions -------------------------------
+    rng = np.random.default_rng(LM_SEED)
+    params = torch.from_numpy(synthetic.synthetic_params(LM_B, seed=LM_SEED))
+    fc = flame_ref.FlameConstants.from_model(model)
+    tgt3d = flame_ref.vertices_3d(fc, torch.from_numpy(synthetic.synthetic_params(LM_B, seed=LM_SEED + 1)), zero_rotation=True)
+    tgt2d = flame_ref.reprojected_vertices(fc, torch.from_numpy(synthetic.synthetic_params(LM_B, seed=LM_SEED + 2)))
+    logits, t8 = rs.iou_inputs(LM_SEED + 3, LM_B, LM_C, 64, 64)
+    lmk = rng.uniform(0.1, 0.9, (LM_B, LM_C, 2)).astype(np.float32)
+    lmk_t = rng.uniform(0.1, 0.9, (LM_B, LM_C, 2)).astype(np.float32)
+    pres = (rng.random((LM_B, LM_C)) < 0.8).astype(np.float32)
+    out.update({"lm_seed": LM_SEED, "lm_batch": LM_B, "lm_channels": LM_C, "lm_epoch": LM_EPOCH, "lm_landmarks": lmk,
+                "lm_landmarks_target": lmk_t, "lm_presence": pres, "region_names": np.array(list(REGIONS)),
+                "region_weights": np.array([w for w, _ in REGIONS.values()])})
+    with tempfile.TemporaryDirectory() as d:
+        for k, (_, idx) in REGIONS.items():
+            np.save(os.path.join(d, k + ".npy"), idx)
+            out["region_" + k] = idx
+        folder = {"folder": d, "files": {k: k + ".npy" for k in REGIONS}}
+        v_cfg = {"flame_indices": folder, "weights": {"head": .5, "face_w_ears": .75, "face": 1.}}
+        r_cfg = {"flame_indices": folder, "weights": {"face": .5, "face_w_ears": .5}}
+        for red in ("sum", "mean", "none"):
+            crits = [R.keypoint_losses.IoULoss(), R.Vertices3DLoss("l2", LM_B, FLAME_CONSTS, v_cfg),
+                     R.ReprojectionLoss("smooth_l1", LM_B, FLAME_CONSTS, 256, r_cfg), R.vis_loss.LandmarksLossWVisibility("smooth_l1")]
+            module = R.loss_module.LossModule(
+                names=["heatmap_loss", "vertices3d_loss", "reprojection_loss", "landmarks_loss"],
+                output_keys=["OUTPUT_LANDMARKS_HEATMAP", "OUTPUT_3DMM_PARAMS", "OUTPUT_3DMM_PARAMS",
+                             ["OUTPUT_2D_LANDMARKS", "TARGET_2D_LANDMARKS_PRESENCE"]],
+                target_keys=["TARGET_LANDMARKS_HEATMAP", "TARGET_3D_MODEL_VERTICES", "TARGET_2D_FULL_LANDMARKS",
+                             ["TARGET_2D_LANDMARKS", "TARGET_2D_LANDMARKS_PRESENCE"]],
+                criterions=crits, weights=[1.0, 50.0, 0.05, 100.0], schedule=[0, 0, 0, LM_EPOCH + 1], reduction=red)
+            p = params.clone().requires_grad_(True)
+            x = torch.from_numpy(logits).requires_grad_(True)
+            preds = {"OUTPUT_LANDMARKS_HEATMAP": x, "OUTPUT_3DMM_PARAMS": p * 1.0, "OUTPUT_2D_LANDMARKS": torch.from_numpy(lmk)}
+            tgts = {"TARGET_LANDMARKS_HEATMAP": R.flame.uint8_to_float32(torch.from_numpy(t8)), "TARGET_3D_MODEL_VERTICES": tgt3d,
+                    "TARGET_2D_FULL_LANDMARKS": tgt2d, "TARGET_2D_LANDMARKS": torch.from_numpy(lmk_t),
+                    "TARGET_2D_LANDMARKS_PRESENCE": torch.from_numpy(pres)}
+            total, terms = module(preds, tgts, LM_EPOCH)
+            assert "landmarks_loss" not in terms  # gated by the schedule
+            gp, gx = torch.autograd.grad(total.sum(), (p, x))
+            out[f"lm_{red}_total"] = total.detach().numpy()
+            for k, v in terms.items():
+                out[f"lm_{red}_{k}"] = np.float32(v.detach())
+            if red == "sum":
+                out["lm_sum_grad_params"], out["lm_sum_grad_heatmap"] = gp.numpy(), gx.numpy()
+            # the same module at an epoch where all four terms are live
+            total4, terms4 = module(preds, tgts, LM_EPOCH + 1)
+            out[f"lm_{red}_total_all"] = total4.detach().numpy()
+            out[f"lm_{red}_landmarks_loss"] = np.float32(terms4["landmarks_loss"].detach())
+    np.savez_compressed(OUT, **out)
+    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+
+
+if __name__ == "__main__":
+    main()

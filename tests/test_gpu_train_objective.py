@@ -1,0 +1,436 @@
+"""GPU: the training-objective kernels (csrc/train_objective.hip) through `coder`, `losses`, `metrics` and `loss_module`,
+against the reference's own results (tests/golden/train_objective_golden.npz) and the float64 restatement
+(tests/train_objective_restatement.py). Every fp32 bar is also met by the reference's torch fp32 statement on this GPU."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import train_objective_restatement as rs
+from dad_3dheads_amd import landmarks, synthetic
+from dad_3dheads_amd.coder import HeatmapCoder
+from dad_3dheads_amd.flame import FLAME_CONSTS
+from dad_3dheads_amd.head_mesh import HeadMesh
+from dad_3dheads_amd.loss_module import LossModule
+from dad_3dheads_amd.losses import IoULoss, LandmarksLossWVisibility
+from dad_3dheads_amd import metrics
+from oracle import flame_ref
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_objective_golden.npz")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _cases(g, key):
+    return [c.split(":") for c in g[key]]
+
+
+def _cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+# ---- heatmap encode --------------------------------------------------------------------------------------------------
+def test_encode_is_the_reference_coder_byte_for_byte(golden):
+    for name, img, stride, radius in _cases(golden, "coder_cases"):
+        radius = radius if radius == "pointwise" else int(radius)
+        kp, pr = golden[f"coder_{name}_keypoints"], golden[f"coder_{name}_presence"]
+        coder = HeatmapCoder({"img_size": int(img), "stride": int(stride), "radius": radius}, kp.shape[1])
+        for form in ("raw", "uint8", "float"):
+            got = coder.encode(_cu(kp), _cu(pr), form=form).cpu().numpy()
+            ref = golden[f"coder_{name}_{form}"]
+            assert got.dtype == ref.dtype and got.tobytes() == ref.tobytes(), (name, form)
+        assert int(coder.invalid_points.item()) == 0  # the NaN points are absent
+        item = coder(kp[0], pr[0])  # the per-item NumPy contract
+        assert item.dtype == np.float32 and item.tobytes() == golden[f"coder_{name}_raw"][0].tobytes()
+
+
+@pytest.mark.parametrize("batch", [2, 64, 256])
+def test_encode_batches_match_the_restatement(batch):
+    rng = np.random.default_rng(batch)
+    kp = rng.uniform(-30, 290, (batch, 68, 2)).astype(np.float32)
+    pr = rng.random((batch, 68)) < 0.9
+    coder = HeatmapCoder({"img_size": 256, "stride": 4, "radius": 5}, 68)
+    got = coder.encode(_cu(kp), _cu(pr), form="uint8")
+    assert got.shape == (batch, 68, 64, 64) and got.dtype == torch.uint8
+    assert got.cpu().numpy().tobytes() == rs.encode(kp, pr, 64, 4, 5, "uint8").tobytes()
+    again = coder.encode(_cu(kp), _cu(pr), form="uint8")
+    assert torch.equal(got, again)
+
+
+def test_invalid_points_are_counted_and_strict_raises():
+    kp = np.full((3, 4, 2), 100.0, dtype=np.float32)
+    pr = np.ones((3, 4), dtype=bool)
+    kp[0, 1, 0], kp[2, 3, 1], kp[1, 2, 0] = np.nan, np.inf, np.nan
+    pr[1, 2] = False  # absent: not counted
+    coder = HeatmapCoder({"img_size": 256, "stride": 4, "radius": 5}, 4)
+    out = coder.encode(_cu(kp), _cu(pr), form="float")
+    assert int(coder.invalid_points.item()) == 2
+    assert float(out[0, 1].abs().sum()) == 0.0 and float(out[2, 3].abs().sum()) == 0.0 and float(out[0, 0].sum()) > 0
+    coder.encode(_cu(kp), _cu(pr), form="raw")
+    assert int(coder.invalid_points.item()) == 4  # accumulates until the caller resets it
+    with pytest.raises(ValueError):
+        coder.encode(_cu(kp), _cu(pr), strict=True)
+    with pytest.raises(ValueError):
+        coder(kp[0], pr[0])
+
+
+# ---- heatmap IoU -----------------------------------------------------------------------------------------------------
+def _torch_iou(x, t):
+    """keypoint_losses.py:11-30, the reference's statement."""
+    def op_sum(v):
+        return v.view(v.shape[0], v.shape[1], -1).sum(2)
+
+    y = torch.sigmoid(x)
+    iou = (op_sum(t * y) + 1e-6) / (op_sum(t ** 2) + op_sum(y ** 2) - op_sum(t * y) + 1e-6)
+    return 1 - torch.mean(iou), iou
+
+
+def _iou64(x, t):
+    """The float64 restatement, on the device for large batches."""
+    s = torch.sigmoid(x.double())
+    t = ((t.double() / 255.0).float() if t.dtype == torch.uint8 else t).double()  # the fp32 target get_input makes
+    ax = tuple(range(2, x.ndim))
+    st, tt, ss = (t * s).sum(ax), (t * t).sum(ax), (s * s).sum(ax)
+    n, d = st + 1e-6, tt + ss - st + 1e-6
+    iou = n / d
+    k = (-1.0 / (iou.numel() * d * d))[..., None, None]
+    grad = k * (t * d[..., None, None] - n[..., None, None] * (2 * s - t)) * s * (1 - s)
+    return 1 - iou.mean(), iou, grad
+
+
+def _check_iou(loss, iou, grad, ref_loss, ref_iou, ref_grad):
+    assert abs(float(loss) - float(ref_loss)) <= 2e-7
+    if iou is not None:
+        assert float(((iou.double() - ref_iou).abs() / ref_iou.abs()).max()) <= 1e-6
+    gmax = float(ref_grad.abs().max())
+    assert float((grad.double() - ref_grad).abs().max()) <= 2e-6 * gmax
+
+
+def test_iou_loss_meets_the_golden_and_the_restatement(golden):
+    for name, seed, b, c, h, w in _cases(golden, "iou_cases"):
+        logits, t8 = rs.iou_inputs(int(seed), int(b), int(c), int(h), int(w))
+        x0 = _cu(logits)
+        t_u8 = _cu(t8)
+        t_f = _cu(t8.astype(np.float32) / np.float32(255.0))
+        ref_loss, ref_iou, ref_grad = _iou64(x0, t_u8)
+        assert abs(float(ref_loss) - float(golden[f"iou_{name}_loss"])) <= 2e-7
+        for tgt in (t_u8, t_f):
+            x = x0.clone().requires_grad_(True)
+            loss = IoULoss()(x, tgt)
+            loss.backward()
+            _check_iou(loss.detach(), None, x.grad, ref_loss, ref_iou, ref_grad)
+            assert float((x.grad.cpu() - torch.from_numpy(golden[f"iou_{name}_grad"])).abs().max()) <= 2e-6 * float(ref_grad.abs().max())
+            assert float(x.grad[0, 0].abs().max()) < 1e-25  # saturated logits: s (1 - s) underflows
+            assert abs(float(metrics.soft_iou(torch.sigmoid(x0), tgt)) - float(golden[f"iou_{name}_soft_iou"])) <= 2e-7
+        # the reference's own torch fp32 statement on this GPU meets the same bars
+        x = x0.clone().requires_grad_(True)
+        loss, iou = _torch_iou(x, t_f)
+        loss.backward()
+        _check_iou(loss.detach(), iou.detach(), x.grad, ref_loss, ref_iou, ref_grad)
+
+
+@pytest.mark.parametrize("batch,hw", [(2, (64, 64)), (64, (64, 64)), (256, (64, 64)), (3, (5, 7)), (4, (37, 41))])
+def test_iou_loss_batches_and_ragged_shapes(batch, hw):
+    logits, t8 = rs.iou_inputs(500 + batch, batch, 68 if hw == (64, 64) else 6, *hw)
+    x0, t = _cu(logits), _cu(t8)
+    ref_loss, ref_iou, ref_grad = _iou64(x0, t)
+    x = x0.clone().requires_grad_(True)
+    loss = IoULoss()(x, t)
+    loss.backward()
+    from dad_3dheads_amd.losses import heatmap_iou_terms
+    p, _, _, sums, out = heatmap_iou_terms(x0, t, sigmoid=True)
+    n, d = sums[:, 0] + 1e-6, sums[:, 1] + sums[:, 2] - sums[:, 0] + 1e-6
+    _check_iou(loss.detach(), (n / d).view_as(ref_iou), x.grad, ref_loss, ref_iou, ref_grad)
+    assert float(out[0]) == float(loss)
+    # the torch fp32 statement meets the same bars at this size too
+    x = x0.clone().requires_grad_(True)
+    tl, ti = _torch_iou(x, t.float() / 255.0)
+    tl.backward()
+    _check_iou(tl.detach(), ti.detach(), x.grad, ref_loss, ref_iou, ref_grad)
+
+
+def test_iou_loss_is_bit_reproducible_and_propagates_nan():
+    logits, t8 = rs.iou_inputs(7, 8, 68, 64, 64)
+    runs = []
+    for _ in range(2):
+        x = _cu(logits).requires_grad_(True)
+        loss = IoULoss()(x, _cu(t8))
+        loss.backward()
+        runs.append((loss.detach().clone(), x.grad.clone()))
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+    bad = logits.copy()
+    bad[3, 5, 10, 11] = np.nan
+    x = _cu(bad).requires_grad_(True)
+    loss = IoULoss()(x, _cu(t8))
+    loss.backward()
+    assert torch.isnan(loss)
+    nan = torch.isnan(x.grad)
+    assert bool(nan[3, 5].all()) and int(nan.sum()) == 64 * 64
+
+
+def test_encode_then_iou_on_uint8_equals_the_float_path():
+    rng = np.random.default_rng(3)
+    kp, pr = rng.uniform(0, 256, (16, 68, 2)).astype(np.float32), rng.random((16, 68)) < 0.9
+    coder = HeatmapCoder({"img_size": 256, "stride": 4, "radius": 5}, 68)
+    t8, tf = coder.encode(_cu(kp), _cu(pr), form="uint8"), coder.encode(_cu(kp), _cu(pr), form="float")
+    assert torch.equal(t8.cpu().float().div(255.0), tf.cpu())  # the float form is uint8 / 255 as torch divides on the CPU
+    logits = torch.randn((16, 68, 64, 64), generator=torch.Generator().manual_seed(2)).cuda()
+    res = []
+    for t in (t8, tf):
+        x = logits.clone().requires_grad_(True)
+        loss = IoULoss()(x, t)
+        loss.backward()
+        res.append((loss.detach(), x.grad))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+
+
+def test_iou_refuses_a_target_that_requires_grad():
+    x = torch.zeros((1, 2, 4, 4), device="cuda", requires_grad=True)
+    with pytest.raises(RuntimeError, match="prediction only"):
+        IoULoss()(x, torch.zeros((1, 2, 4, 4), device="cuda", requires_grad=True))
+
+
+# ---- landmark loss with visibility -----------------------------------------------------------------------------------
+def test_visibility_loss_meets_the_golden(golden):
+    pred, pp, tgt, tp = rs.visibility_inputs(81, 3, 68)
+    for crit in rs.CRITERIA:
+        for p_np, key in ((pred, "vis"), (np.where(np.isnan(pred), np.float32(0.25), pred), "vis_clean")):
+            x = _cu(p_np).requires_grad_(True)
+            loss = LandmarksLossWVisibility(crit)([x, _cu(pp)], [_cu(tgt), _cu(tp)])
+            loss.backward()
+            val64, grad64 = rs.visibility_loss(p_np, pp, tgt, tp, crit)
+            g = x.grad.cpu().numpy()
+            ref_g = golden[f"{key}_{crit}_grad"]
+            assert np.array_equal(np.isnan(g), np.isnan(ref_g)) and np.array_equal(np.isnan(g), np.isnan(grad64))
+            fin = ~np.isnan(grad64)
+            assert np.abs(g[fin] - grad64[fin]).max() <= 1e-6 * np.abs(grad64[fin]).max()
+            if key == "vis":
+                assert torch.isnan(loss)  # NaN * presence 0 is NaN: the reference multiplies
+            else:
+                assert abs(float(loss) - val64) <= 1e-6 * abs(val64)
+                assert abs(float(golden[f"{key}_{crit}_loss"]) - val64) <= 1e-6 * abs(val64)
+
+
+@pytest.mark.parametrize("batch", [2, 64, 256])
+def test_visibility_loss_batches(batch):
+    pred, pp, tgt, tp = rs.visibility_inputs(900 + batch, batch, 68)
+    pred = np.nan_to_num(pred)
+    for crit in rs.CRITERIA:
+        x = _cu(pred).requires_grad_(True)
+        loss = LandmarksLossWVisibility(crit)([x, _cu(pp)], [_cu(tgt), _cu(tp)])
+        (loss * 3.0).backward()
+        val64, grad64 = rs.visibility_loss(pred, pp, tgt, tp, crit)
+        assert abs(float(loss) - val64) <= 1e-6 * abs(val64)
+        assert np.abs(x.grad.cpu().numpy() - 3.0 * grad64).max() <= 1e-6 * 3.0 * np.abs(grad64).max()
+        # the reference's torch fp32 statement meets the same bars
+        xr = _cu(pred).requires_grad_(True)
+        fn = {"l1": torch.nn.L1Loss, "l2": torch.nn.MSELoss, "smooth_l1": torch.nn.SmoothL1Loss}[crit]()
+        ref = fn(xr * _cu(pp)[..., None], _cu(tgt) * _cu(tp)[..., None])
+        ref.backward()
+        assert abs(float(ref) - val64) <= 1e-6 * abs(val64)
+        assert np.abs(xr.grad.cpu().numpy() - grad64).max() <= 1e-6 * np.abs(grad64).max()
+
+
+# ---- keypoint metrics ------------------------------------------------------------------------------------------------
+def test_keypoint_metrics_meet_the_golden(golden):
+    for name, seed, b, n, dims, spread in _cases(golden, "kp_cases"):
+        p, q, pres, bbox = rs.keypoint_inputs(int(seed), int(b), int(n), int(dims), float(spread))
+        if int(dims) == 2:
+            out, err = metrics.keypoint_errors(_cu(p), _cu(q), _cu(bbox), presence=_cu(pres), pred_scale=256, target_scale=256,
+                                               thresholds=(0.05, 0.1))
+            e64, n64 = rs.keypoint_errors(p, q, bbox, presence=pres, pred_scale=256, target_scale=256)
+        else:
+            idx = golden[f"{name}_index"]
+            out, err = metrics.keypoint_errors(_cu(p), _cu(q), None, index=idx, cube=True, thresholds=(0.05, 0.1))
+            e64, n64 = rs.keypoint_errors(p, q, None, index=idx, cube=True)
+        e = err.cpu().numpy()
+        assert np.allclose(e[:, 0], e64, rtol=1e-6, atol=0) and np.array_equal(e[:, 1], n64)
+        assert abs(float(out[0]) - float(golden[f"{name}_nme"])) <= 1e-6 * float(golden[f"{name}_nme"])
+        assert np.allclose(e[:, 0] / e[:, 1], golden[f"{name}_nme_items"], rtol=1e-6, atol=0)
+        assert float(out[1]) == float(golden[f"{name}_fr_0.05"]) and float(out[2]) == float(golden[f"{name}_fr_0.1"])
+    # the functional surface
+    p, q, pres, bbox = rs.keypoint_inputs(91, 16, 68, 2, 0.02)
+    pt, qt = _cu(p * 256 * pres[..., None]), _cu(q * pres[..., None] * 256)
+    assert abs(float(metrics.keypoints_nme(pt, qt, _cu(bbox))) - float(golden["kp2d_nme"])) <= 1e-6 * float(golden["kp2d_nme"])
+    assert float(metrics.percentage_of_errors_below_IOD(pt, qt, _cu(bbox), threshold=0.1)) == float(golden["kp2d_fr_0.1"])
+
+
+@pytest.mark.parametrize("batch", [64, 256])
+def test_keypoint_metrics_batches(batch):
+    p, q, pres, bbox = rs.keypoint_inputs(40 + batch, batch, 2094, 3, 0.03)
+    idx = np.arange(0, 2094, 1)
+    out, err = metrics.keypoint_errors(_cu(p), _cu(q), None, index=idx, cube=True, thresholds=(0.05, 0.1))
+    e64, n64 = rs.keypoint_errors(p, q, None, index=idx, cube=True)
+    assert np.allclose(err[:, 0].cpu().numpy(), e64, rtol=1e-6, atol=0)
+    nme, rates = rs.nme_and_rates(e64, n64)
+    assert abs(float(out[0]) - nme) <= 1e-6 * nme
+    ratio = e64 / n64
+    for k, thr in enumerate((0.05, 0.1)):
+        if np.all(np.abs(ratio - thr) >= 1e-5 * thr):
+            assert float(out[1 + k]) == rates[k]
+
+
+def test_metric_classes_accumulate_over_three_steps():
+    fr, nme, iou = metrics.FailureRate(threshold=0.1), metrics.KeypointsNME(), metrics.SoftIoUMetric()
+    vals = []
+    for step in range(3):
+        p, q, pres, bbox = rs.keypoint_inputs(60 + step, 8, 68, 2, 0.02)
+        gts = {"keypoints": _cu(q * 256), "bboxes": _cu(bbox)}
+        e64, n64 = rs.keypoint_errors(p, q, bbox, pred_scale=256, target_scale=256)
+        v_fr, v_nme = fr(_cu(p * 256), gts), nme(_cu(p * 256), gts)
+        logits, t8 = rs.iou_inputs(70 + step, 2, 5, 16, 16)
+        v_iou = iou(torch.sigmoid(_cu(logits)), _cu(t8))
+        n, r = rs.nme_and_rates(e64, n64, (0.1,))
+        assert float(v_fr) == r[0] and abs(float(v_nme) - 100 * n) <= 1e-6 * 100 * n
+        vals.append((r[0], 100 * n, float(v_iou)))
+    assert abs(float(fr.compute()) - np.mean([v[0] for v in vals])) <= 1e-6
+    assert abs(float(nme.compute()) - np.mean([v[1] for v in vals])) <= 1e-5 * np.mean([v[1] for v in vals])
+    assert abs(float(iou.compute()) - np.mean([v[2] for v in vals])) <= 1e-6
+    assert float(fr.states["total"]) == 3.0 and float(iou.states["total"]) == 3.0
+    fr.reset()
+    assert float(fr.states["total"]) == 0.0
+
+
+# ---- StepMetrics and LossModule on the decode --------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hm(flame_model, static):
+    return HeadMesh(flame_model=flame_model, landmarks=landmarks.canonical("445", static), static=static, device=0)
+
+
+def test_step_metrics_match_the_restatement(hm, flame_consts):
+    b, c = 6, 68
+    face = np.arange(0, 5023, 3)
+    params = _cu(synthetic.synthetic_params(b, seed=120))
+    tgt3d = flame_ref.vertices_3d(flame_consts, torch.from_numpy(synthetic.synthetic_params(b, seed=121)), zero_rotation=True)
+    tgt2d = flame_ref.reprojected_vertices(flame_consts, torch.from_numpy(synthetic.synthetic_params(b, seed=122)))
+    logits, t8 = rs.iou_inputs(123, b, c, 64, 64)
+    rng = np.random.default_rng(124)
+    lmk, lmk_t = rng.uniform(0.1, 0.9, (b, c, 2)).astype(np.float32), rng.uniform(0.1, 0.9, (b, c, 2)).astype(np.float32)
+    pres = (rng.random((b, c)) < 0.8).astype(np.float32)
+    bbox = np.stack([np.zeros(b), np.zeros(b), rng.integers(150, 250, b), rng.integers(150, 250, b)], 1).astype(np.int64)
+    outputs = {"OUTPUT_LANDMARKS_HEATMAP": _cu(logits), "OUTPUT_2D_LANDMARKS": _cu(lmk), "OUTPUT_3DMM_PARAMS": params}
+    targets = {"TARGET_LANDMARKS_HEATMAP": _cu(t8), "TARGET_2D_LANDMARKS": _cu(lmk_t), "TARGET_2D_LANDMARKS_PRESENCE": _cu(pres),
+               "TARGET_2D_FULL_LANDMARKS": tgt2d.cuda(), "TARGET_3D_MODEL_VERTICES": tgt3d.cuda(), "INPUT_BBOX_KEY": _cu(bbox)}
+    sm = metrics.StepMetrics(hm, {"face": face}, 256)
+    got = sm(outputs, targets)
+    assert set(got) == {"heatmap_iou", "fr_2d_005", "fr_2d_01", "nme_2d", "reproject_fr_2d_005", "reproject_fr_2d_01",
+                        "reproject_nme_2d", "fr_3d_005", "fr_3d_01", "nme_3d"}
+    assert abs(float(got["heatmap_iou"]) - rs.soft_iou(rs.sigmoid64(logits), t8)) <= 2e-7
+    proj = hm.reprojected_vertices(params.clone(), to_2d=True).cpu().numpy()
+    v3 = hm.vertices_3d(params, zero_rotation=True).cpu().numpy()
+    branches = {"": rs.keypoint_errors(lmk, lmk_t, bbox, presence=pres, pred_scale=256, target_scale=256),
+                "reproject_": rs.keypoint_errors(proj, tgt2d.numpy(), bbox, index=face),
+                "3d": rs.keypoint_errors(v3, tgt3d.numpy(), None, index=face, cube=True)}
+    for prefix, (e, n) in branches.items():
+        nme, rates = rs.nme_and_rates(e, n)
+        names = (f"fr_3d_005", "fr_3d_01", "nme_3d") if prefix == "3d" else (f"{prefix}fr_2d_005", f"{prefix}fr_2d_01", f"{prefix}nme_2d")
+        assert abs(float(got[names[2]]) - 100 * nme) <= 1e-6 * 100 * nme, names
+        assert [float(got[names[0]]), float(got[names[1]])] == rates, names
+    again = sm(outputs, targets)
+    run = sm.compute()
+    assert float(run["nme_3d"]) == pytest.approx(float(again["nme_3d"]), rel=1e-6)
+    assert float(sm.metrics_3d.nme.states["total"]) == 2.0
+
+
+def _loss_module(golden, flame_model, static, reduction):
+    import tempfile
+
+    d = tempfile.mkdtemp()
+    for k in golden["region_names"]:
+        np.save(os.path.join(d, f"{k}.npy"), golden[f"region_{k}"])
+    folder = {"folder": d, "files": {str(k): f"{k}.npy" for k in golden["region_names"]}}
+    b = int(golden["lm_batch"])
+    cfg = {"reduction": reduction, "criterions": [
+        {"name": "heatmap_loss", "target_key": "TARGET_LANDMARKS_HEATMAP", "output_key": "OUTPUT_LANDMARKS_HEATMAP", "weight": 1.,
+         "loss": {"_target_": "model_training.losses.IoULoss"}},
+        {"name": "vertices3d_loss", "target_key": "TARGET_3D_MODEL_VERTICES", "output_key": "OUTPUT_3DMM_PARAMS", "weight": 50.,
+         "loss": {"_target_": "model_training.losses.Vertices3DLoss", "criterion": "l2", "batch_size": b, "consts": FLAME_CONSTS,
+                  "weights_and_indices": {"flame_indices": folder, "weights": {"head": .5, "face_w_ears": .75, "face": 1.}}}},
+        {"name": "reprojection_loss", "target_key": "TARGET_2D_FULL_LANDMARKS", "output_key": "OUTPUT_3DMM_PARAMS", "weight": 0.05,
+         "loss": {"_target_": "model_training.losses.ReprojectionLoss", "criterion": "smooth_l1", "batch_size": b,
+                  "consts": FLAME_CONSTS, "img_size": 256,
+                  "weights_and_indices": {"flame_indices": folder, "weights": {"face": .5, "face_w_ears": .5}}}},
+        {"name": "landmarks_loss", "target_key": ["TARGET_2D_LANDMARKS", "TARGET_2D_LANDMARKS_PRESENCE"],
+         "output_key": ["OUTPUT_2D_LANDMARKS", "TARGET_2D_LANDMARKS_PRESENCE"], "weight": 100., "epoch_start": int(golden["lm_epoch"]) + 1,
+         "loss": {"_target_": "model_training.losses.LandmarksLossWVisibility", "criterion": "smooth_l1"}}]}
+    return LossModule.from_config(cfg, head_mesh_kwargs={"flame_model": flame_model, "static": static, "device": 0})
+
+
+def _lm_inputs(golden, flame_consts):
+    seed, b, c = int(golden["lm_seed"]), int(golden["lm_batch"]), int(golden["lm_channels"])
+    params = torch.from_numpy(synthetic.synthetic_params(b, seed=seed))
+    tgt3d = flame_ref.vertices_3d(flame_consts, torch.from_numpy(synthetic.synthetic_params(b, seed=seed + 1)), zero_rotation=True)
+    tgt2d = flame_ref.reprojected_vertices(flame_consts, torch.from_numpy(synthetic.synthetic_params(b, seed=seed + 2)))
+    logits, t8 = rs.iou_inputs(seed + 3, b, c, 64, 64)
+    targets = {"TARGET_LANDMARKS_HEATMAP": _cu(t8), "TARGET_3D_MODEL_VERTICES": tgt3d.cuda(), "TARGET_2D_FULL_LANDMARKS": tgt2d.cuda(),
+               "TARGET_2D_LANDMARKS": _cu(golden["lm_landmarks_target"]), "TARGET_2D_LANDMARKS_PRESENCE": _cu(golden["lm_presence"])}
+    return params.cuda(), _cu(logits), _cu(golden["lm_landmarks"]), targets
+
+
+@pytest.mark.parametrize("reduction", ["sum", "mean", "none"])
+def test_loss_module_four_hip_criteria_against_the_golden(golden, flame_model, flame_consts, static, reduction):
+    module = _loss_module(golden, flame_model, static, reduction)
+    params, logits, lmk, targets = _lm_inputs(golden, flame_consts)
+    epoch = int(golden["lm_epoch"])
+    p, x = params.clone().requires_grad_(True), logits.clone().requires_grad_(True)
+    total, terms = module({"OUTPUT_LANDMARKS_HEATMAP": x, "OUTPUT_3DMM_PARAMS": p * 1.0, "OUTPUT_2D_LANDMARKS": lmk}, targets, epoch)
+    assert list(terms) == ["heatmap_loss", "vertices3d_loss", "reprojection_loss"]  # the schedule gates landmarks_loss
+    for k, v in terms.items():
+        ref = float(golden[f"lm_{reduction}_{k}"])
+        assert abs(float(v) - ref) <= 1e-4 * max(abs(ref), 1e-3), (k, float(v), ref)
+    ref_total = golden[f"lm_{reduction}_total"]
+    assert np.allclose(total.detach().cpu().numpy(), ref_total, rtol=1e-4, atol=0)
+    if reduction == "sum":
+        gp, gx = torch.autograd.grad(total, (p, x))
+        ref_gp, ref_gx = golden["lm_sum_grad_params"], golden["lm_sum_grad_heatmap"]
+        assert np.abs(gp.cpu().numpy() - ref_gp).max() <= 2e-4 * np.abs(ref_gp).max()
+        assert np.abs(gx.cpu().numpy() - ref_gx).max() <= 2e-6 * np.abs(ref_gx).max()
+    total4, terms4 = module({"OUTPUT_LANDMARKS_HEATMAP": x, "OUTPUT_3DMM_PARAMS": p * 1.0, "OUTPUT_2D_LANDMARKS": lmk}, targets, epoch + 1)
+    ref = float(golden[f"lm_{reduction}_landmarks_loss"])
+    assert abs(float(terms4["landmarks_loss"]) - ref) <= 1e-6 * abs(ref)
+    assert np.allclose(total4.detach().cpu().numpy(), golden[f"lm_{reduction}_total_all"], rtol=1e-4, atol=0)
+
+
+def test_objective_forward_backward_replays_from_a_graph(golden, flame_model, flame_consts, static):
+    """The whole four-term objective, forward and backward, captured on one stream; the replay is bit-equal to eager."""
+    module = _loss_module(golden, flame_model, static, "sum")
+    params, logits, lmk, targets = _lm_inputs(golden, flame_consts)
+    static_p, static_x = params.clone().requires_grad_(True), logits.clone().requires_grad_(True)
+    static_l = lmk.clone().requires_grad_(True)
+    epoch = int(golden["lm_epoch"]) + 1
+
+    def step(p, x, l_):
+        total, _ = module({"OUTPUT_LANDMARKS_HEATMAP": x, "OUTPUT_3DMM_PARAMS": p * 1.0, "OUTPUT_2D_LANDMARKS": l_}, targets, epoch)
+        total.backward()
+        return total
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            static_p.grad = static_x.grad = static_l.grad = None
+            step(static_p, static_x, static_l)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    static_p.grad = static_x.grad = static_l.grad = None
+    with torch.cuda.graph(graph):
+        static_total = step(static_p, static_x, static_l)
+    for seed in (131, 132):
+        new_p = _cu(synthetic.synthetic_params(int(golden["lm_batch"]), seed=seed))
+        new_x = logits + 0.1 * seed
+        with torch.no_grad():
+            static_p.copy_(new_p), static_x.copy_(new_x)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = (static_total.clone(), static_p.grad.clone(), static_x.grad.clone(), static_l.grad.clone())
+        p, x, l_ = new_p.clone().requires_grad_(True), new_x.clone().requires_grad_(True), lmk.clone().requires_grad_(True)
+        eager = step(p, x, l_)
+        torch.cuda.synchronize()
+        assert torch.equal(got[0], eager.detach())
+        assert torch.equal(got[1], p.grad) and torch.equal(got[2], x.grad) and torch.equal(got[3], l_.grad)
