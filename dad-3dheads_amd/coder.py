@@ -8,7 +8,8 @@ and the kernel (csrc/train_objective.hip) only places it, so every form is byte-
 
 Use `encode` in the training step, after the batch is on the GPU: it needs 35 KB of keypoints instead of the 17.8 MB of
 uint8 heatmaps a B = 64 batch carries from the loader. `__call__` keeps the reference's per-item NumPy contract, but it runs
-on the GPU: a forked DataLoader worker must not initialise HIP, so do not call it inside the loader.
+on the GPU: a forked DataLoader worker must not initialise HIP, so do not call it inside the loader. Use `dataset.FlameDataset`
+(CPU-only items) with its collate and `dataset.FlameBatchBuilder`, which calls `encode` after the batch is on the device.
 """
 from __future__ import annotations
 

@@ -1165,6 +1165,28 @@ dad3d_status dad3d_project_vertices(const float* vertices, const float* model_vi
                                    static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_gt_keypoints(const float* vertices, const float* model_view, const float* projection,
+                                const int32_t* frames, int batch, int nver, const int32_t* index, const int32_t* corners,
+                                const float* weights, int n_subset, int out_size, int resize_mode, float* full, float* subset_px,
+                                float* subset_norm, uint8_t* presence, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 0 && nver >= 0 && n_subset >= 0 && out_size > 0, "dad3d_gt_keypoints: bad argument");
+    DAD3D_REQUIRE(resize_mode == DAD3D_RESIZE_LONGEST_MAX_SIZE || resize_mode == DAD3D_RESIZE_RESIZE,
+                  "dad3d_gt_keypoints: unknown resize mode %d", resize_mode);
+    DAD3D_REQUIRE(batch <= 65535, "dad3d_gt_keypoints: batch %d beyond the launch grid", batch);
+    DAD3D_REQUIRE((long long)nver + n_subset <= 0x7fffff00LL, "dad3d_gt_keypoints: %d + %d points beyond the launch grid", nver,
+                  n_subset);
+    DAD3D_REQUIRE(n_subset == 0 || ((index != nullptr) != (corners != nullptr) && (corners == nullptr) == (weights == nullptr)),
+                  "dad3d_gt_keypoints: give either index or corners + weights for the subset");
+    if (batch == 0 || nver + n_subset == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(vertices && model_view && projection && frames, "dad3d_gt_keypoints: null input");
+    DAD3D_REQUIRE((nver == 0 || full) && (n_subset == 0 || (subset_px && subset_norm && presence)), "dad3d_gt_keypoints: null output");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    GtKeypointsArgs a{vertices, model_view, projection, frames, index, corners, weights, full, subset_px, subset_norm, presence,
+                      nver, n_subset, out_size, resize_mode};
+    return launch_gt_keypoints(a, batch, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_preprocess_images(const int64_t* descs, int batch, int out_size, const float* mean, const float* std,
                                      float* out, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && out_size > 0, "dad3d_preprocess_images: bad argument");

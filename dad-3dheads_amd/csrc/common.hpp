@@ -442,6 +442,23 @@ dad3d_status launch_heatmap_iou_grad(const IouArgs& a, bool vec, hipStream_t s);
 dad3d_status launch_visibility_loss(const VisibilityLossArgs& a, hipStream_t s);
 dad3d_status launch_keypoint_errors(const KeypointErrArgs& a, hipStream_t s);
 
+// training-batch ground truth (train_batch.hip): one lane per (item, subset point or vertex)
+struct GtKeypointsArgs {
+    const float* vertices;    // [B,nver,3]
+    const float* model_view;  // [B,16] row-major
+    const float* projection;  // [B,16] row-major
+    const int* frames;        // [B,8] image height, crop x, y, w, h, pad_top, pad_left, 0
+    const int* index;         // [n_subset] vertex ids (index mode), or null
+    const int* corners;       // [n_subset,3] vertex ids of the embedding faces (68-landmark mode), or null
+    const float* weights;     // [n_subset,3] barycentric weights (68-landmark mode)
+    float* full;              // [B,nver,2]
+    float* subset_px;         // [B,n_subset,2]
+    float* subset_norm;       // [B,n_subset,2]
+    uint8_t* presence;        // [B,n_subset]
+    int nver, n_subset, out_size, mode;
+};
+dad3d_status launch_gt_keypoints(const GtKeypointsArgs& a, int batch, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -5,9 +5,11 @@
 //     world = MV . [v; 1]          clip = P . world          xy = clip.xy / clip.w
 //     xy    = (x, H - y) - (crop_x, crop_y)                   xy_int = (int) xy   (visualize.py:22 `.astype(int)`)
 // One lane per vertex, matrices of the image in SGPR-uniform registers; a streaming kernel: 12 B in, 8 (+16 +8) B out
-// per vertex, HBM-bound. Products are summed k = 0..3 in order without contraction; numpy's sgemm may fuse or
-// reorder them, so agreement with the reference is to fp32 rounding (tests: 1e-3 px at image scale), not bitwise.
+// per vertex, HBM-bound. The arithmetic is projection_math.hpp's, shared with the training-batch kernel (train_batch.hip);
+// numpy's sgemm may fuse or reorder the products, so agreement with the reference is to fp32 rounding (tests: 1e-3 px at
+// image scale), not bitwise.
 #include "common.hpp"
+#include "projection_math.hpp"
 
 namespace dad3d {
 namespace {
@@ -16,22 +18,14 @@ __global__ __launch_bounds__(256) void project_vertices_kernel(const float* __re
                                                                const float* __restrict__ projection, const float* __restrict__ frame,
                                                                int nver, float* __restrict__ world_homo, float* __restrict__ xy,
                                                                int32_t* __restrict__ xy_int) {
-#pragma clang fp contract(off)
     const size_t b = blockIdx.y;
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nver) return;
-    const float* mv = model_view + b * 16;
-    const float* pm = projection + b * 16;
     const float* p = vertices + (b * nver + v) * 3;
-    const float in[4] = {p[0], p[1], p[2], 1.0f};
-    float w4[4], c4[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w4[i] = ((mv[4 * i] * in[0] + mv[4 * i + 1] * in[1]) + mv[4 * i + 2] * in[2]) + mv[4 * i + 3] * in[3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c4[i] = ((pm[4 * i] * w4[0] + pm[4 * i + 1] * w4[1]) + pm[4 * i + 2] * w4[2]) + pm[4 * i + 3] * w4[3];
-    const float height = frame[b * 3], cx = frame[b * 3 + 1], cy = frame[b * 3 + 2];
-    const float x = c4[0] / c4[3] - cx;
-    const float y = (height - c4[1] / c4[3]) - cy;
+    float w4[4];
+    model_view_point(model_view + b * 16, p[0], p[1], p[2], w4);
+    const float2 xy2 = project_onto_image(projection + b * 16, w4, frame[b * 3], frame[b * 3 + 1], frame[b * 3 + 2]);
+    const float x = xy2.x, y = xy2.y;
     const size_t o = b * nver + v;
     if (world_homo) reinterpret_cast<float4*>(world_homo)[o] = make_float4(w4[0], w4[1], w4[2], w4[3]);
     if (xy) reinterpret_cast<float2*>(xy)[o] = make_float2(x, y);

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .head_mesh import HeadMesh
+from .resize_geometry import calculate_paddings, py3round  # noqa: F401  (public names of this module)
 
 # keys of the CNN's output dict (model_training/data/config.py:16-23: every constant's value is its own name)
 OUTPUT_3DMM_PARAMS = "OUTPUT_3DMM_PARAMS"
@@ -33,20 +34,6 @@ OUTPUT_2D_LANDMARKS = "OUTPUT_2D_LANDMARKS"
 OUTPUT_LANDMARKS_HEATMAP = "OUTPUT_LANDMARKS_HEATMAP"
 _MEAN = (0.485, 0.456, 0.406)
 _STD = (0.229, 0.224, 0.225)
-
-
-def py3round(x: float) -> int:
-    """albumentations.augmentations.geometric.py3round (imported at predictor.py:12)."""
-    if abs(round(x) - x) == 0.5:
-        return int(2.0 * round(x / 2.0))
-    return int(round(x))
-
-
-def calculate_paddings(orig_h: int, orig_w: int) -> List[int]:
-    """model_training/model/utils.py:71-77 -> [top, bottom, left, right]."""
-    m = max(orig_h, orig_w)
-    top, left = int((m - orig_h) / 2), int((m - orig_w) / 2)
-    return [top, m - orig_h - top, left, m - orig_w - left]
 
 
 def find_3dmm_idx(key: str, consts: Dict[str, int]) -> int:

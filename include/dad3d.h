@@ -323,6 +323,30 @@ DAD3D_EXPORT dad3d_status dad3d_project_vertices(const float* vertices, const fl
                                     int32_t* xy_int, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ground-truth keypoints of a training batch: FlameDataset's per-sample geometry (model_training/data/flame_dataset.py:115-199)
+ * for B items in one launch, replacing `_load_mesh` (:115-127), `_project_vertices_onto_image` (:130-141),
+ * `_get_2d_landmarks_w_presence` (:143-171, with get_68_landmarks of data/utils.py:120-206), the keypoint half of
+ * `_transform` (albumentations 1.0.0 LongestMaxSize + PadIfNeeded or Resize on KeypointParams("xy"), :173-191) and the
+ * `landmarks / img_size` of `_form_anno_dict` (:198). All DEVICE pointers:
+ *   vertices [B,nver,3], model_view [B,4,4], projection [B,4,4] float32, row-major (the annotation JSON's layout)
+ *   frames   [B,8] int32 = (full image height, crop x, crop y, crop w, crop h, pad_top, pad_left, 0); the pads are
+ *            PadIfNeeded's on the LongestMaxSize-resized crop (ignored in DAD3D_RESIZE_RESIZE mode); w, h > 0
+ *   subset   index mode: index [n_subset] vertex ids, corners = weights = NULL;
+ *            68-landmark mode: corners [n_subset,3] vertex ids of the embedding faces, weights [n_subset,3], index = NULL.
+ *            Ids outside [0, nver) give a NaN point (absent), never a read.
+ * Outputs: full [B,nver,2] (TARGET_2D_FULL_LANDMARKS, out_size pixels), subset_px [B,n_subset,2] (out_size pixels: the heatmap
+ * coder's input), subset_norm [B,n_subset,2] = subset_px / out_size (TARGET_2D_LANDMARKS), presence [B,n_subset] uint8
+ * (0 < x < w and 0 < y < h in crop pixels). The resize step runs in float64 and rounds to fp32 once (the pinned numpy 1.22
+ * promotes np.float32 * float to float64). Agreement with the numpy reference is fp32 rounding in the two 4x4 products
+ * (sgemm order), exact after them. Stream-ordered, no allocation, no atomics, no host sync.
+ * --------------------------------------------------------------------------------------------- */
+enum { DAD3D_RESIZE_LONGEST_MAX_SIZE = 0, DAD3D_RESIZE_RESIZE = 1 };
+DAD3D_EXPORT dad3d_status dad3d_gt_keypoints(const float* vertices, const float* model_view, const float* projection,
+                                const int32_t* frames, int batch, int nver, const int32_t* index, const int32_t* corners,
+                                const float* weights, int n_subset, int out_size, int resize_mode, float* full, float* subset_px,
+                                float* subset_norm, uint8_t* presence, int device, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference's mesh losses, VALUE and GRADIENT w.r.t. the prediction, on vertices that are already in HBM (the outputs of
  * the differentiable decode). All pointers are DEVICE pointers; nothing is allocated, both calls can be captured into a graph.
  *
