@@ -4,21 +4,26 @@ Authoring-container only (needs /root/reference; the GPU box has none). Used by
 tests/golden/make_decode_golden.py to generate the committed fixtures and by
 tests/test_oracle_flame.py::test_oracle_bitwise_equals_live_reference (auto-skipped when the reference tree is absent).
 
-The reference cannot be imported as-is here: `hydra`, `smplx`,
-`pytorch_toolbelt` are not installed and `static/flame.pkl` is missing. This module registers
-minimal `sys.modules` stand-ins for exactly those imports:
+The reference cannot be imported as-is here: `hydra`, `smplx`, `pytorch_toolbelt`, `omegaconf`,
+`coloredlogs`, `cv2`, `skimage` and `fire` are not installed and `static/flame.pkl` is missing. This module holds the only
+stand-in helpers (`stand_in`, `bypass_package_init`) and the shared stand-ins (`install_stand_ins`):
 
-    hydra.utils.instantiate        (model_training/model/__init__.py:1)  -> never called on this path
-    pytorch_toolbelt.utils         (model_training/model/utils.py:12)    -> never called on this path
+    hydra.utils.instantiate        (model_training/model/__init__.py:1)  -> calls the class a config names
+    pytorch_toolbelt.utils         (model_training/model/utils.py:12)    -> image_to_tensor: HWC -> CHW
     smplx.utils.{Struct,to_tensor,to_np}  (flame.py:6, model/utils.py:2) -> 3 tiny helpers re-stated
     smplx.lbs.lbs                  (flame.py:5)                          -> oracle.flame_ref.lbs
+    smplx.lbs.find_dynamic_lmk_idx_and_bcoords  (data/utils.py, benchmark utils.py) -> the zero-pose case, re-stated
+    omegaconf, coloredlogs, cv2, skimage.io, fire                        -> names only, never called
 
-and patches `model_training.model.flame.get_flame_model` to hand back the seeded synthetic model.
+The generators under tests/golden/ register what is theirs alone through the same `stand_in`. The module
+patches `model_training.model.flame.get_flame_model` to hand back the seeded synthetic model.
 Everything else -- `HeadMesh`, `FLAMELayer`, `FlameParams`, `rot_mat_from_6dof` -- is the reference's
 code, byte for byte, executed from where it lies. Nothing is copied into this repository.
 """
 from __future__ import annotations
 
+import functools
+import importlib
 import os
 import sys
 import types
@@ -33,42 +38,77 @@ def reference_available() -> bool:
     return os.path.isfile(os.path.join(REFERENCE_ROOT, "model_training", "head_mesh.py"))
 
 
-def _install_stubs():
+def stand_in(name, **attrs):
+    """Register an empty module with `attrs` as `sys.modules[name]`, replacing whatever holds that name, and hang it on its parent
+    package when that is registered too. Every stand-in of this module and of the generators under tests/golden/ is made here."""
+    m = types.ModuleType(name)
+    m.__dict__.update(attrs)
+    sys.modules[name] = m
+    parent, _, leaf = name.rpartition(".")
+    if parent in sys.modules:
+        setattr(sys.modules[parent], leaf, m)
+    return m
+
+
+def bypass_package_init(package):
+    """Register the reference package `package` (`model_training.data`, ...) as an empty package over its own directory: its
+    sub-modules import from where they lie, its `__init__` (which pulls in more uninstalled imports) never runs."""
+    return stand_in(package, __path__=[os.path.join(REFERENCE_ROOT, *package.split("."))])
+
+
+class Struct:
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def _to_tensor(array, dtype=torch.float32):
+    return (array if torch.is_tensor(array) else torch.tensor(array)).to(dtype)
+
+
+def _to_np(array, dtype=np.float32):
+    if "scipy.sparse" in str(type(array)):
+        array = array.todense()
+    return np.array(array, dtype=dtype)
+
+
+def find_dynamic_lmk_idx_and_bcoords(vertices, pose, dynamic_lmk_faces_idx, dynamic_lmk_b_coords, neck_kin_chain, dtype=torch.float32):
+    """`smplx.lbs.find_dynamic_lmk_idx_and_bcoords` for the only way the reference calls it: a ZERO pose. Every rotation of the
+    neck chain is then the identity, the yaw angle is 0 and the function returns row 0 of the contour tables (smplx 0.1.26,
+    lbs.py: `y_rot_angle = round(clamp(-yaw * 180 / pi, max=39))`, negative angles remapped, then `index_select(table, 0,
+    y_rot_angle)`). PARITY UNPINNED for this one function, like `smplx.lbs.lbs` (see oracle/flame_ref.py)."""
+    assert float(pose.abs().max()) == 0.0, "the stand-in covers the reference's only call: a zero pose"
+    y_rot_angle = torch.zeros(vertices.shape[0], dtype=torch.long)
+    return torch.index_select(dynamic_lmk_faces_idx, 0, y_rot_angle), torch.index_select(dynamic_lmk_b_coords, 0, y_rot_angle)
+
+
+def _instantiate(cfg, *args):
+    """`hydra.utils.instantiate` for a config that names a class: `cfg["_target_"]`, imported and called with `args`."""
+    module, _, name = cfg["_target_"].rpartition(".")
+    return getattr(importlib.import_module(module), name)(*args)
+
+
+@functools.lru_cache(maxsize=None)
+def install_stand_ins():
+    """The stand-ins every path through the reference shares, each defined here once with all the attributes any of its users
+    reads. Installed by name, whatever held the name before, once per process: what a generator registers afterwards through
+    `stand_in` (a `cv2` that serves its seeded images, say) is not undone by a later `load_reference_*` call."""
     from . import flame_ref
 
-    def _mod(name):
-        m = types.ModuleType(name)
-        sys.modules[name] = m
-        return m
-
-    if "hydra" not in sys.modules:
-        hydra = _mod("hydra")
-        hydra.utils = _mod("hydra.utils")
-        hydra.utils.instantiate = lambda *a, **k: (_ for _ in ()).throw(RuntimeError("stub"))
-    if "pytorch_toolbelt" not in sys.modules:
-        ptb = _mod("pytorch_toolbelt")
-        ptb.utils = _mod("pytorch_toolbelt.utils")
-    if "smplx" not in sys.modules:
-        smplx = _mod("smplx")
-        su = _mod("smplx.utils")
-        sl = _mod("smplx.lbs")
-        smplx.utils, smplx.lbs = su, sl
-
-        class Struct:
-            def __init__(self, **kw):
-                for k, v in kw.items():
-                    setattr(self, k, v)
-
-        def to_tensor(array, dtype=torch.float32):
-            return (array if torch.is_tensor(array) else torch.tensor(array)).to(dtype)
-
-        def to_np(array, dtype=np.float32):
-            if "scipy.sparse" in str(type(array)):
-                array = array.todense()
-            return np.array(array, dtype=dtype)
-
-        su.Struct, su.to_tensor, su.to_np = Struct, to_tensor, to_np
-        sl.lbs = lambda *a, **k: flame_ref.lbs(*a, **k)  # noqa: E731
+    stand_in("smplx")
+    stand_in("smplx.utils", Struct=Struct, to_tensor=_to_tensor, to_np=_to_np)
+    stand_in("smplx.lbs", lbs=lambda *a, **k: flame_ref.lbs(*a, **k), find_dynamic_lmk_idx_and_bcoords=find_dynamic_lmk_idx_and_bcoords)
+    stand_in("hydra")
+    stand_in("hydra.utils", instantiate=_instantiate, get_original_cwd=os.getcwd)
+    stand_in("pytorch_toolbelt")
+    stand_in("pytorch_toolbelt.modules")  # imported by layers.py:8, used only by heads no model here builds
+    stand_in("pytorch_toolbelt.utils", image_to_tensor=lambda img: torch.from_numpy(np.ascontiguousarray(np.moveaxis(img, -1, 0))))
+    stand_in("omegaconf", OmegaConf=type("OmegaConf", (), {}), DictConfig=dict, ListConfig=list)
+    stand_in("coloredlogs", DEFAULT_FIELD_STYLES={}, DEFAULT_LEVEL_STYLES={}, install=lambda *a, **k: None)
+    stand_in("cv2")
+    stand_in("skimage")
+    stand_in("skimage.io", imread=None)
+    stand_in("fire", Fire=lambda *a, **k: None)
 
 
 def load_reference_head_mesh(model, flame_config=None, image_size: int = 256):
@@ -76,13 +116,12 @@ def load_reference_head_mesh(model, flame_config=None, image_size: int = 256):
     if not reference_available():
         raise FileNotFoundError(f"reference tree not found at {REFERENCE_ROOT}")
     sys.dont_write_bytecode = True  # the reference tree is read-only
-    _install_stubs()
+    install_stand_ins()
     if REFERENCE_ROOT not in sys.path:
         sys.path.insert(0, REFERENCE_ROOT)
     import model_training.model.flame as ref_flame  # noqa: E402  (reference code)
     from model_training.head_mesh import HeadMesh  # noqa: E402  (reference code)
 
-    Struct = sys.modules["smplx.utils"].Struct
     fields = {k: getattr(model, k) for k in ("f", "v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights")}
     ref_flame.get_flame_model = lambda flame_path=None: Struct(**fields)
     with torch.no_grad():
@@ -92,28 +131,10 @@ def load_reference_head_mesh(model, flame_config=None, image_size: int = 256):
 def load_reference_losses(model):
     """The reference's own `Vertices3DLoss` / `ReprojectionLoss` classes (model_training/losses/*.py, unmodified),
     wired to `model` like `load_reference_head_mesh`. The package `__init__` (which pulls in unrelated losses with more
-    uninstalled imports) is bypassed by registering an empty package module; `model_training/utils.py` gets stand-ins
-    for `omegaconf`, `coloredlogs` and `hydra.utils.get_original_cwd`, none of which the loss path calls."""
-    load_reference_head_mesh(model)  # stubs, sys.path and the patched get_flame_model
-
-    def _mod(name):
-        m = types.ModuleType(name)
-        sys.modules[name] = m
-        return m
-
-    if "omegaconf" not in sys.modules:
-        oc = _mod("omegaconf")
-        oc.OmegaConf, oc.DictConfig = type("OmegaConf", (), {}), dict
-    if "coloredlogs" not in sys.modules:
-        cl = _mod("coloredlogs")
-        cl.DEFAULT_FIELD_STYLES, cl.install = {}, (lambda *a, **k: None)
-    if not hasattr(sys.modules["hydra.utils"], "get_original_cwd"):
-        sys.modules["hydra.utils"].get_original_cwd = os.getcwd
-    if "model_training.losses" not in sys.modules:
-        pkg = _mod("model_training.losses")
-        pkg.__path__ = [os.path.join(REFERENCE_ROOT, "model_training", "losses")]
-    import importlib
-
+    uninstalled imports) is bypassed; `model_training/utils.py` finds the stand-ins for `omegaconf`, `coloredlogs` and
+    `hydra.utils.get_original_cwd`, none of which the loss path calls."""
+    load_reference_head_mesh(model)  # stand-ins, sys.path and the patched get_flame_model
+    bypass_package_init("model_training.losses")
     v3d = importlib.import_module("model_training.losses.vertices_3d_loss")
     rep = importlib.import_module("model_training.losses.reprojection_loss")
     return v3d.Vertices3DLoss, rep.ReprojectionLoss
@@ -192,29 +213,18 @@ def load_reference_regressor(seed: int = 0, num_classes: int = 68):
     if not reference_available():
         raise FileNotFoundError(f"reference tree not found at {REFERENCE_ROOT}")
     sys.dont_write_bytecode = True
-    _install_stubs()
+    install_stand_ins()
     if REFERENCE_ROOT not in sys.path:
         sys.path.insert(0, REFERENCE_ROOT)
-    if "pytorch_toolbelt.modules" not in sys.modules:
-        mods = types.ModuleType("pytorch_toolbelt.modules")
-        sys.modules["pytorch_toolbelt.modules"] = mods
-        sys.modules["pytorch_toolbelt"].modules = mods
-    if "pytorchcv" not in sys.modules:
-        cv = types.ModuleType("pytorchcv")
-        provider = types.ModuleType("pytorchcv.model_provider")
-        cv.model_provider = provider
-        sys.modules["pytorchcv"], sys.modules["pytorchcv.model_provider"] = cv, provider
 
-        def get_model(name, pretrained=False, **kwargs):
-            if name != "resnet50":
-                raise ValueError(f"stand-in only declares resnet50, not {name}")
-            return types.SimpleNamespace(features=_pytorchcv_resnet50_features())
+    def get_model(name, pretrained=False, **kwargs):
+        if name != "resnet50":
+            raise ValueError(f"stand-in only declares resnet50, not {name}")
+        return types.SimpleNamespace(features=_pytorchcv_resnet50_features())
 
-        provider.get_model = get_model
-    if "model_training.data" not in sys.modules:  # its __init__ pulls in the datasets (albumentations, cv2): bypassed,
-        pkg = types.ModuleType("model_training.data")  # only data/config.py (string constants) is needed
-        pkg.__path__ = [os.path.join(REFERENCE_ROOT, "model_training", "data")]
-        sys.modules["model_training.data"] = pkg
+    stand_in("pytorchcv")
+    stand_in("pytorchcv.model_provider", get_model=get_model)
+    bypass_package_init("model_training.data")  # its __init__ pulls in the datasets (albumentations): only data/config.py is needed
     from model_training.model.flame_regression import FlameRegression  # noqa: E402  (reference code)
 
     state = torch.random.get_rng_state()

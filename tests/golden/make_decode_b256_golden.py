@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 from dad_3dheads_amd import synthetic  # noqa: E402
 from oracle import reference_runner  # noqa: E402
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_b256_golden.npz")
+OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_b256_golden.npz")
 SEED = 104
 
 

@@ -4,8 +4,8 @@ benchmark.py `DADEvaluator`, utils.py), executed unmodified from its directory.
 
 Runs ONLY where the reference checkout is present (DAD3D_REFERENCE_ROOT, default /root/reference). Stand-ins for what is not
 installed there:
-  cv2, smplx   the zero-pose stub of make_lmk68_fixture.py (the scorer calls get_68_landmarks, always at a zero pose)
-  fire         a module with a no-op `Fire` (only the script's __main__ uses it)
+  cv2, smplx, fire   the stand-ins of oracle/reference_runner.py (the scorer calls get_68_landmarks, always at a zero pose;
+               only the script's __main__ uses `Fire`)
   kaolin       `kaolin.metrics.pointcloud.chamfer_distance(p1, p2, w1, w2)` restated in float64 as the one-sided squared
                distance w1 * mean_{q in p1} min_{p in p2} |q - p|^2 + w2 * (the other way round): kaolin's definition with its
                default squared=True (an assumption: kaolin is not installed anywhere this project runs)
@@ -29,14 +29,16 @@ import json
 import os
 import sys
 import tempfile
-import types
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("DAD3D_REFERENCE_ROOT", "/root/reference")
+sys.path.insert(0, ROOT)
+from oracle import reference_runner  # noqa: E402
+
+REF = reference_runner.REFERENCE_ROOT
 BENCH = os.path.join(REF, "dad_3dheads_benchmark")
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "eval_golden.npz")
 N_MAX = 5200
@@ -53,13 +55,9 @@ def kaolin_stub():
             out.append(w1 * d1.mean() + w2 * d2.mean())
         return torch.stack(out)
 
-    kaolin, metrics, pointcloud = (types.ModuleType(n) for n in ("kaolin", "kaolin.metrics", "kaolin.metrics.pointcloud"))
-    pointcloud.chamfer_distance = chamfer_distance
-    kaolin.metrics, metrics.pointcloud = metrics, pointcloud
-    sys.modules.update({"kaolin": kaolin, "kaolin.metrics": metrics, "kaolin.metrics.pointcloud": pointcloud})
-    fire = types.ModuleType("fire")
-    fire.Fire = lambda *a, **k: None
-    sys.modules["fire"] = fire
+    reference_runner.stand_in("kaolin")
+    reference_runner.stand_in("kaolin.metrics")
+    reference_runner.stand_in("kaolin.metrics.pointcloud", chamfer_distance=chamfer_distance)
 
 
 def rot(axis_angle):
@@ -71,7 +69,6 @@ def rot(axis_angle):
 
 
 def build_items():
-    sys.path.insert(0, ROOT)
     from dad_3dheads_amd import synthetic
     from dad_3dheads_amd.benchmark_export import Landmarks68
 
@@ -153,12 +150,9 @@ def to_json(d):
 
 
 def main():
-    sys.path.insert(0, HERE)
-    from make_lmk68_fixture import install_stubs
-
     d = build_items()
     gt, sub = to_json(d)
-    install_stubs()
+    reference_runner.install_stand_ins()
     kaolin_stub()
     sys.dont_write_bytecode = True
     tmp = tempfile.mkdtemp()

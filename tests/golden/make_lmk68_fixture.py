@@ -3,12 +3,9 @@
 outputs of the reference's OWN `get_68_landmarks` (dad_3dheads_benchmark/utils.py:99-117 == model_training/data/utils.py:
 188-204), executed unmodified from where it lies.
 
-Runs ONLY in the authoring container (needs /root/reference). Stand-ins for the two imports that are not installed:
-`cv2` (never called on this path) and `smplx` -- `Struct` (attribute bag) and `find_dynamic_lmk_idx_and_bcoords`,
-restated for the only way the reference calls it: a ZERO pose. With a zero pose every rotation of the neck chain is the
-identity, the yaw angle is 0 and the function returns row 0 of the contour tables (smplx 0.1.26, lbs.py: `y_rot_angle =
-round(clamp(-yaw * 180 / pi, max=39))`, negative angles remapped, then `index_select(table, 0, y_rot_angle)`); the stub
-asserts the pose really is zero. PARITY UNPINNED for that one function, like `smplx.lbs.lbs` (see oracle/flame_ref.py).
+Runs ONLY in the authoring container (needs /root/reference). The two imports that are not installed, `cv2` (never called
+on this path) and `smplx` (`Struct` and the zero-pose `find_dynamic_lmk_idx_and_bcoords`, PARITY UNPINNED), are the
+stand-ins of oracle/reference_runner.py.
 
   face_idx   int64 [68]     dynamic row 0 (17 contour points) then the 51 static points
   b_coords   f32   [68,3]
@@ -18,40 +15,19 @@ The tables are (c) the FLAME / DAD-3DHeads authors (see NOTICE.md); data, not co
 import os
 import pickle
 import sys
-import types
 
 import numpy as np
 import torch
 
-REF = os.environ.get("DAD3D_REFERENCE_ROOT", "/root/reference")
-BENCH = os.path.join(REF, "dad_3dheads_benchmark")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from oracle import reference_runner  # noqa: E402
+
+BENCH = os.path.join(reference_runner.REFERENCE_ROOT, "dad_3dheads_benchmark")
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "lmk68_embedding.npz")
 
 
-def install_stubs():
-    sys.modules.setdefault("cv2", types.ModuleType("cv2"))
-    smplx = types.ModuleType("smplx")
-    lbs = types.ModuleType("smplx.lbs")
-    utils = types.ModuleType("smplx.utils")
-
-    class Struct:
-        def __init__(self, **kw):
-            for k, v in kw.items():
-                setattr(self, k, v)
-
-    def find_dynamic_lmk_idx_and_bcoords(vertices, pose, dynamic_lmk_faces_idx, dynamic_lmk_b_coords, neck_kin_chain, dtype=torch.float32):
-        assert float(pose.abs().max()) == 0.0, "the stub covers the reference's only call: a zero pose"
-        y_rot_angle = torch.zeros(vertices.shape[0], dtype=torch.long)
-        return torch.index_select(dynamic_lmk_faces_idx, 0, y_rot_angle), torch.index_select(dynamic_lmk_b_coords, 0, y_rot_angle)
-
-    lbs.find_dynamic_lmk_idx_and_bcoords = find_dynamic_lmk_idx_and_bcoords
-    utils.Struct = Struct
-    smplx.lbs, smplx.utils = lbs, utils
-    sys.modules.update({"smplx": smplx, "smplx.lbs": lbs, "smplx.utils": utils})
-
-
 def main():
-    install_stubs()
+    reference_runner.install_stand_ins()
     sys.dont_write_bytecode = True
     sys.path.insert(0, BENCH)
     os.chdir(BENCH)  # the reference opens "data/static/..." relative to its own directory

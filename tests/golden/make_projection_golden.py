@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """tests/golden/projection_golden.npz: outputs of the reference's OWN `visualize.get_2d_keypoints` (visualize.py:10-22),
-imported unmodified from /root/reference with stand-ins for its uninstalled imports (`fire`, `cv2`, `demo_utils`: none is
-touched by that function), on seeded annotation-shaped inputs (5023 vertices, a rigid model-view matrix, an OpenGL-style
-perspective matrix scaled to pixels like the dataset's). Authoring container only."""
+imported unmodified from /root/reference with stand-ins for its uninstalled imports (`fire`, `cv2` from
+oracle/reference_runner.py, `demo_utils` here: none is touched by that function), on seeded annotation-shaped inputs (5023
+vertices, a rigid model-view matrix, an OpenGL-style perspective matrix scaled to pixels like the dataset's). Authoring
+container only."""
 import os
 import sys
-import types
 
 import numpy as np
 
-REF = os.environ.get("DAD3D_REFERENCE_ROOT", "/root/reference")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from oracle import reference_runner  # noqa: E402
+
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "projection_golden.npz")
 
 
@@ -28,12 +30,10 @@ def annotation(rng, n=5023):
 
 
 def main():
-    for name in ("fire", "cv2", "demo_utils"):
-        sys.modules.setdefault(name, types.ModuleType(name))
-    sys.modules["fire"].Fire = lambda *a, **k: None
-    sys.modules["demo_utils"].draw_points = sys.modules["demo_utils"].get_output_path = None
+    reference_runner.install_stand_ins()  # fire, cv2
+    reference_runner.stand_in("demo_utils", draw_points=None, get_output_path=None)
     sys.dont_write_bytecode = True
-    sys.path.insert(0, REF)
+    sys.path.insert(0, reference_runner.REFERENCE_ROOT)
     import visualize  # the reference's module
 
     rng = np.random.default_rng(2024)

@@ -5,9 +5,9 @@
 and run on seeded scenes (tests/train_batch_restatement.py). Authoring container only.
 
 Stand-ins (`sys.modules`) for what is not installed here:
-  smplx          `Struct` and the zero-pose `find_dynamic_lmk_idx_and_bcoords` of make_lmk68_fixture.py (PARITY UNPINNED)
-  hydra.utils    `instantiate(cfg, *args)` -> the reference's HeatmapCoder(*args)
-  pytorch_toolbelt.utils.image_to_tensor   HWC -> CHW torch tensor
+  smplx, hydra.utils, pytorch_toolbelt.utils, omegaconf, coloredlogs, skimage   the shared ones of oracle/reference_runner.py:
+                 the zero-pose `find_dynamic_lmk_idx_and_bcoords` (PARITY UNPINNED), `instantiate(cfg, *args)` -> the
+                 reference's HeatmapCoder(*args), `image_to_tensor` HWC -> CHW
   cv2            `imread` / `cvtColor` serve the seeded images; `resize` is oracle/preprocess_ref.py (PARITY UNPINNED)
   albumentations an albumentations 1.0.0 restatement of Compose, KeypointParams(format="xy", remove_invisible=False),
                  LongestMaxSize, PadIfNeeded, Resize and Normalize (PARITY UNPINNED: the package is absent here). Keypoint
@@ -24,15 +24,15 @@ import json
 import os
 import sys
 import tempfile
-import types
 
 import numpy as np
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-REF = os.environ.get("DAD3D_REFERENCE_ROOT", "/root/reference")
+from oracle import reference_runner  # noqa: E402
+
+REF = reference_runner.REFERENCE_ROOT
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_batch_golden.npz")
 IMAGES = {}  # file name -> seeded image, served by the cv2.imread stand-in
 FULL_STRIDE = 2  # every other vertex of the full landmarks is stored (size)
@@ -50,13 +50,6 @@ ITEMS = {
     "resize_mean_445": [(300, 400, 120, "face"), (400, 300, 330, "face"), (300, 300, 100, "thin"), (300, 300, 80, "ortho_edges")],
     "lms_mean_68_edges": [(256, 256, 200, "full"), (300, 300, 100, "thin"), (300, 300, 80, "ortho_edges"), (301, 203, 70, "face")],
 }
-
-
-def _mod(name, **attrs):
-    m = types.ModuleType(name)
-    m.__dict__.update(attrs)
-    sys.modules[name] = m
-    return m
 
 
 def albumentations_restatement():
@@ -138,40 +131,20 @@ def albumentations_restatement():
                 data["keypoints"] = [(x, y) for x, y, _, _ in data["keypoints"]]
             return data
 
-    return _mod("albumentations", Compose=Compose, BasicTransform=object, KeypointParams=KeypointParams, LongestMaxSize=LongestMaxSize,
+    return reference_runner.stand_in("albumentations", Compose=Compose, BasicTransform=object, KeypointParams=KeypointParams, LongestMaxSize=LongestMaxSize,
                 PadIfNeeded=PadIfNeeded, Resize=Resize, Normalize=Normalize)
 
 
 def load_reference():
     from oracle import preprocess_ref as pp
 
-    from oracle import reference_runner as rr
-
-    rr._install_stubs()  # smplx (Struct, lbs), hydra, pytorch_toolbelt as the other goldens install them
-
-    def find_dynamic_lmk_idx_and_bcoords(vertices, pose, faces_idx, b_coords, neck_kin_chain, dtype=torch.float32):
-        assert float(pose.abs().max()) == 0.0, "the stand-in covers the reference's only call: a zero pose"
-        row = torch.zeros(vertices.shape[0], dtype=torch.long)
-        return torch.index_select(faces_idx, 0, row), torch.index_select(b_coords, 0, row)
-
-    sys.modules["smplx.lbs"].find_dynamic_lmk_idx_and_bcoords = find_dynamic_lmk_idx_and_bcoords
-    sys.modules["hydra.utils"].get_original_cwd = os.getcwd
-    if "omegaconf" not in sys.modules:
-        _mod("omegaconf", OmegaConf=None, DictConfig=dict, ListConfig=list)
-    sys.modules["hydra.utils"].instantiate = lambda cfg, *a: importlib.import_module(
-        cfg["_target_"].rsplit(".", 1)[0]).__dict__[cfg["_target_"].rsplit(".", 1)[1]](*a)
-    sys.modules["pytorch_toolbelt.utils"].image_to_tensor = lambda img: torch.from_numpy(np.ascontiguousarray(np.moveaxis(img, -1, 0)))
-    _mod("cv2", imread=lambda path, flag=None: IMAGES[os.path.basename(path)], cvtColor=lambda img, code: img, IMREAD_COLOR=1,
+    reference_runner.install_stand_ins()
+    reference_runner.stand_in("cv2", imread=lambda path, flag=None: IMAGES[os.path.basename(path)], cvtColor=lambda img, code: img, IMREAD_COLOR=1,
          COLOR_BGR2RGB=4, BORDER_CONSTANT=0, INTER_LINEAR=1,
          resize=lambda img, dsize, interpolation=1: pp.resize_linear_u8(img, dsize[1], dsize[0]))
-    _mod("skimage")
-    sys.modules["skimage"].io = _mod("skimage.io", imread=None)
-    _mod("coloredlogs", install=lambda *a, **k: None, DEFAULT_FIELD_STYLES={}, DEFAULT_LEVEL_STYLES={})
     albumentations_restatement()
     sys.path.insert(0, REF)
-    for pkg in ("model_training.data",):  # its __init__ pulls in the lightning datasets: bypassed
-        m = _mod(pkg)
-        m.__path__ = [os.path.join(REF, *pkg.split("."))]
+    reference_runner.bypass_package_init("model_training.data")  # its __init__ pulls in the lightning datasets
     cwd = os.getcwd()
     os.chdir(REF)  # load_2d_indices / get_relative_path read paths relative to the reference tree
     try:

@@ -6,7 +6,8 @@ LossModule case are the reference's `Vertices3DLoss` / `ReprojectionLoss` throug
 synthetic FLAME model. Inputs come from seeds (tests/train_objective_restatement.py); only small gradients are stored.
 
 The data and metrics modules import packages that are not installed here (cv2, skimage.io, smplx.lbs, torchmetrics,
-hydra.utils): this script installs `sys.modules` stand-ins for them, none of which the code paths run here call.
+hydra.utils): oracle/reference_runner.py holds the stand-ins for them (`torchmetrics` is this script's own), none of which the
+code paths run here call.
 Authoring container only."""
 import importlib
 import os
@@ -31,34 +32,13 @@ LM_SEED, LM_B, LM_C, LM_EPOCH = 101, 2, 5, 3
 REGIONS = {"face": (1.0, np.arange(0, 5023, 5)), "face_w_ears": (0.75, np.arange(1000, 3000, 3)), "head": (0.5, np.arange(0, 5023, 11))}
 
 
-def _mod(name):
-    m = types.ModuleType(name)
-    sys.modules[name] = m
-    return m
-
-
 def load_reference(model):
     from oracle import reference_runner as rr
 
-    v3d, rep = rr.load_reference_losses(model)  # stubs for hydra, smplx, pytorch_toolbelt, omegaconf, coloredlogs; sys.path
-    ref = rr.REFERENCE_ROOT
-    if "cv2" not in sys.modules:
-        _mod("cv2")
-    if "skimage" not in sys.modules:
-        sk = _mod("skimage")
-        sk.io = _mod("skimage.io")
-        sk.io.imread = None
-    sys.modules["smplx.lbs"].find_dynamic_lmk_idx_and_bcoords = None
-    if "torchmetrics" not in sys.modules:
-        tm = _mod("torchmetrics")
-        tm.Metric = type("Metric", (), {})
-        tm.MetricCollection = dict
-    if not hasattr(sys.modules["hydra.utils"], "instantiate"):
-        sys.modules["hydra.utils"].instantiate = None
+    v3d, rep = rr.load_reference_losses(model)  # the shared stand-ins (cv2, skimage.io, smplx.lbs, hydra.utils among them); sys.path
+    rr.stand_in("torchmetrics", Metric=type("Metric", (), {}), MetricCollection=dict)
     for pkg in ("model_training.data", "model_training.metrics", "model_training.train"):
-        if pkg not in sys.modules:  # their __init__ pull in datasets / lightning: bypassed
-            m = _mod(pkg)
-            m.__path__ = [os.path.join(ref, *pkg.split("."))]
+        rr.bypass_package_init(pkg)  # their __init__ pull in datasets / lightning
     get = importlib.import_module
     return types.SimpleNamespace(
         coder=get("model_training.data.coder"), data_utils=get("model_training.data.utils"),

@@ -27,7 +27,6 @@ function's output; the photo is the reference's demo image (see demo_image.npz).
 """
 import os
 import sys
-import types
 
 import numpy as np
 import torch
@@ -99,7 +98,7 @@ def main():
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from dad_3dheads_amd import synthetic
-    from oracle import flame_ref
+    from oracle import flame_ref, reference_runner
     import uv_texture_restatement as R
 
     static = synthetic.load_static()
@@ -113,13 +112,10 @@ def main():
         photo = z["resized"]
 
     # the reference's module, unmodified, with its two third-party imports stood in for
-    psbody, psmesh = types.ModuleType("psbody"), types.ModuleType("psbody.mesh")
-    psmesh.Mesh = R.RestatedMesh
-    psbody.mesh = psmesh
-    mt, hm = types.ModuleType("model_training"), types.ModuleType("model_training.head_mesh")
-    hm.HeadMesh = object
-    mt.head_mesh = hm
-    sys.modules.update({"psbody": psbody, "psbody.mesh": psmesh, "model_training": mt, "model_training.head_mesh": hm})
+    reference_runner.stand_in("psbody")
+    psmesh = reference_runner.stand_in("psbody.mesh", Mesh=R.RestatedMesh)
+    reference_runner.stand_in("model_training")
+    reference_runner.stand_in("model_training.head_mesh", HeadMesh=object)
     sys.dont_write_bytecode = True
     sys.path.insert(0, REF)
     from inference.uv_texture import UVTextureCreator

@@ -11,7 +11,6 @@ import json
 import os
 import sys
 import tempfile
-import types
 
 import numpy as np
 import torch
@@ -25,16 +24,11 @@ SEED, BATCH = 205, 2
 def load_reference_demo_utils(model):
     from oracle import reference_runner as rr
 
-    rr.load_reference_head_mesh(model)  # stubs for hydra / smplx / pytorch_toolbelt, sys.path, patched get_flame_model
-    for name in ("cv2", "inference", "inference.uv_texture", "inference.pncc_estimator"):
-        if name not in sys.modules:
-            sys.modules[name] = types.ModuleType(name)
-    sys.modules["inference.uv_texture"].UVTextureCreator = type("UVTextureCreator", (), {})
-    sys.modules["inference.pncc_estimator"].PNCCEstimator = type("PNCCEstimator", (), {})
-    if "model_training.utils" not in sys.modules:  # the real one imports omegaconf / coloredlogs; only a name is needed
-        mu = types.ModuleType("model_training.utils")
-        mu.load_indices_from_npy = lambda p: np.load(p)
-        sys.modules["model_training.utils"] = mu
+    rr.load_reference_head_mesh(model)  # the shared stand-ins (cv2 among them), sys.path, patched get_flame_model
+    rr.stand_in("inference")
+    rr.stand_in("inference.uv_texture", UVTextureCreator=type("UVTextureCreator", (), {}))
+    rr.stand_in("inference.pncc_estimator", PNCCEstimator=type("PNCCEstimator", (), {}))
+    rr.stand_in("model_training.utils", load_indices_from_npy=lambda p: np.load(p))  # only a name is needed
     import importlib
 
     return importlib.import_module("demo_utils")

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import eval_restatement as er  # noqa: E402
 from dad_3dheads_amd import _lib, evaluation, synthetic  # noqa: E402
 from dad_3dheads_amd.benchmark_export import Landmarks68  # noqa: E402
+from event_timer import event_time  # noqa: E402
 
 
 def items(golden, b, seed):
@@ -46,18 +47,6 @@ def documents(golden, d):
              has_7=np.ones(len(d["height"]), np.int8), has_pred=np.ones(len(d["height"]), np.int8))
     gt, sub = er.golden_json(g)
     return json.dumps(gt), json.dumps(sub)
-
-
-def event_time(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def run(golden, static, b, iters):
@@ -90,7 +79,7 @@ def run(golden, static, b, iters):
             t(d["pred_lmk7"]), t(d["pred_rotation"]))
     kw = dict(landmarks=Landmarks68(static["faces"], device=dev), head_indices=torch.from_numpy(static["head_indices"]).to(dev),
               face_indices=torch.from_numpy(golden["face_indices"].astype(np.int64)).to(dev))
-    t_eval = event_time(lambda: evaluation.evaluate_batch(*args, **kw), iters)
+    t_eval = event_time(lambda: evaluation.evaluate_batch(*args, **kw), iters, 1)
 
     # the kernels alone, on inputs of the evaluated shapes
     face = torch.randn(b, 2094, 3, device=dev)
@@ -100,8 +89,8 @@ def run(golden, static, b, iters):
     sim[:, 1:10] = torch.eye(3, device=dev).reshape(9)
     head = kw["head_indices"]
     g, w = pts[:, head].contiguous(), pts[:, head].contiguous()
-    t_nn = event_time(lambda: evaluation.nearest(face, pts, args[7], sim), iters)
-    t_z5 = event_time(lambda: evaluation.z5_ranks(g, w), iters)
+    t_nn = event_time(lambda: evaluation.nearest(face, pts, args[7], sim), iters, 1)
+    t_z5 = event_time(lambda: evaluation.z5_ranks(g, w), iters, 1)
     return {"B": b, "json_parse_s": t_json, "host_s": t_host, "kernel_nearest_s": t_nn, "kernel_z5_s": t_z5,
             "evaluate_batch_s": t_eval, "items_per_s_evaluate_batch": b / t_eval, "items_per_s_kernels": b / (t_nn + t_z5),
             "items_per_s_with_json": b / (t_json + t_host + t_eval), "max_counts": int(d["pred_counts"].max())}

@@ -18,20 +18,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from dad_3dheads_amd import landmarks, synthetic  # noqa: E402
 from dad_3dheads_amd.head_mesh import HeadMesh  # noqa: E402
 from dad_3dheads_amd.Sim3DR import Mesh  # noqa: E402
+from event_timer import event_time  # noqa: E402
 from oracle import sim3dr_ref  # noqa: E402
-
-
-def gpu_time(fn, iters=200, warm=20):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def main():
@@ -42,13 +30,13 @@ def main():
     # ---- config 3 --------------------------------------------------------------------------------------
     p256 = torch.from_numpy(synthetic.synthetic_params(256, seed=0)).cuda()
     bufs = {}
-    t = gpu_time(lambda: hm.flame.decode(p256, verts3d=True, proj=False, out=bufs))
+    t = event_time(lambda: hm.flame.decode(p256, verts3d=True, proj=False, out=bufs), 200, 20)
     out["config3_decode_b256"] = {"images_per_s": 256 / t, "us_per_batch": t * 1e6,
                                    "tflops_algorithmic": 14.5e6 * 256 / t / 1e12}
     for b in (64, 1024, 2048):
         pb = torch.from_numpy(synthetic.synthetic_params(b, seed=1)).cuda()
         bb = {}
-        t = gpu_time(lambda: hm.decode(pb, to_2d=True, landmarks=False, landmarks_px=True, out=bb), iters=100)
+        t = event_time(lambda: hm.decode(pb, to_2d=True, landmarks=False, landmarks_px=True, out=bb), 100, 20)
         out[f"decode_b{b}_full_outputs"] = {"images_per_s": b / t, "us_per_batch": t * 1e6,
                                             "tflops_algorithmic": 14.5e6 * b / t / 1e12}
     # ---- config 5 share --------------------------------------------------------------------------------
@@ -64,26 +52,26 @@ def main():
     light = mesh.phong_light(verts, normals)
     tmpl = torch.from_numpy(st["template_geo"]).cuda()
     ncc = ((tmpl - tmpl.min(0).values) / (tmpl.max(0).values - tmpl.min(0).values)).float()[None].expand(B, -1, -1).contiguous()
-    t_norm = gpu_time(lambda: mesh.get_normal(verts, out=normals))
-    t_light = gpu_time(lambda: mesh.phong_light(verts, normals))
-    t_nlight = gpu_time(lambda: mesh.phong_light(verts, None))
-    t_rast = gpu_time(lambda: mesh.rasterize(verts, light, img))
-    t_pncc = gpu_time(lambda: mesh_pncc.rasterize(verts, ncc, img))
+    t_norm = event_time(lambda: mesh.get_normal(verts, out=normals), 200, 20)
+    t_light = event_time(lambda: mesh.phong_light(verts, normals), 200, 20)
+    t_nlight = event_time(lambda: mesh.phong_light(verts, None), 200, 20)
+    t_rast = event_time(lambda: mesh.rasterize(verts, light, img), 200, 20)
+    t_pncc = event_time(lambda: mesh_pncc.rasterize(verts, ncc, img), 200, 20)
 
     def pipeline():
         hm.flame.decode(p, proj=True, to_2d=False, flip_z=True, out=dec)
         lt = mesh.phong_light(dec["proj"], None)  # normals + light in one launch
         mesh.rasterize(dec["proj"], lt, img)
 
-    t_pipe = gpu_time(pipeline, iters=100)
+    t_pipe = event_time(pipeline, 100, 20)
     lbuf = torch.empty_like(verts)
 
     def pipeline3():  # three launches: decode, geometry (+ normals + light), tiles
         hm.flame.decode(p, proj=True, to_2d=False, flip_z=True, out=dec)
         mesh.render(dec["proj"], img, light_out=lbuf)
 
-    t_pipe3 = gpu_time(pipeline3, iters=100)
-    t_render = gpu_time(lambda: mesh.render(verts, img, light_out=lbuf))
+    t_pipe3 = event_time(pipeline3, 100, 20)
+    t_render = event_time(lambda: mesh.render(verts, img, light_out=lbuf), 200, 20)
 
     # the same chain with two batches in flight: one forked decode handle, one mesh handle and one buffer set per stream
     lanes = []

@@ -18,20 +18,8 @@ from dad_3dheads_amd import landmarks, synthetic  # noqa: E402
 from dad_3dheads_amd.flame import FLAME_CONSTS  # noqa: E402
 from dad_3dheads_amd.head_mesh import HeadMesh  # noqa: E402
 from dad_3dheads_amd.losses import normalize_to_cube  # noqa: E402
+from event_timer import event_time  # noqa: E402
 from oracle import flame_ref  # noqa: E402
-
-
-def gpu_time(fn, iters=100, warm=10):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def main():
@@ -72,8 +60,8 @@ def main():
             pr = hm.reprojected_vertices(q, to_2d=True)
             torch.autograd.backward([v, pr], [gv, gp])
 
-        t_step, t_dec = gpu_time(step), gpu_time(decode_only)
-        t_step_torch = gpu_time(lambda: step(False))
+        t_step, t_dec = event_time(step, 100, 10), event_time(decode_only, 100, 10)
+        t_step_torch = event_time(lambda: step(False), 100, 10)
         fused_vs_torch = float((step(True) - step(False)).abs().max() / step(False).abs().max())
 
         # the same step captured once into a hipGraph (its launches replayed without host work)
@@ -93,7 +81,7 @@ def main():
         static_p.grad = None
         with torch.cuda.graph(graph):
             graph_body()
-        t_graph = gpu_time(graph.replay)
+        t_graph = event_time(graph.replay, 100, 10)
         step()  # eager gradient of the same parameters
         g_eager = step()
         graph.replay()
@@ -111,16 +99,16 @@ def main():
         g_posed, g_c, g_params = torch.empty_like(posed), torch.empty_like(c72), torch.empty_like(params)
         g_in = torch.empty((b, 436), device="cuda")
         h = layer._handle
-        t_chain = gpu_time(lambda: lib.dad3d_flame_pose_chain(h, params.data_ptr(), b, inputs.data_ptr(), c72.data_ptr(), None))
+        t_chain = event_time(lambda: lib.dad3d_flame_pose_chain(h, params.data_ptr(), b, inputs.data_ptr(), c72.data_ptr(), None), 100, 10)
         v3 = torch.empty((b, 5023, 3), device="cuda")
-        t_fwd = gpu_time(lambda: lib.dad3d_flame_decode_posed(h, params.data_ptr(), b, _lib.ZERO_ROTATION, v3.data_ptr(), None, posed.data_ptr(), None))
-        t_fwd0 = gpu_time(lambda: lib.dad3d_flame_decode(h, params.data_ptr(), b, _lib.ZERO_ROTATION, v3.data_ptr(), None, None, None, None))
-        t_vert = gpu_time(lambda: lib.dad3d_flame_decode_backward(h, b, _lib.ZERO_ROTATION, c72.data_ptr(), posed.data_ptr(), gv.data_ptr(),
-                                                                  None, g_posed.data_ptr(), g_c.data_ptr(), None))
-        t_gemm2 = gpu_time(lambda: torch.matmul(g_posed, tables.basis.T, out=g_in))
-        t_gemm_hip = gpu_time(lambda: lib.dad3d_flame_grad_inputs(h, g_posed.data_ptr(), b, g_in.data_ptr(), None))
-        t_vjp = gpu_time(lambda: lib.dad3d_flame_pose_chain_backward(h, params.data_ptr(), b, g_in.data_ptr(), g_c.data_ptr(),
-                                                                     g_params.data_ptr(), None))
+        t_fwd = event_time(lambda: lib.dad3d_flame_decode_posed(h, params.data_ptr(), b, _lib.ZERO_ROTATION, v3.data_ptr(), None, posed.data_ptr(), None), 100, 10)
+        t_fwd0 = event_time(lambda: lib.dad3d_flame_decode(h, params.data_ptr(), b, _lib.ZERO_ROTATION, v3.data_ptr(), None, None, None, None), 100, 10)
+        t_vert = event_time(lambda: lib.dad3d_flame_decode_backward(h, b, _lib.ZERO_ROTATION, c72.data_ptr(), posed.data_ptr(), gv.data_ptr(),
+                                                                  None, g_posed.data_ptr(), g_c.data_ptr(), None), 100, 10)
+        t_gemm2 = event_time(lambda: torch.matmul(g_posed, tables.basis.T, out=g_in), 100, 10)
+        t_gemm_hip = event_time(lambda: lib.dad3d_flame_grad_inputs(h, g_posed.data_ptr(), b, g_in.data_ptr(), None), 100, 10)
+        t_vjp = event_time(lambda: lib.dad3d_flame_pose_chain_backward(h, params.data_ptr(), b, g_in.data_ptr(), g_c.data_ptr(),
+                                                                     g_params.data_ptr(), None), 100, 10)
         out[f"b{b}"] = {
             "losses_fwd_bwd_us": t_step * 1e6, "images_per_s": b / t_step,
             "two_decodes_fwd_bwd_us": t_dec * 1e6,

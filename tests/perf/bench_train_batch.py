@@ -31,22 +31,10 @@ sys.path.insert(0, os.path.dirname(HERE))
 import train_batch_restatement as rs  # noqa: E402
 from dad_3dheads_amd import synthetic  # noqa: E402
 from dad_3dheads_amd.dataset import RESIZE_MODES, FlameBatchBuilder, RawBatchCollate  # noqa: E402
+from event_timer import event_time  # noqa: E402
 
 CONFIG = {"img_size": 256, "stride": 4, "num_classes": 68, "keypoints": {"2d_subset_name": "multipie_keypoints"},
           "transform": {"normalize": "imagenet", "resize_mode": "longest_max_size"}}
-
-
-def event_time(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def raw_items(b, st, seed=0):
@@ -101,11 +89,11 @@ def bench(b, iters, st):
     keypoints()
     out = {"batch": b, "crop_sides": "log-uniform [64, 640] px per axis, seed 0",
            "crop_side_median": float(np.median(sides)), "crop_bytes": int(raw["crops"].numel())}
-    out["h2d_s"] = event_time(h2d, iters)
-    out["image_s"] = event_time(image, iters)
-    out["keypoints_s"] = event_time(keypoints, iters)
-    out["heatmap_s"] = event_time(heatmap, iters)
-    out["builder_s"] = event_time(whole, iters)
+    out["h2d_s"] = event_time(h2d, iters, 3)
+    out["image_s"] = event_time(image, iters, 3)
+    out["keypoints_s"] = event_time(keypoints, iters, 3)
+    out["heatmap_s"] = event_time(heatmap, iters, 3)
+    out["builder_s"] = event_time(whole, iters, 3)
     taps = int(sum(min(int(h), 256) * min(int(w), 256) for h, w in sides)) * 3  # bytes the resize can touch (<= crop)
     out["h2d_bytes"], out["h2d_gbps"] = h2d_bytes, h2d_bytes / out["h2d_s"] / 1e9
     out["image_bytes"] = b * 3 * 256 * 256 * 4 + taps

@@ -36,21 +36,9 @@ from dad_3dheads_amd.coder import HeatmapCoder  # noqa: E402
 from dad_3dheads_amd.flame import FLAME_CONSTS  # noqa: E402
 from dad_3dheads_amd.loss_module import LossModule  # noqa: E402
 from dad_3dheads_amd.losses import IoULoss  # noqa: E402
+from event_timer import event_time  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
-
-
-def event_time(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 class TorchIoU(torch.nn.Module):
@@ -106,7 +94,7 @@ def iou_leg(b, iters):
         ref(x, tf).backward()
 
     res = {"batch": b, "channels": c, "hw": s * s}
-    res["iou_fused_s"] = event_time(fused, iters)
+    res["iou_fused_s"] = event_time(fused, iters, 3)
     # the same autograd step replayed from a graph: the device time without the host's per-launch work
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -118,11 +106,11 @@ def iou_leg(b, iters):
     x.grad = None
     with torch.cuda.graph(graph):
         crit(x, t).backward()
-    res["iou_fused_graph_s"] = event_time(graph.replay, iters)
+    res["iou_fused_graph_s"] = event_time(graph.replay, iters, 3)
     x.grad = None
-    res["iou_fwd_s"] = event_time(fwd, iters)
-    res["iou_bwd_s"] = event_time(bwd, iters)
-    res["iou_torch_s"] = event_time(torch_stmt, iters)
+    res["iou_fwd_s"] = event_time(fwd, iters, 3)
+    res["iou_bwd_s"] = event_time(bwd, iters, 3)
+    res["iou_torch_s"] = event_time(torch_stmt, iters, 3)
     fwd_bytes, bwd_bytes = 5 * n, 9 * n
     res.update({"fwd_bytes": fwd_bytes, "bwd_bytes": bwd_bytes,
                 "iou_fwd_gbps": fwd_bytes / res["iou_fwd_s"] / 1e9, "iou_bwd_gbps": bwd_bytes / res["iou_bwd_s"] / 1e9,
@@ -139,7 +127,7 @@ def encode_leg(b, iters, cpu_reps):
     coder = HeatmapCoder({"img_size": 256, "stride": 4, "radius": 5}, 68)
     kd, pd = torch.from_numpy(kp).cuda(), torch.from_numpy(pr).cuda()
     out = torch.empty((b, 68, 64, 64), dtype=torch.uint8, device="cuda")
-    res = {"batch": b, "encode_s": event_time(lambda: coder.encode(kd, pd, form="uint8", out=out), iters)}
+    res = {"batch": b, "encode_s": event_time(lambda: coder.encode(kd, pd, form="uint8", out=out), iters, 3)}
     res["encode_bytes"] = out.numel()
     res["encode_gbps"] = out.numel() / res["encode_s"] / 1e9
     t0 = time.perf_counter()
@@ -203,7 +191,7 @@ def objective_leg(b, iters):
             total.backward()
         return f
 
-    res = {"batch": b, "objective_s": event_time(run(hip), iters), "objective_baseline_s": event_time(run(base), iters)}
+    res = {"batch": b, "objective_s": event_time(run(hip), iters, 3), "objective_baseline_s": event_time(run(base), iters, 3)}
     res["objective_vs_baseline"] = res["objective_baseline_s"] / res["objective_s"]
     return res
 

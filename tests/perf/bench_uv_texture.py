@@ -28,21 +28,10 @@ sys.path.insert(0, os.path.dirname(HERE))
 import uv_texture_restatement as R  # noqa: E402
 from dad_3dheads_amd import _lib, synthetic  # noqa: E402
 from dad_3dheads_amd.uv_texture import UVTextureCreator  # noqa: E402
+from event_timer import event_time  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 CHUNK = 8  # kUvBakeChunk
-
-
-def event_time(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def run(creator, td, b, iters):
@@ -60,9 +49,9 @@ def run(creator, td, b, iters):
         m.vertex_normals(verts, out=normals)
         m.bake(verts, normals, images, out=tex)
 
-    t_k = event_time(kernels, iters)
-    t_b = event_time(lambda: creator.bake_batch(params, images, out=tex), iters)
-    n_norm = event_time(lambda: m.vertex_normals(verts, out=normals), iters)
+    t_k = event_time(kernels, iters, 1)
+    t_b = event_time(lambda: creator.bake_batch(params, images, out=tex), iters, 1)
+    n_norm = event_time(lambda: m.vertex_normals(verts, out=normals), iters, 1)
     written = int(tex.any(-1).sum().item())
     chunks = (b + CHUNK - 1) // CHUNK
     nbytes = {"texture_writes": b * s * s * 3, "photo_gathers": b * n_cand * 3,

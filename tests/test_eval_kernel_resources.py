@@ -1,33 +1,11 @@
-"""CPU: the benchmark scorer's kernels (csrc/mesh_eval.hip) stay free of scratch and spills. Compiled for gfx950 with
-`-Rpass-analysis=kernel-resource-usage` as in tests/test_kernel_resources.py (hipcc cross-compiles without a GPU)."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dad-3dheads_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "--cuda-device-only",
-         "-Rpass-analysis=kernel-resource-usage"]
+"""CPU: the benchmark scorer's kernels (csrc/mesh_eval.hip) stay free of scratch and spills. Compiled for gfx950 with the flags of
+csrc/Makefile and `-Rpass-analysis=kernel-resource-usage` (tests/kernel_resources.py)."""
+from kernel_resources import needs_hipcc, resource_usage
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_mesh_eval_no_scratch_no_spills(tmp_path):
-    out = subprocess.run([HIPCC, *FLAGS, "-c", os.path.join(CSRC, "mesh_eval.hip"), "-o", str(tmp_path / "mesh_eval.o")],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark: .*?Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark: .*?\s{2,}([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+    kernels = resource_usage("mesh_eval.hip", tmp_path)
     nn = [n for n in kernels if "nearest_kernel" in n]
     z5 = [n for n in kernels if "z5_rank_kernel" in n]
     assert len(nn) == 8 and len(z5) == 1, list(kernels)  # k = 1..8
