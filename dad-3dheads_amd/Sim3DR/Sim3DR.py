@@ -85,3 +85,35 @@ def rasterize_triangles(vertices, triangles, height, width, depth_buffer=None):
                                          bary.ctypes.data, t.shape[0], height, width)
     _raise_if_failed(lib)
     return depth, tri_buf, bary
+
+
+def render_texture(vertices, triangles, texture, tex_coords, tex_triangles, h, w, c=3, mapping_type=1, bg=None):
+    """`_render_texture_core` (rasterize_kernel.cpp:358-463; rasterize.pyx comments its binding out, so the reference's
+    Python cannot reach it) with the argument order of the C++ function and ITS indexing: `tex_coords [T,3]` float32 read at
+    stride 3, x through `tex_triangles`, y through the mesh triangle. `texture [tex_h,tex_w,tex_c]` float32,
+    `mapping_type` 0 = nearest, otherwise bilinear. Returns the float32 image `[h,w,c]`, drawn over a copy of `bg` (zeros
+    when None) with the depth buffer started at -1e8. Runs through the batched device entry (`Mesh.render_texture`)."""
+    import torch
+
+    from .mesh import Mesh
+
+    _lib.load()
+    v = _typed(vertices, np.float32, 2, "vertices")
+    t = _typed(triangles, np.int32, 2, "triangles")
+    tex = _typed(texture, np.float32, 3, "texture")
+    tc = _typed(tex_coords, np.float32, 2, "tex_coords")
+    tt = _typed(tex_triangles, np.int32, 2, "tex_triangles")
+    if bg is None:
+        image = np.zeros((h, w, c), dtype=np.float32)
+    else:
+        image = _typed(bg, np.float32, 3, "image").copy()
+        if image.shape != (h, w, c):
+            raise ValueError(f"image: expected shape {(h, w, c)}, got {image.shape}")
+    if v.shape[1] != 3 or t.shape[1] != 3 or tc.shape[1] != 3 or tt.shape != t.shape:
+        raise ValueError("vertices [nver,3], triangles [ntri,3], tex_coords [T,3] and tex_triangles [ntri,3] expected")
+    _lib.require_gpu()
+    mesh = Mesh(t, v.shape[0]).set_texcoords(tc, tt)
+    dev = mesh.torch_device
+    out = mesh.render_texture(torch.from_numpy(v[None]).to(dev), torch.from_numpy(tex).to(dev), torch.from_numpy(image[None]).to(dev),
+                              mapping="nearest" if mapping_type == 0 else "bilinear", indexing="reference")
+    return out[0].cpu().numpy()

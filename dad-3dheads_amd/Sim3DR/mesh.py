@@ -40,6 +40,8 @@ class Mesh:
         _lib.require_gpu()
         self.device_index = torch.cuda.current_device() if device is None else int(device)
         self.ntri, self.nver = int(tri.shape[0]), int(nver)
+        self._triangles = tri  # host copy: the default tex_triangles of set_texcoords
+        self.has_texcoords = False
         h = C.c_void_p()
         _lib.check(self._lib.dad3d_mesh_create(tri.ctypes.data, self.ntri, self.nver, self.device_index, C.byref(h)))
         self._handle = h
@@ -119,6 +121,67 @@ class Mesh:
         _lib.check(self._lib.dad3d_mesh_rasterize_triangles(self._handle, v.data_ptr(), depth.data_ptr(), tri_buf.data_ptr(),
                                                             bary.data_ptr(), b, h, w, self._stream()))
         return depth, tri_buf, bary
+
+    # -- textured render ---------------------------------------------------------------------------
+    def set_texcoords(self, tex_coords, tex_triangles=None) -> "Mesh":
+        """Attach the (static) texture coordinates of `render_texture`: `tex_coords [T,2]` or `[T,3]` float32 in texel
+        units (x = column, y = row; a third column is ignored) and `tex_triangles [ntri,3]` int32 indices into them
+        (`None`: the mesh's own triangles, for one coordinate per vertex). Host arrays, uploaded once; returns self."""
+        tc = np.ascontiguousarray(np.asarray(tex_coords))
+        if tc.dtype != np.float32:
+            raise ValueError(f"Buffer dtype mismatch, expected 'float' but got '{tc.dtype}'")
+        if tc.ndim != 2 or tc.shape[1] not in (2, 3):
+            raise ValueError(f"tex_coords must have shape [T, 2] or [T, 3], got {tc.shape}")
+        if tex_triangles is None:
+            if self._triangles is None:
+                raise ValueError("tex_triangles: required for this mesh")
+            tt = self._triangles
+        else:
+            tt = np.ascontiguousarray(np.asarray(tex_triangles))
+        if tt.dtype != np.int32:
+            raise ValueError(f"Buffer dtype mismatch, expected 'int' but got '{tt.dtype}'")
+        if tt.shape != (self.ntri, 3):
+            raise ValueError(f"tex_triangles must have shape [{self.ntri}, 3], got {tt.shape}")
+        _lib.check(self._lib.dad3d_mesh_set_texcoords(self._handle, tc.ctypes.data, tc.shape[0], tc.shape[1], tt.ctypes.data))
+        self.has_texcoords = True
+        return self
+
+    def render_texture(self, vertices: Tensor, texture: Tensor, out_or_bg: Tensor, depth: Optional[Tensor] = None,
+                       mapping: str = "bilinear", indexing: str = "corner") -> Tensor:
+        """`_render_texture_core` (rasterize_kernel.cpp:358-463) per image, in place on `out_or_bg` (returned): the mesh
+        drawn with a texture sampled at the interpolated texture coordinates of `set_texcoords`.
+
+        vertices [B,nver,3] float32; texture [B,th,tw,tc] or one shared [th,tw,tc], float32 or uint8; out_or_bg [B,h,w,c]
+        float32 (bit-exact with the reference) or uint8 (the float result through `(unsigned char)`), 1 <= c <= min(4, tc),
+        written where the mesh is drawn and kept elsewhere; depth [B,h,w] float32 in/out or None (start from -1e8).
+        mapping "bilinear" | "nearest". indexing "corner" (x and y through `tex_triangles`) or "reference" (the C++
+        function's own indexing: y through the mesh triangle). Pixels in the two-pixel border band of the image take any
+        triangle whose bounding box reaches them, as in the reference. Async on the current stream, no host copy."""
+        v = self._verts(vertices)
+        if mapping not in ("bilinear", "nearest"):
+            raise ValueError(f"mapping: 'bilinear' or 'nearest', got {mapping!r}")
+        if indexing not in ("corner", "reference"):
+            raise ValueError(f"indexing: 'corner' or 'reference', got {indexing!r}")
+        dtypes = {torch.float32: _lib.DTYPE_F32, torch.uint8: _lib.DTYPE_U8}
+        img, tex = out_or_bg, texture
+        for t, name, dims in ((img, "out_or_bg", (4,)), (tex, "texture", (3, 4))):
+            if t.dtype not in dtypes or t.ndim not in dims or not t.is_contiguous() or t.device != self.torch_device:
+                raise ValueError(f"{name}: expected a contiguous float32 or uint8 tensor with {' or '.join(map(str, dims))} dims on "
+                                 f"{self.torch_device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        b, h, w, c = img.shape
+        if v.shape[0] != b or (tex.ndim == 4 and tex.shape[0] != b):
+            raise ValueError("vertices/texture/out_or_bg batch mismatch")
+        th, tw, tc = tex.shape[-3:]
+        dptr = None
+        if depth is not None:
+            if tuple(depth.shape) != (b, h, w):
+                raise ValueError("depth: expected [B, h, w] like out_or_bg")
+            dptr = _chk(depth, torch.float32, 3, "depth", self.torch_device).data_ptr()
+        _lib.check(self._lib.dad3d_mesh_render_texture(
+            self._handle, img.data_ptr(), dtypes[img.dtype], v.data_ptr(), tex.data_ptr(), dtypes[tex.dtype], int(tex.ndim == 4), dptr,
+            b, h, w, c, th, tw, tc, 0 if mapping == "nearest" else 1,
+            _lib.TEX_INDEX_REFERENCE if indexing == "reference" else _lib.TEX_INDEX_CORNER, self._stream()))
+        return img
 
     # -- lighting ----------------------------------------------------------------------------------
     def phong_light(self, vertices: Tensor, normals: Optional[Tensor] = None, ambient: float = 0.3, directional: float = 0.6,

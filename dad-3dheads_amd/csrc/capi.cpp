@@ -911,11 +911,13 @@ struct dad3d_mesh {
     int ntri = 0, nver = 0;
     int *d_tri = nullptr, *d_adj_ptr = nullptr, *d_adj_face = nullptr;
     int4* d_adj_tri = nullptr;
+    std::vector<int> h_tri;  // the triangle list on the host (dad3d_mesh_set_texcoords reads it)
     uint2* d_nc_faces[kNormalChunkings] = {};  // chunk face lists of the normals kernels (NormalChunksDev)
     unsigned short* d_nc_slot[kNormalChunkings] = {};
     uint4* d_nc_row8[kNormalChunkings] = {};
     NormalChunksDev nc[kNormalChunkings] = {};
     unsigned long long* d_trace = nullptr;  // diagnostics (dad3d_mesh_debug_trace)
+    float4* d_tex_tri[2] = {};  // texel coordinates per triangle corner, [ntri][2] (dad3d_mesh_set_texcoords): corner / reference indexing
     void* d_raster = nullptr;  // per-image triangle boxes + corner planes, grown on demand (one stream at a time)
     size_t raster_bytes = 0;
     int raster_batch = 0, raster_h = 0, raster_w = 0;
@@ -961,6 +963,7 @@ dad3d_status dad3d_mesh_create(const int32_t* tri, int ntri, int nver, int devic
     m->ntri = ntri;
     m->nver = nver;
     std::vector<int> tri_v(tri, tri + 3 * (size_t)ntri);
+    m->h_tri = tri_v;
     std::vector<int4> adj_tri(face.size());
     for (size_t e = 0; e < face.size(); ++e) {
         const int f = face[e];
@@ -1076,7 +1079,8 @@ dad3d_status dad3d_mesh_create(const int32_t* tri, int ntri, int nver, int devic
 void dad3d_mesh_destroy(dad3d_mesh* m) {
     if (!m) return;
     DeviceGuard guard(m->device);
-    for (void* p : {(void*)m->d_tri, (void*)m->d_adj_ptr, (void*)m->d_adj_face, (void*)m->d_adj_tri, m->d_raster})
+    for (void* p : {(void*)m->d_tri, (void*)m->d_adj_ptr, (void*)m->d_adj_face, (void*)m->d_adj_tri, m->d_raster, (void*)m->d_tex_tri[0],
+                    (void*)m->d_tex_tri[1]})
         if (p) (void)hipFree(p);
     for (int k = 0; k < kNormalChunkings; ++k)
         for (void* p : {(void*)m->d_nc_faces[k], (void*)m->d_nc_slot[k], (void*)m->d_nc_row8[k]})
@@ -1151,6 +1155,64 @@ dad3d_status dad3d_mesh_rasterize_triangles(dad3d_mesh* m, const float* vertices
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
     return launch_rasterize(m->dev(), m->nc, m->d_raster, m->d_trace, nullptr, vertices, nullptr, depth, tri_buf, bary, batch, h, w, 3, 0, 1,
                             nullptr, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_mesh_set_texcoords(dad3d_mesh* m, const float* tex_coords, int n_tex, int stride, const int32_t* tex_triangles) {
+    DAD3D_REQUIRE(m, "dad3d_mesh_set_texcoords: null handle");
+    DAD3D_REQUIRE(stride == 2 || stride == 3, "dad3d_mesh_set_texcoords: tex_coords rows of 2 or 3 floats, got %d", stride);
+    DAD3D_REQUIRE(n_tex >= 0 && (tex_coords || n_tex == 0) && (tex_triangles || m->ntri == 0), "dad3d_mesh_set_texcoords: bad argument");
+    const size_t nt = (size_t)m->ntri;
+    for (size_t i = 0; i < 3 * nt; ++i)
+        DAD3D_REQUIRE(tex_triangles[i] >= 0 && tex_triangles[i] < n_tex, "texture triangle index %d out of range [0,%d)", tex_triangles[i], n_tex);
+    // reference indexing (rasterize_kernel.cpp:398-403) reads row tri[i] of tex_coords for y: possible when every mesh index is a row
+    bool ref_ok = stride == 3;
+    for (size_t i = 0; i < 3 * nt && ref_ok; ++i) ref_ok = m->h_tri[i] < n_tex;
+    std::vector<float4> corner(2 * nt), ref(ref_ok ? 2 * nt : 0);
+    for (size_t f = 0; f < nt; ++f) {
+        float cx[3], cy[3], ry[3];
+        for (int k = 0; k < 3; ++k) {
+            const size_t t = (size_t)tex_triangles[3 * f + k];
+            cx[k] = tex_coords[stride * t], cy[k] = tex_coords[stride * t + 1];
+            ry[k] = ref_ok ? tex_coords[stride * (size_t)m->h_tri[3 * f + k] + 1] : 0.0f;
+        }
+        corner[2 * f] = make_float4(cx[0], cy[0], cx[1], cy[1]);
+        corner[2 * f + 1] = make_float4(cx[2], cy[2], 0.0f, 0.0f);
+        if (ref_ok) {
+            ref[2 * f] = make_float4(cx[0], ry[0], cx[1], ry[1]);
+            ref[2 * f + 1] = make_float4(cx[2], ry[2], 0.0f, 0.0f);
+        }
+    }
+    DeviceGuard guard(m->device);
+    DAD3D_HIP_TRY(hipDeviceSynchronize());  // a launch in flight may still read the tables being replaced
+    for (float4*& p : m->d_tex_tri) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    if (nt == 0) return DAD3D_OK;
+    if (dad3d_status st = upload(&m->d_tex_tri[DAD3D_TEX_INDEX_CORNER], corner)) return st;
+    return ref_ok ? upload(&m->d_tex_tri[DAD3D_TEX_INDEX_REFERENCE], ref) : DAD3D_OK;
+}
+
+dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, int image_dtype, const float* vertices, const void* texture,
+                                       int texture_dtype, int texture_batched, float* depth, int batch, int h, int w, int c, int tex_h,
+                                       int tex_w, int tex_c, int mapping_type, int indexing, void* stream) {
+    // the scalar arguments first: a bad one is refused before the handle is looked at or any device work starts
+    DAD3D_REQUIRE(batch >= 0 && h >= 0 && w >= 0, "dad3d_mesh_render_texture: negative batch or image size");
+    DAD3D_REQUIRE((image_dtype == DAD3D_DTYPE_F32 || image_dtype == DAD3D_DTYPE_U8) && (texture_dtype == DAD3D_DTYPE_F32 || texture_dtype == DAD3D_DTYPE_U8),
+                  "dad3d_mesh_render_texture: image and texture are float32 (DAD3D_DTYPE_F32) or uint8 (DAD3D_DTYPE_U8)");
+    DAD3D_REQUIRE(tex_h >= 1 && tex_w >= 1 && tex_c >= 1 && (size_t)tex_h * tex_w * tex_c < (1ull << 31), "dad3d_mesh_render_texture: texture of %d x %d x %d", tex_h, tex_w, tex_c);
+    DAD3D_REQUIRE(c >= 1 && c <= 4 && c <= tex_c, "dad3d_mesh_render_texture: c = %d channels, need 1..4 and at most tex_c = %d", c, tex_c);
+    DAD3D_REQUIRE(indexing == DAD3D_TEX_INDEX_CORNER || indexing == DAD3D_TEX_INDEX_REFERENCE, "dad3d_mesh_render_texture: unknown indexing mode %d", indexing);
+    DAD3D_REQUIRE(m, "dad3d_mesh_render_texture: null handle");
+    if (batch == 0 || h == 0 || w == 0 || m->ntri == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(image && vertices && texture, "dad3d_mesh_render_texture: null buffer");
+    DAD3D_REQUIRE(m->d_tex_tri[DAD3D_TEX_INDEX_CORNER], "dad3d_mesh_render_texture: no texture coordinates attached (dad3d_mesh_set_texcoords)");
+    DAD3D_REQUIRE(m->d_tex_tri[indexing], "dad3d_mesh_render_texture: reference indexing needs tex_coords rows of 3 floats, one for every vertex a triangle names");
+    DeviceGuard guard(m->device);
+    if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
+    return launch_render_texture(m->dev(), m->d_raster, image, image_dtype == DAD3D_DTYPE_U8, vertices, m->d_tex_tri[indexing], texture,
+                                 texture_dtype == DAD3D_DTYPE_U8, texture_batched ? (size_t)tex_h * tex_w * tex_c : 0, depth, batch, h, w, c, tex_h,
+                                 tex_w, tex_c, mapping_type == 0, static_cast<hipStream_t>(stream));
 }
 
 dad3d_status dad3d_project_vertices(const float* vertices, const float* model_view, const float* projection,

@@ -300,6 +300,11 @@ dad3d_status raster_scratch_init(const MeshDev& m, void* scratch, int batch, int
 dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc, void* scratch, unsigned long long* trace, uint8_t* image, const float* vertices,
                               const float* colors, float* depth, int32_t* tri_buf, float* bary, int batch, int h,
                               int w, int c, int render_flags, int mode, const dad3d_light* light_cfg, hipStream_t s, float alpha = 1.0f);
+// _render_texture_core: tex_tri [ntri][2] float4 = the texel coordinates of every triangle's corners (x0 y0 x1 y1 | x2 y2 - -);
+// image / texture float32 or uint8; tex_image_stride = elements between two images' textures, 0 for one shared texture
+dad3d_status launch_render_texture(const MeshDev& m, void* scratch, void* image, int image_u8, const float* vertices, const float4* tex_tri,
+                                   const void* texture, int texture_u8, size_t tex_image_stride, float* depth, int batch, int h, int w, int c,
+                                   int tex_h, int tex_w, int tex_c, int nearest, hipStream_t s);
 dad3d_status launch_phong(const MeshDev& m, const NormalChunksDev* nc, float* light, const float* vertices, const float* normals,
                           float* normals_out, int batch, const dad3d_light& cfg, hipStream_t s);
 

@@ -2,7 +2,8 @@
 //
 // Replaces the serial loops of Sim3DR/lib/rasterize_kernel.cpp:
 //   _get_tri_normal 87-120, _get_ver_normal 125-153, _get_normal 158-215,
-//   _rasterize 219-292 (+ get_point_weight 54-82), _rasterize_triangles 295-353 (+ is_point_in_tri 26-52)
+//   _rasterize 219-292 (+ get_point_weight 54-82), _rasterize_triangles 295-353 (+ is_point_in_tri 26-52),
+//   _render_texture_core 358-463
 // and the numpy lighting of Sim3DR/lighting.py:37-62.
 //
 // THIS FILE IS COMPILED WITH -ffp-contract=off: the reference extension is an SSE2 build without FMA
@@ -1570,6 +1571,205 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// textured render (_render_texture_core, rasterize_kernel.cpp:358-463)
+// ------------------------------------------------------------------------------------------------
+// The third flavour of the tile kernel, on the geometry kernel's records, tile lists and work queue (the boxes are those of
+// _rasterize). What differs from raster_kernel<0>:
+//   * coverage (:423): is_point_in_tri (u >= 0, v >= 0, u + v < 1) OR the pixel lies in the two-pixel border band of the
+//     image (x < 2 || x > w - 3 || y < 2 || y > h - 3), where every triangle whose box reaches the pixel competes with
+//     extrapolated weights. Reference behaviour, kept.
+//   * the depth test (:427) is the `>` of _rasterize with alpha == 1 and the image is written, never read: the same key
+//     maximum (deepest fragment, ties to the lowest triangle, NaN never wins).
+//   * resolve (:430-453): the winner's weights are recomputed, tex_p = tex_p0 * w0 + tex_p1 * w1 + tex_p2 * w2 (Point
+//     operators: per component, left to right), clamped with std::max(std::min(t, size - 1), 0), then nearest
+//     (int(round(.)), half away from zero) or bilinear (ul*(1-xd)*(1-yd) + ur*xd*(1-yd) + dl*(1-xd)*yd + dr*xd*yd, floor /
+//     ceil indices), every operation rounded on its own.
+// The texel coordinates arrive per TRIANGLE CORNER (tex_tri: two float4 per triangle, x0 y0 x1 y1 | x2 y2 - -), laid out by
+// dad3d_mesh_set_texcoords for either indexing mode -- the reference's quirk (x through tex_triangles, y through the mesh
+// triangle, :398-403) is resolved once on the host, the kernel knows one layout.
+// Where the reference indexes the texture with whatever a NaN converts to, the indices here are clamped into the texture
+// after the conversion (NaN -> row / column 0): no read outside the texture, and a non-finite image of a batch touches
+// only its own pixels.
+// The walk is the one of raster_blend_kernel (a wave reads 64 list entries; a small box is walked by its own lane, a large
+// one by the whole wave); the texel gathers of the resolve (up to four texels x c) are served by L2.
+struct TextureArgs {  // only what the kernel reads: every member is a scalar register for the whole launch
+    const int* tri;          // [ntri][3]
+    const float3u* rec;      // RasterScratch: records, tile lists, queue header, queue
+    const unsigned* lists;
+    unsigned* qhdr;
+    const uint2* queue;
+    void* image;             // [B][h][w][c]  IMG
+    const float* vertices;   // [B][nver][3]
+    const float4* tex_tri;   // [ntri][2]
+    const void* texture;     // [B or 1][tex_h][tex_w][tex_c]  TEX
+    size_t tex_image_stride; // elements between two images' textures; 0: one texture for all
+    float* depth;            // [B][h][w] in/out or null
+    int ntri, nver, tiles_x, ntiles, h, w, c, tex_h, tex_w, tex_c, nearest;
+};
+
+__device__ __forceinline__ int texel_index(float t, int size) {  // (int) of an already rounded coordinate, kept inside the texture
+    return min(max(f2i_x86(t), 0), size - 1);
+}
+
+template <class IMG, class TEX>
+__global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void render_texture_kernel(TextureArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned long long keys[kTile * kTile];  // orderable depth << 32 | ~triangle
+    __shared__ unsigned s_next;
+    const unsigned* kw = reinterpret_cast<const unsigned*>(keys);
+    const int tid = threadIdx.x;
+    const int ntiles = a.ntiles;
+    const size_t nt = a.ntri;
+    const unsigned n_items = a.qhdr[0];
+    unsigned item = blockIdx.x;
+    while (item < n_items) {
+        const uint2 qe = a.queue[item];
+        const int level = (qe.x >> 24) & 3, part = qe.x >> 26, n_total = (int)qe.y;
+        const size_t b = (qe.x & 0xFFFFFFu) / ntiles;
+        const int tile = (qe.x & 0xFFFFFFu) % ntiles;
+        const int edge = kTile >> level, edge_shift = kTileShift - level;
+        const int tx0 = (tile % a.tiles_x) * kTile + (part & ((1 << level) - 1)) * edge;
+        const int ty0 = (tile / a.tiles_x) * kTile + (part >> level) * edge;
+        const int tw = min(edge, a.w - tx0), th = min(edge, a.h - ty0);
+        const int tx1 = tx0 + tw - 1, ty1 = ty0 + th - 1;
+        const float3u* rec_b = a.rec + b * nt;
+        const float* vb = a.vertices + b * a.nver * 3;
+        const unsigned* glist = a.lists + (b * ntiles + tile) * nt;
+        float* depth_b = a.depth ? a.depth + b * (size_t)a.h * a.w : nullptr;
+        if (tw > 0 && th > 0) {  // a part can lie beyond the image edge
+            for (int p = tid; p < edge * th; p += kRasterThreads) {
+                const int ly = p >> edge_shift, lx = p & (edge - 1);
+                if (lx >= tw) continue;
+                const float z0 = depth_b ? depth_b[(size_t)(ty0 + ly) * a.w + tx0 + lx] : -1e8f;
+                keys[ly * kTile + lx] = ((unsigned long long)depth_order(z0) << 32) | kNoTri;
+            }
+            __syncthreads();
+            struct Corners {  // what a lane keeps of its triangle: the three corners, inv, the box clipped to the item
+                float x0, y0, z0, x1, y1, z1, x2, y2, z2, inv;
+                int bx0, bx1, by0, by1;
+            };
+            auto load_tri = [&](unsigned f, Corners& c) {
+                const float3u rc = rec_b[f];
+                const unsigned bbx = __float_as_uint(rc.y), bby = __float_as_uint(rc.z);
+                c.bx0 = max((int)(bbx & 0xffff), tx0), c.bx1 = min((int)(bbx >> 16), tx1);
+                c.by0 = max((int)(bby & 0xffff), ty0), c.by1 = min((int)(bby >> 16), ty1);
+                if (c.bx1 < c.bx0 || c.by1 < c.by0) return false;
+                const int i0 = a.tri[3 * (size_t)f], i1 = a.tri[3 * (size_t)f + 1], i2 = a.tri[3 * (size_t)f + 2];
+                c.x0 = vb[3 * i0], c.y0 = vb[3 * i0 + 1], c.z0 = vb[3 * i0 + 2];
+                c.x1 = vb[3 * i1], c.y1 = vb[3 * i1 + 1], c.z1 = vb[3 * i1 + 2];
+                c.x2 = vb[3 * i2], c.y2 = vb[3 * i2 + 1], c.z2 = vb[3 * i2 + 2];
+                c.inv = rc.x;
+                return true;
+            };
+            auto test_pixel = [&](const TriSetup& ts, float z0, float z1, float z2, unsigned f, int x, int y) {
+                float u, v;
+                tri_uv(ts, (float)x, (float)y, u, v);
+                const bool band = x < 2 || x > a.w - 3 || y < 2 || y > a.h - 3;
+                if (!(band || (u >= 0.0f && v >= 0.0f && (u + v < 1.0f)))) return;
+                const float w0 = 1.0f - u - v;
+                const float z = w0 * z0 + v * z1 + u * z2;
+                if (z != z) return;  // NaN never passes `>`
+                const unsigned long long key = ((unsigned long long)depth_order_number(z) << 32) | (0xFFFFFFFEu - f);
+                (void)__hip_atomic_fetch_max(&keys[(y - ty0) * kTile + (x - tx0)], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            constexpr unsigned kBigClass = DAD3D_BLEND_BIG_CLASS;  // area class >= this: the whole wave takes the triangle
+            const int lane = tid & 63;
+            for (int base = (tid >> 6) * 64; base < n_total; base += kRasterThreads) {
+                const int i = base + lane;
+                const unsigned e = i < n_total ? glist[i] : ~0u;
+                const unsigned f_own = e & kIdMask;
+                Corners c{};
+                const bool ok = e != ~0u && load_tri(f_own, c);
+                const bool big = ok && (e >> 28) >= kBigClass;
+                if (ok && !big) {
+                    const TriSetup ts = setup_from_corners(c.x0, c.y0, c.x1, c.y1, c.x2, c.y2, c.inv);
+                    for (int y = c.by0; y <= c.by1; ++y)
+                        for (int x = c.bx0; x <= c.bx1; ++x) test_pixel(ts, c.z0, c.z1, c.z2, f_own, x, y);
+                }
+                unsigned long long todo = __ballot(big);
+                while (todo) {  // wave-uniform loop: one large triangle at a time, all 64 lanes on its box
+                    const int j = __builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    auto bf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
+                    auto bi = [&](int v) { return __builtin_amdgcn_readlane(v, j); };
+                    const unsigned f = (unsigned)bi((int)f_own);
+                    const TriSetup ts = setup_from_corners(bf(c.x0), bf(c.y0), bf(c.x1), bf(c.y1), bf(c.x2), bf(c.y2), bf(c.inv));
+                    const float z0 = bf(c.z0), z1 = bf(c.z1), z2 = bf(c.z2);
+                    const int x0 = bi(c.bx0), x1 = bi(c.bx1), y0 = bi(c.by0), y1 = bi(c.by1);
+                    const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);
+                    const float rcp_bw = __builtin_amdgcn_rcpf((float)bw);
+                    for (int p = lane; p < area; p += 64) {
+                        // exact p / bw for p < 4096, bw <= 64 (see raster_blend_kernel)
+                        const int py = (int)(((float)p + 0.5f) * rcp_bw), px = p - py * bw;
+                        test_pixel(ts, z0, z1, z2, f, x0 + px, y0 + py);
+                    }
+                }
+            }
+            __syncthreads();
+            // resolve: a lane owns a pixel, the lanes of a wave a run of one row
+            // Its arguments are read again from the kernarg segment here (kernarg_reload) instead of living in scalar registers
+            // through the walk, which needs its own for the loop masks.
+#define DAD3D_TEX_ARG(type, member) kernarg_reload<type>(offsetof(TextureArgs, member))
+            const int n_chan = DAD3D_TEX_ARG(int, c), tex_h = DAD3D_TEX_ARG(int, tex_h), tex_w = DAD3D_TEX_ARG(int, tex_w);
+            const int tex_c = DAD3D_TEX_ARG(int, tex_c), nearest = DAD3D_TEX_ARG(int, nearest);
+            const float4* tex_tri = DAD3D_TEX_ARG(const float4*, tex_tri);
+            const TEX* tex = static_cast<const TEX*>(DAD3D_TEX_ARG(const void*, texture)) + b * DAD3D_TEX_ARG(size_t, tex_image_stride);
+            IMG* img_b = static_cast<IMG*>(DAD3D_TEX_ARG(void*, image)) + b * (size_t)a.h * a.w * n_chan;
+            float* depth_r = DAD3D_TEX_ARG(float*, depth);
+            if (depth_r) depth_r += b * (size_t)a.h * a.w;
+#undef DAD3D_TEX_ARG
+            const float xmax = (float)(tex_w - 1), ymax = (float)(tex_h - 1);
+            for (int p = tid; p < edge * th; p += kRasterThreads) {
+                const int ly = p >> edge_shift, lx = p & (edge - 1);
+                if (lx >= tw) continue;
+                const unsigned lo = kw[2 * (ly * kTile + lx)];
+                if (lo == kNoTri) continue;  // nothing beat the incoming depth: pixel and depth stay as they are
+                const unsigned f = 0xFFFFFFFEu - lo;
+                const int i0 = a.tri[3 * (size_t)f], i1 = a.tri[3 * (size_t)f + 1], i2 = a.tri[3 * (size_t)f + 2];
+                const float4 ta = tex_tri[2 * (size_t)f], tb = tex_tri[2 * (size_t)f + 1];
+                const TriSetup ts = setup_from_corners(vb[3 * i0], vb[3 * i0 + 1], vb[3 * i1], vb[3 * i1 + 1], vb[3 * i2], vb[3 * i2 + 1], rec_b[f].x);
+                float u, v;
+                tri_uv(ts, (float)(tx0 + lx), (float)(ty0 + ly), u, v);
+                const float w0 = 1.0f - u - v;
+                const size_t pix = (size_t)(ty0 + ly) * a.w + tx0 + lx;
+                if (depth_r) depth_r[pix] = w0 * vb[3 * i0 + 2] + v * vb[3 * i1 + 2] + u * vb[3 * i2 + 2];
+                float px = ta.x * w0 + ta.z * v + tb.x * u;
+                float py = ta.y * w0 + ta.w * v + tb.y * u;
+                px = std_max(std_min(px, xmax), 0.0f);
+                py = std_max(std_min(py, ymax), 0.0f);
+                IMG* out = img_b + pix * n_chan;
+                auto texel = [&](int y, int x, int k) { return (float)tex[((size_t)y * tex_w + x) * tex_c + k]; };
+                auto store = [&](int k, float val) {
+                    if (std::is_same<IMG, float>::value) out[k] = (IMG)val;
+                    else out[k] = (IMG)(f2i_x86(val) & 0xff);  // (unsigned char) of the float
+                };
+                if (nearest) {
+                    const int y = texel_index(roundf(py), tex_h), x = texel_index(roundf(px), tex_w);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)  // 1..4 channels: a fixed bound and a guard
+                        if (k < n_chan) store(k, texel(y, x, k));
+                } else {
+                    const float fy = floorf(py), fx = floorf(px);
+                    const float yd = py - fy, xd = px - fx;
+                    const int yf = texel_index(fy, tex_h), yc = texel_index(ceilf(py), tex_h);
+                    const int xf = texel_index(fx, tex_w), xc = texel_index(ceilf(px), tex_w);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (k < n_chan) {
+                            const float ul = texel(yf, xf, k), ur = texel(yf, xc, k), dl = texel(yc, xf, k), dr = texel(yc, xc, k);
+                            store(k, ul * (1.0f - xd) * (1.0f - yd) + ur * xd * (1.0f - yd) + dl * (1.0f - xd) * yd + dr * xd * yd);
+                        }
+                }
+            }
+        }
+        __syncthreads();  // the keys are reused by the next item
+        if (tid == 0) s_next = gridDim.x + atomicAdd(&a.qhdr[1], 1u);
+        __syncthreads();
+        item = s_next;
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1765,6 +1965,7 @@ dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, v
         }
         DAD3D_HIP_TRY(hipGetLastError());
     }
+    if (mode == 3) return DAD3D_OK;  // geometry, lists and queue only: launch_render_texture runs its own tile kernel on them
     RasterArgs a{m, sc, image, vertices, colors, depth, tri_buf, bary, trace, h, w, c, reverse};
     const int blocks = (int)std::min<size_t>(persistent_blocks[mode ? 1 : 0], nlists * kMaxSubs);
     if (mode == 0)
@@ -1774,6 +1975,39 @@ dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, v
     else  // one workgroup per CU: 80 KB of LDS
         hipLaunchKernelGGL(raster_blend_kernel, dim3(std::min<size_t>(persistent_blocks[0] / 2 + 1, nlists * kMaxSubs)), dim3(kRasterThreads), 0, s,
                            a, alpha);
+    DAD3D_HIP_TRY(hipGetLastError());
+    return DAD3D_OK;
+}
+
+// _render_texture_core for a batch: the geometry launch of launch_rasterize (same boxes, lists and queue), then the texture tile kernel
+dad3d_status launch_render_texture(const MeshDev& m, void* scratch, void* image, int image_u8, const float* vertices, const float4* tex_tri,
+                                   const void* texture, int texture_u8, size_t tex_image_stride, float* depth, int batch, int h, int w, int c,
+                                   int tex_h, int tex_w, int tex_c, int nearest, hipStream_t s) {
+    DAD3D_REQUIRE(c >= 1 && c <= 4 && c <= tex_c, "render_texture: 1 to 4 channels and no more than the texture's %d, got %d", tex_c, c);
+    DAD3D_REQUIRE(tex_h >= 1 && tex_w >= 1, "render_texture: empty texture");
+    if (batch == 0 || h == 0 || w == 0 || m.ntri == 0) return DAD3D_OK;
+    if (dad3d_status st = launch_rasterize(m, nullptr, scratch, nullptr, nullptr, vertices, nullptr, nullptr, nullptr, nullptr, batch, h, w, 3, 0, 3,
+                                           nullptr, s))
+        return st;
+    static int cus = 0;  // the same for every device of the node (one GPU model)
+    if (!cus) {
+        int dev = 0, n = 0;
+        DAD3D_HIP_TRY(hipGetDevice(&dev));
+        DAD3D_HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        cus = std::max(n, 1);
+    }
+    const ScratchLayout lay(m, batch, h, w);
+    char* base = static_cast<char*>(scratch);
+    TextureArgs a{m.tri, reinterpret_cast<const float3u*>(base + lay.rec), reinterpret_cast<const unsigned*>(base + lay.lists),
+                  reinterpret_cast<unsigned*>(base + lay.qhdr), reinterpret_cast<const uint2*>(base + lay.queue), image, vertices, tex_tri,
+                  texture, tex_image_stride, depth, m.ntri, m.nver, tiles_of(w), tiles_of(w) * tiles_of(h), h, w, c, tex_h, tex_w, tex_c, nearest};
+    const size_t nlists = (size_t)batch * tiles_of(h) * tiles_of(w);
+    // two workgroups per CU (launch bounds: four waves per SIMD), persistent
+    const dim3 grid((unsigned)std::min<size_t>(2 * (size_t)cus, nlists * kMaxSubs)), block(kRasterThreads);
+    if (image_u8 && texture_u8) hipLaunchKernelGGL((render_texture_kernel<uint8_t, uint8_t>), grid, block, 0, s, a);
+    else if (image_u8) hipLaunchKernelGGL((render_texture_kernel<uint8_t, float>), grid, block, 0, s, a);
+    else if (texture_u8) hipLaunchKernelGGL((render_texture_kernel<float, uint8_t>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((render_texture_kernel<float, float>), grid, block, 0, s, a);
     DAD3D_HIP_TRY(hipGetLastError());
     return DAD3D_OK;
 }

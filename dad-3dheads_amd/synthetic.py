@@ -198,6 +198,27 @@ def synthetic_texture_data(img_size: int = 256, seed: int = 0, static: Optional[
             "img_size": s}
 
 
+def synthetic_texcoords(img_size: int = 256, static: Optional[dict] = None) -> dict:
+    """The corner layout that goes with `synthetic_texture_data`: the same cylindrical map as texture coordinates.
+
+        vt  float64 [V,2]   (u, v) in [0, 1] per vertex, v up (the OBJ convention): texel column u * (S - 1), texel row
+                            (1 - v) * (S - 1) -- exactly the positions `synthetic_texture_data(S)` rasterises its faces at
+        ft  int32 [F,3]     per face the rows of `vt` of its corners; -1 -1 -1 for a face across the seam (the atlas leaves
+                            those out too), which has no texture coordinates
+
+    `img_size` only enters the seam rule (the atlas states it in texel units). The map has no duplicated seam vertices (the seam faces are dropped instead), so `ft` repeats the face list."""
+    st = static if static is not None else load_static()
+    faces = st["faces"].astype(np.int64)
+    v = st["template_geo"].astype(np.float64)
+    u = _diamond_angle(v[:, 0], v[:, 2]) / 4.0
+    h = (v[:, 1] - v[:, 1].min()) / (v[:, 1].max() - v[:, 1].min())
+    fx = (u * (int(img_size) - 1))[faces]
+    seam = fx.max(1) - fx.min(1) > 0.5 * int(img_size)  # the atlas' own rule, in its texel units
+    ft = faces.astype(np.int32)
+    ft[seam] = -1
+    return {"vt": np.stack([u, h], 1), "ft": ft}
+
+
 def texture_data_digest(texture_data: dict) -> str:
     """sha256 over the atlas' arrays in key order (dtype, shape and bytes): guards golden textures against drift."""
     h = hashlib.sha256()

@@ -32,6 +32,7 @@ from torch import Tensor
 
 from . import _lib
 from .head_mesh import HeadMesh
+from .Sim3DR.mesh import Mesh
 from .synthetic import load_static
 
 
@@ -69,6 +70,17 @@ def texel_table(texture_data: dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray,
     if not (len(texel) == len(verts) == len(bary)):
         raise ValueError(f"texture_data: {len(texel)} pixel ids, {len(verts)} vertex triples, {len(bary)} barycentric rows")
     return np.ascontiguousarray(texel), verts, bary, s
+
+
+def texel_coords(vt: np.ndarray, size: int) -> np.ndarray:
+    """Texture coordinates `vt [T,2]` in [0, 1] (u to the right, v UP: the OBJ convention) -> float32 texel units for an
+    S x S texture: column u * (S - 1), row (1 - v) * (S - 1), so that (0, 1) is the centre of texel [0, 0] and (1, 0) the
+    centre of texel [S-1, S-1]. This is the convention `synthetic.synthetic_texcoords` is written in; whether upstream's
+    `texture_data.npy` follows it is unverified (the file is absent)."""
+    vt = np.asarray(vt, dtype=np.float64)
+    if vt.ndim != 2 or vt.shape[1] < 2:
+        raise ValueError(f"vt must have shape [T, 2], got {vt.shape}")
+    return np.stack([vt[:, 0] * (size - 1), (1.0 - vt[:, 1]) * (size - 1)], 1)
 
 
 def _check_image(image) -> np.ndarray:
@@ -147,7 +159,10 @@ class UVTextureCreator:
     `device`) when no `head_mesh` is given, as in `pncc.PNCCEstimator`."""
 
     def __init__(self, texture_data: Union[str, dict, None] = None, head_mesh: Optional[HeadMesh] = None,
-                 static: Optional[dict] = None, **head_mesh_kwargs):
+                 static: Optional[dict] = None, tex_coords: Optional[np.ndarray] = None,
+                 tex_triangles: Optional[np.ndarray] = None, **head_mesh_kwargs):
+        self._tex_layout = None if tex_coords is None else (tex_coords, tex_triangles)
+        self._renderer: Optional[Mesh] = None
         self.texture_data = _resolve_texture_data(texture_data)
         texel_table(self.texture_data)  # refuse an out-of-range texel before any device work
         st = static if static is not None else load_static()
@@ -232,3 +247,69 @@ class UVTextureCreator:
         verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, mutate=mutate)["proj"]
         normals = m.vertex_normals(verts, out=self._normals[:b])
         return m.bake(verts, normals, images, hw=hw, out=out)
+
+    # -- textured render: the other half of the bake -------------------------------------------------------
+    def set_texcoords(self, tex_coords: np.ndarray, tex_triangles: np.ndarray) -> None:
+        """The corner layout `render_batch` samples with: `tex_coords [T,2]` in TEXEL units of the S x S texture (x = column,
+        y = row) and `tex_triangles [F,3]`, one row per face of the head topology, a negative row for a face without texture
+        coordinates (left out of the render). Replaces what the atlas' `vt` / `ft` keys or the constructor gave."""
+        self._tex_layout = (tex_coords, tex_triangles)
+        self._renderer = None
+
+    @property
+    def renderer(self) -> Mesh:
+        """The `Sim3DR.Mesh` of the faces that have texture coordinates, with those attached; built on first use.
+
+        The layout comes from `set_texcoords` / the constructor's `tex_coords`, `tex_triangles`, else from the atlas' keys
+        `vt` [T,2] and `ft` [F,3] through `texel_coords` (upstream's `texture_data.npy` is believed to carry them: unverified,
+        the file is absent; `synthetic.synthetic_texcoords` supplies them for the synthetic atlas)."""
+        if self._renderer is None:
+            if self._tex_layout is not None:
+                tc, ft = self._tex_layout
+            elif "vt" in self.texture_data and "ft" in self.texture_data:
+                tc, ft = texel_coords(self.texture_data["vt"], self.img_size), self.texture_data["ft"]
+            else:
+                raise ValueError("render_batch needs texture coordinates: texture_data has no 'vt' / 'ft' keys; pass tex_coords and "
+                                 "tex_triangles (texel units) to the constructor or to set_texcoords")
+            faces = np.asarray(self.flame_model["f"]).astype(np.int32)
+            ft = np.asarray(ft).astype(np.int64)
+            if ft.shape != faces.shape:
+                raise ValueError(f"tex_triangles: expected one row per face {faces.shape}, got {ft.shape}")
+            keep = (ft >= 0).all(1)
+            mesh = Mesh(np.ascontiguousarray(faces[keep]), int(self.head_mesh.flame.n_verts), device=self.head_mesh.flame.device_index)
+            mesh.set_texcoords(np.ascontiguousarray(np.asarray(tc)[:, :2], dtype=np.float32), np.ascontiguousarray(ft[keep], dtype=np.int32))
+            self._renderer = mesh
+        return self._renderer
+
+    def reserve_render(self, batch: int, size: Optional[Tuple[int, int]] = None) -> None:
+        """Size the raster scratch of `render_batch` for `batch` images of `size` (one throw-away render of a collapsed mesh),
+        so that a later call of that shape allocates nothing and can be captured in a graph."""
+        mesh = self.renderer
+        h, w = size if size is not None else (self.head_mesh._image_size,) * 2
+        dev = mesh.torch_device
+        mesh.render_texture(torch.zeros((batch, mesh.nver, 3), dtype=torch.float32, device=dev),
+                            torch.zeros((1, 1, 3), dtype=torch.uint8, device=dev),
+                            torch.zeros((batch, h, w, 3), dtype=torch.uint8, device=dev))
+
+    def render_batch(self, params: Tensor, textures: Tensor, bg: Optional[Tensor] = None, size: Optional[Tuple[int, int]] = None,
+                     mapping: str = "bilinear", out: Optional[Tensor] = None, mutate: bool = True) -> Tensor:
+        """`params [B,413]` fp32 and `textures` (what `bake_batch` returns: `[B,S,S,3]` uint8, or one shared `[S,S,3]`; float32
+        works too) on the GPU -> the textured heads `[B,H,W,3]` on the GPU: the head re-rendered at the pose of `params`.
+
+        One fused decode launch (`proj=True, to_2d=False`, z flipped as `PNCCEstimator.render_batch` does, because Sim3DR keeps
+        the LARGER depth), then the geometry and tile launches of `Mesh.render_texture` (`_render_texture_core`,
+        rasterize_kernel.cpp:358-463). The image is `out` when given (`bg` is copied into it first, without `bg` its own content is the
+        background), else `bg` itself (rendered into, like `PNCCEstimator.render_batch`), else black uint8 of `size=(H, W)` (the head mesh's image size by default). No host sync; capturable in a graph after one call
+        of the same shape or after `reserve_render(batch, size)`, with `out` given."""
+        mesh = self.renderer
+        b = params.shape[0]
+        if out is None:
+            if bg is not None:
+                out = bg
+            else:
+                h, w = size if size is not None else (self.head_mesh._image_size,) * 2
+                out = torch.zeros((b, h, w, 3), dtype=torch.uint8, device=mesh.torch_device)
+        elif bg is not None:
+            out.copy_(bg)
+        verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=mutate)["proj"]
+        return mesh.render_texture(verts, textures, out, mapping=mapping)

@@ -310,6 +310,44 @@ enum { DAD3D_RENDER_REVERSE = 1, DAD3D_RENDER_CLEAR = 2 };
 DAD3D_EXPORT dad3d_status dad3d_mesh_render(dad3d_mesh* m, uint8_t* image, const float* vertices, float* light, float* depth, int batch,
                                int h, int w, const dad3d_light* cfg, int flags, void* stream);
 
+/* Batched `_render_texture_core` (rasterize_kernel.cpp:358-463, declared in rasterize.h:102-109; the reference's Cython binding
+ * comments it out): a head drawn with a texture instead of per-vertex colours. Two launches: the geometry kernel of
+ * dad3d_mesh_rasterize (same boxes), then a tile kernel with
+ *   coverage (:423)  is_point_in_tri (u >= 0, v >= 0, u + v < 1) OR the pixel lies in the two-pixel border band of the image
+ *                    (x < 2 || x > w - 3 || y < 2 || y > h - 3): there every triangle whose box reaches the pixel competes with
+ *                    extrapolated weights. Reference behaviour, kept.
+ *   depth (:425-427) `>`: the deepest fragment, ties to the lowest triangle index, NaN never wins.
+ *   texel (:432-453) tex_p = tex_p0 * w0 + tex_p1 * w1 + tex_p2 * w2, clamped to [0, size - 1]; mapping_type 0 = nearest
+ *                    (round half away from zero), otherwise bilinear over the floor / ceil texels. Unfused, in the reference's
+ *                    order: bit-exact on the float path.
+ * dad3d_mesh_set_texcoords attaches the (static) texture coordinates, HOST arrays uploaded once: tex_coords [n_tex, stride] fp32
+ * in texel units (x = column, y = row; stride 2 or 3, a third column is ignored), tex_triangles int32 [ntri,3] with indices in
+ * [0, n_tex). It synchronises the device and may be called again to replace them. Both indexing modes are laid out from it:
+ *   DAD3D_TEX_INDEX_CORNER     x and y of corner k of triangle i from row tex_triangles[i][k]: what a UV layout with seams needs.
+ *                              The reference gives the same image when it is called on the unrolled mesh (one vertex per corner).
+ *   DAD3D_TEX_INDEX_REFERENCE  the reference as it is (:398-403): x from row tex_triangles[i][k], y from row triangles[i][k] (the
+ *                              MESH triangle), rows of 3 floats. Available when stride == 3 and every vertex index is < n_tex.
+ * dad3d_mesh_render_texture, DEVICE buffers:
+ *   image    [B,h,w,c] float32 or uint8 (image_dtype), written where a fragment wins, untouched elsewhere. uint8: the float
+ *            result through (unsigned char), i.e. the float image's astype(uint8).
+ *   vertices [B,nver,3] fp32 (pixel x, pixel y, depth)
+ *   texture  [B,tex_h,tex_w,tex_c] (texture_batched != 0) or one [tex_h,tex_w,tex_c] for all images, float32 or uint8
+ *            (texture_dtype; uint8 texels are widened to float first). The first c channels are used.
+ *   depth    [B,h,w] fp32 in/out, or NULL = start from -1e8 and discard
+ * c outside 1..4 or above tex_c, an unknown dtype or indexing mode, a missing table -> DAD3D_E_INVALID. Where the reference
+ * indexes the texture with whatever a non-finite coordinate converts to, the row / column here is clamped into the texture after
+ * the conversion (NaN reads row / column 0): nothing outside the texture is read and a non-finite image of a batch changes only
+ * its own pixels. `nver` and `tex_nver` of the reference are unused there and have no counterpart. Scratch, stream rule and limits
+ * as for dad3d_mesh_rasterize. */
+enum { DAD3D_TEX_INDEX_CORNER = 0, DAD3D_TEX_INDEX_REFERENCE = 1 };
+enum { DAD3D_DTYPE_F32 = 0, DAD3D_DTYPE_U8 = 1 };
+DAD3D_EXPORT dad3d_status dad3d_mesh_set_texcoords(dad3d_mesh* m, const float* tex_coords, int n_tex, int stride,
+                                                   const int32_t* tex_triangles);
+DAD3D_EXPORT dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, int image_dtype, const float* vertices,
+                                                    const void* texture, int texture_dtype, int texture_batched, float* depth,
+                                                    int batch, int h, int w, int c, int tex_h, int tex_w, int tex_c,
+                                                    int mapping_type, int indexing, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Matrix projection of meshes (GT annotations): model_training/data/flame_dataset.py:115-141 (`_load_mesh`,
  * `_project_vertices_onto_image`), visualize.py:10-22 (`get_2d_keypoints`). All DEVICE pointers:
