@@ -1249,6 +1249,30 @@ dad3d_status dad3d_gt_keypoints(const float* vertices, const float* model_view, 
     return launch_gt_keypoints(a, batch, static_cast<hipStream_t>(stream));
 }
 
+size_t dad3d_obj_format_scratch_bytes(int batch, int nver) {
+    return batch < 0 || nver < 0 ? 0 : obj_format_scratch_bytes(batch, nver);
+}
+
+dad3d_status dad3d_obj_format_vertices(const float* vertices, int batch, int nver, uint8_t* text, size_t text_stride, int64_t* lengths,
+                                       int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 0 && nver >= 0, "dad3d_obj_format_vertices: bad argument");
+    DAD3D_REQUIRE(batch <= 65535 && nver <= 0x7fffffff / DAD3D_OBJ_MAX_LINE_BYTES, "dad3d_obj_format_vertices: batch %d / %d vertices beyond the launch grid",
+                  batch, nver);
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE((vertices || nver == 0) && text && lengths && flags && scratch, "dad3d_obj_format_vertices: null argument");
+    DAD3D_REQUIRE(text_stride >= (size_t)nver * DAD3D_OBJ_MAX_LINE_BYTES, "dad3d_obj_format_vertices: text_stride %zu is below the worst case of %d vertices (%zu bytes)",
+                  text_stride, nver, (size_t)nver * DAD3D_OBJ_MAX_LINE_BYTES);
+    DAD3D_REQUIRE(text_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(text) & 15) == 0, "dad3d_obj_format_vertices: text and text_stride must be 16-byte aligned");
+    DAD3D_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && (reinterpret_cast<uintptr_t>(lengths) & 7) == 0 && (reinterpret_cast<uintptr_t>(flags) & 3) == 0,
+                  "dad3d_obj_format_vertices: lengths / flags / scratch are misaligned");
+    DAD3D_REQUIRE(scratch_bytes >= obj_format_scratch_bytes(batch, nver), "dad3d_obj_format_vertices: %zu bytes of scratch, %zu needed", scratch_bytes,
+                  obj_format_scratch_bytes(batch, nver));
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    ObjFormatArgs a{vertices, text, text_stride, lengths, flags, scratch, batch, nver};
+    return launch_obj_format(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_preprocess_images(const int64_t* descs, int batch, int out_size, const float* mean, const float* std,
                                      float* out, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && out_size > 0, "dad3d_preprocess_images: bad argument");

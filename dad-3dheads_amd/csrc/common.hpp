@@ -464,6 +464,20 @@ struct GtKeypointsArgs {
 };
 dad3d_status launch_gt_keypoints(const GtKeypointsArgs& a, int batch, hipStream_t s);
 
+// the .obj vertex text (obj_text.hip): `v %.8f %.8f %.8f\n` per vertex, the bytes MeshSaver writes (demo_utils.py:130-144)
+struct ObjFormatArgs {
+    const float* vertices;  // [B,N,3]
+    unsigned char* text;    // [B][text_stride], 16-byte aligned rows; mesh b's lines start at b * text_stride
+    size_t text_stride;     // >= N * DAD3D_OBJ_MAX_LINE_BYTES, a multiple of 16
+    int64_t* lengths;       // [B] bytes of mesh b's text; 0 for a flagged mesh
+    int32_t* flags;         // [B] DAD3D_OBJ_FLAG_* bits: the mesh holds a value outside the domain and has no text
+    void* scratch;          // obj_format_scratch_bytes(B, N): {length, flag bits} per tile of 256 lines
+    int batch, nver;
+};
+inline int obj_format_tiles(int nver) { return nver > 256 ? (nver + 255) / 256 : 1; }
+size_t obj_format_scratch_bytes(int batch, int nver);
+dad3d_status launch_obj_format(const ObjFormatArgs& a, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

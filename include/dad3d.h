@@ -13,6 +13,7 @@
 #ifndef DAD3D_H_
 #define DAD3D_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 /* libdad3d_hip.so is built with -fvisibility=hidden: the functions declared here and the five C++-linkage Sim3DR doubles of
@@ -519,6 +520,28 @@ DAD3D_EXPORT dad3d_status dad3d_uvmap_vertex_normals(dad3d_uvmap* m, double* nor
                                         void* stream);
 DAD3D_EXPORT dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* vertices, const double* normals,
                               const uint8_t* images, const int32_t* hw, int batch, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The vertex block of the demo's `.obj` files (demo_utils.py:130-144 `MeshSaver.__call__`): for every mesh of a batch the bytes of
+ * its N lines `v %.8f %.8f %.8f\n`, exactly what Python's `'%.8f' % float(x)` prints, made on the device with 64-bit integer
+ * arithmetic. All DEVICE pointers:
+ *   vertices [batch,nver,3] float32, contiguous
+ *   text     [batch][text_stride] bytes, 16-byte aligned; text_stride a multiple of 16, at least nver * DAD3D_OBJ_MAX_LINE_BYTES.
+ *            Mesh b's lines are text[b * text_stride .. + lengths[b]); bytes behind them are left as they were
+ *   lengths  [batch] int64   flags [batch] int32   scratch: dad3d_obj_format_scratch_bytes(batch, nver) bytes, 8-byte aligned
+ * Domain: finite values with |x| < 2^37. A mesh that holds any other value gets its DAD3D_OBJ_FLAG_* bits set, a length of 0 and
+ * no text: the caller formats that mesh on the host (`nan`, `inf`, up to 39 integer digits). flags[b] == 0 otherwise.
+ * Two launches on `stream`, no allocation, no synchronisation: can be captured into a graph. Arguments (NULL, negative sizes, a
+ * stride or scratch below what the shape needs, alignment) are validated before any device work -> DAD3D_E_INVALID.
+ * dad3d_obj_format_scratch_bytes (demo_utils.py:130-144, host-only) returns 0 for a negative size.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_OBJ_MAX_LINE_BYTES 71 /* "v" + 3 x (" " "-" 12 digits "." 8 digits) + "\n" */
+#define DAD3D_OBJ_FLAG_NONFINITE 0x1
+#define DAD3D_OBJ_FLAG_LARGE 0x2
+DAD3D_EXPORT size_t dad3d_obj_format_scratch_bytes(int batch, int nver);
+DAD3D_EXPORT dad3d_status dad3d_obj_format_vertices(const float* vertices, int batch, int nver, uint8_t* text, size_t text_stride,
+                                       int64_t* lengths, int32_t* flags, void* scratch, size_t scratch_bytes, int device,
+                                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
