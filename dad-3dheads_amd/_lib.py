@@ -19,6 +19,7 @@ DTYPE_F32, DTYPE_U8 = 0, 1
 EVAL_SELF_EXCLUDE, EVAL_MAX_K, EVAL_MAX_HEAD, EVAL_MAX_ANCHORS = 0x1, 8, 4096, 8
 HEATMAP_RAW, HEATMAP_UINT8, HEATMAP_FLOAT = 0, 1, 2
 OBJ_MAX_LINE_BYTES, OBJ_FLAG_NONFINITE, OBJ_FLAG_LARGE = 71, 0x1, 0x2
+JSON_MAX_NUMBER_BYTES, JSON_MAX_LITERAL_BYTES, JSON_FLAG_NONFINITE = 23, 64, 0x1
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -129,6 +130,9 @@ SIGNATURES = {
     "dad3d_uvmap_bake": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dad3d_obj_format_scratch_bytes": (C.c_size_t, [_I, _I]),
     "dad3d_obj_format_vertices": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
+    "dad3d_json_format_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "dad3d_json_format_values": (_I, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
+    "dad3d_json_number_host": (_I, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "dad3d_sim3dr_get_tri_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_ver_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_normal": (None, [_P, _P, _P, _I, _I]),

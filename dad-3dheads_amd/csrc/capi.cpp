@@ -1273,6 +1273,48 @@ dad3d_status dad3d_obj_format_vertices(const float* vertices, int batch, int nve
     return launch_obj_format(a, static_cast<hipStream_t>(stream));
 }
 
+size_t dad3d_json_format_scratch_bytes(int batch, int n_slots) {
+    return batch < 1 || n_slots < 1 ? 0 : json_format_scratch_bytes(batch, n_slots);
+}
+
+dad3d_status dad3d_json_format_values(const float* values, int batch, int n_slots, const void* literals, const int32_t* literal_offsets,
+                                      uint8_t* text, size_t text_stride, int64_t* lengths, int32_t* flags, void* scratch,
+                                      size_t scratch_bytes, int device, void* stream) {
+    DAD3D_REQUIRE(batch > 0 && n_slots > 0, "dad3d_json_format_values: batch %d and n_slots %d must be positive", batch, n_slots);
+    DAD3D_REQUIRE(batch <= 65535 && n_slots <= 0x7fffffff / (DAD3D_JSON_MAX_LITERAL_BYTES + DAD3D_JSON_MAX_NUMBER_BYTES) - 1,
+                  "dad3d_json_format_values: batch %d / %d slots beyond the launch grid", batch, n_slots);
+    DAD3D_REQUIRE(values && literals && literal_offsets && text && lengths && flags && scratch, "dad3d_json_format_values: null argument");
+    DAD3D_REQUIRE(literal_offsets[0] == 0, "dad3d_json_format_values: literal_offsets must start at 0");
+    for (int i = 0; i <= n_slots; ++i) {
+        const long long len = (long long)literal_offsets[i + 1] - literal_offsets[i];
+        DAD3D_REQUIRE(len >= 0 && len <= DAD3D_JSON_MAX_LITERAL_BYTES, "dad3d_json_format_values: literal %d is %lld bytes long (0 .. %d allowed)", i,
+                      len, DAD3D_JSON_MAX_LITERAL_BYTES);
+    }
+    const size_t worst = (size_t)literal_offsets[n_slots + 1] + (size_t)n_slots * DAD3D_JSON_MAX_NUMBER_BYTES;
+    DAD3D_REQUIRE(text_stride >= worst, "dad3d_json_format_values: text_stride %zu is below the worst case of the template (%zu bytes)", text_stride,
+                  worst);
+    DAD3D_REQUIRE(text_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(text) & 15) == 0, "dad3d_json_format_values: text and text_stride must be 16-byte aligned");
+    DAD3D_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && (reinterpret_cast<uintptr_t>(lengths) & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(flags) & 3) == 0 && (reinterpret_cast<uintptr_t>(literals) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(values) & 3) == 0,
+                  "dad3d_json_format_values: values / literals / lengths / flags / scratch are misaligned");
+    DAD3D_REQUIRE(scratch_bytes >= json_format_scratch_bytes(batch, n_slots), "dad3d_json_format_values: %zu bytes of scratch, %zu needed", scratch_bytes,
+                  json_format_scratch_bytes(batch, n_slots));
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JsonFormatArgs a{values, literals, text, text_stride, lengths, flags, scratch, batch, n_slots};
+    return launch_json_format(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out, size_t out_stride, int32_t* lengths) {
+    if (n == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(values && out && lengths, "dad3d_json_number_host: null argument");
+    DAD3D_REQUIRE(out_stride >= DAD3D_JSON_MAX_NUMBER_BYTES, "dad3d_json_number_host: out_stride %zu is below the longest number (%d bytes)", out_stride,
+                  DAD3D_JSON_MAX_NUMBER_BYTES);
+    json_number_host(values, n, out, out_stride, lengths);
+    return DAD3D_OK;
+}
+
 dad3d_status dad3d_preprocess_images(const int64_t* descs, int batch, int out_size, const float* mean, const float* std,
                                      float* out, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && out_size > 0, "dad3d_preprocess_images: bad argument");

@@ -478,6 +478,24 @@ inline int obj_format_tiles(int nver) { return nver > 256 ? (nver + 255) / 256 :
 size_t obj_format_scratch_bytes(int batch, int nver);
 dad3d_status launch_obj_format(const ObjFormatArgs& a, hipStream_t s);
 
+// JSON text from a layout template (json_text.hip): per item, literal bytes in front of each of n_slots numbers and a suffix; the
+// numbers as json.dump prints a float32 widened to double (json_number.hpp)
+struct JsonFormatArgs {
+    const float* values;   // [B,n_slots]
+    const void* literals;  // the template image: int32 offsets [n_slots + 2], then the literal bytes they index
+    unsigned char* text;   // [B][text_stride], 16-byte aligned rows
+    size_t text_stride;    // >= literal bytes + n_slots * DAD3D_JSON_MAX_NUMBER_BYTES, a multiple of 16
+    int64_t* lengths;      // [B] bytes of item b's text; 0 for a flagged item
+    int32_t* flags;        // [B] DAD3D_JSON_FLAG_* bits: the item holds NaN / inf and has no text
+    void* scratch;         // json_format_scratch_bytes(B, n_slots): {length, flag bits} per tile of 256 slots
+    int batch, n_slots;
+};
+inline int json_format_tiles(int n_slots) { return (n_slots + 255) / 256; }
+size_t json_format_scratch_bytes(int batch, int n_slots);
+dad3d_status launch_json_format(const JsonFormatArgs& a, hipStream_t s);
+// host: text of values[i] at out + i * out_stride (DAD3D_JSON_MAX_NUMBER_BYTES at most), its length in lengths[i]; -1 for NaN / inf
+void json_number_host(const float* values, size_t n, unsigned char* out, size_t out_stride, int* lengths);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -13,6 +13,7 @@
 //                            (offset mod 16), and copies the image out in aligned 16-byte stores. Only the up to 15 bytes a
 //                            tile shares a 16-byte unit with its neighbour on either end leave as byte stores.
 #include "common.hpp"
+#include "text_tile.hpp"
 
 namespace dad3d {
 namespace {
@@ -93,22 +94,6 @@ __device__ inline int obj_put_number(unsigned char* s, int p, const ObjNumber& n
         f /= 10u;
     }
     return p + 9;
-}
-
-__device__ inline int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// sum over the 256 lanes of the workgroup; red: 4 ints of LDS, reusable after the call
-__device__ inline int block_sum(int v, int* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return v;
 }
 
 // bitwise OR over the workgroup (__syncthreads_or answers 0 / 1 per call: one call per flag bit)
@@ -210,16 +195,8 @@ __global__ __launch_bounds__(kObjTile) void obj_write_text_kernel(const float* _
     }
     __syncthreads();
 
-    unsigned char* out = text + (size_t)b * text_stride + (size_t)(before - lead);
-    const int end = lead + tile_len;
-    for (int c = tid; c * 16 < end; c += kObjTile) {
-        const int lo = c * 16, hi = lo + 16;
-        if (lo >= lead && hi <= end) {
-            reinterpret_cast<uint4*>(out)[c] = stage[c];
-        } else {  // a unit shared with the neighbouring tile: only this tile's bytes
-            for (int i = max(lo, lead); i < min(hi, end); ++i) out[i] = s[i];
-        }
-    }
+    // whole 16-byte units as one store each; a unit shared with the neighbouring tile: only this tile's bytes
+    copy_tile_out(stage, text + (size_t)b * text_stride + (size_t)(before - lead), lead, lead + tile_len);
 }
 
 }  // namespace

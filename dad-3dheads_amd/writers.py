@@ -4,8 +4,14 @@ whole batch of decoded meshes with the constant face block rendered once.
 
 The vertex block of a float32 CUDA batch is formatted on the GPU (`ObjFormatter`, csrc/obj_text.hip: the same bytes from 64-bit
 integer arithmetic); a mesh that holds a value outside the kernel's domain (NaN, inf, |x| >= 2^37) is flagged
-there and formatted by `_vertex_block` here. The JSON writers stay on the host (`json.dump` prints the shortest round-trip
-form of a double, another algorithm), as do the face block (a constant) and `MeshSaver.__call__` for one host mesh.
+there and formatted by `_vertex_block` here. The face block (a constant) and `MeshSaver.__call__` for one host mesh stay on the
+host.
+
+JSON of a float32 CUDA batch is formatted on the GPU too (`JsonFormatter`, csrc/json_text.hip): a `JsonTemplate`
+holds the literal bytes of one item's layout, the numbers between them are `float.__repr__` of the value widened to double --
+the shortest round-trip form `json.dump` prints -- from 128-bit integer products. `flame_params_json_batch` /
+`save_flame_params_batch` write the bytes of `JsonSaver` that way; an item that holds NaN or an infinity is flagged on the device
+and formatted here (`_json_item_host`). `JsonSaver`, `get_flame_params` and `flame_params_batch` are the host path, unchanged.
 """
 from __future__ import annotations
 
@@ -19,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .flame import FLAME_CONSTS, FlameParams
+from .flame import _SLICE_ORDER, FLAME_CONSTS, FlameParams
 
 
 def get_mesh(predictions: Dict[str, torch.Tensor], faces: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -75,21 +81,24 @@ class JsonSaver:
             json.dump(flame_params, out)
 
 
-class ObjText:
-    """What `ObjFormatter.format` returns: the vertex text of `batch` meshes in HBM. Mesh b's bytes are
-    `text[b, :lengths[b]]` (byte offset `b * stride` of the buffer); `flags[b] != 0` marks a mesh the kernel left to the host.
-    The buffers belong to the formatter: they hold this batch until its next `format`."""
+class _DeviceText:
+    """Text of `batch` items in a formatter's HBM buffer. Item b's bytes are `text[b, :lengths[b]]` (byte offset `b * stride` of
+    the buffer); `flags[b] != 0` marks an item the kernel left to the host (`_host_item`). The buffers belong to the formatter:
+    they hold this batch until its next `format`."""
 
-    def __init__(self, formatter: "ObjFormatter", vertices: torch.Tensor, batch: int):
-        self.formatter, self.vertices, self.batch = formatter, vertices, batch
+    def __init__(self, formatter: "_TextBuffers", batch: int):
+        self.formatter, self.batch = formatter, batch
         self.text, self.stride = formatter._text[:batch], formatter.stride
         self.lengths, self.flags = formatter._lengths[:batch], formatter._flags[:batch]
         self.offsets = [b * self.stride for b in range(batch)]
         self._copy: Optional[Tuple[np.ndarray, np.ndarray, int, torch.cuda.Event]] = None
 
+    def _host_item(self, b: int) -> bytes:
+        raise NotImplementedError
+
     def begin_host_copy(self) -> None:
         """Waits for the lengths and flags (one small copy), then enqueues the copy of the text that exists -- `batch` rows of the
-        longest mesh's length, not of the worst-case stride -- into the formatter's pinned buffer, without waiting for it."""
+        longest item's length, not of the worst-case stride -- into the formatter's pinned buffer, without waiting for it."""
         if self._copy is not None:
             return
         f, b = self.formatter, self.batch
@@ -107,8 +116,8 @@ class ObjText:
         self._copy = (lengths, flags, width, done)
 
     def to_host(self) -> List[Any]:
-        """The vertex block of every mesh as bytes on the host: a `memoryview` into the formatter's pinned buffer (valid until
-        its next `to_host`), or `bytes` from the host formatter for a flagged mesh."""
+        """The text of every item as bytes on the host: a `memoryview` into the formatter's pinned buffer (valid until its next
+        `to_host`), or `bytes` from the host formatter for a flagged item."""
         self.begin_host_copy()
         lengths, flags, width, done = self._copy
         done.synchronize()
@@ -116,13 +125,42 @@ class ObjText:
         out: List[Any] = []
         for b in range(self.batch):
             if flags[b]:
-                out.append(_vertex_block(self.vertices[b].detach().cpu().numpy()).encode("ascii"))
+                out.append(self._host_item(b))
             else:
                 out.append(host[b * width : b * width + int(lengths[b])])
         return out
 
 
-class ObjFormatter:
+class _TextBuffers:
+    """The buffers of a device text formatter: `capacity` rows of `stride` bytes of text, lengths and flags, the kernels' scratch
+    and the pinned host side of the copy."""
+
+    def _reserve_buffers(self, batch: int, scratch_bytes: int) -> None:
+        dev = self.torch_device
+        self.capacity = batch
+        self._text = torch.empty((batch, max(self.stride, 16)), dtype=torch.uint8, device=dev)
+        self._meta = torch.zeros(12 * batch, dtype=torch.uint8, device=dev)  # lengths int64 [batch] | flags int32 [batch]
+        self._lengths, self._flags = self._meta[: 8 * batch].view(torch.int64), self._meta[8 * batch :].view(torch.int32)
+        self._scratch_bytes = int(scratch_bytes)
+        self._scratch = torch.empty(max(self._scratch_bytes, 8), dtype=torch.uint8, device=dev)
+        self._meta_host = torch.empty(12 * batch, dtype=torch.uint8).pin_memory()
+        self._host = torch.empty(batch * max(self.stride, 16), dtype=torch.uint8).pin_memory()
+
+
+class ObjText(_DeviceText):
+    """What `ObjFormatter.format` returns: the vertex text of `batch` meshes in HBM. Mesh b's bytes are
+    `text[b, :lengths[b]]` (byte offset `b * stride` of the buffer); `flags[b] != 0` marks a mesh the kernel left to the host.
+    The buffers belong to the formatter: they hold this batch until its next `format`."""
+
+    def __init__(self, formatter: "ObjFormatter", vertices: torch.Tensor, batch: int):
+        super().__init__(formatter, batch)
+        self.vertices = vertices
+
+    def _host_item(self, b: int) -> bytes:
+        return _vertex_block(self.vertices[b].detach().cpu().numpy()).encode("ascii")
+
+
+class ObjFormatter(_TextBuffers):
     """The `v %.8f %.8f %.8f` lines of a batch of meshes, formatted on the GPU (`dad3d_obj_format_vertices`).
 
     `reserve(batch)` allocates the device text buffer (`batch` rows of the worst case, 71 bytes per line), lengths, flags,
@@ -144,15 +182,7 @@ class ObjFormatter:
         batch = max(int(batch), 1)
         if batch <= self.capacity:
             return
-        dev = self.torch_device
-        self.capacity = batch
-        self._text = torch.empty((batch, max(self.stride, 16)), dtype=torch.uint8, device=dev)
-        self._meta = torch.zeros(12 * batch, dtype=torch.uint8, device=dev)  # lengths int64 [batch] | flags int32 [batch]
-        self._lengths, self._flags = self._meta[: 8 * batch].view(torch.int64), self._meta[8 * batch :].view(torch.int32)
-        self._scratch_bytes = int(self._lib.dad3d_obj_format_scratch_bytes(batch, self.n_verts))
-        self._scratch = torch.empty(max(self._scratch_bytes, 8), dtype=torch.uint8, device=dev)
-        self._meta_host = torch.empty(12 * batch, dtype=torch.uint8).pin_memory()
-        self._host = torch.empty(batch * max(self.stride, 16), dtype=torch.uint8).pin_memory()
+        self._reserve_buffers(batch, self._lib.dad3d_obj_format_scratch_bytes(batch, self.n_verts))
 
     def format(self, vertices: torch.Tensor) -> ObjText:
         if (not isinstance(vertices, torch.Tensor) or vertices.device != self.torch_device or vertices.dtype != torch.float32
@@ -258,6 +288,226 @@ def save_obj_from_params(head_mesh, params: torch.Tensor, paths: Sequence[str], 
         pending = launch(i + 1) if i + 1 < len(starts) else None
         _write_obj_files(blocks, face_text, paths[starts[i] : starts[i] + batch_size])
     torch.cuda.current_stream(dev).wait_stream(side)
+
+
+_SLOT = object()  # a number's place in the token stream of a template
+
+
+def _structure_tokens(spec: Any) -> Iterable[Any]:
+    if isinstance(spec, dict):
+        yield "{"
+        for i, (key, value) in enumerate(spec.items()):
+            yield (", " if i else "") + json.dumps(str(key)) + ": "
+            yield from _structure_tokens(value)
+        yield "}"
+    elif isinstance(spec, list):
+        yield "["
+        for i, value in enumerate(spec):
+            if i:
+                yield ", "
+            yield from _structure_tokens(value)
+        yield "]"
+    elif isinstance(spec, tuple):  # a shape: () is one bare number
+        if not spec:
+            yield _SLOT
+            return
+        yield "["
+        for i in range(int(spec[0])):
+            if i:
+                yield ", "
+            yield from _structure_tokens(tuple(spec[1:]))
+        yield "]"
+    elif isinstance(spec, (int, np.integer)) and not isinstance(spec, bool) and spec >= 0:
+        yield from _structure_tokens((int(spec),))  # a flat list of that many numbers
+    else:
+        raise ValueError(f"JsonTemplate: a leaf is a slot count or a shape (tuple), got {spec!r}")
+
+
+class JsonTemplate:
+    """The layout of one JSON item around its `n_slots` numbers: `literals[i]` is the text in front of number i, `literals[n_slots]`
+    the suffix that closes the item. No literal may be longer than `_lib.JSON_MAX_LITERAL_BYTES` (ValueError)."""
+
+    def __init__(self, literals: Sequence[bytes]):
+        self.literals = [bytes(x) for x in literals]
+        if not self.literals:
+            raise ValueError("JsonTemplate: needs at least the suffix")
+        self.n_slots = len(self.literals) - 1
+        for i, lit in enumerate(self.literals):
+            if len(lit) > _lib.JSON_MAX_LITERAL_BYTES:
+                raise ValueError(f"JsonTemplate: literal {i} ({lit[:24]!r}...) is {len(lit)} bytes long, the formatter takes "
+                                 f"{_lib.JSON_MAX_LITERAL_BYTES}")
+        self.offsets = np.zeros(self.n_slots + 2, dtype=np.int32)
+        np.cumsum([len(x) for x in self.literals], out=self.offsets[1:])
+        self.literal_bytes = b"".join(self.literals)
+        self.worst_case = len(self.literal_bytes) + self.n_slots * _lib.JSON_MAX_NUMBER_BYTES
+        self.stride = max((self.worst_case + 15) // 16 * 16, 16)
+
+    @classmethod
+    def from_structure(cls, spec: Any) -> "JsonTemplate":
+        """`spec`: nested dicts and lists as `json.dumps` renders them (separators `", "` and `": "`, keys through
+        `json.dumps(str(k))`), with leaves that say where the numbers go: an int n is a flat list of n numbers (0: `[]`), a tuple
+        is the shape of nested lists of numbers (`(68, 2)`: 68 pairs; `()`: one bare number)."""
+        literals, cur = [], []
+        for token in _structure_tokens(spec):
+            if token is _SLOT:
+                literals.append("".join(cur).encode("ascii"))
+                cur = []
+            else:
+                cur.append(token)
+        literals.append("".join(cur).encode("ascii"))
+        return cls(literals)
+
+    def render(self, numbers: Sequence[Any]) -> bytes:
+        """The item with `numbers[i]` (bytes or str) in slot i."""
+        assert len(numbers) == self.n_slots
+        parts: List[bytes] = []
+        for lit, num in zip(self.literals, numbers):
+            parts.append(lit)
+            parts.append(num if isinstance(num, bytes) else str(num).encode("ascii"))
+        parts.append(self.literals[-1])
+        return b"".join(parts)
+
+    def device_image(self, device: torch.device) -> torch.Tensor:
+        """What `dad3d_json_format_values` reads on the device: the int32 offsets, then the literal bytes."""
+        image = np.frombuffer(self.offsets.tobytes() + self.literal_bytes, dtype=np.uint8).copy()
+        return torch.from_numpy(image).to(device)
+
+
+def _json_item_host(template: JsonTemplate, row: Any) -> bytes:
+    """One item on the host, the numbers as `json.dumps` prints a float: `float.__repr__`, `NaN`, `Infinity`, `-Infinity`."""
+    values = (row.detach().cpu() if isinstance(row, torch.Tensor) else torch.as_tensor(np.asarray(row))).to(torch.float64).reshape(-1)
+    return template.render([json.dumps(v) for v in values.tolist()])
+
+
+class JsonText(_DeviceText):
+    """What `JsonFormatter.format` returns: the JSON text of `batch` items in HBM, the contract of `ObjText`. A flagged item
+    (NaN, an infinity, or a flag the caller ORed in) is formatted on the host: by `host_item(b)` when the caller gave one, else
+    from the float32 values by `_json_item_host`."""
+
+    def __init__(self, formatter: "JsonFormatter", values: torch.Tensor, batch: int, host_item=None):
+        super().__init__(formatter, batch)
+        self.values, self.host_item = values, host_item
+
+    def _host_item(self, b: int) -> bytes:
+        if self.host_item is not None:
+            return self.host_item(b)
+        return _json_item_host(self.formatter.template, self.values[b])
+
+
+class JsonFormatter(_TextBuffers):
+    """The JSON text of a batch of items of one layout, formatted on the GPU (`dad3d_json_format_values`).
+
+    `reserve(batch)` allocates the device text buffer (`batch` rows of the template's worst case: its literal bytes + 23 per
+    number), lengths, flags, scratch, a float32 staging buffer `[batch, n_slots]` (`staging(batch)`: for callers that gather
+    their fields on the device) and one pinned host buffer; `format(values)` launches on the current stream with no allocation
+    and no sync once the batch fits (capturable in a graph); `JsonText.to_host()` brings the bytes over."""
+
+    def __init__(self, template: JsonTemplate, device: Optional[int] = None):
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        if template.n_slots < 1:
+            raise ValueError("JsonFormatter: a template without numbers is a constant: template.render([])")
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.torch_device = torch.device("cuda", self.device)
+        self.template, self.n_slots, self.stride = template, template.n_slots, template.stride
+        self._image = template.device_image(self.torch_device)
+        self._offsets = np.ascontiguousarray(template.offsets)
+        self.capacity = 0
+
+    def reserve(self, batch: int) -> None:
+        batch = max(int(batch), 1)
+        if batch <= self.capacity:
+            return
+        self._reserve_buffers(batch, self._lib.dad3d_json_format_scratch_bytes(batch, self.n_slots))
+        self._staging = torch.zeros((batch, self.n_slots), dtype=torch.float32, device=self.torch_device)
+
+    def staging(self, batch: int) -> torch.Tensor:
+        self.reserve(batch)
+        return self._staging[:batch]
+
+    def format(self, values: torch.Tensor, host_item=None, extra_flags: Optional[torch.Tensor] = None) -> JsonText:
+        """`values [B,n_slots]` -> `JsonText`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
+        kernels: a non-zero entry sends that item to `host_item(b)`."""
+        if (not isinstance(values, torch.Tensor) or values.device != self.torch_device or values.dtype != torch.float32
+                or not values.is_contiguous() or values.ndim != 2 or values.shape[1] != self.n_slots):
+            raise ValueError(f"values: expected a contiguous float32 tensor [B,{self.n_slots}] on {self.torch_device}, got "
+                             f"{getattr(values, 'dtype', type(values))} {tuple(getattr(values, 'shape', ()))} on "
+                             f"{getattr(values, 'device', 'the host')}"
+                             + ("" if not isinstance(values, torch.Tensor) or values.is_contiguous() else " (not contiguous)"))
+        b = values.shape[0]
+        if b == 0:
+            self.reserve(1)
+            return JsonText(self, values, 0, host_item)
+        self.reserve(b)
+        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
+        _lib.check(self._lib.dad3d_json_format_values(values.data_ptr(), b, self.n_slots, self._image.data_ptr(), self._offsets.ctypes.data,
+                                                      self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
+                                                      self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(),
+                                                      self.device, stream))
+        if extra_flags is not None:
+            self._flags[:b].bitwise_or_(extra_flags)
+        return JsonText(self, values, b, host_item)
+
+
+def _flame_params_layout(constants: Dict[str, int]) -> Tuple[Dict[str, int], List[int]]:
+    """({key: count} in the key order of `get_flame_params`, the params column of every number in that order)."""
+    first, cur = {}, 0
+    for key in _SLICE_ORDER:
+        first[key] = cur
+        cur += int(constants[key])
+    keys = list(vars(FlameParams.from_3dmm(torch.zeros((1, cur)), constants)))
+    return {k: int(constants[k]) for k in keys}, [first[k] + i for k in keys for i in range(int(constants[k]))]
+
+
+_json_formatters: Dict[Tuple[int, Tuple[Tuple[str, int], ...]], Tuple[JsonFormatter, torch.Tensor]] = {}
+
+
+def _params_formatter_for(params: torch.Tensor, constants: Dict[str, int]) -> Tuple[JsonFormatter, torch.Tensor]:
+    key = (params.device.index, tuple((k, int(v)) for k, v in constants.items()))
+    hit = _json_formatters.get(key)
+    if hit is None:
+        spec, columns = _flame_params_layout(constants)
+        fmt = JsonFormatter(JsonTemplate.from_structure(spec), device=key[0])
+        hit = _json_formatters[key] = (fmt, torch.tensor(columns, dtype=torch.int64, device=params.device))
+    return hit
+
+
+def _params_on_device_path(params: Any, constants: Dict[str, int]) -> bool:
+    return (isinstance(params, torch.Tensor) and params.is_cuda and params.dtype == torch.float32 and params.ndim == 2
+            and params.is_contiguous() and params.shape[1] == sum(int(constants[k]) for k in _SLICE_ORDER) and params.shape[1] > 0)
+
+
+def _format_flame_params(params: torch.Tensor, constants: Dict[str, int]) -> JsonText:
+    fmt, columns = _params_formatter_for(params, constants)
+    staged = fmt.staging(params.shape[0])
+    torch.index_select(params.detach(), 1, columns, out=staged)  # the key order of the file is not the column order
+    return fmt.format(staged)
+
+
+def flame_params_json_batch(params: torch.Tensor, constants: Dict[str, int] = FLAME_CONSTS) -> List[bytes]:
+    """`params [B,413]` -> the bytes `JsonSaver` writes for every row: row i is
+    `json.dumps(get_flame_params({"3dmm_params": params[i:i+1]}, constants)).encode()`. A contiguous float32 CUDA tensor is
+    formatted on the GPU; anything else by `json.dumps`."""
+    if _params_on_device_path(params, constants):
+        return [bytes(x) for x in _format_flame_params(params, constants).to_host()]
+    return [json.dumps(d).encode("ascii") for d in flame_params_batch(params, constants)]
+
+
+def save_flame_params_batch(params: torch.Tensor, paths: Sequence[str], formatter: str = "auto") -> None:
+    """`params [B,413]` -> one flame_params `.json` per row, the files `JsonSaver()(get_flame_params(...), path)` writes. A
+    contiguous float32 CUDA tensor is formatted on the GPU and only text crosses to the host; a CPU tensor, another dtype, a
+    non-contiguous tensor or `formatter="host"` goes through `JsonSaver`. Same bytes either way."""
+    if formatter not in ("auto", "host"):
+        raise ValueError(f"formatter: expected 'auto' or 'host', got {formatter!r}")
+    assert params.ndim == 2 and params.shape[0] == len(paths)
+    if formatter == "auto" and _params_on_device_path(params, FLAME_CONSTS):
+        for block, path in zip(_format_flame_params(params, FLAME_CONSTS).to_host(), paths):
+            with open(path, "wb") as f:
+                f.write(block)
+        return
+    saver = JsonSaver()
+    for row, path in zip(flame_params_batch(params), paths):
+        saver(row, path)
 
 
 def flame_params_batch(params: torch.Tensor, constants: Dict[str, int] = FLAME_CONSTS) -> List[Dict[str, List[float]]]:

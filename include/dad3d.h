@@ -544,6 +544,41 @@ DAD3D_EXPORT dad3d_status dad3d_obj_format_vertices(const float* vertices, int b
                                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * JSON text as `json.dump` writes it, made on the device from a layout template: the value of one image in a benchmark submission
+ * (`{"68_landmarks_2d": [[x, y], ...], "N_landmarks_3d": [...], "7_landmarks_3d": [...], "rotation_matrix": [...]}`, the submission
+ * format of dad_3dheads_benchmark/README.md:78-95) and the demo's flame_params file (demo_utils.py:114-118,147-153: `get_flame_params`
+ * through `JsonSaver`). An item is n_slots numbers; the template holds the literal bytes in front of each number and a suffix that
+ * closes the item. A number is float.__repr__ of the float32 widened to double: the shortest decimal string that reads back to that
+ * double, positional while -4 < decimal point position <= 16, else d[.ddd]e+-XX, at most DAD3D_JSON_MAX_NUMBER_BYTES bytes; made from
+ * 64 x 64 -> 128-bit integer products against a table of powers of ten, no floating point.
+ *   values          DEVICE [batch,n_slots] float32, contiguous
+ *   literals        DEVICE the template image, 4-byte aligned: int32 offsets [n_slots + 2], then the literal bytes. Literal i, in front
+ *                   of slot i, is bytes [offsets[i], offsets[i + 1]); the suffix is literal n_slots
+ *   literal_offsets HOST   the same n_slots + 2 offsets: ascending from 0, no literal longer than DAD3D_JSON_MAX_LITERAL_BYTES. They
+ *                   are what the arguments are validated against without touching the device
+ *   text            DEVICE [batch][text_stride] bytes, 16-byte aligned; text_stride a multiple of 16, at least the template's worst
+ *                   case offsets[n_slots + 1] + n_slots * DAD3D_JSON_MAX_NUMBER_BYTES. Item b's text is text[b * text_stride ..
+ *                   + lengths[b]); bytes behind it are left as they were
+ *   lengths         DEVICE [batch] int64   flags DEVICE [batch] int32
+ *   scratch         DEVICE dad3d_json_format_scratch_bytes(batch, n_slots) bytes, 8-byte aligned
+ * An item that holds NaN or +-inf gets DAD3D_JSON_FLAG_NONFINITE, a length of 0 and no text: the caller formats it on the host
+ * (`NaN`, `Infinity`, `-Infinity`). flags[b] == 0 otherwise. Two launches on `stream`, no allocation, no synchronisation: can be
+ * captured into a graph. Arguments (NULL, batch <= 0, n_slots <= 0, a literal over the cap, a stride or scratch below what the
+ * template needs, alignment) are validated before any device work -> DAD3D_E_INVALID. dad3d_json_format_scratch_bytes (host-only)
+ * returns 0 for a size below 1.
+ * dad3d_json_number_host runs the same number routine on the CPU, HOST pointers: the text of values[i] goes to
+ * out[i * out_stride ..) (out_stride >= DAD3D_JSON_MAX_NUMBER_BYTES), its length to lengths[i]; -1 and no text for NaN / +-inf.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_JSON_MAX_NUMBER_BYTES 23 /* "-1.1754942106924411e-38", "-0.00010000000474974513" */
+#define DAD3D_JSON_MAX_LITERAL_BYTES 64
+#define DAD3D_JSON_FLAG_NONFINITE 0x1
+DAD3D_EXPORT size_t dad3d_json_format_scratch_bytes(int batch, int n_slots);
+DAD3D_EXPORT dad3d_status dad3d_json_format_values(const float* values, int batch, int n_slots, const void* literals,
+                                      const int32_t* literal_offsets, uint8_t* text, size_t text_stride, int64_t* lengths,
+                                      int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out, size_t out_stride, int32_t* lengths);
+
+/* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
  * in one launch: LongestMaxSize (cv2.resize INTER_LINEAR, 8-bit fixed-point path) -> PadIfNeeded (centred, 0) -> Normalize
  * ((x - 255 mean) * (1 / (255 std)), float32) -> CHW. All DEVICE pointers:
