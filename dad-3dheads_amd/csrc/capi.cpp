@@ -1315,6 +1315,91 @@ dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out,
     return DAD3D_OK;
 }
 
+size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes) {
+    return n_bytes < 1 || n_bytes > 0x7fffffffLL ? 0 : json_parse_scratch_bytes(n_bytes);
+}
+
+namespace {
+inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+}  // namespace
+
+dad3d_status dad3d_json_parse_index(const uint8_t* text, int64_t n_bytes, void* scratch, size_t scratch_bytes, int32_t* counts, int device,
+                                    void* stream) {
+    DAD3D_REQUIRE(n_bytes > 0 && n_bytes <= 0x7fffffffLL, "dad3d_json_parse_index: n_bytes %lld must be in 1 .. 2^31 - 1", (long long)n_bytes);
+    DAD3D_REQUIRE(text && scratch && counts, "dad3d_json_parse_index: null argument");
+    DAD3D_REQUIRE(aligned_to(text, 16) && aligned_to(scratch, 16) && aligned_to(counts, 4), "dad3d_json_parse_index: text / scratch / counts are misaligned");
+    DAD3D_REQUIRE(scratch_bytes >= json_parse_scratch_bytes(n_bytes), "dad3d_json_parse_index: %zu bytes of scratch, %zu needed", scratch_bytes,
+                  json_parse_scratch_bytes(n_bytes));
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    return launch_json_parse_index(text, n_bytes, scratch, counts, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_json_parse_lists(const uint8_t* text, int64_t n_bytes, const void* scratch, size_t scratch_bytes, int32_t* tok_pos,
+                                    int32_t* tok_brk, int64_t tok_cap, int32_t* brk_pos, int32_t* brk_key, int32_t* brk_nonnum, int32_t* brk_tok,
+                                    int64_t brk_cap, int device, void* stream) {
+    DAD3D_REQUIRE(n_bytes > 0 && n_bytes <= 0x7fffffffLL, "dad3d_json_parse_lists: n_bytes %lld must be in 1 .. 2^31 - 1", (long long)n_bytes);
+    DAD3D_REQUIRE(tok_cap >= 0 && brk_cap >= 0, "dad3d_json_parse_lists: negative capacity");
+    DAD3D_REQUIRE(text && scratch && (tok_cap == 0 || (tok_pos && tok_brk)) && (brk_cap == 0 || (brk_pos && brk_key && brk_nonnum && brk_tok)),
+                  "dad3d_json_parse_lists: null argument");
+    DAD3D_REQUIRE(aligned_to(scratch, 16) && aligned_to(tok_pos, 4) && aligned_to(tok_brk, 4) && aligned_to(brk_pos, 4) && aligned_to(brk_key, 4) &&
+                      aligned_to(brk_nonnum, 4) && aligned_to(brk_tok, 4),
+                  "dad3d_json_parse_lists: scratch / lists are misaligned");
+    DAD3D_REQUIRE(scratch_bytes >= json_parse_scratch_bytes(n_bytes), "dad3d_json_parse_lists: %zu bytes of scratch, %zu needed", scratch_bytes,
+                  json_parse_scratch_bytes(n_bytes));
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JsonParseListsArgs a{scratch, tok_pos, tok_brk, brk_pos, brk_key, brk_nonnum, brk_tok, n_bytes, tok_cap, brk_cap};
+    return launch_json_parse_lists(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_json_parse_check_arrays(const uint8_t* text, int64_t n_bytes, const int32_t* tok_pos, const int32_t* tok_brk, int64_t n_tokens,
+                                           const int32_t* brk_pos, const int32_t* brk_key, const int32_t* brk_tok, int64_t n_brackets,
+                                           const int32_t* arr_open, const int32_t* arr_close, int32_t* arr_rows, int64_t n_arrays, int device,
+                                           void* stream) {
+    DAD3D_REQUIRE(n_bytes > 0 && n_bytes <= 0x7fffffffLL, "dad3d_json_parse_check_arrays: n_bytes %lld must be in 1 .. 2^31 - 1", (long long)n_bytes);
+    DAD3D_REQUIRE(n_tokens >= 0 && n_brackets >= 0 && n_arrays >= 0 && n_tokens <= n_bytes && n_brackets <= n_bytes && n_arrays <= n_brackets,
+                  "dad3d_json_parse_check_arrays: %lld tokens / %lld brackets / %lld arrays do not fit a document of %lld bytes", (long long)n_tokens,
+                  (long long)n_brackets, (long long)n_arrays, (long long)n_bytes);
+    if (n_arrays == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(text && (n_tokens == 0 || (tok_pos && tok_brk)) && brk_pos && brk_key && brk_tok && arr_open && arr_close && arr_rows,
+                  "dad3d_json_parse_check_arrays: null argument");
+    DAD3D_REQUIRE(aligned_to(tok_pos, 4) && aligned_to(tok_brk, 4) && aligned_to(brk_pos, 4) && aligned_to(brk_key, 4) && aligned_to(brk_tok, 4) &&
+                      aligned_to(arr_open, 4) && aligned_to(arr_close, 4) && aligned_to(arr_rows, 4),
+                  "dad3d_json_parse_check_arrays: lists are misaligned");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JsonParseCheckArgs a{text, tok_pos, tok_brk, brk_pos, brk_key, brk_tok, arr_open, arr_close, arr_rows, n_bytes, n_tokens, n_brackets, n_arrays};
+    return launch_json_parse_check_arrays(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_json_parse_extract(const uint8_t* text, int64_t n_bytes, const int32_t* tok_pos, int64_t n_tokens, const int32_t* records,
+                                      int64_t n_records, int64_t n_values, double* values, uint8_t* is_int, int64_t values_cap, int device,
+                                      void* stream) {
+    DAD3D_REQUIRE(n_bytes > 0 && n_bytes <= 0x7fffffffLL, "dad3d_json_parse_extract: n_bytes %lld must be in 1 .. 2^31 - 1", (long long)n_bytes);
+    DAD3D_REQUIRE(n_tokens >= 0 && n_records >= 0 && n_values >= 0 && n_tokens <= n_bytes && n_values <= n_tokens && n_records <= n_values,
+                  "dad3d_json_parse_extract: %lld records / %lld values do not fit %lld tokens", (long long)n_records, (long long)n_values,
+                  (long long)n_tokens);
+    DAD3D_REQUIRE(values_cap >= n_values, "dad3d_json_parse_extract: room for %lld values, %lld needed", (long long)values_cap, (long long)n_values);
+    if (n_values == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(n_records > 0, "dad3d_json_parse_extract: %lld values but no record", (long long)n_values);
+    DAD3D_REQUIRE(text && tok_pos && records && values && is_int, "dad3d_json_parse_extract: null argument");
+    DAD3D_REQUIRE(aligned_to(tok_pos, 4) && aligned_to(records, 4) && aligned_to(values, 8), "dad3d_json_parse_extract: lists / values are misaligned");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JsonParseExtractArgs a{text, tok_pos, records, values, is_int, n_bytes, n_tokens, n_records, n_values};
+    return launch_json_parse_extract(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_json_parse_number_host(const uint8_t* text, const int64_t* starts, const int64_t* ends, size_t n, uint64_t* bits_out,
+                                          uint8_t* is_int_out, uint32_t* flags_out) {
+    if (n == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(text && starts && ends && bits_out && is_int_out && flags_out, "dad3d_json_parse_number_host: null argument");
+    json_parse_number_host(text, reinterpret_cast<const long long*>(starts), reinterpret_cast<const long long*>(ends), n,
+                           reinterpret_cast<unsigned long long*>(bits_out), is_int_out, flags_out);
+    return DAD3D_OK;
+}
+
 dad3d_status dad3d_preprocess_images(const int64_t* descs, int batch, int out_size, const float* mean, const float* std,
                                      float* out, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && out_size > 0, "dad3d_preprocess_images: bad argument");

@@ -496,6 +496,36 @@ dad3d_status launch_json_format(const JsonFormatArgs& a, hipStream_t s);
 // host: text of values[i] at out + i * out_stride (DAD3D_JSON_MAX_NUMBER_BYTES at most), its length in lengths[i]; -1 for NaN / inf
 void json_number_host(const float* values, size_t n, unsigned char* out, size_t out_stride, int* lengths);
 
+// JSON read back on the device (json_parse.hip): index the document, compact its token and bracket lists, check candidate arrays, extract
+// the values of the lifted ones; the entries of include/dad3d.h one to one
+struct JsonParseListsArgs {
+    const void* scratch;
+    int32_t *tok_pos, *tok_brk, *brk_pos, *brk_key, *brk_nonnum, *brk_tok;
+    long long n_bytes, tok_cap, brk_cap;
+};
+struct JsonParseCheckArgs {
+    const unsigned char* text;
+    const int32_t *tok_pos, *tok_brk, *brk_pos, *brk_key, *brk_tok, *arr_open, *arr_close;
+    int32_t* arr_rows;
+    long long n_bytes, n_tokens, n_brackets, n_arrays;
+};
+struct JsonParseExtractArgs {
+    const unsigned char* text;
+    const int32_t *tok_pos, *records;
+    double* values;
+    unsigned char* is_int;
+    long long n_bytes, n_tokens, n_records, n_values;
+};
+int json_parse_tiles(long long n_bytes);
+size_t json_parse_scratch_bytes(long long n_bytes);
+dad3d_status launch_json_parse_index(const unsigned char* text, long long n_bytes, void* scratch, int* counts, hipStream_t s);
+dad3d_status launch_json_parse_lists(const JsonParseListsArgs& a, hipStream_t s);
+dad3d_status launch_json_parse_check_arrays(const JsonParseCheckArgs& a, hipStream_t s);
+dad3d_status launch_json_parse_extract(const JsonParseExtractArgs& a, hipStream_t s);
+// host: the number routine on token i = text[starts[i], ends[i])
+void json_parse_number_host(const unsigned char* text, const long long* starts, const long long* ends, size_t n, unsigned long long* bits,
+                            unsigned char* is_int, unsigned* flags);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

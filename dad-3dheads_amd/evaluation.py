@@ -46,7 +46,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, json_reader
 from .benchmark_export import SEVEN_OF_68, Landmarks68
 from .projection import project_batch
 from .synthetic import load_static
@@ -202,10 +202,12 @@ def metrics_reached(prediction: Optional[Mapping[str, Any]], n_head_min: int) ->
     for i, (key, shape) in enumerate(checks):
         if key not in prediction:
             return i, f"missing {key!r}"
-        try:
-            arr = np.asarray(prediction[key], dtype=np.float32)
-        except (TypeError, ValueError):
-            return i, f"malformed {key!r}"
+        arr = prediction[key]
+        if not isinstance(arr, json_reader.DeviceArray):  # a handle is a regular array of numbers: its .shape and .size, no copy
+            try:
+                arr = np.asarray(arr, dtype=np.float32)
+            except (TypeError, ValueError):
+                return i, f"malformed {key!r}"
         if shape is None:  # `torch.Tensor(...).view(-1, 3)[head_indices]` (benchmark.py:152-154)
             if arr.size % 3 or arr.size // 3 < n_head_min:
                 return i, f"{key!r} holds {arr.size / 3:g} points; head_indices needs {n_head_min}"
@@ -226,12 +228,16 @@ class DADEvaluator:
 
     face_indices: the reference's `model_training/model/static/flame_indices/face.npy` (array or path; reference data, not
     shipped with this package). `z5="knn"` selects the README's nearest-neighbour Z5 (different numbers, module docstring).
-    Skipped items are logged and listed in `self.warnings` as (id, reason)."""
+    Skipped items are logged and listed in `self.warnings` as (id, reason). `reader="device"` reads both documents through
+    `json_reader.load`: the same trees, the arrays of numbers parsed on the GPU and gathered into the batch tensors there."""
 
     def __init__(self, ground_truth_path: str, submission_path: str, face_indices, z5: str = "reference", batch_size: int = 64,
-                 device: Optional[Union[int, torch.device]] = None, static: Optional[dict] = None):
+                 device: Optional[Union[int, torch.device]] = None, static: Optional[dict] = None, reader: str = "host"):
         if z5 not in ("reference", "knn"):
             raise ValueError(f"z5 must be 'reference' or 'knn', not {z5!r}")
+        if reader not in ("host", "device"):
+            raise ValueError(f"reader must be 'host' or 'device', not {reader!r}")
+        self.reader = reader
         _lib.require_gpu()
         st = static if static is not None else load_static()
         self.target_file_path = ground_truth_path
@@ -253,34 +259,65 @@ class DADEvaluator:
         the fields of the metrics an item does not reach."""
         dev, bsz = self.device, len(items)
         n_min = int(self.head_indices.max()) + 1
-        verts = [np.asarray(p["N_landmarks_3d"], dtype=np.float32).reshape(-1, 3) if reach > 2 else np.zeros((0, 3), np.float32)
-                 for _, p, reach in items]
-        n_max = max(1, n_min, max(len(v) for v in verts))
-        pv = np.zeros((bsz, n_max, 3), np.float32)
-        for i, v in enumerate(verts):
-            pv[i, :len(v)] = v
-        # placeholders for the fields of metrics an item does not reach; non-degenerate, so Procrustes' SVD stays finite
-        field = lambda p, key, shape: (np.asarray(p[key], dtype=np.float32) if key in p and np.shape(p[key]) == shape  # noqa: E731
-                                       else np.eye(*shape, dtype=np.float32))
         t = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)  # noqa: E731
+        handle = json_reader.DeviceArray
+        shape_of = lambda x: x.shape if isinstance(x, handle) else np.shape(x)  # noqa: E731
+
+        def stack(xs):
+            """float32 [B, ...] of one field: handles of one document and one shape are gathered from its values and cast on the
+            device (round to nearest even, as np.asarray(list, dtype=np.float32) rounds); lists take the host conversion."""
+            first = xs[0]
+            if not any(isinstance(x, handle) for x in xs):
+                return t(np.stack([np.asarray(x, dtype=np.float32) for x in xs]))
+            if all(isinstance(x, handle) and x.document is first.document and x.shape == first.shape for x in xs):
+                offsets = torch.tensor([x.offset for x in xs], dtype=torch.int64).to(first.document.values.device)
+                index = offsets[:, None] + torch.arange(first.count, device=offsets.device)
+                return first.document.values[index].to(torch.float32).view(len(xs), *first.shape).to(dev)
+            return torch.stack([x.float32().to(dev) if isinstance(x, handle) else t(np.asarray(x, dtype=np.float32)) for x in xs])
+
+        # predicted vertices, padded to the longest: a handle stays on the device, a list is converted once on the host
+        points = [None if reach <= 2 else p["N_landmarks_3d"] if isinstance(p["N_landmarks_3d"], handle)
+                  else np.asarray(p["N_landmarks_3d"], dtype=np.float32).reshape(-1, 3) for _, p, reach in items]
+        n_pts = [0 if v is None else v.count // 3 if isinstance(v, handle) else len(v) for v in points]
+        n_max = max(1, n_min, max(n_pts))
+        if not any(isinstance(v, handle) for v in points):
+            host = np.zeros((bsz, n_max, 3), np.float32)
+            for i, v in enumerate(points):
+                if v is not None:
+                    host[i, :len(v)] = v
+            pv = t(host)
+        else:
+            pv = torch.zeros((bsz, n_max, 3), dtype=torch.float32, device=dev)
+            if all(isinstance(v, handle) for v in points) and len(set(n_pts)) == 1:
+                pv[:, :n_pts[0]] = stack(points).view(bsz, -1, 3)
+            else:
+                for i, v in enumerate(points):
+                    if v is not None:
+                        pv[i, :n_pts[i]] = v.float32().to(dev).view(-1, 3) if isinstance(v, handle) else t(v)
+        # placeholders for the fields of metrics an item does not reach; non-degenerate, so Procrustes' SVD stays finite
+        field = lambda p, key, shape: (p[key] if key in p and shape_of(p[key]) == shape else np.eye(*shape, dtype=np.float32))  # noqa: E731
         out = evaluate_batch(
-            t(np.stack([np.asarray(a["vertices"], dtype=np.float32) for a, _, _ in items])),
-            t(np.stack([np.asarray(a["model_view_matrix"], dtype=np.float32) for a, _, _ in items])),
-            t(np.stack([np.asarray(a["projection_matrix"], dtype=np.float32) for a, _, _ in items])),
+            stack([a["vertices"] for a, _, _ in items]),
+            stack([a["model_view_matrix"] for a, _, _ in items]),
+            stack([a["projection_matrix"] for a, _, _ in items]),
             t(np.asarray([a["bbox"] for a, _, _ in items], dtype=np.float64), torch.float64),
             t(np.asarray([a["image_height"] for a, _, _ in items], dtype=np.float32)),
-            t(np.stack([field(p, "68_landmarks_2d", (68, 2)) for _, p, _ in items])),
-            t(pv), t(np.asarray([len(v) for v in verts], dtype=np.int32), torch.int32),
-            t(np.stack([field(p, "7_landmarks_3d", (7, 3)) for _, p, _ in items])),
-            t(np.stack([field(p, "rotation_matrix", (3, 3)) for _, p, _ in items])),
+            stack([field(p, "68_landmarks_2d", (68, 2)) for _, p, _ in items]),
+            pv, t(np.asarray(n_pts, dtype=np.int32), torch.int32),
+            stack([field(p, "7_landmarks_3d", (7, 3)) for _, p, _ in items]),
+            stack([field(p, "rotation_matrix", (3, 3)) for _, p, _ in items]),
             landmarks=self.landmarks, head_indices=self._head, face_indices=self._face, z5=self.z5)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def __call__(self) -> Tuple[Dict[str, float], Dict[str, Dict[str, Dict[Any, float]]]]:
-        with open(self.prediction_file_path) as f:
-            submission = json.load(f)
-        with open(self.target_file_path) as f:
-            ground_truth = json.load(f)
+        if self.reader == "device":  # the arrays of numbers stay on the device as handles (json_reader.py)
+            submission = json_reader.load(self.prediction_file_path, self.device).root
+            ground_truth = json_reader.load(self.target_file_path, self.device).root
+        else:
+            with open(self.prediction_file_path) as f:
+                submission = json.load(f)
+            with open(self.target_file_path) as f:
+                ground_truth = json.load(f)
         n_min = int(self.head_indices.max()) + 1
         self.warnings = []
         lists = {name: [] for name, _ in METRICS}
@@ -328,8 +365,9 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     ap.add_argument("--face-indices", required=True, help="flame_indices/face.npy of the reference model data")
     ap.add_argument("--z5", choices=("reference", "knn"), default="reference")
     ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--reader", choices=("host", "device"), default="host", help="device: parse the arrays of numbers of both files on the GPU")
     args = ap.parse_args(argv)
-    ev = DADEvaluator(args.gt, args.submission, face_indices=args.face_indices, z5=args.z5, batch_size=args.batch_size)
+    ev = DADEvaluator(args.gt, args.submission, face_indices=args.face_indices, z5=args.z5, batch_size=args.batch_size, reader=args.reader)
     overall, attribute = ev()
     print(summary_text(overall, attribute))
     if ev.warnings:

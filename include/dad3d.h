@@ -579,6 +579,62 @@ DAD3D_EXPORT dad3d_status dad3d_json_format_values(const float* values, int batc
 DAD3D_EXPORT dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out, size_t out_stride, int32_t* lengths);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reading JSON back: the large arrays of numbers of a document lifted into float64 on the device, with the doubles `json.load` makes
+ * (dad_3dheads_benchmark/benchmark.py:177-180, the two `json.load` calls of `DADEvaluator.__call__`). The device lifts only what it has
+ * validated and converted exactly; every other byte stays with the host parser, so a result can never differ from `json.load`.
+ * The document is `text`, n_bytes < 2^31 bytes on the DEVICE, 16-byte aligned, worked on in tiles of DAD3D_JSON_PARSE_TILE_BYTES. Every
+ * scan is per-tile totals, a scan of the totals, then apply, as separate launches: no workgroup waits on another. Four stream-ordered
+ * entries, all DEVICE pointers unless said otherwise; none allocates or synchronises, and each validates its arguments (NULL, sizes,
+ * alignment, scratch) before any device work -> DAD3D_E_INVALID:
+ *   dad3d_json_parse_index   string state (a quote behind an odd run of backslashes is escaped; parity of the others), the class of
+ *                            every byte (one byte each, in `scratch`) and the totals. counts [4] int32 = {number tokens, brackets
+ *                            `[` `]` outside strings, non-numeric bytes, final bracket depth}. A token is a maximal run of
+ *                            `0-9 + - . e E` outside strings; a non-numeric byte is one inside a string, a quote, or any byte outside
+ *                            strings that is not `[ ] ,`, space, tab, LF, CR or a token byte. Four launches.
+ *   dad3d_json_parse_lists   after _index on the same scratch: compacts the tokens and brackets in document order. Token i: tok_pos[i]
+ *                            = its first byte, tok_brk[i] = brackets in front of it. Bracket j: brk_pos[j], brk_key[j] = the depth
+ *                            inside it (a `[` and its `]` share a key), brk_nonnum[j] / brk_tok[j] = non-numeric bytes / tokens in
+ *                            front of it. Only the first tok_cap / brk_cap entries are written. One launch.
+ *   dad3d_json_parse_check_arrays  for n_arrays candidate spans (bracket indices arr_open[a] < arr_close[a] of a matched pair with no
+ *                            non-numeric byte inside), one workgroup each: arr_rows[a] = 0 for shape (n,), r for shape (r, n / r), -1
+ *                            when the span is not liftable: brackets deeper than two levels, ragged or empty rows, a token beside a
+ *                            row, malformed separators (with whitespace skipped: `[` or `,` in front of every token and inner `[`,
+ *                            a token or `]` in front of that `,`, `,` or `]` behind every token and inner `]`, no `,` in front of a
+ *                            `]`), or a token the number routine flags. One launch.
+ *   dad3d_json_parse_extract for n_records lifted arrays, records [n_records][DAD3D_JSON_PARSE_RECORD_INTS] int32 = {byte of `[`,
+ *                            byte behind `]`, first value index, count, rows, first token index}, first value indices ascending from 0:
+ *                            one lane per value writes values[v] (float64) and is_int[v] (1: the token has no fraction and no
+ *                            exponent part). n_values = the sum of the counts; nothing behind it is written. One launch.
+ * dad3d_json_parse_scratch_bytes (host-only): the scratch both of the first two entries take, 0 for n_bytes < 1 or >= 2^31.
+ * dad3d_json_parse_number_host runs the number routine on the CPU, HOST pointers: token i is text[starts[i], ends[i]); its double's
+ * bits go to bits_out[i], is_int_out[i], and flags_out[i] = 0 or DAD3D_JSON_PARSE_FLAG_* (then bits_out[i] = 0). The routine is exact
+ * integer arithmetic (Eisel-Lemire against a 128-bit table of powers of five) and flags what it will not decide.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_JSON_PARSE_TILE_BYTES 4096 /* 256 lanes x 16 bytes */
+#define DAD3D_JSON_PARSE_RECORD_INTS 6
+#define DAD3D_JSON_PARSE_FLAG_GRAMMAR 0x1   /* not -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? */
+#define DAD3D_JSON_PARSE_FLAG_DIGITS 0x2    /* more than 19 significant digits */
+#define DAD3D_JSON_PARSE_FLAG_BIG_INT 0x4   /* an integer token beyond 2^53 */
+#define DAD3D_JSON_PARSE_FLAG_SUBNORMAL 0x8 /* below the smallest normal double */
+#define DAD3D_JSON_PARSE_FLAG_OVERFLOW 0x10 /* beyond the largest double */
+#define DAD3D_JSON_PARSE_FLAG_AMBIGUOUS 0x20 /* the truncated product cannot decide the rounding */
+DAD3D_EXPORT size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes);
+DAD3D_EXPORT dad3d_status dad3d_json_parse_index(const uint8_t* text, int64_t n_bytes, void* scratch, size_t scratch_bytes, int32_t* counts,
+                                    int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_json_parse_lists(const uint8_t* text, int64_t n_bytes, const void* scratch, size_t scratch_bytes,
+                                    int32_t* tok_pos, int32_t* tok_brk, int64_t tok_cap, int32_t* brk_pos, int32_t* brk_key,
+                                    int32_t* brk_nonnum, int32_t* brk_tok, int64_t brk_cap, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_json_parse_check_arrays(const uint8_t* text, int64_t n_bytes, const int32_t* tok_pos, const int32_t* tok_brk,
+                                           int64_t n_tokens, const int32_t* brk_pos, const int32_t* brk_key, const int32_t* brk_tok,
+                                           int64_t n_brackets, const int32_t* arr_open, const int32_t* arr_close, int32_t* arr_rows,
+                                           int64_t n_arrays, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_json_parse_extract(const uint8_t* text, int64_t n_bytes, const int32_t* tok_pos, int64_t n_tokens,
+                                      const int32_t* records, int64_t n_records, int64_t n_values, double* values, uint8_t* is_int,
+                                      int64_t values_cap, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_json_parse_number_host(const uint8_t* text, const int64_t* starts, const int64_t* ends, size_t n,
+                                          uint64_t* bits_out, uint8_t* is_int_out, uint32_t* flags_out);
+
+/* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
  * in one launch: LongestMaxSize (cv2.resize INTER_LINEAR, 8-bit fixed-point path) -> PadIfNeeded (centred, 0) -> Normalize
  * ((x - 255 mean) * (1 / (255 std)), float32) -> CHW. All DEVICE pointers:
