@@ -23,6 +23,7 @@ JSON_MAX_NUMBER_BYTES, JSON_MAX_LITERAL_BYTES, JSON_FLAG_NONFINITE = 23, 64, 0x1
 JSON_PARSE_TILE_BYTES, JSON_PARSE_RECORD_INTS = 4096, 6
 (JSON_PARSE_FLAG_GRAMMAR, JSON_PARSE_FLAG_DIGITS, JSON_PARSE_FLAG_BIG_INT, JSON_PARSE_FLAG_SUBNORMAL, JSON_PARSE_FLAG_OVERFLOW,
  JSON_PARSE_FLAG_AMBIGUOUS) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+PNG_SEGMENT_BYTES, ZLIB_SECOND_DISTANCE, PNG_FLAG_INTERNAL, DEFLATE_HEADER_BYTES = 8192, 4, 0x1, 640
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -142,6 +143,13 @@ SIGNATURES = {
     "dad3d_json_parse_check_arrays": (_I, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _I, _P]),
     "dad3d_json_parse_extract": (_I, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _I, _P]),
     "dad3d_json_parse_number_host": (_I, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "dad3d_png_max_bytes": (C.c_size_t, [_I, _I, _I]),
+    "dad3d_png_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "dad3d_png_encode": (_I, [_P, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
+    "dad3d_zlib_max_bytes": (C.c_size_t, [C.c_int64]),
+    "dad3d_zlib_scratch_bytes": (C.c_size_t, [_I, C.c_int64]),
+    "dad3d_zlib_compress": (_I, [_P, _I, C.c_int64, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
+    "dad3d_deflate_tables_host": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dad3d_sim3dr_get_tri_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_ver_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_normal": (None, [_P, _P, _P, _I, _I]),

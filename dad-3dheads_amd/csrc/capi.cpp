@@ -1315,6 +1315,70 @@ dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out,
     return DAD3D_OK;
 }
 
+static bool png_shape_ok(int h, int w, int c) {
+    return h >= 1 && w >= 1 && c >= 1 && c <= 4 && (long long)w * c < 0x7fffffffll && png_stream_bytes(h, w, c) < 0x80000000ll;
+}
+
+size_t dad3d_png_max_bytes(int h, int w, int c) { return png_shape_ok(h, w, c) ? png_max_bytes(h, w, c) : 0; }
+
+size_t dad3d_png_scratch_bytes(int batch, int h, int w, int c) {
+    return batch >= 1 && batch <= 65535 && png_shape_ok(h, w, c) ? png_scratch_bytes(batch, h, w, c) : 0;
+}
+
+size_t dad3d_zlib_max_bytes(int64_t n) { return n >= 1 && n < 0x80000000ll ? zlib_max_bytes(n) : 0; }
+
+size_t dad3d_zlib_scratch_bytes(int batch, int64_t n) {
+    return batch >= 1 && batch <= 65535 && n >= 1 && n < 0x80000000ll ? zlib_scratch_bytes(batch, n) : 0;
+}
+
+static dad3d_status deflate_checked(const char* who, DeflateArgs& a, size_t max_bytes, size_t need_scratch, size_t scratch_bytes, int device,
+                                    void* stream) {
+    DAD3D_REQUIRE(a.batch >= 1 && a.batch <= 65535, "%s: batch %d outside 1 .. 65535", who, a.batch);
+    DAD3D_REQUIRE(a.data && a.out && a.lengths && a.flags && a.scratch, "%s: null argument", who);
+    DAD3D_REQUIRE(a.out_stride >= max_bytes, "%s: out_stride %zu is below the worst case of the shape (%zu bytes)", who, a.out_stride, max_bytes);
+    DAD3D_REQUIRE(a.out_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0, "%s: out and out_stride must be 16-byte aligned", who);
+    DAD3D_REQUIRE((reinterpret_cast<uintptr_t>(a.scratch) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.lengths) & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(a.flags) & 3) == 0,
+                  "%s: lengths / flags / scratch are misaligned", who);
+    DAD3D_REQUIRE(scratch_bytes >= need_scratch, "%s: %zu bytes of scratch, %zu needed", who, scratch_bytes, need_scratch);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    return launch_deflate(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_png_encode(const uint8_t* images, int batch, int h, int w, int c, uint8_t* out, size_t out_stride, int64_t* lengths,
+                              int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream) {
+    DAD3D_REQUIRE(c >= 1 && c <= 4, "dad3d_png_encode: %d channels (1 .. 4: grey, grey + alpha, RGB, RGBA)", c);
+    DAD3D_REQUIRE(h >= 1 && w >= 1, "dad3d_png_encode: an image of %d x %d", h, w);
+    DAD3D_REQUIRE(png_shape_ok(h, w, c), "dad3d_png_encode: the filtered stream of a %d x %d x %d image passes 2^31 bytes", h, w, c);
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_png_encode: batch %d outside 1 .. 65535", batch);
+    DeflateArgs a{images, out, out_stride, lengths, flags, scratch, 0, batch, 1, h, w, c};
+    return deflate_checked("dad3d_png_encode", a, png_max_bytes(h, w, c), png_scratch_bytes(batch, h, w, c), scratch_bytes, device, stream);
+}
+
+dad3d_status dad3d_zlib_compress(const uint8_t* data, int batch, int64_t n, uint8_t* out, size_t out_stride, int64_t* lengths, int32_t* flags,
+                                 void* scratch, size_t scratch_bytes, int device, void* stream) {
+    DAD3D_REQUIRE(n >= 1 && n < 0x80000000ll, "dad3d_zlib_compress: a stream of %lld bytes (1 .. 2^31 - 1)", (long long)n);
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_zlib_compress: batch %d outside 1 .. 65535", batch);
+    DeflateArgs a{data, out, out_stride, lengths, flags, scratch, n, batch, 0, 0, 0, 0};
+    return deflate_checked("dad3d_zlib_compress", a, zlib_max_bytes(n), zlib_scratch_bytes(batch, n), scratch_bytes, device, stream);
+}
+
+dad3d_status dad3d_deflate_tables_host(const uint32_t* ll_hist, const uint32_t* d_hist, uint8_t* ll_len, uint8_t* d_len, uint8_t* cl_len,
+                                       uint16_t* ll_code, uint16_t* d_code, uint16_t* cl_code, uint8_t* header, int32_t* header_bits,
+                                       uint32_t* dynamic_bits, uint32_t* fixed_bits) {
+    DAD3D_REQUIRE(ll_hist && d_hist && ll_len && d_len && cl_len && ll_code && d_code && cl_code && header && header_bits && dynamic_bits && fixed_bits,
+                  "dad3d_deflate_tables_host: null argument");
+    unsigned long long total = 0;
+    for (int i = 0; i < 286 + 30; ++i) {
+        const uint32_t v = i < 286 ? ll_hist[i] : d_hist[i - 286];
+        DAD3D_REQUIRE(v < (1u << 22), "dad3d_deflate_tables_host: a count of %u (below 2^22)", v);
+        total += v;
+    }
+    DAD3D_REQUIRE(total < (1ull << 26), "dad3d_deflate_tables_host: %llu symbols in one block (below 2^26)", total);
+    return deflate_tables_host(ll_hist, d_hist, ll_len, d_len, cl_len, ll_code, d_code, cl_code, header, header_bits, dynamic_bits, fixed_bits);
+}
+
 size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes) {
     return n_bytes < 1 || n_bytes > 0x7fffffffLL ? 0 : json_parse_scratch_bytes(n_bytes);
 }

@@ -496,6 +496,29 @@ dad3d_status launch_json_format(const JsonFormatArgs& a, hipStream_t s);
 // host: text of values[i] at out + i * out_stride (DAD3D_JSON_MAX_NUMBER_BYTES at most), its length in lengths[i]; -1 for NaN / inf
 void json_number_host(const float* values, size_t n, unsigned char* out, size_t out_stride, int* lengths);
 
+// PNG files / zlib streams (png_encode.hip): filter, deflate per segment of DAD3D_PNG_SEGMENT_BYTES, assemble
+struct DeflateArgs {
+    const unsigned char* data;  // png: images [B,h,w,c]; else the streams [B,n]
+    unsigned char* out;         // [B][out_stride], 16-byte aligned rows
+    size_t out_stride;
+    int64_t* lengths;           // [B]
+    int32_t* flags;             // [B] DAD3D_PNG_FLAG_*
+    void* scratch;              // png_scratch_bytes / zlib_scratch_bytes: the filtered streams | payload slots | segment records
+    long long n;                // bytes per stream (zlib)
+    int batch, png, h, w, c;
+};
+int png_segments(long long n);
+long long png_stream_bytes(int h, int w, int c);
+size_t png_max_bytes(int h, int w, int c);
+size_t png_scratch_bytes(int batch, int h, int w, int c);
+size_t zlib_max_bytes(long long n);
+size_t zlib_scratch_bytes(int batch, long long n);
+dad3d_status launch_deflate(const DeflateArgs& a, hipStream_t s);
+// host: deflate_tables (deflate_tables.hpp) on one pair of histograms
+dad3d_status deflate_tables_host(const unsigned* ll_hist, const unsigned* d_hist, unsigned char* ll_len, unsigned char* d_len, unsigned char* cl_len,
+                                 unsigned short* ll_code, unsigned short* d_code, unsigned short* cl_code, unsigned char* header, int* header_bits,
+                                 unsigned* dynamic_bits, unsigned* fixed_bits);
+
 // JSON read back on the device (json_parse.hip): index the document, compact its token and bracket lists, check candidate arrays, extract
 // the values of the lifted ones; the entries of include/dad3d.h one to one
 struct JsonParseListsArgs {

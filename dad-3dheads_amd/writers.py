@@ -12,6 +12,9 @@ holds the literal bytes of one item's layout, the numbers between them are `floa
 the shortest round-trip form `json.dump` prints -- from 128-bit integer products. `flame_params_json_batch` /
 `save_flame_params_batch` write the bytes of `JsonSaver` that way; an item that holds NaN or an infinity is flagged on the device
 and formatted here (`_json_item_host`). `JsonSaver`, `get_flame_params` and `flame_params_batch` are the host path, unchanged.
+
+Images (`ImageSaver` of the demo, demo_utils.py:122-127) are written as PNG: a uint8 CUDA batch is filtered, deflated and framed on
+the GPU (`PngEncoder`, csrc/png_encode.hip; `png_batch`, `save_png_batch`), a host image by PIL (`ImageSaver`).
 """
 from __future__ import annotations
 
@@ -515,6 +518,188 @@ def flame_params_batch(params: torch.Tensor, constants: Dict[str, int] = FLAME_C
     fp = FlameParams.from_3dmm(params.detach().cpu(), constants)
     fields = {k: v.tolist() for k, v in vars(fp).items()}
     return [{k: rows[i] for k, rows in fields.items()} for i in range(params.shape[0])]
+
+
+def _png_host(image: np.ndarray) -> bytes:
+    """One image on the host with PIL: uint8 [H,W,C], C = 1..4, stored in the order it is given."""
+    from PIL import Image
+
+    arr = np.ascontiguousarray(image)
+    if arr.ndim == 2:
+        arr = arr[:, :, None]
+    if arr.dtype != np.uint8 or arr.ndim != 3 or not 1 <= arr.shape[2] <= 4:
+        raise ValueError(f"image: expected uint8 [H,W,C] with C in 1..4, got {arr.dtype} {arr.shape}")
+    buf = io.BytesIO()
+    Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(buf, format="PNG")  # L / LA / RGB / RGBA from the shape
+    return buf.getvalue()
+
+
+class ImageSaver:
+    """demo_utils.py:122-127 without cv2: the reference swaps the channels for `cv2.imwrite`, which swaps them back when it writes,
+    so the file holds the array's own order. One host image, encoded on the host (as `MeshSaver` stays on the host)."""
+
+    def __init__(self) -> None:
+        self.extension = ".png"
+
+    def __call__(self, image: np.ndarray, output_path: str) -> None:
+        with open(output_path, "wb") as f:
+            f.write(_png_host(np.asarray(image)))
+
+
+class PngData(_DeviceText):
+    """What `PngEncoder.encode` returns: the PNG files of `batch` images in HBM, the contract of `ObjText`. A flagged item (the
+    encoder's own consistency check, or a flag the caller ORed in) is encoded on the host with PIL."""
+
+    def __init__(self, encoder: "PngEncoder", images: torch.Tensor, batch: int):
+        super().__init__(encoder, batch)
+        self.images = images
+
+    def _host_item(self, b: int) -> bytes:
+        return _png_host(self.images[b].detach().cpu().numpy())
+
+
+class PngEncoder(_TextBuffers):
+    """A batch of uint8 images `[B,H,W,C]`, C = 1..4, as PNG files made on the GPU (`dad3d_png_encode`, csrc/png_encode.hip,
+    DESIGN.md 4.15): row filters, deflate per segment of `_lib.PNG_SEGMENT_BYTES` with Huffman tables built on the device, CRC-32
+    and Adler-32. Lossless; the bytes are this encoder's own.
+
+    `reserve(batch)` allocates the device file buffer (`batch` rows of `dad3d_png_max_bytes`), lengths, flags, scratch and one
+    pinned host buffer; `encode(images)` launches three kernels on the current stream with no allocation and no sync once the
+    batch fits (capturable in a graph); `PngData.to_host()` brings the files over."""
+
+    def __init__(self, height: int, width: int, channels: int, device: Optional[int] = None):
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.torch_device = torch.device("cuda", self.device)
+        self.height, self.width, self.channels = int(height), int(width), int(channels)
+        worst = self._lib.dad3d_png_max_bytes(self.height, self.width, self.channels)
+        if worst == 0:
+            raise ValueError(f"PngEncoder: cannot encode images of {self.height} x {self.width} x {self.channels} (1..4 channels, a "
+                             "filtered stream below 2^31 bytes)")
+        self.stride = (worst + 15) // 16 * 16
+        self.capacity = 0
+
+    def reserve(self, batch: int) -> None:
+        batch = max(int(batch), 1)
+        if batch <= self.capacity:
+            return
+        self._reserve_buffers(batch, self._lib.dad3d_png_scratch_bytes(batch, self.height, self.width, self.channels))
+
+    def encode(self, images: torch.Tensor, extra_flags: Optional[torch.Tensor] = None) -> PngData:
+        """`images [B,H,W,C]` -> `PngData`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
+        kernels: a non-zero entry sends that item to the host encoder."""
+        shape = (self.height, self.width, self.channels)
+        if (not isinstance(images, torch.Tensor) or images.device != self.torch_device or images.dtype != torch.uint8
+                or not images.is_contiguous() or images.ndim != 4 or tuple(images.shape[1:]) != shape):
+            raise ValueError(f"images: expected a contiguous uint8 tensor [B,{shape[0]},{shape[1]},{shape[2]}] on {self.torch_device}, got "
+                             f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))} on "
+                             f"{getattr(images, 'device', 'the host')}"
+                             + ("" if not isinstance(images, torch.Tensor) or images.is_contiguous() else " (not contiguous)"))
+        b = images.shape[0]
+        if b == 0:
+            self.reserve(1)
+            return PngData(self, images, 0)
+        self.reserve(b)
+        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
+        _lib.check(self._lib.dad3d_png_encode(images.data_ptr(), b, *shape, self._text.data_ptr(), self._text.stride(0),
+                                              self._lengths.data_ptr(), self._flags.data_ptr(), self._scratch.data_ptr(),
+                                              self._scratch.numel(), self.device, stream))
+        if extra_flags is not None:
+            self._flags[:b].bitwise_or_(extra_flags)
+        return PngData(self, images, b)
+
+
+_png_encoders: Dict[Tuple[int, int, int, int], PngEncoder] = {}
+
+
+def _png_encoder_for(images: torch.Tensor) -> PngEncoder:
+    key = (images.device.index, int(images.shape[1]), int(images.shape[2]), int(images.shape[3]))
+    enc = _png_encoders.get(key)
+    if enc is None:
+        enc = _png_encoders[key] = PngEncoder(*key[1:], device=key[0])
+    return enc
+
+
+def _png_on_device_path(images: Any) -> bool:
+    return (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.ndim == 4
+            and 1 <= images.shape[3] <= 4 and images.shape[1] >= 1 and images.shape[2] >= 1 and images.is_contiguous())
+
+
+def _png_host_batch(images: Any) -> List[bytes]:
+    arr = images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
+    return [_png_host(a) for a in arr]
+
+
+def png_batch(images: Any) -> List[bytes]:
+    """`images [B,H,W,C]` uint8 -> the bytes of one PNG file per image. A contiguous uint8 CUDA tensor is encoded on the GPU;
+    anything else (a numpy array, a CPU tensor) by PIL on the host. The files differ in bytes and decode to the same pixels."""
+    if _png_on_device_path(images):
+        return [bytes(x) for x in _png_encoder_for(images).encode(images.detach()).to_host()]
+    return _png_host_batch(images)
+
+
+def save_png_batch(images: Any, paths: Sequence[str], encoder: str = "auto") -> None:
+    """`images [B,H,W,C]` uint8 -> one `.png` per image. A contiguous uint8 CUDA tensor is encoded on the GPU (`PngEncoder`; a
+    flagged image is encoded here) and only the files cross to the host; a numpy array, a CPU tensor, a non-contiguous tensor or
+    `encoder="host"` takes the host path: one copy of the pixels, PIL per image."""
+    if encoder not in ("auto", "host"):
+        raise ValueError(f"encoder: expected 'auto' or 'host', got {encoder!r}")
+    assert len(images) == len(paths)
+    if encoder == "auto" and _png_on_device_path(images):
+        blocks = _png_encoder_for(images).encode(images.detach()).to_host()
+    else:
+        blocks = _png_host_batch(images)
+    for block, path in zip(blocks, paths):
+        with open(path, "wb") as f:
+            f.write(block)
+
+
+class _ZlibData(_DeviceText):
+    def __init__(self, owner: "_ZlibCompressor", data: torch.Tensor, batch: int):
+        super().__init__(owner, batch)
+        self.data = data
+
+    def _host_item(self, b: int) -> bytes:
+        import zlib
+
+        return zlib.compress(self.data[b].detach().cpu().numpy().tobytes(), 1)
+
+
+class _ZlibCompressor(_TextBuffers):
+    """The deflate of `PngEncoder` on plain byte rows `[B,n]`: one zlib stream per row (`dad3d_zlib_compress`)."""
+
+    def __init__(self, n: int, device: int):
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.device, self.torch_device, self.n = int(device), torch.device("cuda", int(device)), int(n)
+        worst = self._lib.dad3d_zlib_max_bytes(self.n)
+        if worst == 0:
+            raise ValueError(f"zlib_compress_batch: rows of {self.n} bytes (1 .. 2^31 - 1)")
+        self.stride = (worst + 15) // 16 * 16
+        self.capacity = 0
+
+    def compress(self, data: torch.Tensor) -> _ZlibData:
+        b = data.shape[0]
+        if b > self.capacity:
+            self._reserve_buffers(b, self._lib.dad3d_zlib_scratch_bytes(b, self.n))
+        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
+        _lib.check(self._lib.dad3d_zlib_compress(data.data_ptr(), b, self.n, self._text.data_ptr(), self._text.stride(0),
+                                                 self._lengths.data_ptr(), self._flags.data_ptr(), self._scratch.data_ptr(),
+                                                 self._scratch.numel(), self.device, stream))
+        return _ZlibData(self, data, b)
+
+
+def zlib_compress_batch(data: torch.Tensor) -> List[bytes]:
+    """`data [B,n]` uint8 on a GPU -> one zlib stream (RFC 1950) per row, from the deflate kernels of `PngEncoder`:
+    `zlib.decompress(out[i]) == data[i]`."""
+    if (not isinstance(data, torch.Tensor) or not data.is_cuda or data.dtype != torch.uint8 or data.ndim != 2 or not data.is_contiguous()
+            or data.shape[1] < 1):
+        raise ValueError(f"data: expected a contiguous uint8 CUDA tensor [B,n], n >= 1, got {getattr(data, 'dtype', type(data))} "
+                         f"{tuple(getattr(data, 'shape', ()))} on {getattr(data, 'device', 'the host')}")
+    if data.shape[0] == 0:
+        return []
+    return [bytes(x) for x in _ZlibCompressor(int(data.shape[1]), data.device.index).compress(data.detach()).to_host()]
 
 
 def get_output_path(input_image_path: str, outputs_folder: str, type_of_output: str, extension: str) -> str:

@@ -579,6 +579,48 @@ DAD3D_EXPORT dad3d_status dad3d_json_format_values(const float* values, int batc
 DAD3D_EXPORT dad3d_status dad3d_json_number_host(const float* values, size_t n, uint8_t* out, size_t out_stride, int32_t* lengths);
 
 /* ---------------------------------------------------------------------------------------------
+ * Images as PNG files, and byte rows as zlib streams, made on the device: what the demo's `ImageSaver` (demo_utils.py:122-127)
+ * hands to an image library. Lossless and fixed by the PNG / zlib / deflate specifications (RFC 1950, 1951); the bytes are this
+ * encoder's own, not those of any other.
+ *   images  DEVICE [batch,h,w,c] uint8, contiguous, c = 1 / 2 / 3 / 4 -> colour type 0 / 4 / 2 / 6, bit depth 8, no interlace; the
+ *           array is stored in the order it is given
+ *   data    DEVICE [batch,n] uint8, contiguous (dad3d_zlib_compress)
+ *   out     DEVICE [batch][out_stride] bytes, 16-byte aligned; out_stride a multiple of 16, at least dad3d_png_max_bytes(h, w, c) /
+ *           dad3d_zlib_max_bytes(n). Item b's file is out[b * out_stride .. + lengths[b]); bytes behind it are left as they were
+ *   lengths DEVICE [batch] int64   flags DEVICE [batch] int32   scratch DEVICE dad3d_*_scratch_bytes(..) bytes, 16-byte aligned
+ * The filtered stream (per row the type byte of the filter with the smallest sum of |signed byte|, lowest type on a tie, then
+ * the filtered row; for dad3d_zlib_compress the data itself) is cut into segments of DAD3D_PNG_SEGMENT_BYTES. A segment is one
+ * deflate block -- stored, fixed or dynamic Huffman, whichever is shortest; matches at distances 1 and c
+ * (DAD3D_ZLIB_SECOND_DISTANCE for a zlib stream), greedy -- and the empty stored block 00 00 FF FF. A PNG holds the zlib header,
+ * every segment and the trailer (03 00 + Adler-32) in IDAT chunks of their own; a zlib stream is the same bytes without chunks.
+ * flags[b] == 0 unless the encoder's own consistency check failed (DAD3D_PNG_FLAG_INTERNAL: length 0, the caller encodes that
+ * item on the host). Three launches (two for a zlib stream) on `stream`, no allocation, no synchronisation: can be captured
+ * into a graph. Arguments (NULL, c outside 1..4, h or w < 1, batch outside 1..65535, a filtered stream of 2^31 bytes or more, a
+ * stride or scratch below what the shape needs, alignment) are validated before any device work -> DAD3D_E_INVALID. The
+ * *_max_bytes / *_scratch_bytes calls are host-only and return 0 for such a shape.
+ * dad3d_deflate_tables_host runs the encoder's table routine on the CPU, HOST pointers: histograms ll_hist[286] (end of block
+ * counted) and d_hist[30], every count below 2^22 -> code lengths (15 bits at most; 7 for the code-length alphabet cl_*[19]),
+ * canonical codes numbered as in RFC 1951 3.2.2, the block header (BFINAL = 0, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length
+ * code, the run-length coded lengths) packed low bit first into header[DAD3D_DEFLATE_HEADER_BYTES], its bit count, and the bits
+ * of the whole block as a dynamic and as a fixed block.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_PNG_SEGMENT_BYTES 8192
+#define DAD3D_ZLIB_SECOND_DISTANCE 4
+#define DAD3D_PNG_FLAG_INTERNAL 0x1
+#define DAD3D_DEFLATE_HEADER_BYTES 640
+DAD3D_EXPORT size_t dad3d_png_max_bytes(int h, int w, int c);
+DAD3D_EXPORT size_t dad3d_png_scratch_bytes(int batch, int h, int w, int c);
+DAD3D_EXPORT dad3d_status dad3d_png_encode(const uint8_t* images, int batch, int h, int w, int c, uint8_t* out, size_t out_stride,
+                                           int64_t* lengths, int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream);
+DAD3D_EXPORT size_t dad3d_zlib_max_bytes(int64_t n);
+DAD3D_EXPORT size_t dad3d_zlib_scratch_bytes(int batch, int64_t n);
+DAD3D_EXPORT dad3d_status dad3d_zlib_compress(const uint8_t* data, int batch, int64_t n, uint8_t* out, size_t out_stride, int64_t* lengths,
+                                              int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_deflate_tables_host(const uint32_t* ll_hist, const uint32_t* d_hist, uint8_t* ll_len, uint8_t* d_len,
+                                                    uint8_t* cl_len, uint16_t* ll_code, uint16_t* d_code, uint16_t* cl_code, uint8_t* header,
+                                                    int32_t* header_bits, uint32_t* dynamic_bits, uint32_t* fixed_bits);
+
+/* ---------------------------------------------------------------------------------------------
  * Reading JSON back: the large arrays of numbers of a document lifted into float64 on the device, with the doubles `json.load` makes
  * (dad_3dheads_benchmark/benchmark.py:177-180, the two `json.load` calls of `DADEvaluator.__call__`). The device lifts only what it has
  * validated and converted exactly; every other byte stays with the host parser, so a result can never differ from `json.load`.
