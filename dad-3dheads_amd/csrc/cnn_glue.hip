@@ -72,7 +72,7 @@ struct Vec16<__half> {
     }
 };
 
-// y[p][c] = act(y[p][c] + bias[c] (+ z[p][c])); one 16-byte vector per thread and trip, channel-vector index = vector % (C / N)
+// y[p][c] = act(y[p][c] + bias[c] (+ z[p][c])), act = identity or ReLU (NaN -> NaN, -inf -> 0); one 16-byte vector per thread and trip, channel-vector index = vector % (C / N)
 template <typename T, bool HAS_Z, bool RELU>
 __global__ void nhwc_bias_act_kernel(T* y, const T* bias, const T* z, size_t n_vec, int cvec) {
     constexpr int N = Vec16<T>::N;
@@ -85,7 +85,7 @@ __global__ void nhwc_bias_act_kernel(T* y, const T* bias, const T* z, size_t n_v
         for (int k = 0; k < N; ++k) {
             float v = a[k] + b[k];
             if (HAS_Z) v += r[k];
-            a[k] = RELU ? fmaxf(v, 0.0f) : v;
+            a[k] = RELU ? __builtin_elementwise_maximum(v, 0.0f) : v;  // IEEE 754-2019 maximum (v_maximum3_f32), not fmaxf: a NaN stays a NaN, as in the framework's ReLU
         }
         Vec16<T>::store(y + i * N, a);
     }

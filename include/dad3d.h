@@ -692,7 +692,9 @@ DAD3D_EXPORT dad3d_status dad3d_preprocess_images(const int64_t* descs, int batc
  * (NHWC, dense) DEVICE tensors of fp32 / fp16 / bf16 elements; `channels` a multiple of 16 bytes' worth (4 / 8).
  *   dad3d_nhwc_bias_act    y = act(y + bias[c] (+ z)), in place: the folded BatchNorm's shift, the bottleneck's identity and the
  *                          ReLU behind a convolution in ONE pass (model_training/model/layers.py conv-bn-relu blocks; pytorchcv's
- *                          ResUnit `x = body(x) + identity; x = activ(x)`, built at model_training/model/encoders.py:42-48)
+ *                          ResUnit `x = body(x) + identity; x = activ(x)`, built at model_training/model/encoders.py:42-48).
+ *                          (y + bias) + z in fp32, ONE rounding to nearest even at the store; the ReLU is F.relu's: a NaN stays a
+ *                          NaN, -inf becomes 0
  *   dad3d_nhwc_resize_sum  out = sum_k weights[k] * nearest_resize(x_k -> [oh, ow]), k < n_inputs <= 3: a BiFPN node's weighted
  *                          fusion with its F.interpolate folded in (model_training/model/bifpn.py:98-125) */
 #define DAD3D_DTYPE_F32 0
