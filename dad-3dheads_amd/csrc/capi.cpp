@@ -1379,6 +1379,55 @@ dad3d_status dad3d_deflate_tables_host(const uint32_t* ll_hist, const uint32_t* 
     return deflate_tables_host(ll_hist, d_hist, ll_len, d_len, cl_len, ll_code, d_code, cl_code, header, header_bits, dynamic_bits, fixed_bits);
 }
 
+size_t dad3d_png_decode_scratch_bytes(int64_t* desc, int batch, int32_t* max_segments) {
+    if (!desc || !max_segments || batch < 1 || batch > 65535) return 0;
+    static_assert(sizeof(long long) == sizeof(int64_t), "descriptor rows");
+    int most = 0;
+    const size_t bytes = png_decode_layout(reinterpret_cast<long long*>(desc), batch, &most);
+    *max_segments = most;
+    return bytes;
+}
+
+dad3d_status dad3d_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, int max_segments, uint8_t* out,
+                              size_t out_bytes, int32_t* flags, int32_t* info, void* scratch, size_t scratch_bytes, int force_general, int device,
+                              void* stream) {
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_png_decode: batch %d outside 1 .. 65535", batch);
+    DAD3D_REQUIRE(files && desc && out && flags && info && scratch, "dad3d_png_decode: null argument");
+    DAD3D_REQUIRE(max_segments >= 1 && max_segments <= (1 << 18), "dad3d_png_decode: max_segments %d outside 1 .. 2^18", max_segments);
+    DAD3D_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && reinterpret_cast<uintptr_t>(desc) % 8 == 0,
+                  "dad3d_png_decode: scratch must be 16-byte aligned, desc 8-byte aligned");
+    DAD3D_REQUIRE(scratch_bytes >= (size_t)batch * 16, "dad3d_png_decode: %zu bytes of scratch for a batch of %d", scratch_bytes, batch);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    PngDecodeArgs a{files, files_bytes, reinterpret_cast<const long long*>(desc), batch, max_segments, force_general ? 1 : 0, out, out_bytes,
+                    flags, info, static_cast<unsigned char*>(scratch), scratch_bytes};
+    return launch_png_decode(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_zlib_decompress(const uint8_t* streams, size_t streams_bytes, const int64_t* desc, int batch, uint8_t* out, size_t out_bytes,
+                                   int64_t* lengths, int32_t* flags, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_zlib_decompress: batch %d outside 1 .. 65535", batch);
+    DAD3D_REQUIRE(streams && desc && out && lengths && flags, "dad3d_zlib_decompress: null argument");
+    DAD3D_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0 && reinterpret_cast<uintptr_t>(desc) % 8 == 0,
+                  "dad3d_zlib_decompress: out must be 16-byte aligned, desc 8-byte aligned");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    ZlibDecompressArgs a{streams, streams_bytes, reinterpret_cast<const long long*>(desc), batch, out, out_bytes, lengths, flags};
+    return launch_zlib_decompress(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_inflate_host(const uint8_t* const* ranges, const int64_t* range_bytes, int n_ranges, uint8_t* out, int64_t capacity,
+                                int64_t* length, int32_t* flag) {
+    DAD3D_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (ranges && range_bytes)) && length && flag && capacity >= 0 && (out || capacity == 0),
+                  "dad3d_inflate_host: null or negative argument");
+    for (int i = 0; i < n_ranges; ++i)
+        DAD3D_REQUIRE(range_bytes[i] >= 0 && (ranges[i] || range_bytes[i] == 0), "dad3d_inflate_host: range %d of %lld bytes", i, (long long)range_bytes[i]);
+    long long n = 0;
+    *flag = inflate_host(ranges, reinterpret_cast<const long long*>(range_bytes), n_ranges, out, capacity, &n);
+    *length = n;
+    return DAD3D_OK;
+}
+
 size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes) {
     return n_bytes < 1 || n_bytes > 0x7fffffffLL ? 0 : json_parse_scratch_bytes(n_bytes);
 }

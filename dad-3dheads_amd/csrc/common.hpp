@@ -519,6 +519,36 @@ dad3d_status deflate_tables_host(const unsigned* ll_hist, const unsigned* d_hist
                                  unsigned short* ll_code, unsigned short* d_code, unsigned short* cl_code, unsigned char* header, int* header_bits,
                                  unsigned* dynamic_bits, unsigned* fixed_bits);
 
+// PNG files / zlib streams read back (png_decode.hip): scan, inflate per segment, inflate or accept, unfilter and store
+struct PngDecodeArgs {
+    const unsigned char* files;  // every file of the batch, at the offsets of the descriptor rows
+    size_t files_bytes;
+    const long long* desc;       // DEVICE [B][DAD3D_PNG_DECODE_DESC_INTS]
+    int batch, max_segments, force_general;
+    unsigned char* out;
+    size_t out_bytes;
+    int32_t* flags;              // [B] DAD3D_PNG_DECODE_FLAG_*
+    int32_t* info;               // [B] DAD3D_PNG_DECODE_INFO_*
+    unsigned char* scratch;      // png_decode_layout: file states | per file: filtered stream, IDAT ranges, segment records
+    size_t scratch_bytes;
+};
+size_t png_decode_layout(long long* desc_host, int batch, int* max_segments);
+dad3d_status launch_png_decode(const PngDecodeArgs& a, hipStream_t s);
+struct ZlibDecompressArgs {
+    const unsigned char* streams;
+    size_t streams_bytes;
+    const long long* desc;  // DEVICE [B][DAD3D_ZLIB_DECODE_DESC_INTS]
+    int batch;
+    unsigned char* out;
+    size_t out_bytes;
+    int64_t* lengths;
+    int32_t* flags;
+};
+dad3d_status launch_zlib_decompress(const ZlibDecompressArgs& a, hipStream_t s);
+// host: inflate.hpp on a list of byte ranges; returns the flag
+int inflate_host(const unsigned char* const* ranges, const long long* range_bytes, int n_ranges, unsigned char* out, long long capacity,
+                 long long* length);
+
 // JSON read back on the device (json_parse.hip): index the document, compact its token and bracket lists, check candidate arrays, extract
 // the values of the lifted ones; the entries of include/dad3d.h one to one
 struct JsonParseListsArgs {

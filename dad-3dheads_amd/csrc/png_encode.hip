@@ -16,6 +16,7 @@
 //                           copied to its unaligned place through an LDS image (text_tile.hpp); the first workgroup of an item
 //                           combines the Adler sums and writes the head, the trailer, the length and the flag
 #include "common.hpp"
+#include "crc32.hpp"
 #include "deflate_tables.hpp"
 #include "text_tile.hpp"
 
@@ -27,7 +28,6 @@ constexpr int kLanes = 256;
 constexpr int kPerLane = kSeg / kLanes;  // 32: a lane's positions are one 32-bit mask
 constexpr int kSlot = kSeg + 16;         // a segment's payload in scratch: stored block (5 + n) + the empty stored block (5) at most
 constexpr unsigned kAdlerMod = 65521u;
-constexpr unsigned kCrcPoly = 0xEDB88320u;
 static_assert(kPerLane == 32 && kLanes == kTextTile, "the match masks are one word per lane");
 
 struct SegRecord {
@@ -37,33 +37,6 @@ struct SegRecord {
     int flag, kind, pad0, pad1;
 };
 static_assert(sizeof(SegRecord) == 32, "scratch layout");
-
-// ---- CRC-32 (reflected, polynomial EDB88320): bit 31 of a word is the coefficient of x^0 ----
-__host__ __device__ constexpr unsigned gf_mul(unsigned a, unsigned b) {
-    unsigned p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
-    }
-    return p;
-}
-// x^(8 k) mod P by square and multiply from the top bit; k < 2^16
-__device__ inline unsigned gf_x_pow_bytes(unsigned k) {
-    unsigned p = 0x80000000u;
-    for (int bit = 15; bit >= 0; --bit) {
-        p = gf_mul(p, p);
-        if ((k >> bit) & 1u) p = gf_mul(p, 0x00800000u);  // x^8
-    }
-    return p;
-}
-__device__ inline unsigned crc_bitwise(unsigned crc, unsigned byte) {
-    crc ^= byte;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) crc = (crc >> 1) ^ ((crc & 1u) ? kCrcPoly : 0u);
-    return crc;
-}
-// the CRC of A || B from the CRCs of A and B
-__device__ inline unsigned crc_append(unsigned crc_a, unsigned crc_b, unsigned bytes_b) { return gf_mul(gf_x_pow_bytes(bytes_b), crc_a) ^ crc_b; }
 
 __device__ inline unsigned long long wave_sum64(unsigned long long v) {
 #pragma unroll

@@ -202,3 +202,36 @@ class FaceMeshPredictor:
             results.append({"points": np.reshape(pts, (-1, 2)), "projected_vertices": proj[i : i + 1],
                             "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]})
         return results
+
+    def predict_files(self, sources: Sequence[Any], device_outputs: bool = False) -> List[Dict[str, Any]]:
+        """`predict_batch` fed with PNG files (paths or bytes, any sizes): the files are decoded to RGB on the device
+        (png_reader.PngDecoder, channels=3) and the decoded images go to the preprocess launch where they lie, so no decoded pixel
+        crosses the bus. The result dicts are those of `predict_batch` on `np.asarray(Image.open(f).convert("RGB"))`; what follows
+        the preprocess launch is `predict_batch`'s own code."""
+        from .png_reader import PngDecoder
+
+        decoded = PngDecoder(self.device).decode(sources, channels=3).tensors()  # alive until the launch has consumed them
+        batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)) for t in decoded])
+        return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs)
+
+    def _results_of(self, batch: torch.Tensor, shapes: Sequence[Tuple[int, int]], device_outputs: bool) -> List[Dict[str, Any]]:
+        """What `predict_batch` does behind its preprocess launch, for images of the sizes `shapes` = [(h, w)]."""
+        out = self.process(batch)
+        params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
+        geo = [self._geometry(s) for s in shapes]
+        pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
+        lm = self._landmarks_68(out)
+        if lm is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(),
+                                                             params.shape[0], pads_scale.data_ptr(), 0.0, 0.0, 1.0, stream))
+            params = params if device_outputs else params.cpu()
+            return [{"3dmm_params": params[i : i + 1]} for i in range(len(shapes))]
+        v3d, proj, params = self._readjust_and_decode(params, pads_scale, device_outputs)
+        results = []
+        for i, (pads, scale, _) in enumerate(geo):
+            pts = lm[i].clip(min=0, max=self._img_size) - np.array([[pads[2], pads[0]]])
+            pts = (pts / scale).astype(int)
+            results.append({"points": np.reshape(pts, (-1, 2)), "projected_vertices": proj[i : i + 1],
+                            "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]})
+        return results

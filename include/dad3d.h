@@ -621,6 +621,53 @@ DAD3D_EXPORT dad3d_status dad3d_deflate_tables_host(const uint32_t* ll_hist, con
                                                     int32_t* header_bits, uint32_t* dynamic_bits, uint32_t* fixed_bits);
 
 /* ---------------------------------------------------------------------------------------------
+ * PNG files and zlib streams read back on the device, bit-equal to `PIL.Image.open` and `zlib.decompress` (RFC 1950, 1951, the PNG
+ * specification): 8-bit grey, grey + alpha, RGB and RGBA files without interlace, of any sizes in one call.
+ *   files   DEVICE: the bytes of every file, file b at files[desc[b][0] .. + desc[b][1])
+ *   desc    DEVICE [batch][DAD3D_PNG_DECODE_DESC_INTS] int64: file offset, file bytes (below 2^31), height, width and channels as
+ *           the file's IHDR states them (the caller has read the signature and IHDR, nothing else, to size the outputs), offset of
+ *           the image in `out`, its row stride in bytes (at least width * out channels), out channels 1 .. 4, and four columns
+ *           that dad3d_png_decode_scratch_bytes fills: where the item's filtered stream, IDAT range table (and its capacity) and
+ *           segment records lie in `scratch`
+ *   out     DEVICE: image b is [height][row stride] bytes from out[desc[b][5]], `width * out channels` of each row written; bytes
+ *           between and behind the rows, and behind an item, are left as they were
+ *   flags   DEVICE [batch] int32: 0, or why the item was not decoded -- DAD3D_PNG_DECODE_FLAG_MALFORMED (signature, a chunk's
+ *           CRC-32 or length, chunk order, an unknown critical chunk, IHDR against the row, the zlib stream, its Adler-32, its
+ *           length, a filter type above 4, or a row that points outside the buffers) or _UNSUPPORTED (a valid file outside this
+ *           decoder: palette, 16-bit, depth below 8, Adam7). The pixels of a flagged item are unspecified; the caller decodes it on
+ *           the host. Nothing outside the item's own places is read or written whatever the file holds.
+ *   info    DEVICE [batch] int32: DAD3D_PNG_DECODE_INFO_SEGMENTED when the file had the layout dad3d_png_encode writes (an IDAT
+ *           with the zlib header, IDATs ending in 00 00 FF FF, an IDAT with 03 00 + Adler-32) and every IDAT inflated by itself:
+ *           complete non-final blocks ending on its last byte, no distance more than 4 bytes in front of its own output (those 4
+ *           are resolved from the IDAT before, as the encoder's matches need), DAD3D_PNG_SEGMENT_BYTES bytes each and the
+ *           rest in the last, the combined Adler-32 equal to the trailer. Any other file, and every file when
+ *           `force_general` is nonzero, goes through the serial inflate of the whole stream in the same call.
+ * Out channels follow PIL's `convert`: grey is replicated, alpha is dropped or 255, L = (19595 R + 38470 G + 7471 B + 32768) >> 16.
+ * dad3d_png_decode_scratch_bytes is host-only: it reads columns 1 .. 4 and 7 of HOST rows, fills columns 8 .. 11, gives the grid
+ * width `max_segments` and returns the bytes of scratch (16-byte aligned), 0 for a row outside the limits (a filtered stream of
+ * 2^31 bytes or more). Five launches on `stream` (three with force_general), no allocation, no synchronisation: can be captured.
+ * dad3d_zlib_decompress is the inverse of dad3d_zlib_compress for any zlib stream: desc DEVICE [batch][DAD3D_ZLIB_DECODE_DESC_INTS]
+ * int64 = offset and bytes of the stream in `streams`, offset (a multiple of 16) and capacity of its place in `out` (16-byte
+ * aligned). lengths[b] = the bytes written, flags[b] = 0, _MALFORMED or _OVERFLOW (the stream holds more than the capacity; length 0).
+ * dad3d_inflate_host runs the same inflate routine on the CPU, HOST pointers: the stream is the concatenation of n_ranges byte
+ * ranges (empty ones allowed); *flag as above, *length = the bytes written into out[0, capacity).
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_PNG_DECODE_DESC_INTS 12
+#define DAD3D_ZLIB_DECODE_DESC_INTS 4
+#define DAD3D_PNG_DECODE_FLAG_MALFORMED 0x1
+#define DAD3D_PNG_DECODE_FLAG_UNSUPPORTED 0x2
+#define DAD3D_PNG_DECODE_FLAG_OVERFLOW 0x4
+#define DAD3D_PNG_DECODE_INFO_SEGMENTED 0x1
+DAD3D_EXPORT size_t dad3d_png_decode_scratch_bytes(int64_t* desc, int batch, int32_t* max_segments);
+DAD3D_EXPORT dad3d_status dad3d_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, int max_segments,
+                                           uint8_t* out, size_t out_bytes, int32_t* flags, int32_t* info, void* scratch, size_t scratch_bytes,
+                                           int force_general, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_zlib_decompress(const uint8_t* streams, size_t streams_bytes, const int64_t* desc, int batch, uint8_t* out,
+                                                size_t out_bytes, int64_t* lengths, int32_t* flags, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_inflate_host(const uint8_t* const* ranges, const int64_t* range_bytes, int n_ranges, uint8_t* out,
+                                             int64_t capacity, int64_t* length, int32_t* flag);
+
+/* ---------------------------------------------------------------------------------------------
  * Reading JSON back: the large arrays of numbers of a document lifted into float64 on the device, with the doubles `json.load` makes
  * (dad_3dheads_benchmark/benchmark.py:177-180, the two `json.load` calls of `DADEvaluator.__call__`). The device lifts only what it has
  * validated and converted exactly; every other byte stays with the host parser, so a result can never differ from `json.load`.
