@@ -17,6 +17,7 @@
 // in registers and reduces them once at the end; an image is split over `nsplit` workgroups so that small batches
 // still fill the chip, and a second tiny kernel adds the partials in a fixed order: no atomics, so the gradient is
 // bit-reproducible run to run. HBM-bound streaming: per image 3 x 60 KB read (v_posed, the two gradients), 60 KB written.
+#include "collectives.hpp"
 #include "common.hpp"
 
 namespace dad3d {
@@ -26,12 +27,6 @@ namespace {
 constexpr int kBwdThreads = 512;  // 8 waves: 256 VGPRs per lane for the 72 running sums
 constexpr int kBwdWaves = kBwdThreads / 64;
 constexpr float kOffsetZ = 0.05f;  // flame.py:13 MESH_OFFSET_Z
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kBwdThreads) void flame_backward_kernel(BackwardArgs a) {
     __shared__ float c[kBackwardConsts];
@@ -112,7 +107,7 @@ __global__ __launch_bounds__(kBwdThreads) void flame_backward_kernel(BackwardArg
     // 72 sums over the workgroup: wave butterflies, then 16 partials per value through LDS
 #pragma unroll
     for (int i = 0; i < kBackwardConsts; ++i) {
-        const float t = wave_sum64(acc[i]);
+        const float t = wave_sum(acc[i]);
         if (lane == 0) red[wave][i] = t;
     }
     __syncthreads();
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(64) void pose_chain_kernel(ChainArgs a) {
     }
     float J[3 * kNumJoints];
 #pragma unroll
-    for (int o = 0; o < 3 * kNumJoints; ++o) J[o] = a.j0[o] + wave_sum64(jacc[o]);
+    for (int o = 0; o < 3 * kNumJoints; ++o) J[o] = a.j0[o] + wave_sum(jacc[o]);
     float pose[12], rot6[6];
 #pragma unroll
     for (int c = 0; c < 3; ++c) pose[c] = (a.lay.neck_n == 3) ? p[a.lay.neck_off + c] : 0.0f;

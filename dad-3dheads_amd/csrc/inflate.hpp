@@ -16,6 +16,8 @@
 // of the segment before); a distance may reach that far and no further.
 #pragma once
 
+#include "png_common.hpp"
+
 #ifndef DAD3D_HD
 #define DAD3D_HD __host__ __device__ inline
 #endif
@@ -24,7 +26,6 @@ namespace dad3d {
 
 constexpr int kInflateMalformed = 0x1, kInflateOverflow = 0x4;  // DAD3D_PNG_DECODE_FLAG_MALFORMED / _OVERFLOW
 constexpr int kInflateZlib = 0, kInflateSegment = 1;
-constexpr unsigned kInflateAdlerMod = 65521u;
 
 // canonical codes as counts per length and symbols in code order; `lengths` and `offs` are the table builder's work space
 struct InflateWork {
@@ -346,9 +347,9 @@ struct HostInflateOut {
     void lit(int x) {
         out[n++] = (unsigned char)x;
         a += (unsigned)x;
-        if (a >= kInflateAdlerMod) a -= kInflateAdlerMod;
+        if (a >= kAdlerMod) a -= kAdlerMod;
         b += a;
-        if (b >= kInflateAdlerMod) b -= kInflateAdlerMod;
+        if (b >= kAdlerMod) b -= kAdlerMod;
     }
     void copy(int dist, int len) {
         for (int i = 0; i < len; ++i) lit(out[n - dist]);

@@ -12,7 +12,7 @@
 //   json_compact_kernel        token and bracket lists in document order, each entry with the counts in front of it
 //   json_check_arrays_kernel   one workgroup per candidate array: shape, separators and every token through the number routine
 //   json_values_kernel         one lane per value of a lifted array: json_parse_number -> float64 bits + is_int
-// Stores are plain vector stores; there are no atomics.
+// Stores are plain vector stores; there are no atomics. The sums and scans over a workgroup are those of collectives.hpp.
 #include "common.hpp"
 #include "json_parse_number.hpp"
 #include "text_tile.hpp"
@@ -65,24 +65,6 @@ __device__ inline void store_chunk(unsigned char* __restrict__ dst, long long ba
     }
 }
 
-// the sum of v over the lanes in front of this one, and the workgroup's total
-__device__ inline int block_exclusive_scan(int v, int* red, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) red[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += red[w];
-    total = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
 // bit k: byte k of the chunk is a quote with an even run of backslashes in front of it
 __device__ inline unsigned unescaped_quotes(const unsigned char* __restrict__ text, long long base, const uint4& v, int valid) {
     unsigned mask = 0;
@@ -98,17 +80,17 @@ __device__ inline unsigned unescaped_quotes(const unsigned char* __restrict__ te
 }
 
 __global__ __launch_bounds__(kLanes) void json_tile_quotes_kernel(const unsigned char* __restrict__ text, long long n, int* __restrict__ tile_quotes) {
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const long long base = (long long)blockIdx.x * DAD3D_JSON_PARSE_TILE_BYTES + threadIdx.x * kLaneBytes;
     int valid;
     const uint4 v = load_chunk(text, base, n, valid);
-    const int total = block_sum(__popc(unescaped_quotes(text, base, v, valid)), red);
+    const int total = block_sum<kTextWaves>((int)__popc(unescaped_quotes(text, base, v, valid)), red);
     if (threadIdx.x == 0) tile_quotes[blockIdx.x] = total;
 }
 
 // data [ncols][ntiles] -> exclusive scan of every column in place, its total to totals[col] (when given). One workgroup.
 __global__ __launch_bounds__(kLanes) void json_scan_tiles_kernel(int* __restrict__ data, int ntiles, int ncols, int* __restrict__ totals) {
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     for (int col = 0; col < ncols; ++col) {
         int* column = data + (size_t)col * ntiles;
         int carry = 0;
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(kLanes) void json_scan_tiles_kernel(int* __restrict
             const int i = start + (int)threadIdx.x;
             const int v = i < ntiles ? column[i] : 0;
             int total;
-            const int before = block_exclusive_scan(v, red, total);
+            const int before = block_exclusive_scan<kTextWaves>(v, red, total);
             if (i < ntiles) column[i] = carry + before;
             carry += total;
         }
@@ -127,13 +109,13 @@ __global__ __launch_bounds__(kLanes) void json_scan_tiles_kernel(int* __restrict
 __global__ __launch_bounds__(kLanes) void json_classify_kernel(const unsigned char* __restrict__ text, long long n, int ntiles,
                                                                const int* __restrict__ tile_quotes, unsigned char* __restrict__ cls,
                                                                int* __restrict__ tile_totals) {
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const long long base = (long long)blockIdx.x * DAD3D_JSON_PARSE_TILE_BYTES + threadIdx.x * kLaneBytes;
     int valid;
     const uint4 v = load_chunk(text, base, n, valid);
     const unsigned quotes = unescaped_quotes(text, base, v, valid);
     int total;
-    const int before = block_exclusive_scan(__popc(quotes), red, total);
+    const int before = block_exclusive_scan<kTextWaves>(__popc(quotes), red, total);
     unsigned in_string = (unsigned)(tile_quotes[blockIdx.x] + before) & 1u;
     // a token starts at a token byte outside strings whose predecessor is no token byte (inside a string it could not be: the
     // string state changes at quotes only)
@@ -172,10 +154,10 @@ __global__ __launch_bounds__(kLanes) void json_classify_kernel(const unsigned ch
         }
     }
     store_chunk(cls, base, valid, out);
-    n_tok = block_sum(n_tok, red);
-    n_brk = block_sum(n_brk, red);
-    n_nonnum = block_sum(n_nonnum, red);
-    depth = block_sum(depth, red);
+    n_tok = block_sum<kTextWaves>(n_tok, red);
+    n_brk = block_sum<kTextWaves>(n_brk, red);
+    n_nonnum = block_sum<kTextWaves>(n_nonnum, red);
+    depth = block_sum<kTextWaves>(depth, red);
     if (threadIdx.x == 0) {
         tile_totals[0 * (size_t)ntiles + blockIdx.x] = n_tok;
         tile_totals[1 * (size_t)ntiles + blockIdx.x] = n_brk;
@@ -191,7 +173,7 @@ struct JsonLists {
 
 __global__ __launch_bounds__(kLanes) void json_compact_kernel(const unsigned char* __restrict__ cls, long long n, int ntiles,
                                                               const int* __restrict__ tile_before, JsonLists out) {
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const long long base = (long long)blockIdx.x * DAD3D_JSON_PARSE_TILE_BYTES + threadIdx.x * kLaneBytes;
     int valid;
     const uint4 v = load_chunk(cls, base, n, valid);
@@ -205,10 +187,10 @@ __global__ __launch_bounds__(kLanes) void json_compact_kernel(const unsigned cha
         d += (code == kOpen) - (code == kClose);
     }
     int total;
-    long long tok = (long long)tile_before[0 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan(n_tok, red, total);
-    long long brk = (long long)tile_before[1 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan(n_brk, red, total);
-    int nonnum = tile_before[2 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan(n_nonnum, red, total);
-    int depth = tile_before[3 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan(d, red, total);
+    long long tok = (long long)tile_before[0 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan<kTextWaves>(n_tok, red, total);
+    long long brk = (long long)tile_before[1 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan<kTextWaves>(n_brk, red, total);
+    int nonnum = tile_before[2 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan<kTextWaves>(n_nonnum, red, total);
+    int depth = tile_before[3 * (size_t)ntiles + blockIdx.x] + block_exclusive_scan<kTextWaves>(d, red, total);
 #pragma unroll 1  // 16 copies of the divergent stores below cost more registers than the loop saves
     for (int k = 0; k < kLaneBytes; ++k) {
         const unsigned code = byte_of(v, k);

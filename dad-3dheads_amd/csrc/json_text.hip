@@ -32,7 +32,7 @@ __device__ inline int literal_length(const int* __restrict__ offsets, int i) {
 
 __global__ __launch_bounds__(kJsonTile) void json_slot_lengths_kernel(const float* __restrict__ values, int n_slots, int ntiles,
                                                                       const int* __restrict__ offsets, int2* __restrict__ tile_info) {
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int slot = tile * kJsonTile + tid;
     int len = 0, bad = 0;
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kJsonTile) void json_slot_lengths_kernel(const floa
         }
     }
     if (tile == ntiles - 1 && tid == kJsonTile - 1) len += literal_length(offsets, n_slots);  // the suffix
-    len = block_sum(len, red);
+    len = block_sum<kTextWaves>(len, red);
     bad = __syncthreads_or(bad);
     if (tid == 0) tile_info[(size_t)b * ntiles + tile] = make_int2(len, bad ? DAD3D_JSON_FLAG_NONFINITE : 0);
 }
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kJsonTile) void json_write_text_kernel(const float*
                                                                     size_t text_stride, long long* __restrict__ lengths,
                                                                     int* __restrict__ flags) {
     __shared__ uint4 stage[kJsonStageVecs];
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const bool last = tile == ntiles - 1;
 
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(kJsonTile) void json_write_text_kernel(const float*
         before += t < tile ? info.x : 0;
         why |= info.y;
     }
-    before = block_sum(before, red);
-    total = block_sum(total, red);
+    before = block_sum<kTextWaves>(before, red);
+    total = block_sum<kTextWaves>(total, red);
     why = __syncthreads_or(why) ? DAD3D_JSON_FLAG_NONFINITE : 0;
     if (last && tid == 0) {
         lengths[b] = why ? 0 : total;
@@ -87,23 +87,13 @@ __global__ __launch_bounds__(kJsonTile) void json_write_text_kernel(const float*
         json_number(__float_as_uint(values[(size_t)b * n_slots + slot]), n);
         len = lit + json_number_length(n);
     }
-    // exclusive scan of the 256 slot lengths
-    int incl = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if ((tid & 63) >= d) incl += up;
-    }
-    if ((tid & 63) == 63) red[tid >> 6] = incl;
-    __syncthreads();
-    int wave_base = 0;
-    for (int w = 0; w < (tid >> 6); ++w) wave_base += red[w];
-    int tile_len = red[0] + red[1] + red[2] + red[3];
+    int tile_len;
+    const int slot_at = block_exclusive_scan<kTextWaves>(len, red, tile_len);
 
     const int lead = before & 15;  // image byte i is text byte (before - lead) + i: 16-byte units line up
     unsigned char* s = reinterpret_cast<unsigned char*>(stage);
     if (slot < n_slots) {
-        unsigned char* p = s + lead + wave_base + incl - len;
+        unsigned char* p = s + lead + slot_at;
         for (int i = 0; i < lit; ++i) *p++ = literals[lit_at + i];
         json_put_number(p, n);
     }

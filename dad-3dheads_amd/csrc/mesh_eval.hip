@@ -16,6 +16,7 @@
 // Distances are the direct-difference form (qx-px)^2 + (qy-py)^2 + (qz-pz)^2 in fp32, never |q|^2 + |p|^2 - 2 q.p: the
 // expansion cancels at world-scale coordinates (the reference's own `cdist` noise). Neither kernel allocates; both are
 // stream-ordered and can be captured into a graph.
+#include "collectives.hpp"
 #include "common.hpp"
 
 namespace dad3d {
@@ -137,8 +138,9 @@ __global__ __launch_bounds__(kZ5Threads) void z5_rank_kernel(EvalZ5Args a) {
         c += (g[i * 3 + 2] >= g[o * 3 + 2]) == (w[i * 3 + 2] >= w[o * 3 + 2]);
         if (a.order) a.order[ob + i] = o;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    // Not block_sum of collectives.hpp: only lane 0 needs the sum and `red` is not used again, and the 16 waves' second barrier
+    // costs this kernel 0.3 % (profiles/collectives_refactor_ab.md).
+    c = wave_sum(c);
     if ((tid & 63) == 0) red[tid >> 6] = c;
     __syncthreads();
     if (tid == 0) {

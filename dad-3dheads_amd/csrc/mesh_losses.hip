@@ -41,6 +41,10 @@ __device__ __forceinline__ float crit_slope(int crit, float d) {
     return fabsf(d) < 1.0f ? d : sgn;
 }
 
+// Not yet block_sum of collectives.hpp: the barrier comes first here (it also orders block_arg's reads of redv). With the header's
+// protocol the eager training step measured slower, in runs whose host-bound scatter the record could not bound; moving over
+// remains open (profiles/collectives_refactor_ab.md). The order of the additions is the header's: butterfly 32..1, then the
+// waves ascending.
 __device__ __forceinline__ float block_sum(float v, float* red, int tid) {  // every thread gets the sum; red: kLossWaves floats
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

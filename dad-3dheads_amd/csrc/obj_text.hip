@@ -18,7 +18,7 @@
 namespace dad3d {
 namespace {
 
-constexpr int kObjTile = 256;                                 // lines per workgroup, one per lane
+constexpr int kObjTile = kTextTile;                           // lines per workgroup, one per lane
 constexpr int kObjMaxLine = DAD3D_OBJ_MAX_LINE_BYTES;         // "v" + 3 x (" " + "-" + 12 digits + "." + 8 digits) + "\n"
 constexpr int kObjStageVecs = (kObjTile * kObjMaxLine + 15 + 15) / 16;  // the tile image: up to 15 bytes of lead-in + the lines
 
@@ -111,7 +111,7 @@ __device__ inline void load_tile(const float* __restrict__ vertices, size_t firs
 __global__ __launch_bounds__(kObjTile) void obj_line_lengths_kernel(const float* __restrict__ vertices, int nver, int ntiles,
                                                                      int2* __restrict__ tile_info) {
     __shared__ float sv[kObjTile * 3];
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int lines = min(kObjTile, nver - tile * kObjTile);
     load_tile(vertices, ((size_t)b * nver + (size_t)tile * kObjTile) * 3, lines * 3, sv);
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kObjTile) void obj_line_lengths_kernel(const float*
             if (obj_number(sv[tid * 3 + c], n, why)) len += n.length();
         }
     }
-    len = block_sum(len, red);
+    len = block_sum<kTextWaves>(len, red);
     why = block_or_flags(why);
     if (tid == 0) tile_info[(size_t)b * ntiles + tile] = make_int2(len, why);
 }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kObjTile) void obj_write_text_kernel(const float* _
                                                                    int* __restrict__ flags) {
     __shared__ uint4 stage[kObjStageVecs];
     __shared__ float sv[kObjTile * 3];
-    __shared__ int red[4];
+    __shared__ int red[kTextWaves];
     const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
 
     // this tile's offset in the mesh's text, the mesh's length and flag: every workgroup sums its mesh's tiles
@@ -146,8 +146,8 @@ __global__ __launch_bounds__(kObjTile) void obj_write_text_kernel(const float* _
         before += t < tile ? info.x : 0;
         why |= info.y;
     }
-    before = block_sum(before, red);
-    total = block_sum(total, red);
+    before = block_sum<kTextWaves>(before, red);
+    total = block_sum<kTextWaves>(total, red);
     why = block_or_flags(why);
     if (tile == 0 && tid == 0) {
         lengths[b] = why ? 0 : total;
@@ -168,7 +168,9 @@ __global__ __launch_bounds__(kObjTile) void obj_write_text_kernel(const float* _
             len += n[c].length();
         }
     }
-    // exclusive scan of the 256 line lengths
+    // exclusive scan of the 256 line lengths. Not block_exclusive_scan of collectives.hpp: its closing barrier costs this kernel
+    // 0.6 to 0.9 % (profiles/collectives_refactor_ab.md); here the barrier in front of the copy-out is the only one the scan needs,
+    // because `red` is not written again.
     int incl = len;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -179,6 +181,7 @@ __global__ __launch_bounds__(kObjTile) void obj_write_text_kernel(const float* _
     __syncthreads();
     int wave_base = 0;
     for (int w = 0; w < (tid >> 6); ++w) wave_base += red[w];
+    static_assert(kTextWaves == 4, "the tile length below adds four wave totals");
     const int tile_len = red[0] + red[1] + red[2] + red[3];
 
     const int lead = before & 15;  // image byte i is text byte (before - lead) + i: 16-byte units line up

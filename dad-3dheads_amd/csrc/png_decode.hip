@@ -28,9 +28,11 @@
 // The 64 lanes of a wave run inflate.hpp with the same values; the policies below use the lane: the input is staged through LDS in
 // pieces of kStage bytes, the output goes into a circular window in LDS (history and write buffer in one), copies and stored bytes
 // are spread over the lanes, and each full piece of kFlush bytes leaves in 4-byte stores with its Adler sums taken on the way.
+#include "collectives.hpp"
 #include "common.hpp"
 #include "crc32.hpp"
 #include "inflate.hpp"
+#include "png_common.hpp"
 
 namespace dad3d {
 namespace {
@@ -64,25 +66,6 @@ constexpr unsigned kTailValue = 0xffu, kLeadFirst = 0x03020100u, kLeadSecond = 0
 struct Range {
     int at, bytes;  // from the start of the file
 };
-
-__device__ inline unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-__device__ inline unsigned wave_xor(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, kWave);
-    return v;
-}
-__device__ inline unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, d, kWave), hi = __shfl_xor((unsigned)(v >> 32), d, kWave);
-        v += (unsigned long long)hi << 32 | lo;
-    }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // the policies of inflate.hpp for one wave
@@ -156,10 +139,10 @@ struct WaveOut {
             out[flushed + i] = (unsigned char)x;
             sa += x, sb += (unsigned)(m - i) * x;
         }
-        sa = __builtin_amdgcn_readfirstlane(wave_sum(sa)) % kInflateAdlerMod;
-        sb = __builtin_amdgcn_readfirstlane(wave_sum(sb % kInflateAdlerMod)) % kInflateAdlerMod;
-        b = (b + (unsigned)m * a + sb) % kInflateAdlerMod;  // m a < 2^28
-        a = (a + sa) % kInflateAdlerMod;
+        sa = __builtin_amdgcn_readfirstlane(wave_sum(sa)) % kAdlerMod;
+        sb = __builtin_amdgcn_readfirstlane(wave_sum(sb % kAdlerMod)) % kAdlerMod;
+        b = (b + (unsigned)m * a + sb) % kAdlerMod;  // m a < 2^28
+        a = (a + sa) % kAdlerMod;
         flushed += m;
     }
     __device__ void flush_full() {
@@ -481,11 +464,11 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const unsigned char*
             ok = ok && r.ok;
             const long long end = min((long long)(j + 1) * kSeg, n_stream);
             s1 += r.a;
-            s2 = (s2 + r.b + (unsigned long long)r.a * (unsigned long long)((n_stream - end) % kInflateAdlerMod)) % kInflateAdlerMod;
+            s2 = (s2 + r.b + (unsigned long long)r.a * (unsigned long long)((n_stream - end) % kAdlerMod)) % kAdlerMod;
         }
-        s1 = wave_sum64(s1 % kInflateAdlerMod), s2 = wave_sum64(s2);
-        const unsigned a = (unsigned)((1 + s1) % kInflateAdlerMod);
-        const unsigned bb = (unsigned)(((unsigned long long)(n_stream % kInflateAdlerMod) + s2) % kInflateAdlerMod);
+        s1 = wave_sum(s1 % kAdlerMod), s2 = wave_sum(s2);
+        const unsigned a = (unsigned)((1 + s1) % kAdlerMod);
+        const unsigned bb = (unsigned)(((unsigned long long)(n_stream % kAdlerMod) + s2) % kAdlerMod);
         if (__all(ok) && be32(f + ranges[st.ranges - 1].at + 2) == (bb << 16 | a)) {
             if (lane == 0) info[b] = DAD3D_PNG_DECODE_INFO_SEGMENTED;
             return;
@@ -520,11 +503,6 @@ __global__ __launch_bounds__(kWave) void zlib_inflate_kernel(const unsigned char
 // ---------------------------------------------------------------------------------------------------------------------------
 // unfilter and store
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ inline int paeth(int a, int b, int c) {
-    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
 // Lane r holds row 64 band + r and is at pixel t - r in step t. Its left pixel is its own last result, the pixel above is lane
 // r - 1's last result (one shuffle) and the pixel above left is what that shuffle gave one step before. Lane 63 writes its row back
 // over the filtered bytes; after a fence lane 0 of the next band reads it as the row above.
@@ -565,7 +543,7 @@ __global__ __launch_bounds__(kWave) void png_unfilter_kernel(const long long* __
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int fa = (a >> (8 * k)) & 255, fb = (up >> (8 * k)) & 255, fc = (c >> (8 * k)) & 255;
-                const int pred = type == 0 ? 0 : type == 1 ? fa : type == 2 ? fb : type == 3 ? (fa + fb) >> 1 : paeth(fa, fb, fc);
+                const int pred = type == 0 ? 0 : type == 1 ? fa : type == 2 ? fb : type == 3 ? (fa + fb) >> 1 : png_paeth(fa, fb, fc);
                 raw |= (((f >> (8 * k)) + (unsigned)pred) & 255u) << (8 * k);
             }
             left = raw, up_before = up;

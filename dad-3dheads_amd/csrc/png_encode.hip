@@ -15,9 +15,11 @@
 //   png_assemble_kernel     one workgroup per (segment, item): offsets from the payload lengths, chunk words around the payload,
 //                           copied to its unaligned place through an LDS image (text_tile.hpp); the first workgroup of an item
 //                           combines the Adler sums and writes the head, the trailer, the length and the flag
+// The sums, the xor and the scan over a workgroup are those of collectives.hpp; Paeth and the Adler modulus those of png_common.hpp.
 #include "common.hpp"
 #include "crc32.hpp"
 #include "deflate_tables.hpp"
+#include "png_common.hpp"
 #include "text_tile.hpp"
 
 namespace dad3d {
@@ -27,7 +29,6 @@ constexpr int kSeg = DAD3D_PNG_SEGMENT_BYTES;
 constexpr int kLanes = 256;
 constexpr int kPerLane = kSeg / kLanes;  // 32: a lane's positions are one 32-bit mask
 constexpr int kSlot = kSeg + 16;         // a segment's payload in scratch: stored block (5 + n) + the empty stored block (5) at most
-constexpr unsigned kAdlerMod = 65521u;
 static_assert(kPerLane == 32 && kLanes == kTextTile, "the match masks are one word per lane");
 
 struct SegRecord {
@@ -38,55 +39,9 @@ struct SegRecord {
 };
 static_assert(sizeof(SegRecord) == 32, "scratch layout");
 
-__device__ inline unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, d, 64), hi = __shfl_xor((unsigned)(v >> 32), d, 64);
-        v += (unsigned long long)hi << 32 | lo;
-    }
-    return v;
-}
-__device__ inline unsigned long long block_sum64(unsigned long long v, unsigned long long* red) {
-    v = wave_sum64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return v;
-}
-__device__ inline unsigned block_xor(unsigned v, int* red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (int)v;
-    __syncthreads();
-    v = (unsigned)(red[0] ^ red[1] ^ red[2] ^ red[3]);
-    __syncthreads();
-    return v;
-}
-// exclusive prefix of v over the 256 lanes; *total = the sum
-__device__ inline int block_exclusive_scan(int v, int* red, int* total) {
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if ((threadIdx.x & 63) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += red[w];
-    *total = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // filter
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ inline int png_paeth(int a, int b, int c) {
-    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
 __device__ inline unsigned png_cost(int v) { return v < 128 ? (unsigned)v : (unsigned)(256 - v); }
 __device__ inline int png_filtered(int type, int x, int a, int b, int c) {
     const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : png_paeth(a, b, c);
@@ -95,7 +50,7 @@ __device__ inline int png_filtered(int type, int x, int a, int b, int c) {
 
 __global__ __launch_bounds__(kLanes) void png_filter_kernel(const unsigned char* __restrict__ images, int h, int row_bytes, int c,
                                                             unsigned char* __restrict__ stream, size_t stream_stride) {
-    __shared__ unsigned long long red[4];
+    __shared__ unsigned long long red[kTextWaves];
     __shared__ int chosen;
     const int y = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const unsigned char* cur = images + ((size_t)b * h + y) * row_bytes;
@@ -110,7 +65,7 @@ __global__ __launch_bounds__(kLanes) void png_filter_kernel(const unsigned char*
     int type = 0;
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
-        const unsigned long long s = block_sum64(sum[t], red);
+        const unsigned long long s = block_sum<kTextWaves>(sum[t], red);
         if (t == 0 || s < best) best = s, type = t;  // a tie keeps the lower type
     }
     if (tid == 0) chosen = type;
@@ -155,8 +110,8 @@ __global__ __launch_bounds__(kLanes) void deflate_segment_kernel(const unsigned 
     __shared__ unsigned ll_hist[kDeflateLitCodes], d_hist[kDeflateDistCodes];
     __shared__ DeflateTables tab;
     __shared__ DeflateWork work;
-    __shared__ int scan1[kLanes], scan2[kLanes], red[4];
-    __shared__ unsigned long long red64[4];
+    __shared__ int scan1[kLanes], scan2[kLanes], red[kTextWaves];
+    __shared__ unsigned long long red64[kTextWaves];
 
     const int seg = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const long long base = (long long)seg * kSeg;
@@ -324,7 +279,7 @@ __global__ __launch_bounds__(kLanes) void deflate_segment_kernel(const unsigned 
             }
         }
         int token_bits;
-        int at = header_bits + block_exclusive_scan(bits, red, &token_bits);
+        int at = header_bits + block_exclusive_scan<kTextWaves>(bits, red, token_bits);
         for (int i = tid; i * 8 < header_bits; i += kLanes) atomicOr(&image[i >> 2], (unsigned)tab.header[i] << (8 * (i & 3)));
 #pragma unroll 1
         for (int k = 0; k < kPerLane; ++k) {
@@ -368,8 +323,8 @@ __global__ __launch_bounds__(kLanes) void deflate_segment_kernel(const unsigned 
             bsum += (unsigned)(n - i) * x;  // 32 terms below 8192 * 255
         }
     }
-    const unsigned adler_a = (unsigned)(block_sum64(a, red64) % kAdlerMod);
-    const unsigned adler_b = (unsigned)(block_sum64(bsum % kAdlerMod, red64) % kAdlerMod);
+    const unsigned adler_a = (unsigned)(block_sum<kTextWaves>((unsigned long long)a, red64) % kAdlerMod);
+    const unsigned adler_b = (unsigned)(block_sum<kTextWaves>((unsigned long long)(bsum % kAdlerMod), red64) % kAdlerMod);
     __syncthreads();
     const int piece = (payload_bytes + kLanes - 1) / kLanes;
     const int first = min(tid * piece, payload_bytes), last = min(first + piece, payload_bytes);
@@ -379,7 +334,7 @@ __global__ __launch_bounds__(kLanes) void deflate_segment_kernel(const unsigned 
         for (int i = first; i < last; ++i) crc = crc_bitwise(crc, image_bytes[i]);
         crc = gf_mul(gf_x_pow_bytes((unsigned)(payload_bytes - last)), ~crc);
     }
-    crc = block_xor(crc, red);
+    crc = (unsigned)block_xor<kTextWaves>((int)crc, red);
 
     uint4* dst = reinterpret_cast<uint4*>(payload + ((size_t)b * nseg + seg) * kSlot);
     for (int i = tid; i * 16 < payload_bytes; i += kLanes) dst[i] = shared_v[i];
@@ -399,7 +354,7 @@ __global__ __launch_bounds__(kLanes) void png_assemble_kernel(const unsigned cha
                                                               unsigned char* __restrict__ out, size_t out_stride,
                                                               long long* __restrict__ lengths, int* __restrict__ flags) {
     __shared__ uint4 stage[(kSlot + 12 + 15 + 15) / 16];
-    __shared__ unsigned long long red64[4];
+    __shared__ unsigned long long red64[kTextWaves];
     const int seg = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const SegRecord* rec = records + (size_t)b * nseg;
 
@@ -415,15 +370,15 @@ __global__ __launch_bounds__(kLanes) void png_assemble_kernel(const unsigned cha
             s2 += r.adler_b + (unsigned long long)r.adler_a * (unsigned long long)((n_total - end) % kAdlerMod);  // 256 lanes' terms below 2^33 each
         }
     }
-    before = block_sum64(before, red64);
-    total = block_sum64(total, red64);
-    why = block_sum64(why ? 1 : 0, red64);  // any segment's flag
+    before = block_sum<kTextWaves>(before, red64);
+    total = block_sum<kTextWaves>(total, red64);
+    why = block_sum<kTextWaves>(why ? 1ull : 0ull, red64);  // any segment's flag
     const int head = png ? 47 : 2, wrap = png ? 12 : 0;
     unsigned char* dst = out + (size_t)b * out_stride;
 
     if (seg == 0) {
-        s1 = block_sum64(s1 % kAdlerMod, red64);
-        s2 = block_sum64(s2 % kAdlerMod, red64);
+        s1 = block_sum<kTextWaves>(s1 % kAdlerMod, red64);
+        s2 = block_sum<kTextWaves>(s2 % kAdlerMod, red64);
         if (tid == 0) {
             const unsigned adler1 = (unsigned)((1 + s1) % kAdlerMod);
             const unsigned adler2 = (unsigned)(((unsigned long long)(n_total % kAdlerMod) + s2) % kAdlerMod);

@@ -1386,6 +1386,102 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
 #ifndef DAD3D_BLEND_COUNT  // diagnostics build: pass / item / list-entry counters into the dad3d_mesh_debug_trace buffer
 #define DAD3D_BLEND_COUNT 0
 #endif
+// What raster_blend_kernel and render_texture_kernel share: the decode of a work-queue entry, a lane's view of a triangle, the walk
+// over the item's tile list and the claim of the next item. Everything is inlined into the two kernels.
+struct QueueItem {  // a work-queue entry: part `part` of the 2^level x 2^level parts of a tile, as a rectangle of the image
+    int level, part, n_total, tile, edge, tx0, ty0, tw, th, tx1, ty1;  // tw, th <= 0: the part lies beyond the image edge
+    size_t b;
+};
+__device__ __forceinline__ QueueItem decode_queue_entry(uint2 qe, int ntiles, int tiles_x, int w, int h) {
+    QueueItem q;
+    q.level = (qe.x >> 24) & 3, q.part = qe.x >> 26, q.n_total = (int)qe.y;
+    q.b = (qe.x & 0xFFFFFFu) / ntiles;
+    q.tile = (qe.x & 0xFFFFFFu) % ntiles;
+    q.edge = kTile >> q.level;
+    q.tx0 = (q.tile % tiles_x) * kTile + (q.part & ((1 << q.level) - 1)) * q.edge;
+    q.ty0 = (q.tile / tiles_x) * kTile + (q.part >> q.level) * q.edge;
+    q.tw = min(q.edge, w - q.tx0), q.th = min(q.edge, h - q.ty0);
+    q.tx1 = q.tx0 + q.tw - 1, q.ty1 = q.ty0 + q.th - 1;
+    return q;
+}
+
+struct Corners {  // what a lane keeps of its triangle: the three corners, inv, the box clipped to the item
+    float x0, y0, z0, x1, y1, z1, x2, y2, z2, inv;
+    int bx0, bx1, by0, by1;
+};
+// false: the triangle's box misses the item
+__device__ __forceinline__ bool load_tri(const QueueItem& q, const float3u* rec_b, const int* tri, const float* vb, unsigned f, Corners& c) {
+    const float3u rc = rec_b[f];
+    const unsigned bbx = __float_as_uint(rc.y), bby = __float_as_uint(rc.z);
+    c.bx0 = max((int)(bbx & 0xffff), q.tx0), c.bx1 = min((int)(bbx >> 16), q.tx1);
+    c.by0 = max((int)(bby & 0xffff), q.ty0), c.by1 = min((int)(bby >> 16), q.ty1);
+    if (c.bx1 < c.bx0 || c.by1 < c.by0) return false;
+    const int i0 = tri[3 * (size_t)f], i1 = tri[3 * (size_t)f + 1], i2 = tri[3 * (size_t)f + 2];
+    c.x0 = vb[3 * i0], c.y0 = vb[3 * i0 + 1], c.z0 = vb[3 * i0 + 2];
+    c.x1 = vb[3 * i1], c.y1 = vb[3 * i1 + 1], c.z1 = vb[3 * i1 + 2];
+    c.x2 = vb[3 * i2], c.y2 = vb[3 * i2 + 1], c.z2 = vb[3 * i2 + 2];
+    c.inv = rc.x;
+    return true;
+}
+
+// The walk over the first n_list entries of an item's tile list; test_pixel(ts, z0, z1, z2, f, x, y) is the kernel's own test of
+// triangle f at a pixel of its box. A triangle's box inside the item holds 1 to 4096 pixels and 70 % of a head's pixel tests come
+// from boxes of more than 32; with one lane per triangle (round 4) a wave took as long as its largest box while most lanes idled.
+// So a wave reads 64 list entries at once; a lane walks its OWN triangle when the entry's area class says <= 32 pixels (class within
+// the tile, an upper bound for a part of it), and the triangles above that are taken one after the other by the whole wave, 64 box
+// pixels per step. Same per-pixel arithmetic, and the kernels' 64-bit LDS atomics make the outcome independent of who tested which
+// pixel -- identical bits (tests/test_gpu_raster_alpha.py, tests/perf/raster_soak.py).
+template <class TestPixel>
+__device__ __forceinline__ void walk_tile_list(const QueueItem& q, int n_list, const unsigned* glist, const float3u* rec_b, const int* tri,
+                                               const float* vb, const TestPixel& test_pixel) {
+    constexpr unsigned kBigClass = DAD3D_BLEND_BIG_CLASS;  // area class >= this: the whole wave takes the triangle
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int base = (tid >> 6) * 64; base < n_list; base += kRasterThreads) {
+        // all 64 triangles of the group are fetched side by side (three dependent round trips, once per group); a large
+        // triangle's data then reaches the other lanes through v_readlane, not through three more round trips each
+        const int i = base + lane;
+        const unsigned e = i < n_list ? glist[i] : ~0u;
+        const unsigned f_own = e & kIdMask;
+        Corners c{};
+        const bool ok = e != ~0u && load_tri(q, rec_b, tri, vb, f_own, c);
+        const bool big = ok && (e >> 28) >= kBigClass;
+        if (ok && !big) {
+            const TriSetup ts = setup_from_corners(c.x0, c.y0, c.x1, c.y1, c.x2, c.y2, c.inv);
+            for (int y = c.by0; y <= c.by1; ++y)
+                for (int x = c.bx0; x <= c.bx1; ++x) test_pixel(ts, c.z0, c.z1, c.z2, f_own, x, y);
+        }
+        unsigned long long todo = __ballot(big);
+        while (todo) {  // wave-uniform loop: one large triangle at a time, all 64 lanes on its box
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            auto bf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
+            auto bi = [&](int v) { return __builtin_amdgcn_readlane(v, j); };
+            const unsigned f = (unsigned)bi((int)f_own);
+            const TriSetup ts = setup_from_corners(bf(c.x0), bf(c.y0), bf(c.x1), bf(c.y1), bf(c.x2), bf(c.y2), bf(c.inv));
+            const float z0 = bf(c.z0), z1 = bf(c.z1), z2 = bf(c.z2);
+            const int x0 = bi(c.bx0), x1 = bi(c.bx1), y0 = bi(c.by0), y1 = bi(c.by1);
+            const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);
+            const float rcp_bw = __builtin_amdgcn_rcpf((float)bw);
+            for (int p = lane; p < area; p += 64) {
+                // exact p / bw for p < 4096, bw <= 64: (p + 0.5) / bw is at least 1 / 128 away from an integer, the product's error < 1e-3
+                const int py = (int)(((float)p + 0.5f) * rcp_bw), px = p - py * bw;
+                test_pixel(ts, z0, z1, z2, f, x0 + px, y0 + py);
+            }
+        }
+    }
+}
+
+// The workgroup's next item. The first barrier ends every use of the item's LDS, the second publishes s_next, the third keeps
+// thread 0's next claim behind everybody's read.
+__device__ __forceinline__ unsigned claim_next_item(unsigned* qhdr, unsigned& s_next) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_next = gridDim.x + atomicAdd(&qhdr[1], 1u);
+    __syncthreads();
+    const unsigned item = s_next;
+    __syncthreads();
+    return item;
+}
+
 // _rasterize with alpha != 1 (rasterize_kernel.cpp:268-284). The reference walks the triangles in index order and blends every
 // fragment that passes the running depth test into the pixel: (unsigned char)((1 - alpha) * old + alpha * 255 * colour), then
 // raises the pixel's depth. Per pixel that is a CHAIN: the fragments that are records (strictly deeper than everything before
@@ -1408,30 +1504,22 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
     const int nc = a.c;
     unsigned item = blockIdx.x;
     while (item < n_items) {
-        const uint2 qe = a.sc.queue[item];
-        const int level = (qe.x >> 24) & 3, part = qe.x >> 26, n_total = (int)qe.y;
-        const size_t b = (qe.x & 0xFFFFFFu) / ntiles;
-        const int tile = (qe.x & 0xFFFFFFu) % ntiles;
-        const int edge = kTile >> level;
-        const int tx0 = (tile % a.sc.tiles_x) * kTile + (part & ((1 << level) - 1)) * edge;
-        const int ty0 = (tile / a.sc.tiles_x) * kTile + (part >> level) * edge;
-        const int tw = min(edge, a.w - tx0), th = min(edge, a.h - ty0);
-        const int tx1 = tx0 + tw - 1, ty1 = ty0 + th - 1;
-        const float3u* rec_b = a.sc.rec + b * nt;
-        const float* vb = a.vertices + b * a.m.nver * 3;
-        const float* cb = a.colors + b * a.m.nver * nc;
-        const unsigned* glist = a.sc.lists + (b * ntiles + tile) * nt;
-        float* depth_b = a.depth ? a.depth + b * a.h * a.w : nullptr;
-        uint8_t* img_b = a.image + b * (size_t)a.h * a.w * nc;
+        const QueueItem q = decode_queue_entry(a.sc.queue[item], ntiles, a.sc.tiles_x, a.w, a.h);
+        const float3u* rec_b = a.sc.rec + q.b * nt;
+        const float* vb = a.vertices + q.b * a.m.nver * 3;
+        const float* cb = a.colors + q.b * a.m.nver * nc;
+        const unsigned* glist = a.sc.lists + (q.b * ntiles + q.tile) * nt;
+        float* depth_b = a.depth ? a.depth + q.b * a.h * a.w : nullptr;
+        uint8_t* img_b = a.image + q.b * (size_t)a.h * a.w * nc;
         auto image_row = [&](int gy) { return a.reverse ? (a.h - 1 - gy) : gy; };
-        if (DAD3D_BLEND_COUNT && a.trace && tid == 0) atomicAdd(a.trace + 1, 1ull), atomicAdd(a.trace + 2, (unsigned long long)n_total);  // items, list entries
-        if (tw > 0 && th > 0) {
-            for (int p = tid; p < edge * th; p += kRasterThreads) {
-                const int ly = p / edge, lx = p % edge;
-                if (lx >= tw) continue;
-                const float z0 = depth_b ? depth_b[(size_t)(ty0 + ly) * a.w + tx0 + lx] : -1e8f;  // Sim3DR.py:23
+        if (DAD3D_BLEND_COUNT && a.trace && tid == 0) atomicAdd(a.trace + 1, 1ull), atomicAdd(a.trace + 2, (unsigned long long)q.n_total);  // items, list entries
+        if (q.tw > 0 && q.th > 0) {
+            for (int p = tid; p < q.edge * q.th; p += kRasterThreads) {
+                const int ly = p / q.edge, lx = p % q.edge;
+                if (lx >= q.tw) continue;
+                const float z0 = depth_b ? depth_b[(size_t)(q.ty0 + ly) * a.w + q.tx0 + lx] : -1e8f;  // Sim3DR.py:23
                 state[ly * kTile + lx] = depth_order(z0);  // next admissible triangle: 0
-                const uint8_t* px = img_b + ((size_t)image_row(ty0 + ly) * a.w + tx0 + lx) * nc;
+                const uint8_t* px = img_b + ((size_t)image_row(q.ty0 + ly) * a.w + q.tx0 + lx) * nc;
                 unsigned wv = 0;
 #pragma unroll
                 for (int ch = 0; ch < 4; ++ch)  // 1..4 channels: a fixed bound and a guard, not a variable trip count (which the
@@ -1439,33 +1527,10 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
                 pixw[ly * kTile + lx] = wv;
             }
             for (;;) {
-                for (int p = tid; p < kTile * th; p += kRasterThreads) keys[p] = ~0ull;
+                for (int p = tid; p < kTile * q.th; p += kRasterThreads) keys[p] = ~0ull;
                 if (tid == 0) s_any = 0;
                 if (DAD3D_BLEND_COUNT && a.trace && tid == 0) atomicAdd(a.trace + 0, 1ull);  // diagnostics build: passes
                 __syncthreads();
-                // The walk of one pass. A triangle's box inside the item holds 1 to 4096 pixels and 70 % of a head's pixel tests come from
-                // boxes of more than 32; with one lane per triangle (round 4) a wave took as long as its largest box while most lanes idled.
-                // Now a wave reads 64 list entries at once; a lane walks its OWN triangle when the entry's area class says <= 32 pixels
-                // (class within the tile, an upper bound for a part of it), and the triangles above that are taken one after the other by
-                // the whole wave, 64 box pixels per step. Same per-pixel arithmetic, and ds_min_u64 makes the candidate independent of
-                // who tested which pixel -- identical bits (tests/test_gpu_raster_alpha.py, tests/perf/raster_soak.py).
-                struct Corners {  // what a lane keeps of its triangle: the three corners, inv, the box clipped to the item
-                    float x0, y0, z0, x1, y1, z1, x2, y2, z2, inv;
-                    int bx0, bx1, by0, by1;
-                };
-                auto load_tri = [&](unsigned f, Corners& c) {
-                    const float3u rc = rec_b[f];
-                    const unsigned bbx = __float_as_uint(rc.y), bby = __float_as_uint(rc.z);
-                    c.bx0 = max((int)(bbx & 0xffff), tx0), c.bx1 = min((int)(bbx >> 16), tx1);
-                    c.by0 = max((int)(bby & 0xffff), ty0), c.by1 = min((int)(bby >> 16), ty1);
-                    if (c.bx1 < c.bx0 || c.by1 < c.by0) return false;
-                    const int i0 = a.m.tri[3 * (size_t)f], i1 = a.m.tri[3 * (size_t)f + 1], i2 = a.m.tri[3 * (size_t)f + 2];
-                    c.x0 = vb[3 * i0], c.y0 = vb[3 * i0 + 1], c.z0 = vb[3 * i0 + 2];
-                    c.x1 = vb[3 * i1], c.y1 = vb[3 * i1 + 1], c.z1 = vb[3 * i1 + 2];
-                    c.x2 = vb[3 * i2], c.y2 = vb[3 * i2 + 1], c.z2 = vb[3 * i2 + 2];
-                    c.inv = rc.x;
-                    return true;
-                };
                 auto test_pixel = [&](const TriSetup& ts, float z0, float z1, float z2, unsigned f, int x, int y) {
                     float u, v;
                     tri_uv(ts, (float)x, (float)y, u, v);
@@ -1473,52 +1538,18 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
                     if (!(u > 0.0f && v > 0.0f && w0 > 0.0f)) return;
                     const float z = w0 * z0 + v * z1 + u * z2;
                     if (z != z) return;  // NaN never passes `>`
-                    const int slot = (y - ty0) * kTile + (x - tx0);
+                    const int slot = (y - q.ty0) * kTile + (x - q.tx0);
                     const unsigned long long st = state[slot];
                     const unsigned dk = depth_order_number(z);
                     if (dk > (unsigned)st && f >= (unsigned)(st >> 32))
                         (void)__hip_atomic_fetch_min(&keys[slot], ((unsigned long long)f << 32) | dk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 };
-                constexpr unsigned kBlendBigClass = DAD3D_BLEND_BIG_CLASS;  // area class >= this: the whole wave takes the triangle
-                const int lane = tid & 63;
-                for (int base = (tid >> 6) * 64; base < ((DAD3D_BLEND_ABLATE & 1) ? 0 : n_total); base += kRasterThreads) {
-                    // all 64 triangles of the group are fetched side by side (three dependent round trips, once per group); a large
-                    // triangle's data then reaches the other lanes through v_readlane, not through three more round trips each
-                    const int i = base + lane;
-                    const unsigned e = i < n_total ? glist[i] : ~0u;
-                    const unsigned f_own = e & kIdMask;
-                    Corners c{};
-                    const bool ok = e != ~0u && load_tri(f_own, c);
-                    const bool big = ok && (e >> 28) >= kBlendBigClass;
-                    if (ok && !big) {
-                        const TriSetup ts = setup_from_corners(c.x0, c.y0, c.x1, c.y1, c.x2, c.y2, c.inv);
-                        for (int y = c.by0; y <= c.by1; ++y)
-                            for (int x = c.bx0; x <= c.bx1; ++x) test_pixel(ts, c.z0, c.z1, c.z2, f_own, x, y);
-                    }
-                    unsigned long long todo = __ballot(big);
-                    while (todo) {  // wave-uniform loop: one large triangle at a time, all 64 lanes on its box
-                        const int j = __builtin_ctzll(todo);
-                        todo &= todo - 1;
-                        auto bf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
-                        auto bi = [&](int v) { return __builtin_amdgcn_readlane(v, j); };
-                        const unsigned f = (unsigned)bi((int)f_own);
-                        const TriSetup ts = setup_from_corners(bf(c.x0), bf(c.y0), bf(c.x1), bf(c.y1), bf(c.x2), bf(c.y2), bf(c.inv));
-                        const float z0 = bf(c.z0), z1 = bf(c.z1), z2 = bf(c.z2);
-                        const int x0 = bi(c.bx0), x1 = bi(c.bx1), y0 = bi(c.by0), y1 = bi(c.by1);
-                        const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);
-                        const float rcp_bw = __builtin_amdgcn_rcpf((float)bw);
-                        for (int p = lane; p < area; p += 64) {
-                            // exact p / bw for p < 4096, bw <= 64: (p + 0.5) / bw is at least 1 / 128 away from an integer, the product's error < 1e-3
-                            const int py = (int)(((float)p + 0.5f) * rcp_bw), px = p - py * bw;
-                            test_pixel(ts, z0, z1, z2, f, x0 + px, y0 + py);
-                        }
-                    }
-                }
+                walk_tile_list(q, (DAD3D_BLEND_ABLATE & 1) ? 0 : q.n_total, glist, rec_b, a.m.tri, vb, test_pixel);
                 __syncthreads();
                 bool any = false;
-                for (int p = tid; p < edge * th; p += kRasterThreads) {
-                    const int ly = p / edge, lx = p % edge;
-                    if (lx >= tw) continue;
+                for (int p = tid; p < q.edge * q.th; p += kRasterThreads) {
+                    const int ly = p / q.edge, lx = p % q.edge;
+                    if (lx >= q.tw) continue;
                     const int slot = ly * kTile + lx;
                     const unsigned long long k = keys[slot];
                     if (k == ~0ull) continue;
@@ -1529,7 +1560,7 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
                     const TriSetup ts = fake ? setup_from_corners(1.f, 2.f, 9.f, 3.f, 4.f, 8.f, 0.02f)
                                              : setup_from_corners(vb[3 * i0], vb[3 * i0 + 1], vb[3 * i1], vb[3 * i1 + 1], vb[3 * i2], vb[3 * i2 + 1], rec_b[f].x);
                     float u, v;
-                    tri_uv(ts, (float)(tx0 + lx), (float)(ty0 + ly), u, v);
+                    tri_uv(ts, (float)(q.tx0 + lx), (float)(q.ty0 + ly), u, v);
                     const float w0 = 1.0f - u - v;
                     unsigned wv = pixw[slot], out = 0;
 #pragma unroll
@@ -1546,28 +1577,24 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
                 if (!s_any || (DAD3D_BLEND_ABLATE & 4)) break;
                 __syncthreads();  // everybody has read s_any before the next pass clears it
             }
-            for (int p = tid; p < edge * th; p += kRasterThreads) {
-                const int ly = p / edge, lx = p % edge;
-                if (lx >= tw) continue;
+            for (int p = tid; p < q.edge * q.th; p += kRasterThreads) {
+                const int ly = p / q.edge, lx = p % q.edge;
+                if (lx >= q.tw) continue;
                 const int slot = ly * kTile + lx;
                 const unsigned long long st = state[slot];
                 if ((st >> 32) == 0) continue;  // no fragment passed: the pixel and its depth stay untouched
                 const unsigned wv = pixw[slot];
-                uint8_t* px = img_b + ((size_t)image_row(ty0 + ly) * a.w + tx0 + lx) * nc;
+                uint8_t* px = img_b + ((size_t)image_row(q.ty0 + ly) * a.w + q.tx0 + lx) * nc;
 #pragma unroll
                 for (int ch = 0; ch < 4; ++ch)
                     if (ch < nc) px[ch] = (uint8_t)((wv >> (8 * ch)) & 0xff);
                 if (depth_b) {  // inverse of the orderable mapping (a depth of -0 is stored as +0: equal as floats)
                     const unsigned dk = (unsigned)st;
-                    depth_b[(size_t)(ty0 + ly) * a.w + tx0 + lx] = __uint_as_float((dk & 0x80000000u) ? (dk & 0x7fffffffu) : ~dk);
+                    depth_b[(size_t)(q.ty0 + ly) * a.w + q.tx0 + lx] = __uint_as_float((dk & 0x80000000u) ? (dk & 0x7fffffffu) : ~dk);
                 }
             }
         }
-        __syncthreads();
-        if (tid == 0) s_next = gridDim.x + atomicAdd(&a.sc.qhdr[1], 1u);
-        __syncthreads();
-        item = s_next;
-        __syncthreads();
+        item = claim_next_item(a.sc.qhdr, s_next);
     }
 }
 
@@ -1591,8 +1618,8 @@ __global__ __launch_bounds__(kRasterThreads) void raster_blend_kernel(RasterArgs
 // Where the reference indexes the texture with whatever a NaN converts to, the indices here are clamped into the texture
 // after the conversion (NaN -> row / column 0): no read outside the texture, and a non-finite image of a batch touches
 // only its own pixels.
-// The walk is the one of raster_blend_kernel (a wave reads 64 list entries; a small box is walked by its own lane, a large
-// one by the whole wave); the texel gathers of the resolve (up to four texels x c) are served by L2.
+// The walk is walk_tile_list, shared with raster_blend_kernel (a wave reads 64 list entries; a small box is walked by its own
+// lane, a large one by the whole wave); the texel gathers of the resolve (up to four texels x c) are served by L2.
 struct TextureArgs {  // only what the kernel reads: every member is a scalar register for the whole launch
     const int* tri;          // [ntri][3]
     const float3u* rec;      // RasterScratch: records, tile lists, queue header, queue
@@ -1623,44 +1650,20 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
     const unsigned n_items = a.qhdr[0];
     unsigned item = blockIdx.x;
     while (item < n_items) {
-        const uint2 qe = a.queue[item];
-        const int level = (qe.x >> 24) & 3, part = qe.x >> 26, n_total = (int)qe.y;
-        const size_t b = (qe.x & 0xFFFFFFu) / ntiles;
-        const int tile = (qe.x & 0xFFFFFFu) % ntiles;
-        const int edge = kTile >> level, edge_shift = kTileShift - level;
-        const int tx0 = (tile % a.tiles_x) * kTile + (part & ((1 << level) - 1)) * edge;
-        const int ty0 = (tile / a.tiles_x) * kTile + (part >> level) * edge;
-        const int tw = min(edge, a.w - tx0), th = min(edge, a.h - ty0);
-        const int tx1 = tx0 + tw - 1, ty1 = ty0 + th - 1;
-        const float3u* rec_b = a.rec + b * nt;
-        const float* vb = a.vertices + b * a.nver * 3;
-        const unsigned* glist = a.lists + (b * ntiles + tile) * nt;
-        float* depth_b = a.depth ? a.depth + b * (size_t)a.h * a.w : nullptr;
-        if (tw > 0 && th > 0) {  // a part can lie beyond the image edge
-            for (int p = tid; p < edge * th; p += kRasterThreads) {
-                const int ly = p >> edge_shift, lx = p & (edge - 1);
-                if (lx >= tw) continue;
-                const float z0 = depth_b ? depth_b[(size_t)(ty0 + ly) * a.w + tx0 + lx] : -1e8f;
+        const QueueItem q = decode_queue_entry(a.queue[item], ntiles, a.tiles_x, a.w, a.h);
+        const int edge_shift = kTileShift - q.level;
+        const float3u* rec_b = a.rec + q.b * nt;
+        const float* vb = a.vertices + q.b * a.nver * 3;
+        const unsigned* glist = a.lists + (q.b * ntiles + q.tile) * nt;
+        float* depth_b = a.depth ? a.depth + q.b * (size_t)a.h * a.w : nullptr;
+        if (q.tw > 0 && q.th > 0) {  // a part can lie beyond the image edge
+            for (int p = tid; p < q.edge * q.th; p += kRasterThreads) {
+                const int ly = p >> edge_shift, lx = p & (q.edge - 1);
+                if (lx >= q.tw) continue;
+                const float z0 = depth_b ? depth_b[(size_t)(q.ty0 + ly) * a.w + q.tx0 + lx] : -1e8f;
                 keys[ly * kTile + lx] = ((unsigned long long)depth_order(z0) << 32) | kNoTri;
             }
             __syncthreads();
-            struct Corners {  // what a lane keeps of its triangle: the three corners, inv, the box clipped to the item
-                float x0, y0, z0, x1, y1, z1, x2, y2, z2, inv;
-                int bx0, bx1, by0, by1;
-            };
-            auto load_tri = [&](unsigned f, Corners& c) {
-                const float3u rc = rec_b[f];
-                const unsigned bbx = __float_as_uint(rc.y), bby = __float_as_uint(rc.z);
-                c.bx0 = max((int)(bbx & 0xffff), tx0), c.bx1 = min((int)(bbx >> 16), tx1);
-                c.by0 = max((int)(bby & 0xffff), ty0), c.by1 = min((int)(bby >> 16), ty1);
-                if (c.bx1 < c.bx0 || c.by1 < c.by0) return false;
-                const int i0 = a.tri[3 * (size_t)f], i1 = a.tri[3 * (size_t)f + 1], i2 = a.tri[3 * (size_t)f + 2];
-                c.x0 = vb[3 * i0], c.y0 = vb[3 * i0 + 1], c.z0 = vb[3 * i0 + 2];
-                c.x1 = vb[3 * i1], c.y1 = vb[3 * i1 + 1], c.z1 = vb[3 * i1 + 2];
-                c.x2 = vb[3 * i2], c.y2 = vb[3 * i2 + 1], c.z2 = vb[3 * i2 + 2];
-                c.inv = rc.x;
-                return true;
-            };
             auto test_pixel = [&](const TriSetup& ts, float z0, float z1, float z2, unsigned f, int x, int y) {
                 float u, v;
                 tri_uv(ts, (float)x, (float)y, u, v);
@@ -1670,41 +1673,9 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
                 const float z = w0 * z0 + v * z1 + u * z2;
                 if (z != z) return;  // NaN never passes `>`
                 const unsigned long long key = ((unsigned long long)depth_order_number(z) << 32) | (0xFFFFFFFEu - f);
-                (void)__hip_atomic_fetch_max(&keys[(y - ty0) * kTile + (x - tx0)], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_max(&keys[(y - q.ty0) * kTile + (x - q.tx0)], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             };
-            constexpr unsigned kBigClass = DAD3D_BLEND_BIG_CLASS;  // area class >= this: the whole wave takes the triangle
-            const int lane = tid & 63;
-            for (int base = (tid >> 6) * 64; base < n_total; base += kRasterThreads) {
-                const int i = base + lane;
-                const unsigned e = i < n_total ? glist[i] : ~0u;
-                const unsigned f_own = e & kIdMask;
-                Corners c{};
-                const bool ok = e != ~0u && load_tri(f_own, c);
-                const bool big = ok && (e >> 28) >= kBigClass;
-                if (ok && !big) {
-                    const TriSetup ts = setup_from_corners(c.x0, c.y0, c.x1, c.y1, c.x2, c.y2, c.inv);
-                    for (int y = c.by0; y <= c.by1; ++y)
-                        for (int x = c.bx0; x <= c.bx1; ++x) test_pixel(ts, c.z0, c.z1, c.z2, f_own, x, y);
-                }
-                unsigned long long todo = __ballot(big);
-                while (todo) {  // wave-uniform loop: one large triangle at a time, all 64 lanes on its box
-                    const int j = __builtin_ctzll(todo);
-                    todo &= todo - 1;
-                    auto bf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
-                    auto bi = [&](int v) { return __builtin_amdgcn_readlane(v, j); };
-                    const unsigned f = (unsigned)bi((int)f_own);
-                    const TriSetup ts = setup_from_corners(bf(c.x0), bf(c.y0), bf(c.x1), bf(c.y1), bf(c.x2), bf(c.y2), bf(c.inv));
-                    const float z0 = bf(c.z0), z1 = bf(c.z1), z2 = bf(c.z2);
-                    const int x0 = bi(c.bx0), x1 = bi(c.bx1), y0 = bi(c.by0), y1 = bi(c.by1);
-                    const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);
-                    const float rcp_bw = __builtin_amdgcn_rcpf((float)bw);
-                    for (int p = lane; p < area; p += 64) {
-                        // exact p / bw for p < 4096, bw <= 64 (see raster_blend_kernel)
-                        const int py = (int)(((float)p + 0.5f) * rcp_bw), px = p - py * bw;
-                        test_pixel(ts, z0, z1, z2, f, x0 + px, y0 + py);
-                    }
-                }
-            }
+            walk_tile_list(q, q.n_total, glist, rec_b, a.tri, vb, test_pixel);
             __syncthreads();
             // resolve: a lane owns a pixel, the lanes of a wave a run of one row
             // Its arguments are read again from the kernarg segment here (kernarg_reload) instead of living in scalar registers
@@ -1713,15 +1684,15 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
             const int n_chan = DAD3D_TEX_ARG(int, c), tex_h = DAD3D_TEX_ARG(int, tex_h), tex_w = DAD3D_TEX_ARG(int, tex_w);
             const int tex_c = DAD3D_TEX_ARG(int, tex_c), nearest = DAD3D_TEX_ARG(int, nearest);
             const float4* tex_tri = DAD3D_TEX_ARG(const float4*, tex_tri);
-            const TEX* tex = static_cast<const TEX*>(DAD3D_TEX_ARG(const void*, texture)) + b * DAD3D_TEX_ARG(size_t, tex_image_stride);
-            IMG* img_b = static_cast<IMG*>(DAD3D_TEX_ARG(void*, image)) + b * (size_t)a.h * a.w * n_chan;
+            const TEX* tex = static_cast<const TEX*>(DAD3D_TEX_ARG(const void*, texture)) + q.b * DAD3D_TEX_ARG(size_t, tex_image_stride);
+            IMG* img_b = static_cast<IMG*>(DAD3D_TEX_ARG(void*, image)) + q.b * (size_t)a.h * a.w * n_chan;
             float* depth_r = DAD3D_TEX_ARG(float*, depth);
-            if (depth_r) depth_r += b * (size_t)a.h * a.w;
+            if (depth_r) depth_r += q.b * (size_t)a.h * a.w;
 #undef DAD3D_TEX_ARG
             const float xmax = (float)(tex_w - 1), ymax = (float)(tex_h - 1);
-            for (int p = tid; p < edge * th; p += kRasterThreads) {
-                const int ly = p >> edge_shift, lx = p & (edge - 1);
-                if (lx >= tw) continue;
+            for (int p = tid; p < q.edge * q.th; p += kRasterThreads) {
+                const int ly = p >> edge_shift, lx = p & (q.edge - 1);
+                if (lx >= q.tw) continue;
                 const unsigned lo = kw[2 * (ly * kTile + lx)];
                 if (lo == kNoTri) continue;  // nothing beat the incoming depth: pixel and depth stay as they are
                 const unsigned f = 0xFFFFFFFEu - lo;
@@ -1729,9 +1700,9 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
                 const float4 ta = tex_tri[2 * (size_t)f], tb = tex_tri[2 * (size_t)f + 1];
                 const TriSetup ts = setup_from_corners(vb[3 * i0], vb[3 * i0 + 1], vb[3 * i1], vb[3 * i1 + 1], vb[3 * i2], vb[3 * i2 + 1], rec_b[f].x);
                 float u, v;
-                tri_uv(ts, (float)(tx0 + lx), (float)(ty0 + ly), u, v);
+                tri_uv(ts, (float)(q.tx0 + lx), (float)(q.ty0 + ly), u, v);
                 const float w0 = 1.0f - u - v;
-                const size_t pix = (size_t)(ty0 + ly) * a.w + tx0 + lx;
+                const size_t pix = (size_t)(q.ty0 + ly) * a.w + q.tx0 + lx;
                 if (depth_r) depth_r[pix] = w0 * vb[3 * i0 + 2] + v * vb[3 * i1 + 2] + u * vb[3 * i2 + 2];
                 float px = ta.x * w0 + ta.z * v + tb.x * u;
                 float py = ta.y * w0 + ta.w * v + tb.y * u;
@@ -1762,11 +1733,7 @@ __global__ __launch_bounds__(kRasterThreads, DAD3D_RASTER_WAVES_PER_SIMD) void r
                 }
             }
         }
-        __syncthreads();  // the keys are reused by the next item
-        if (tid == 0) s_next = gridDim.x + atomicAdd(&a.qhdr[1], 1u);
-        __syncthreads();
-        item = s_next;
-        __syncthreads();
+        item = claim_next_item(a.qhdr, s_next);  // the keys are reused by the next item
     }
 }
 

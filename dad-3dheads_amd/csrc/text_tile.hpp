@@ -1,29 +1,17 @@
-// What the two text formatters (obj_text.hip, json_text.hip) share: workgroups of 256 lanes that sum lengths and copy an LDS image
-// of their tile's bytes out in aligned 16-byte stores.
+// What the text kernels share: workgroups of 256 lanes (kTextTile, kTextWaves) whose sums and scans are the ones of collectives.hpp,
+// and, for obj_text.hip, json_text.hip and png_encode.hip, the copy of an LDS image of the tile's bytes out in aligned 16-byte
+// stores. json_parse.hip takes only the two constants and the collectives from here.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "collectives.hpp"
+
 namespace dad3d {
 namespace {
 
-constexpr int kTextTile = 256;  // lanes per workgroup
-
-__device__ inline int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// sum over the 256 lanes of the workgroup; red: 4 ints of LDS, reusable after the call
-__device__ inline int block_sum(int v, int* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return v;
-}
+constexpr int kTextTile = 256;              // lanes per workgroup
+constexpr int kTextWaves = kTextTile / 64;  // the `red` of a sum or a scan: this many words of LDS
 
 // image bytes [lead, end) of `stage` -> out[lead .. end), `out` 16-byte aligned: whole units as one 16-byte store, a unit shared
 // with the neighbouring tile byte by byte (only this tile's bytes)
