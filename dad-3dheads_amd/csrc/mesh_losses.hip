@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kLossThreads) void cube_stats_kernel(CubeLossArgs a
         }
     }
     CubeFrame fp, ft;
-    int c_star = 0, dummy = 0;
+    int dummy = 0;
     {
         float ext_p[3], ext_t[3];
 #pragma unroll
@@ -126,19 +126,28 @@ __global__ __launch_bounds__(kLossThreads) void cube_stats_kernel(CubeLossArgs a
         }
         fp.scale = ft.scale = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {  // max over the axes of max_n v2 = ext - 0.5 ext; the first axis wins a tie
-            const float sp = ext_p[c] - fp.half[c], s_t = ext_t[c] - ft.half[c];
-            if (sp > fp.scale) fp.scale = sp, c_star = c;
-            ft.scale = fmaxf(ft.scale, s_t);
+        for (int c = 0; c < 3; ++c) {  // max over the axes of max_n v2 = ext - 0.5 ext: the value only, its element is found below
+            fp.scale = fmaxf(fp.scale, ext_p[c] - fp.half[c]);
+            ft.scale = fmaxf(ft.scale, ext_t[c] - ft.half[c]);
         }
     }
     // ---- pass 2: loss sum and the sums behind the gradient of the normalisation ------------------------------------
     const float k = a.region_weight[r] / ((float)a.batch * (float)n * 3.0f);  // weight x mean over [B, N_r, 3]
+    // The scale is v2.max(-1).max(-2) in torch, and each max hands its gradient to the FIRST maximal value: the first position
+    // whose row maximum is the scale, then that vertex's first axis -- (position, axis) in lexicographic order, not the first axis
+    // of largest extent (two axes of equal extent have their maxima at different positions). v2 is recomputed here exactly as
+    // the scale was (x - lo - half), so the comparison is an equality of identical float operations.
     float loss = 0.0f, gsum[3] = {0.0f, 0.0f, 0.0f}, gdot = 0.0f;
+    int star = INT_MAX;  // 3 * position + axis of the scale's element; ascending p within a lane: the first one is kept
     for (int p = tid; p < n; p += kLossThreads) {
         const int v = a.region_idx[p0 + p];
         const float x[3] = {pb[3 * v], pb[3 * v + 1], pb[3 * v + 2]}, y[3] = {tb[3 * v], tb[3 * v + 1], tb[3 * v + 2]};
         float op[3], ot[3];
+        if (star == INT_MAX) {
+#pragma unroll
+            for (int c = 2; c >= 0; --c)  // descending: the first axis is written last
+                if ((x[c] - fp.lo[c]) - fp.half[c] == fp.scale) star = 3 * p + c;
+        }
         cube_apply(fp, x, op);
         cube_apply(ft, y, ot);
 #pragma unroll
@@ -149,12 +158,15 @@ __global__ __launch_bounds__(kLossThreads) void cube_stats_kernel(CubeLossArgs a
             gdot += g * op[c];
         }
     }
+    float no_value = 0.0f;  // all equal: block_arg then keeps the smallest `star`
+    block_arg(true, no_value, star, redv, redp, tid);
+    const int p_star = star / 3, c_star = star % 3;  // a NaN scale equals nothing: no element, and every gradient is NaN anyway
     loss = block_sum(loss, redv, tid);
     gdot = block_sum(gdot, redv, tid);
 #pragma unroll
     for (int c = 0; c < 3; ++c) gsum[c] = block_sum(gsum[c], redv, tid);
     if (tid == 0) {
-        // dL/dscale = -sum(g out) / scale goes to the element that is the overall maximum: (argmax of axis c*, c*).
+        // dL/dscale = -sum(g out) / scale goes to the element that is the overall maximum: (p*, c*) found above.
         // A_c = everything that reaches the column sum of dL/dv1: half of it leaves through max_n v1 (its arg position)
         // and half through min_n v (its arg position), both with a minus sign (v1 = v - min, v2 = v1 - 0.5 max v1).
         const float d_scale = -gdot / fp.scale;
@@ -166,6 +178,7 @@ __global__ __launch_bounds__(kLossThreads) void cube_stats_kernel(CubeLossArgs a
             st[21 + c] = gsum[c] / fp.scale + (c == c_star ? d_scale : 0.0f);
         }
         st[6] = fp.scale, st[7] = __int_as_float(c_star), st[20] = ft.scale, st[24] = d_scale, st[25] = k;
+        st[26] = __int_as_float(p_star);
         a.loss_terms[(size_t)r * a.batch + b] = loss * k;
     }
 }
@@ -184,7 +197,7 @@ __global__ __launch_bounds__(kLossThreads) void cube_grad_kernel(CubeLossArgs a)
 #pragma unroll
         for (int c = 0; c < 3; ++c) fp.lo[c] = st[c], fp.half[c] = st[3 + c], ft.lo[c] = st[14 + c], ft.half[c] = st[17 + c];
         fp.scale = st[6], ft.scale = st[20];
-        const int c_star = __float_as_int(st[7]);
+        const int c_star = __float_as_int(st[7]), p_star = __float_as_int(st[26]);
         float op[3], ot[3];
         cube_apply(fp, x, op);
         cube_apply(ft, y, ot);
@@ -192,7 +205,7 @@ __global__ __launch_bounds__(kLossThreads) void cube_grad_kernel(CubeLossArgs a)
         for (int c = 0; c < 3; ++c) {
             float g = crit_slope(a.criterion, op[c] - ot[c]) * st[25] / fp.scale;
             const int at_max = __float_as_int(st[11 + c]), at_min = __float_as_int(st[8 + c]);
-            if (pos == at_max && c == c_star) g += st[24];
+            if (pos == p_star && c == c_star) g += st[24];
             if (pos == at_max) g -= 0.5f * st[21 + c];
             if (pos == at_min) g -= 0.5f * st[21 + c];
             acc[c] += g;

@@ -293,6 +293,160 @@ def test_fused_loss_kernels_match_the_torch_statement(crit):
             assert float(fused.apply(pred, target, tables, _CRITERION_ID[crit])) == float(got)
 
 
+def _check_fused_losses(crit, weights, indices, pred, target, cube=True, point=True):
+    """Both fused losses on pred / target [B,n_verts,C] (CPU float32) against the float64 torch statement ON THE CPU (its max /
+    min return the first extremal index, as documented): 2e-6 of the value, 2e-5 of the largest gradient entry."""
+    from dad_3dheads_amd.losses import RegionTables, _CubeRegionLoss, _WeightedPointLoss, _CRITERION_ID
+
+    fn = {"l1": torch.nn.L1Loss, "l2": torch.nn.MSELoss, "smooth_l1": torch.nn.SmoothL1Loss}[crit]()
+    tables = RegionTables(weights, indices, pred.shape[1], torch.device("cuda", 0))
+    cases = []
+    if cube and pred.shape[2] == 3:
+        cases.append((_CubeRegionLoss, lambda p, t: torch.stack([fn(normalize_to_cube(p[:, i]), normalize_to_cube(t[:, i])) * w
+                                                                 for w, i in zip(weights, indices)]).sum()))
+    if point:
+        cases.append((_WeightedPointLoss, lambda p, t: torch.stack([fn(p[:, i], t[:, i]) * w for w, i in zip(weights, indices)]).sum()))
+    out = []
+    for fused, stated in cases:
+        p_ref = pred.double().requires_grad_(True)
+        want = stated(p_ref, target.double())
+        want.backward()
+        p = pred.cuda().requires_grad_(True)
+        got = fused.apply(p, target.cuda(), tables, _CRITERION_ID[crit])
+        got.backward()
+        grad, ref_grad = p.grad.cpu().double(), p_ref.grad
+        print(f"{fused.__name__} {crit}: value {float(got):.9g} / {float(want):.9g}, "
+              f"gradient error {float((grad - ref_grad).abs().max()) / float(ref_grad.abs().max()):.2e} of the largest entry")
+        assert abs(float(got) - float(want)) <= 2e-6 * max(1.0, abs(float(want)))
+        assert float((grad - ref_grad).abs().max()) <= 2e-5 * float(ref_grad.abs().max())
+        out.append((grad, ref_grad))
+    return out
+
+
+@pytest.mark.parametrize("crit", ["l1", "l2", "smooth_l1"])
+def test_cube_loss_routes_ties_like_torch(crit):
+    """Exact ties in `normalize_to_cube` (tests/backward_edges.py `tie_cases`: small integers, so float32 and float64 tie alike;
+    torch's routing on them is pinned in tests/test_backward_edges_host.py). The gradient of the scale goes to the first
+    POSITION whose row maximum is the global one, then to that vertex's first axis; image 1 has x and y swapped, so the tie
+    between two axes resolves the other way round there."""
+    import backward_edges as be
+
+    for name, n_verts, regions, pred in be.tie_cases():
+        tgt = be.tie_target(pred)
+        p = torch.from_numpy(np.stack([pred, pred[:, [1, 0, 2]]]))
+        t = torch.from_numpy(np.stack([tgt, tgt[:, [1, 0, 2]]]))
+        print(name)
+        _check_fused_losses(crit, [1.0, 0.5, 2.0][:len(regions)], regions, p, t, point=False)
+
+
+REGION_SIZES = (63, 64, 65, 255, 256, 257, 513)  # around one wave, one stride of the 256-thread loops, two strides
+
+
+@pytest.mark.parametrize("crit", ["l1", "l2", "smooth_l1"])
+def test_cube_loss_region_sizes_with_the_extremum_in_the_last_position(crit):
+    """Two regions per size: the LAST position holds the minimum of every axis in one and the maximum of every axis in the
+    other (the last lane of the last stride, the last wave of `block_arg`); random float data otherwise, regions in shuffled
+    vertex order, two images."""
+    rng = np.random.default_rng(23)
+    n_verts = 2 * sum(REGION_SIZES) + 5
+    scale = 3.0 if crit == "smooth_l1" else 1.0
+    pred = (scale * rng.standard_normal((2, n_verts, 3))).astype(np.float32)
+    target = (scale * rng.standard_normal((2, n_verts, 3))).astype(np.float32)
+    pool = rng.permutation(n_verts)
+    indices, at = [], 0
+    for n in REGION_SIZES:
+        for sign in (-1.0, 1.0):
+            idx = pool[at:at + n]
+            at += n
+            pred[:, idx[-1]] = sign * (np.abs(pred[:, idx]).max(axis=1) + 0.5)  # per image and axis: beyond every other entry
+            indices.append(idx)
+    weights = [0.5 + 0.25 * (k % 5) for k in range(len(indices))]
+    _check_fused_losses(crit, weights, indices, torch.from_numpy(pred), torch.from_numpy(target))
+
+
+@pytest.mark.parametrize("crit", ["l1", "l2", "smooth_l1"])
+def test_zero_extent_regions_are_not_finite(crit):
+    """n = 1 and one vertex listed n times: `normalize_to_cube` divides 0 by 0, the reference's value is NaN, and a finite
+    number from the kernels would be a different function. The other image rows / vertices of the gradient are not judged: the
+    reference's whole step is NaN."""
+    from dad_3dheads_amd.losses import RegionTables, _CubeRegionLoss, _CRITERION_ID
+
+    fn = {"l1": torch.nn.L1Loss, "l2": torch.nn.MSELoss, "smooth_l1": torch.nn.SmoothL1Loss}[crit]()
+    gen = torch.Generator().manual_seed(5)
+    pred, target = torch.randn((2, 40, 3), generator=gen), torch.randn((2, 40, 3), generator=gen)
+    for idx in (np.array([7]), np.array([11] * 5), np.array([3] * 257)):
+        want = fn(normalize_to_cube(pred.double()[:, idx]), normalize_to_cube(target.double()[:, idx]))
+        assert not bool(torch.isfinite(want))
+        tables = RegionTables([1.0], [idx], 40, torch.device("cuda", 0))
+        p = pred.cuda().requires_grad_(True)
+        got = _CubeRegionLoss.apply(p, target.cuda(), tables, _CRITERION_ID[crit])
+        got.backward()
+        assert not bool(torch.isfinite(got)), (idx.size, float(got))
+        assert not bool(torch.isfinite(p.grad[:, idx[0]]).any())
+        others = np.setdiff1d(np.arange(40), idx)
+        assert float(p.grad[:, others].abs().max()) == 0.0  # vertices of no region
+
+
+@pytest.mark.parametrize("n_verts", [255, 256, 257])
+@pytest.mark.parametrize("crit", ["l1", "l2", "smooth_l1"])
+def test_loss_kernels_at_vertex_counts_around_one_block(crit, n_verts):
+    """`cube_grad_kernel` and `point_loss_kernel` run one lane per vertex in blocks of 256: the last block full, one lane short
+    and one lane over, with 2 and 3 components; the last vertex is in a region and the first is in none."""
+    rng = np.random.default_rng(n_verts)
+    indices = [np.arange(1, n_verts), 1 + rng.permutation(n_verts - 1)[:100], np.array([n_verts - 1, 5, n_verts - 2, -1])]
+    scale = 3.0 if crit == "smooth_l1" else 1.0
+    for comps in (3, 2):
+        pred = torch.from_numpy((scale * rng.standard_normal((3, n_verts, comps))).astype(np.float32))
+        target = torch.from_numpy((scale * rng.standard_normal((3, n_verts, comps))).astype(np.float32))
+        for grad, _ in _check_fused_losses(crit, [1.0, 0.5, 2.0], indices, pred, target):
+            assert float(grad[:, 0].abs().max()) == 0.0
+
+
+def test_criteria_at_their_exact_points():
+    """sign(0) = 0: `pred == target` on a whole region gives an L1 / SmoothL1 gradient of exactly 0 there (and of the cube loss:
+    equal inputs normalise to equal values). SmoothL1 at differences of exactly +-1.0, where both branches have the same value
+    and slope: held to the float64 statement, next to 0, +-0.5, +-2 and the floats on either side of 1."""
+    from dad_3dheads_amd.losses import RegionTables, _CubeRegionLoss, _WeightedPointLoss, _CRITERION_ID
+
+    rng = np.random.default_rng(31)
+    n_verts = 300
+    same, other = np.arange(0, 130), np.arange(130, 300)
+    pred = rng.standard_normal((2, n_verts, 3)).astype(np.float32)
+    target = rng.standard_normal((2, n_verts, 3)).astype(np.float32)
+    target[:, same] = pred[:, same]
+    for crit in ("l1", "smooth_l1", "l2"):
+        tables = RegionTables([1.0, 0.5], [same, other], n_verts, torch.device("cuda", 0))
+        for fused in (_CubeRegionLoss, _WeightedPointLoss):
+            p = torch.from_numpy(pred).cuda().requires_grad_(True)
+            fused.apply(p, torch.from_numpy(target).cuda(), tables, _CRITERION_ID[crit]).backward()
+            assert float(p.grad[:, same].abs().max()) == 0.0, (crit, fused.__name__)
+            assert float(p.grad[:, other].abs().min()) > 0.0
+        _check_fused_losses(crit, [1.0, 0.5], [same, other], torch.from_numpy(pred), torch.from_numpy(target))
+    # differences that are exact in float32: target on a grid of 1/4 (0 under the two floats next to 1), pred = target + d
+    one = np.float32(1.0)
+    ds = np.array([0.0, 1.0, -1.0, 0.5, -0.5, 2.0, -2.0, np.nextafter(one, np.float32(0)), np.nextafter(one, np.float32(2)),
+                   -np.nextafter(one, np.float32(0)), -np.nextafter(one, np.float32(2))], dtype=np.float32)
+    for comps in (2, 3):
+        target = (rng.integers(-8, 9, (2, n_verts, comps)) * 0.25).astype(np.float32)
+        d = ds[rng.integers(0, len(ds), target.shape)]
+        d.reshape(-1)[:len(ds)] = ds  # every value at least once
+        target[d * 2.0 != np.round(d * 2.0)] = 0.0
+        pred = (target + d).astype(np.float32)
+        assert np.array_equal((pred - target).astype(np.float32), d) and (np.abs(d) == 1.0).sum() > 100
+        _check_fused_losses("smooth_l1", [1.0, 0.5], [same, other], torch.from_numpy(pred), torch.from_numpy(target), cube=False)
+    # the cube loss on half-integer grids: extents of 4 normalise to multiples of 1/2, so differences of exactly 0 and +-1 occur
+    pred = rng.integers(0, 5, (2, n_verts, 3)).astype(np.float32)
+    target = rng.integers(0, 5, (2, n_verts, 3)).astype(np.float32)
+    for t in (pred, target):
+        t[:, [0, 150], :] = 0.0
+        t[:, [1, 151], :] = 4.0
+    idx = [np.arange(0, 150), np.arange(150, 300)]
+    nd = (normalize_to_cube(torch.from_numpy(pred)[:, idx[0]]) - normalize_to_cube(torch.from_numpy(target)[:, idx[0]])).abs()
+    assert int((nd == 1.0).sum()) > 20 and int((nd == 0.0).sum()) > 20
+    for crit in ("l1", "smooth_l1"):
+        _check_fused_losses(crit, [1.0, 0.5], idx, torch.from_numpy(pred), torch.from_numpy(target), point=False)
+
+
 def test_fused_loss_argument_errors():
     lib = _lib.load()
     buf = torch.zeros((1, 8, 3), device="cuda")
