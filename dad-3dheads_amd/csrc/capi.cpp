@@ -1840,6 +1840,46 @@ dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* ver
     return launch_uv_bake(a, static_cast<hipStream_t>(stream));
 }
 
+static dad3d_status overlay_checked(const char* who, const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points,
+                                    int n_points, int n_prims) {
+    DAD3D_REQUIRE(batch >= 0 && batch <= 65535, "%s: batch %d outside 0 .. 65535", who, batch);
+    DAD3D_REQUIRE(h >= 1 && w >= 1 && h <= DAD3D_OVERLAY_MAX_COORD && w <= DAD3D_OVERLAY_MAX_COORD, "%s: an image of %d x %d (1 .. %d)", who, h,
+                  w, DAD3D_OVERLAY_MAX_COORD);
+    DAD3D_REQUIRE(n_points >= 0 && n_prims >= 0 && n_points <= 0x3fffffff && n_prims <= 0x3fffffff, "%s: %d points, %d primitives", who,
+                  n_points, n_prims);
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(src && dst, "%s: null image", who);
+    DAD3D_REQUIRE(n_prims == 0 || n_points == 0 || points, "%s: null point table", who);
+    return DAD3D_OK;
+}
+
+dad3d_status dad3d_overlay_segments(const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points, int n_points,
+                                    const int32_t* edges, int n_edges, const uint8_t* colors, uint32_t color, int thickness, int device,
+                                    void* stream) {
+    DAD3D_REQUIRE(thickness >= 0 && thickness <= 255, "dad3d_overlay_segments: thickness %d outside 0 (anti-aliased) .. 255", thickness);
+    const dad3d_status st = overlay_checked("dad3d_overlay_segments", src, dst, batch, h, w, points, n_points, n_edges);
+    if (st != DAD3D_OK || batch == 0) return st;
+    DAD3D_REQUIRE(n_edges == 0 || edges, "dad3d_overlay_segments: null edge list");
+    DAD3D_REQUIRE(n_edges == 0 || (reinterpret_cast<uintptr_t>(edges) & 3) == 0, "dad3d_overlay_segments: misaligned edge list");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    OverlaySegmentsArgs a{src, dst, points, edges, colors, color & 0xffffffu, batch, h, w, n_points, n_edges, thickness};
+    return launch_overlay_segments(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_overlay_discs(const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points, int n_points,
+                                 const int32_t* index, int n_discs, int radius, uint32_t color, int device, void* stream) {
+    DAD3D_REQUIRE(radius >= 1 && radius <= DAD3D_OVERLAY_MAX_COORD, "dad3d_overlay_discs: radius %d outside 1 .. %d", radius,
+                  DAD3D_OVERLAY_MAX_COORD);
+    const dad3d_status st = overlay_checked("dad3d_overlay_discs", src, dst, batch, h, w, points, n_points, n_discs);
+    if (st != DAD3D_OK || batch == 0) return st;
+    DAD3D_REQUIRE(index || n_discs <= n_points, "dad3d_overlay_discs: %d discs from %d points without an index list", n_discs, n_points);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    OverlayDiscsArgs a{src, dst, points, index, color & 0xffffffu, batch, h, w, n_points, n_discs, radius};
+    return launch_overlay_discs(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_mesh_debug_trace(dad3d_mesh* m, unsigned long long* device_buffer) {
     DAD3D_REQUIRE(m, "null handle");
     m->d_trace = device_buffer;

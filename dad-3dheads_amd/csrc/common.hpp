@@ -391,6 +391,28 @@ int uv_bake_grid_y(int batch, int chunk);
 dad3d_status launch_uv_vertex_normals(const UvNormalArgs& a, hipStream_t s);
 dad3d_status launch_uv_bake(const UvBakeArgs& a, hipStream_t s);
 
+// the demo's overlays (overlay.hip): segments and discs over a per-image point table, drawn per pixel
+struct OverlaySegmentsArgs {
+    const uint8_t* src;     // [B,h,w,3]
+    uint8_t* dst;           // [B,h,w,3], every byte written; may be src
+    const float* points;    // [B,n_points,2] (x, y)
+    const int* edges;       // [n_edges,2] into the point table, shared by the batch
+    const uint8_t* colors;  // [n_edges,3] or null: `color` for every segment
+    unsigned color;         // channel c in bits 8c .. 8c + 7
+    int batch, h, w, n_points, n_edges;
+    int thickness;          // 0: anti-aliased, one pixel wide; 1 .. 255: solid
+};
+struct OverlayDiscsArgs {
+    const uint8_t* src;
+    uint8_t* dst;
+    const float* points;  // [B,n_points,2]
+    const int* index;     // [n_discs] into the point table, or null: the first n_discs points
+    unsigned color;
+    int batch, h, w, n_points, n_discs, radius;
+};
+dad3d_status launch_overlay_segments(const OverlaySegmentsArgs& a, hipStream_t s);
+dad3d_status launch_overlay_discs(const OverlayDiscsArgs& a, hipStream_t s);
+
 // the rest of the reference's training objective (train_objective.hip): heatmap target, heatmap IoU, visibility landmark
 // loss, keypoint metrics
 struct HeatmapEncodeArgs {

@@ -621,6 +621,38 @@ DAD3D_EXPORT dad3d_status dad3d_deflate_tables_host(const uint32_t* ll_hist, con
                                                     int32_t* header_bits, uint32_t* dynamic_bits, uint32_t* fixed_bits);
 
 /* ---------------------------------------------------------------------------------------------
+ * The demo's overlays drawn on the device: the dots of `draw_points` (demo_utils.py:22-29, cv2.circle filled), the mesh edges of
+ * `draw_mesh` (demo_utils.py:60-62, cv2.line LINE_AA) and the arrows of `draw_pose` (demo_utils.py:90-92, cv2.arrowedLine) as
+ * discs and segments over a point table. All DEVICE pointers:
+ *   src, dst  [batch,h,w,3] uint8, contiguous, h and w at most DAD3D_OVERLAY_MAX_COORD; every byte of dst is written; src == dst
+ *             draws in place (any other overlap is undefined)
+ *   points    [batch,n_points,2] float32 (x, y); a coordinate is truncated toward zero (`astype(int)`)
+ *   edges     [n_edges,2] int32 into the point table, one list for the whole batch; index [n_discs] int32 or NULL (the first
+ *             n_discs points)
+ *   colors    [n_edges,3] uint8 or NULL (`color` for every segment); color = channel 0 | channel 1 << 8 | channel 2 << 16
+ *   thickness 0: anti-aliased, one pixel wide; 1 .. 255: solid          radius 1 .. DAD3D_OVERLAY_MAX_COORD
+ * The strokes are this library's own rules in exact integer arithmetic, not cv2's bits:
+ *   disc      pixel (x, y) takes the colour iff (x - cx)^2 + (y - cy)^2 <= r^2
+ *   solid     pixel q takes the colour iff its centre lies within t / 2 of the segment: with d = p1 - p0, u = q - p0,
+ *             (d.d > 0 and 0 <= u.d <= d.d and 4 (u x d)^2 <= t^2 d.d) or 4 |q - p0|^2 <= t^2 or 4 |q - p1|^2 <= t^2
+ *   AA        for i = 0 .. n = |d_major| the pixel at major coordinate m0 + i sign(d_major) and minor coordinate q >> 8 is blended
+ *             with a = 256 - (q & 255), its neighbour at (q >> 8) + 1 with a = q & 255, where
+ *             q = 256 minor0 + floor((512 i d_minor + n) / (2 n)) (n = 0: q = 256 minor0); dst = (dst (256 - a) + colour a + 128) >> 8
+ * The primitives of a call apply to a pixel in ascending index: the result is that of drawing them one after another. A
+ * primitive with a non-finite coordinate, one outside [-DAD3D_OVERLAY_MAX_COORD, DAD3D_OVERLAY_MAX_COORD] after truncation, or an
+ * index outside [0, n_points) is skipped whole; pixels outside the image are not written. One launch on `stream`, no allocation,
+ * no scratch, no synchronisation: can be captured into a graph. Arguments (NULL, sizes, thickness, radius, batch above 65535) are
+ * validated before any device work -> DAD3D_E_INVALID.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_OVERLAY_MAX_COORD 8192
+DAD3D_EXPORT dad3d_status dad3d_overlay_segments(const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points, int n_points,
+                                                 const int32_t* edges, int n_edges, const uint8_t* colors /* or NULL */, uint32_t color,
+                                                 int thickness, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_overlay_discs(const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points, int n_points,
+                                              const int32_t* index /* or NULL */, int n_discs, int radius, uint32_t color, int device,
+                                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PNG files and zlib streams read back on the device, bit-equal to `PIL.Image.open` and `zlib.decompress` (RFC 1950, 1951, the PNG
  * specification): 8-bit grey, grey + alpha, RGB and RGBA files without interlace, of any sizes in one call.
  *   files   DEVICE: the bytes of every file, file b at files[desc[b][0] .. + desc[b][1])
