@@ -62,6 +62,20 @@ class Mesh:
         return torch.cuda.current_stream(self.torch_device).cuda_stream
 
     # -- normals -----------------------------------------------------------------------------------
+    def normal_plan(self, batch: int = 1, entry: str = "get_normal", h: int = 0, w: int = 0) -> dict:
+        """Which kernel a launch would take, from the launchers' own decision functions; nothing is launched.
+        entry "get_normal" | "phong_light" (normals=None) | "render" (on h x w images; the batch plays no part).
+        -> {"form": "table" | "lds" | "global" | "refused", "chunks": workgroups per image computing normals,
+            "built": the table chunkings `dad3d_mesh_create` built, a subset of (1, 2, 4, 8)}"""
+        entries = {"get_normal": _lib.PLAN_GET_NORMAL, "phong_light": _lib.PLAN_PHONG, "render": _lib.PLAN_RENDER}
+        if entry not in entries:
+            raise ValueError(f"entry: one of {sorted(entries)}, got {entry!r}")
+        form, chunks, built = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._lib.dad3d_mesh_normal_plan(self._handle, entries[entry], int(batch), int(h), int(w), C.byref(form),
+                                                    C.byref(chunks), C.byref(built)))
+        names = {_lib.FORM_REFUSED: "refused", _lib.FORM_TABLE: "table", _lib.FORM_LDS: "lds", _lib.FORM_GLOBAL: "global"}
+        return {"form": names[form.value], "chunks": chunks.value, "built": tuple(1 << k for k in range(4) if built.value >> k & 1)}
+
     def get_normal(self, vertices: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
         """`_get_normal` per image: vertices [B,nver,3] -> unit vertex normals [B,nver,3]."""
         v = self._verts(vertices)

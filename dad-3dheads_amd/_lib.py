@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("DAD3D_LIB_PATH") or os.path.join(_HERE, "libdad3d_hip
 OK, E_INVALID, E_HIP, E_UNSUPPORTED, E_NOMEM = range(5)
 ZERO_ROTATION, TO_2D, MUTATE_PARAMS, FLIP_Z, COMPAT_CROSS_B3 = 0x1, 0x2, 0x4, 0x8, 0x10
 NORMAL_ACCUMULATE = 0x1
+PLAN_GET_NORMAL, PLAN_PHONG, PLAN_RENDER = 0, 1, 2
+FORM_REFUSED, FORM_TABLE, FORM_LDS, FORM_GLOBAL = 0, 1, 2, 3
 TEX_INDEX_CORNER, TEX_INDEX_REFERENCE = 0, 1
 DTYPE_F32, DTYPE_U8 = 0, 1
 EVAL_SELF_EXCLUDE, EVAL_MAX_K, EVAL_MAX_HEAD, EVAL_MAX_ANCHORS = 0x1, 8, 4096, 8
@@ -112,6 +114,7 @@ SIGNATURES = {
     "dad3d_mesh_phong_light": (_I, [_P, _P, _P, _P, _I, C.POINTER(LightC), _P]),
     "dad3d_mesh_normal_phong_light": (_I, [_P, _P, _P, _P, _I, C.POINTER(LightC), _P]),
     "dad3d_mesh_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(LightC), _I, _P]),
+    "dad3d_mesh_normal_plan": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "dad3d_mesh_debug_trace": (_I, [_P, _P]),
     "dad3d_mesh_set_texcoords": (_I, [_P, _P, _I, _I, _P]),
     "dad3d_mesh_render_texture": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

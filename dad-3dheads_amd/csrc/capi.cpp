@@ -1886,6 +1886,24 @@ dad3d_status dad3d_mesh_debug_trace(dad3d_mesh* m, unsigned long long* device_bu
     return DAD3D_OK;
 }
 
+dad3d_status dad3d_mesh_normal_plan(dad3d_mesh* m, int entry, int batch, int h, int w, int* form, int* chunks, int* built_mask) {
+    DAD3D_REQUIRE(m && form && chunks && built_mask, "dad3d_mesh_normal_plan: null argument");
+    DAD3D_REQUIRE(entry == DAD3D_PLAN_GET_NORMAL || entry == DAD3D_PLAN_PHONG || entry == DAD3D_PLAN_RENDER,
+                  "dad3d_mesh_normal_plan: unknown entry %d", entry);
+    DAD3D_REQUIRE(entry == DAD3D_PLAN_RENDER ? (h >= 1 && w >= 1) : batch >= 1, "dad3d_mesh_normal_plan: batch or image size below 1");
+    DAD3D_REQUIRE(m->nver > 0 && (entry != DAD3D_PLAN_RENDER || m->ntri > 0), "dad3d_mesh_normal_plan: an empty mesh launches nothing");
+    DeviceGuard guard(m->device);
+    const NormalPlan p = entry == DAD3D_PLAN_GET_NORMAL ? plan_get_normal(m->dev(), m->nc, batch)
+                         : entry == DAD3D_PLAN_PHONG    ? plan_phong(m->dev(), m->nc, false, batch)
+                                                        : plan_render_light(m->dev(), m->nc, h, w);
+    *form = p.form;
+    *chunks = p.form == DAD3D_FORM_REFUSED ? 0 : p.chunks;
+    *built_mask = 0;
+    for (int k = 0; k < kNormalChunkings; ++k)
+        if (m->nc[k].chunks) *built_mask |= 1 << k;
+    return DAD3D_OK;
+}
+
 dad3d_status dad3d_mesh_phong_light(dad3d_mesh* m, float* light, const float* vertices, const float* normals,
                                     int batch, const dad3d_light* cfg, void* stream) {
     DAD3D_REQUIRE(m && cfg && batch >= 0, "dad3d_mesh_phong_light: bad argument");

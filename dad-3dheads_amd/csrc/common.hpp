@@ -293,6 +293,16 @@ dad3d_status launch_get_normal(const MeshDev& m, const NormalChunksDev* nc, floa
                                int batch, unsigned flags, hipStream_t s);
 // bytes of LDS the face-normal-table kernels need for a chunking with `max_faces` faces in its largest chunk
 size_t normal_table_lds_bytes(int nver, int max_faces);
+// Which kernel form a launch takes and over how many vertex chunks per image: decided here once, for the launchers
+// and for dad3d_mesh_normal_plan alike. form = DAD3D_FORM_*; nc = the table chunking (table form only); lds = dynamic bytes.
+struct NormalPlan {
+    int form, chunks, vpb;
+    const NormalChunksDev* nc;
+    size_t lds;
+};
+NormalPlan plan_get_normal(const MeshDev& m, const NormalChunksDev* nc, int batch);
+NormalPlan plan_phong(const MeshDev& m, const NormalChunksDev* nc, bool normals_given, int batch);  // refused: lds = what it would need
+NormalPlan plan_render_light(const MeshDev& m, const NormalChunksDev* nc, int h, int w);            // the light inside the geometry kernel
 // scratch: raster_scratch_bytes(..) bytes of device memory (per-image triangle boxes, setup planes, per-tile
 // triangle lists), zeroed once with raster_scratch_init before its first use
 size_t raster_scratch_bytes(const MeshDev& m, int batch, int h, int w);

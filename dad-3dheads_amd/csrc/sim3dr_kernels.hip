@@ -370,6 +370,11 @@ __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.0f), 
 // barrier-ed), red = 6 x 16 floats of LDS scratch, row = the prefetched incidence row of vertex v0 (FUSE_NORMALS).
 // NORMALS: 0 = read them from `normals`, 1 = gather the incident faces from their corners (row), 2 = sum the entries of the
 // face-normal table `fn` the caller has filled (srow; the barrier behind the bounds reduction orders the table)
+// Where numpy's formula has no value the light is still finite and in [0, 1]: clip01 is fminf(fmaxf(x, 0), 1), and both return
+// the other operand for a NaN, so a NaN cosine (gmax == 0 on a collapsed mesh, a vertex on light_pos: 0/0) or a NaN specular sum
+// (a negative base under a fractional exponent) makes its term contribute 0 and the other terms stand; an infinite one clips
+// to 1. np.clip keeps the NaN, so the reference's own output is NaN there and there is nothing to equal. All three NORMALS
+// modes and both callers run this one function: the same bits (tests/test_gpu_normals_light_paths.py).
 template <int NORMALS>
 __device__ __forceinline__ void phong_light_chunk(const MeshDev& m, const NormalChunksDev& nc, const float* lv, const float4* fn,
                                                   float (*red)[kStageThreads / 64], size_t b, int v0, int v_end, AdjRow row,
@@ -1790,12 +1795,40 @@ static const NormalChunksDev* pick_normal_chunks(const NormalChunksDev* nc, int 
     return nullptr;
 }
 
+// the staged kernels without a table: the image's vertices in LDS, `chunks` blocks of vpb vertices per image
+static NormalPlan staged_plan(const MeshDev& m, int batch) {
+    const int vpb = staged_verts_per_block(m.nver, batch);
+    return NormalPlan{DAD3D_FORM_LDS, (m.nver + vpb - 1) / vpb, vpb, nullptr, ((size_t)m.nver * 3 + 8) * sizeof(float)};
+}
+static NormalPlan table_plan(const MeshDev& m, const NormalChunksDev* nc) {
+    return NormalPlan{DAD3D_FORM_TABLE, nc->chunks, nc->vpb, nc, normal_table_lds_bytes(m.nver, nc->max_faces)};
+}
+
+NormalPlan plan_get_normal(const MeshDev& m, const NormalChunksDev* nc_all, int batch) {
+    const NormalChunksDev* nc = (DAD3D_NORMALS_OLD) ? nullptr : pick_normal_chunks(nc_all, m.nver, batch);
+    if (nc) return table_plan(m, nc);
+    NormalPlan p = staged_plan(m, batch);
+    if (p.lds <= kMaxDynamicLds) return p;
+    return NormalPlan{DAD3D_FORM_GLOBAL, (m.nver + 255) / 256, 256, nullptr, 0};  // a mesh too large for the LDS: gather from global memory
+}
+
+NormalPlan plan_phong(const MeshDev& m, const NormalChunksDev* nc_all, bool normals_given, int batch) {
+    NormalPlan p = staged_plan(m, batch);
+    if (p.lds > kMaxDynamicLds - 1024) {
+        p.form = DAD3D_FORM_REFUSED;
+        return p;
+    }
+    const NormalChunksDev* nc = (normals_given || DAD3D_NORMALS_OLD) ? nullptr : pick_normal_chunks(nc_all, m.nver, batch);
+    return nc ? table_plan(m, nc) : p;
+}
+
 dad3d_status launch_get_normal(const MeshDev& m, const NormalChunksDev* nc_all, float* ver_normal, const float* vertices,
                                int batch, unsigned flags, hipStream_t s) {
     if (m.nver == 0 || batch == 0) return DAD3D_OK;
-    const size_t lds = ((size_t)m.nver * 3 + 8) * sizeof(float);
-    const NormalChunksDev* nc = pick_normal_chunks(nc_all, m.nver, batch);
-    if (nc && !(DAD3D_NORMALS_OLD)) {
+    const NormalPlan plan = plan_get_normal(m, nc_all, batch);
+    const NormalChunksDev* nc = plan.nc;
+    const size_t lds = plan.lds;
+    if (plan.form == DAD3D_FORM_TABLE) {
         static PerDeviceOnce attr_done;
         const int dev = PerDeviceOnce::current();
         if (!attr_done.done(dev)) {
@@ -1803,9 +1836,9 @@ dad3d_status launch_get_normal(const MeshDev& m, const NormalChunksDev* nc_all, 
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds - 1024));
             attr_done.set(dev);
         }
-        hipLaunchKernelGGL(ver_normal_table_kernel, dim3(nc->chunks, batch), dim3(kStageThreads),
-                           normal_table_lds_bytes(m.nver, nc->max_faces), s, m, *nc, ver_normal, vertices, flags);
-    } else if (lds <= kMaxDynamicLds) {
+        hipLaunchKernelGGL(ver_normal_table_kernel, dim3(plan.chunks, batch), dim3(kStageThreads), lds, s, m, *nc, ver_normal,
+                           vertices, flags);
+    } else if (plan.form == DAD3D_FORM_LDS) {
         static PerDeviceOnce attr_done;
         const int dev = PerDeviceOnce::current();
         if (!attr_done.done(dev)) {
@@ -1813,12 +1846,10 @@ dad3d_status launch_get_normal(const MeshDev& m, const NormalChunksDev* nc_all, 
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds));
             attr_done.set(dev);
         }
-        const int vpb = staged_verts_per_block(m.nver, batch);
-        hipLaunchKernelGGL(ver_normal_lds_kernel, dim3((m.nver + vpb - 1) / vpb, batch), dim3(kStageThreads), lds, s, m,
-                           ver_normal, vertices, flags, vpb);
-    } else {  // a mesh too large for the LDS: gather from global memory
-        hipLaunchKernelGGL(ver_normal_kernel<false>, dim3((m.nver + 255) / 256, batch), dim3(256), 0, s, m, ver_normal,
-                           vertices, flags);
+        hipLaunchKernelGGL(ver_normal_lds_kernel, dim3(plan.chunks, batch), dim3(kStageThreads), lds, s, m, ver_normal, vertices,
+                           flags, plan.vpb);
+    } else {
+        hipLaunchKernelGGL(ver_normal_kernel<false>, dim3(plan.chunks, batch), dim3(plan.vpb), 0, s, m, ver_normal, vertices, flags);
     }
     DAD3D_HIP_TRY(hipGetLastError());
     return DAD3D_OK;
@@ -1852,6 +1883,27 @@ dad3d_status raster_scratch_init(const MeshDev& m, void* scratch, int batch, int
     return DAD3D_OK;
 }
 
+constexpr int kGeoMaxLds = 160 * 1024 - 1024;  // dynamic part: the geometry kernel also has some static words
+static size_t geo_count_bytes(int ntiles) {  // counters, later the queue histogram
+    return std::max<size_t>(2 * (size_t)ntiles, kQueueBuckets) * sizeof(unsigned);
+}
+
+// The light of `render`: chunks = the blocks of an image that light vertices; lds = what the launch asks for.
+NormalPlan plan_render_light(const MeshDev& m, const NormalChunksDev* nc_all, int h, int w) {
+    const int ntiles = tiles_of(w) * tiles_of(h), blocks = (m.ntri + kGeoTrisPerBlock - 1) / kGeoTrisPerBlock;
+    const size_t vlds = ((size_t)m.nver * 3 + 12) * sizeof(float) + geo_count_bytes(ntiles);
+    if (vlds > (size_t)kGeoMaxLds) return NormalPlan{DAD3D_FORM_REFUSED, 0, 0, nullptr, vlds};
+    // lighting through the face-normal table: the finest chunking that has a block for every chunk, if its table fits
+    if (nc_all && !(DAD3D_NORMALS_OLD))
+        for (int k = kNormalChunkings - 1; k >= 0; --k) {
+            const size_t tlds = (((size_t)m.nver * 3 + 12 + 3) & ~(size_t)3) * sizeof(float) + ((2 * (size_t)ntiles + 3) & ~(size_t)3) * sizeof(unsigned) +
+                                16 * (size_t)nc_all[k].max_faces + 64;
+            if (nc_all[k].chunks && nc_all[k].chunks <= blocks && tlds <= (size_t)kGeoMaxLds)
+                return NormalPlan{DAD3D_FORM_TABLE, nc_all[k].chunks, nc_all[k].vpb, &nc_all[k], std::max(vlds, tlds)};
+        }
+    return NormalPlan{DAD3D_FORM_LDS, blocks, blocks ? (m.nver + blocks - 1) / blocks : 0, nullptr, vlds};
+}
+
 dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, void* scratch, unsigned long long* trace, uint8_t* image,
                               const float* vertices, const float* colors, float* depth, int32_t* tri_buf, float* bary,
                               int batch, int h, int w, int c, int render_flags, int mode, const dad3d_light* light_cfg,
@@ -1868,7 +1920,7 @@ dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, v
     static int persistent_blocks[2] = {0, 0};           // the same for every device of the node (one GPU model)
     static PerDeviceOnce raster_attr_done;              // the LDS limit is raised per device
     const int cur_dev = PerDeviceOnce::current();
-    constexpr int kMaxLds = 160 * 1024 - 1024;  // dynamic part: the geometry kernel also has some static words
+    constexpr int kMaxLds = kGeoMaxLds;
     if (!raster_attr_done.done(cur_dev)) {
         DAD3D_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&tri_geometry_kernel<true, 0>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
@@ -1894,20 +1946,13 @@ dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, v
     const int ntiles = sc.tiles_x * sc.tiles_y;
     {
         const dim3 ggrid((m.ntri + kGeoTrisPerBlock - 1) / kGeoTrisPerBlock, batch);
-        const size_t cnt_bytes = std::max<size_t>(2 * (size_t)ntiles, kQueueBuckets) * sizeof(unsigned);  // counters, later the queue histogram
+        const size_t cnt_bytes = geo_count_bytes(ntiles);
         const size_t vlds = ((size_t)m.nver * 3 + 12) * sizeof(float) + cnt_bytes;
         LightJob job{};
-        // lighting through the face-normal table: the finest chunking that has a block for every chunk, if its table fits
-        const NormalChunksDev* lnc = nullptr;
-        size_t tlds = 0;
-        if (light_cfg && nc_all && !(DAD3D_NORMALS_OLD))
-            for (int k = kNormalChunkings - 1; k >= 0 && !lnc; --k) {
-                tlds = (((size_t)m.nver * 3 + 12 + 3) & ~(size_t)3) * sizeof(float) + ((2 * (size_t)ntiles + 3) & ~(size_t)3) * sizeof(unsigned) +
-                       16 * (size_t)nc_all[k].max_faces + 64;
-                if (nc_all[k].chunks && nc_all[k].chunks <= (int)ggrid.x && tlds <= (size_t)kMaxLds) lnc = &nc_all[k];
-            }
         if (light_cfg) {  // colours = per-vertex Phong light computed by the geometry kernel itself
-            DAD3D_REQUIRE(vlds <= (size_t)kMaxLds && c == 3 && mode == 0, "render: needs a 3-channel image and a mesh that fits the LDS");
+            const NormalPlan plan = plan_render_light(m, nc_all, h, w);
+            const NormalChunksDev* lnc = plan.nc;
+            DAD3D_REQUIRE(plan.form != DAD3D_FORM_REFUSED && c == 3 && mode == 0, "render: needs a 3-channel image and a mesh that fits the LDS");
             job.light = const_cast<float*>(colors);
             job.cfg = *light_cfg;
             if (render_flags & DAD3D_RENDER_CLEAR) {
@@ -1921,7 +1966,7 @@ dad3d_status launch_rasterize(const MeshDev& m, const NormalChunksDev* nc_all, v
             }
             if (lnc) {
                 job.nc = *lnc;
-                hipLaunchKernelGGL((tri_geometry_kernel<true, 2>), ggrid, dim3(kGeoThreads), std::max(vlds, tlds), s, m, vertices, sc, h, w, job);
+                hipLaunchKernelGGL((tri_geometry_kernel<true, 2>), ggrid, dim3(kGeoThreads), plan.lds, s, m, vertices, sc, h, w, job);
             } else {
                 hipLaunchKernelGGL((tri_geometry_kernel<true, 1>), ggrid, dim3(kGeoThreads), vlds, s, m, vertices, sc, h, w, job);
             }
@@ -1983,8 +2028,8 @@ dad3d_status launch_render_texture(const MeshDev& m, void* scratch, void* image,
 dad3d_status launch_phong(const MeshDev& m, const NormalChunksDev* nc_all, float* light, const float* vertices, const float* normals,
                           float* normals_out, int batch, const dad3d_light& cfg, hipStream_t s) {
     if (batch == 0 || m.nver == 0) return DAD3D_OK;
-    const size_t lds = ((size_t)m.nver * 3 + 8) * sizeof(float);
-    DAD3D_REQUIRE(lds <= kMaxDynamicLds - 1024, "phong_light: %d vertices exceed the LDS staging capacity", m.nver);
+    const NormalPlan plan = plan_phong(m, nc_all, normals != nullptr, batch);
+    DAD3D_REQUIRE(plan.form != DAD3D_FORM_REFUSED, "phong_light: %d vertices exceed the LDS staging capacity", m.nver);
     static PerDeviceOnce attr_done;
     const int dev = PerDeviceOnce::current();
     if (!attr_done.done(dev)) {
@@ -1996,18 +2041,16 @@ dad3d_status launch_phong(const MeshDev& m, const NormalChunksDev* nc_all, float
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds - 1024));
         attr_done.set(dev);
     }
-    const int vpb = staged_verts_per_block(m.nver, batch);
-    const dim3 grid((m.nver + vpb - 1) / vpb, batch);
-    const NormalChunksDev* nc = (normals || DAD3D_NORMALS_OLD) ? nullptr : pick_normal_chunks(nc_all, m.nver, batch);
+    const dim3 grid(plan.chunks, batch);
     if (normals)
-        hipLaunchKernelGGL(phong_kernel<0>, grid, dim3(kStageThreads), lds, s, m, NormalChunksDev{}, light, vertices, normals,
-                           nullptr, m.nver, cfg, vpb);
-    else if (nc)
-        hipLaunchKernelGGL(phong_kernel<2>, dim3(nc->chunks, batch), dim3(kStageThreads), normal_table_lds_bytes(m.nver, nc->max_faces),
-                           s, m, *nc, light, vertices, nullptr, normals_out, m.nver, cfg, nc->vpb);
+        hipLaunchKernelGGL(phong_kernel<0>, grid, dim3(kStageThreads), plan.lds, s, m, NormalChunksDev{}, light, vertices, normals,
+                           nullptr, m.nver, cfg, plan.vpb);
+    else if (plan.form == DAD3D_FORM_TABLE)
+        hipLaunchKernelGGL(phong_kernel<2>, grid, dim3(kStageThreads), plan.lds, s, m, *plan.nc, light, vertices, nullptr, normals_out,
+                           m.nver, cfg, plan.vpb);
     else
-        hipLaunchKernelGGL(phong_kernel<1>, grid, dim3(kStageThreads), lds, s, m, NormalChunksDev{}, light, vertices, nullptr,
-                           normals_out, m.nver, cfg, vpb);
+        hipLaunchKernelGGL(phong_kernel<1>, grid, dim3(kStageThreads), plan.lds, s, m, NormalChunksDev{}, light, vertices, nullptr,
+                           normals_out, m.nver, cfg, plan.vpb);
     DAD3D_HIP_TRY(hipGetLastError());
     return DAD3D_OK;
 }

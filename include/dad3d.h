@@ -294,6 +294,23 @@ DAD3D_EXPORT dad3d_status dad3d_mesh_phong_light(dad3d_mesh* m, float* light, co
  * terms): light [B,nver,3] from the vertices alone; `ver_normal` [B,nver,3] receives the normals, or NULL. */
 DAD3D_EXPORT dad3d_status dad3d_mesh_normal_phong_light(dad3d_mesh* m, float* light, float* ver_normal, const float* vertices,
                                            int batch, const dad3d_light* cfg, void* stream);
+/* Read-only: which kernel form a launch on this mesh would take, computed by the functions the launchers themselves call;
+ * nothing is launched. `entry`: DAD3D_PLAN_GET_NORMAL (dad3d_mesh_get_normal at `batch`), DAD3D_PLAN_PHONG
+ * (dad3d_mesh_normal_phong_light at `batch`) or DAD3D_PLAN_RENDER (the light inside dad3d_mesh_render's geometry kernel on
+ * h x w images, a shape the raster accepts; it does not depend on the batch). h and w are read for DAD3D_PLAN_RENDER only.
+ *   *form        DAD3D_FORM_TABLE (face-normal table in LDS), DAD3D_FORM_LDS (vertices staged in LDS, faces gathered per
+ *                vertex), DAD3D_FORM_GLOBAL (gathered from global memory) or DAD3D_FORM_REFUSED (the call returns DAD3D_E_INVALID)
+ *   *chunks      workgroups per image that compute normals (vertex chunks); 0 when refused
+ *   *built_mask  bit k set: dad3d_mesh_create built the table of 1 << k chunks (k = 0..3) */
+#define DAD3D_PLAN_GET_NORMAL 0
+#define DAD3D_PLAN_PHONG 1
+#define DAD3D_PLAN_RENDER 2
+#define DAD3D_FORM_REFUSED 0
+#define DAD3D_FORM_TABLE 1
+#define DAD3D_FORM_LDS 2
+#define DAD3D_FORM_GLOBAL 3
+DAD3D_EXPORT dad3d_status dad3d_mesh_normal_plan(dad3d_mesh* m, int entry, int batch, int h, int w, int* form, int* chunks,
+                                    int* built_mask);
 /* Diagnostics: DEVICE buffer of [B * tiles][8 waves][16] uint64 that every wave of the raster kernel fills with
  * 100 MHz wall-clock stamps at its phase boundaries (slots 0-6: start, list sorted, fragments done, after barrier,
  * shaded, after barrier, end; 7: triangles in the tile list; 8-11 / 12-15: wave steps, ticks waiting for records,

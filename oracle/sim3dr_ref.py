@@ -144,18 +144,19 @@ class Sim3DROracle:
         return depth, tri_buf, bary
 
 
-def render_pipeline_ref(oracle: Sim3DROracle, vertices, triangles, bg, light_pos=(0, 0, 5), view_pos=(0, 0, 5),
-                        ambient=0.3, directional=0.6, specular=0.1, specular_exp=5):
-    """Sim3DR/lighting.py:37-71 (`RenderPipeline.__call__`, texture=None) in numpy on top of the oracle.
-    Returns (image, per-vertex light) so the shading stage can be checked separately."""
+def phong_light_ref(normal, vertices, light_pos=(0, 0, 5), view_pos=(0, 0, 5), ambient=0.3, directional=0.6, specular=0.1,
+                    specular_exp=5, color_ambient=(1, 1, 1), color_directional=(1, 1, 1)):
+    """Sim3DR/lighting.py:40-62 in numpy float32, statement for statement: the per-vertex light [nver,3] from the
+    vertices [nver,3] float32 and their normals (`get_normal`'s). Warnings (0/0, negative base under a fractional
+    exponent) are the caller's to silence."""
     _norm = lambda a: a / np.sqrt(np.sum(a**2, axis=1))[:, None]  # noqa: E731  lighting.py:6
-    normal = oracle.get_normal(vertices, triangles)
     light = np.zeros_like(vertices, dtype=np.float32)
-    col = np.array((1, 1, 1), dtype=np.float32)[None, :]
+    col_a = np.array(color_ambient, dtype=np.float32)[None, :]
+    col_d = np.array(color_directional, dtype=np.float32)[None, :]
     lp = np.array(light_pos, dtype=np.float32)[None, :]
     vp = np.array(view_pos, dtype=np.float32)[None, :]
     if ambient > 0:
-        light += ambient * col
+        light += ambient * col_a
     vn = vertices.copy()  # norm_vertices, lighting.py:9-14
     vn -= vn.min(0)[None, :]
     vn /= vn.max()
@@ -164,12 +165,22 @@ def render_pipeline_ref(oracle: Sim3DROracle, vertices, triangles, bg, light_pos
     if directional > 0:
         direction = _norm(lp - vn)
         cos = np.sum(normal * direction, axis=1)[:, None]
-        light += directional * (col * np.clip(cos, 0, 1))
+        light += directional * (col_d * np.clip(cos, 0, 1))
         if specular > 0:
             v2v = _norm(vp - vn)
             reflection = 2 * cos * normal - direction
             spe = np.sum((v2v * reflection) ** specular_exp, axis=1)[:, None]
             spe = np.where(cos != 0, np.clip(spe, 0, 1), np.zeros_like(spe))
-            light += specular * col * np.clip(spe, 0, 1)
-    light = np.clip(light, 0, 1)
+            light += specular * col_d * np.clip(spe, 0, 1)
+    return np.clip(light, 0, 1)
+
+
+def render_pipeline_ref(oracle: Sim3DROracle, vertices, triangles, bg, light_pos=(0, 0, 5), view_pos=(0, 0, 5),
+                        ambient=0.3, directional=0.6, specular=0.1, specular_exp=5, color_ambient=(1, 1, 1),
+                        color_directional=(1, 1, 1)):
+    """Sim3DR/lighting.py:37-71 (`RenderPipeline.__call__`, texture=None) in numpy on top of the oracle.
+    Returns (image, per-vertex light) so the shading stage can be checked separately."""
+    normal = oracle.get_normal(vertices, triangles)
+    light = phong_light_ref(normal, vertices, light_pos, view_pos, ambient, directional, specular, specular_exp, color_ambient,
+                            color_directional)
     return oracle.rasterize(vertices, triangles, light, bg=bg), light
