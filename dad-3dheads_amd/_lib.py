@@ -25,6 +25,9 @@ JSON_MAX_NUMBER_BYTES, JSON_MAX_LITERAL_BYTES, JSON_FLAG_NONFINITE = 23, 64, 0x1
 JSON_PARSE_TILE_BYTES, JSON_PARSE_RECORD_INTS = 4096, 6
 (JSON_PARSE_FLAG_GRAMMAR, JSON_PARSE_FLAG_DIGITS, JSON_PARSE_FLAG_BIG_INT, JSON_PARSE_FLAG_SUBNORMAL, JSON_PARSE_FLAG_OVERFLOW,
  JSON_PARSE_FLAG_AMBIGUOUS) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+(ANNOTATION_FLAG_GRAMMAR, ANNOTATION_FLAG_KEYS, ANNOTATION_FLAG_SHAPE, ANNOTATION_FLAG_NUMBER, ANNOTATION_FLAG_STRING,
+ ANNOTATION_FLAG_RANGE) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+ANNOTATION_MAX_BACKSLASH_RUN, ANNOTATION_MAX_WORD_BYTES, ANNOTATION_MAX_KEY_BYTES, ANNOTATION_MAX_KEYS = 64, 32, 64, 128
 PNG_SEGMENT_BYTES, ZLIB_SECOND_DISTANCE, PNG_FLAG_INTERNAL, DEFLATE_HEADER_BYTES = 8192, 4, 0x1, 640
 PNG_DECODE_DESC_INTS, ZLIB_DECODE_DESC_INTS, PNG_DECODE_INFO_SEGMENTED = 12, 4, 0x1
 PNG_DECODE_FLAG_MALFORMED, PNG_DECODE_FLAG_UNSUPPORTED, PNG_DECODE_FLAG_OVERFLOW = 0x1, 0x2, 0x4
@@ -149,6 +152,7 @@ SIGNATURES = {
     "dad3d_json_parse_check_arrays": (_I, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _I, _P]),
     "dad3d_json_parse_extract": (_I, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _I, _P]),
     "dad3d_json_parse_number_host": (_I, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "dad3d_annotation_parse": (_I, [_P, C.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
     "dad3d_png_max_bytes": (C.c_size_t, [_I, _I, _I]),
     "dad3d_png_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "dad3d_png_encode": (_I, [_P, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),

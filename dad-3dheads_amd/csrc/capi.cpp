@@ -1513,6 +1513,23 @@ dad3d_status dad3d_json_parse_number_host(const uint8_t* text, const int64_t* st
     return DAD3D_OK;
 }
 
+dad3d_status dad3d_annotation_parse(const uint8_t* text, int64_t n_bytes, const int64_t* doc_offsets, const int64_t* doc_sizes, int batch, int n_verts,
+                                    float* vertices, float* model_view, float* projection, int32_t* status, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 0 && batch <= 65535, "dad3d_annotation_parse: batch %d outside 0 .. 65535", batch);
+    DAD3D_REQUIRE(n_verts >= 1 && n_verts <= (1 << 24), "dad3d_annotation_parse: n_verts %d outside 1 .. 2^24", n_verts);
+    DAD3D_REQUIRE(n_bytes >= 0 && n_bytes <= 0x7fffffffLL * 65535, "dad3d_annotation_parse: n_bytes %lld is negative or too large", (long long)n_bytes);
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(text && doc_offsets && doc_sizes && vertices && model_view && projection && status, "dad3d_annotation_parse: null argument");
+    DAD3D_REQUIRE(aligned_to(text, 16) && aligned_to(doc_offsets, 8) && aligned_to(doc_sizes, 8) && aligned_to(vertices, 4) &&
+                      aligned_to(model_view, 4) && aligned_to(projection, 4) && aligned_to(status, 4),
+                  "dad3d_annotation_parse: text must be 16-byte aligned, the tables 8-byte, the outputs 4-byte aligned");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    AnnotationParseArgs a{text, n_bytes, reinterpret_cast<const long long*>(doc_offsets), reinterpret_cast<const long long*>(doc_sizes), batch, n_verts,
+                          vertices, model_view, projection, status};
+    return launch_annotation_parse(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_preprocess_images(const int64_t* descs, int batch, int out_size, const float* mean, const float* std,
                                      float* out, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && out_size > 0, "dad3d_preprocess_images: bad argument");

@@ -611,6 +611,17 @@ dad3d_status launch_json_parse_extract(const JsonParseExtractArgs& a, hipStream_
 void json_parse_number_host(const unsigned char* text, const long long* starts, const long long* ends, size_t n, unsigned long long* bits,
                             unsigned char* is_int, unsigned* flags);
 
+// DAD-3DHeads annotation files read on the device (annotation_parse.hip): one workgroup per document, one launch per batch
+struct AnnotationParseArgs {
+    const unsigned char* text;
+    long long n_bytes;
+    const long long *doc_offsets, *doc_sizes;
+    int batch, n_verts;
+    float *vertices, *model_view, *projection;
+    int32_t* status;
+};
+dad3d_status launch_annotation_parse(const AnnotationParseArgs& a, hipStream_t s);
+
 // predictor preprocessing (preprocess.hip): descs = [B][8] int64 on the device: {src pointer, h, w, new_h, new_w, pad_top,
 // pad_left, row stride in bytes}
 dad3d_status launch_preprocess(const long long* descs, int batch, int out_size, const float mean[3], const float std[3],

@@ -21,39 +21,10 @@ namespace dad3d {
 namespace {
 
 constexpr int kLanes = kTextTile;
-constexpr int kLaneBytes = 16;
+constexpr int kLaneBytes = kTextLaneBytes;
 static_assert(kLanes * kLaneBytes == DAD3D_JSON_PARSE_TILE_BYTES, "a tile is one 16-byte chunk per lane");
 
 enum : unsigned { kWs = 0, kNonNum = 1, kOpen = 2, kClose = 3, kComma = 4, kNum = 5, kNumStart = 6 };
-
-__device__ inline bool is_ws(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
-
-__device__ inline unsigned byte_of(const uint4& v, int k) {  // selects, no indexing into memory: k may be a loop variable
-    const unsigned w = (k >> 2) == 0 ? v.x : (k >> 2) == 1 ? v.y : (k >> 2) == 2 ? v.z : v.w;
-    return (w >> (8 * (k & 3))) & 0xffu;
-}
-
-__device__ inline void put_byte(uint4& v, int k, unsigned b) {
-    const unsigned s = b << (8 * (k & 3));
-    if ((k >> 2) == 0) v.x |= s;
-    else if ((k >> 2) == 1) v.y |= s;
-    else if ((k >> 2) == 2) v.z |= s;
-    else v.w |= s;
-}
-
-// this lane's 16 bytes of `src` (16-byte aligned) from `base`; the bytes at and behind n read as 0
-__device__ inline uint4 load_chunk(const unsigned char* __restrict__ src, long long base, long long n, int& valid) {
-    valid = (int)min((long long)kLaneBytes, max(n - base, 0ll));
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (valid == kLaneBytes) {
-        v = *reinterpret_cast<const uint4*>(src + base);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kLaneBytes; ++k)
-            if (k < valid) put_byte(v, k, src[base + k]);
-    }
-    return v;
-}
 
 __device__ inline void store_chunk(unsigned char* __restrict__ dst, long long base, int valid, const uint4& v) {
     if (valid == kLaneBytes) {

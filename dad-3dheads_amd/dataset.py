@@ -14,6 +14,11 @@ The loader is split at the host / device boundary:
   `dad3d_preprocess_images` (resize, pad, normalise, CHW), `dad3d_gt_keypoints` (model-view, projection, 68 landmarks or
   the index subset, crop shift, presence, albumentations' keypoint geometry) and `dad3d_heatmap_encode`.
 
+`FlameDataset(..., item_form="files")` moves the decoding to the device as well: `__getitem__` only reads the bytes
+of the PNG and of the annotation file, `FileBatchCollate` packs them, and `FlameBatchBuilder` decodes the PNGs (png_reader), parses
+the annotations (`dad3d_annotation_parse`) and crops by address, then runs the same three kernels. That form waits for the device once
+per batch, to read the PNG flags and the annotation status together; the default "raw" form stays free of host syncs.
+
 Images are read with PIL by default (cv2 is not a dependency); pass `reader=` to use another decoder. DAD-3DHeads images
 are PNG, a lossless format, so the decoder does not change the pixels; for JPEG inputs, decoders may differ and parity with
 the reference's cv2.imread is unpinned.
@@ -30,7 +35,7 @@ import torch
 from .landmarks import load_2d_indices
 from .resize_geometry import longest_max_size
 
-__all__ = ["FlameDataset", "RawBatchCollate", "FlameBatchBuilder", "extend_bbox", "ensure_bbox_boundaries", "read_as_rgb",
+__all__ = ["FlameDataset", "RawBatchCollate", "FileBatchCollate", "FlameBatchBuilder", "extend_bbox", "ensure_bbox_boundaries", "read_as_rgb",
            "NORMALIZE", "RESIZE_MODES"]
 
 # model_training/data/config.py keys
@@ -47,6 +52,12 @@ RESIZE_MODES = {"longest_max_size": 0, "resize": 1}  # DAD3D_RESIZE_LONGEST_MAX_
 # keys of a raw item / raw batch
 IMAGE, BBOX, IMAGE_SHAPE, VERTICES, MODEL_VIEW, PROJECTION = "image", "bbox", "image_shape", "vertices", "model_view", "projection"
 CROPS, CROP_DESCS, FRAMES = "crops", "crop_descs", "frames"
+# keys of a file item / file batch
+PNG, DECODED, ANNOTATION = "png", "decoded", "annotation"
+PNG_FILES, PNG_TABLE, DECODED_IMAGES, DECODED_TABLE, ANNOTATIONS, ANNOTATION_TABLE = ("png_files", "png_table", "decoded_images",
+                                                                                      "decoded_table", "annotations", "annotation_table")
+ITEM_FORMS = ("raw", "files")
+_ALIGN = 16  # png_reader._align's and dad3d_annotation_parse's
 
 
 def read_as_rgb(path: str) -> np.ndarray:
@@ -104,10 +115,17 @@ class FlameDataset(torch.utils.data.Dataset):
     """model_training/data/flame_dataset.py:46-205 with a CPU-only `__getitem__` that returns the RAW item (see the module
     docstring); `FlameBatchBuilder` makes the reference's targets from a collated batch of them, on the device.
     `data`: the annotation list (img_path, bbox, annotation_path per item); `config`: the `train` / `val` block of
-    config/dataset/dad_3d_heads.yaml (dataset_root, img_size, num_classes, keypoints, transform, stride)."""
+    config/dataset/dad_3d_heads.yaml (dataset_root, img_size, num_classes, keypoints, transform, stride).
+    `item_form="files"`: `__getitem__` decodes nothing. The item carries the bytes of the PNG and of the annotation file (uint8
+    arrays), the bbox from the same draw and the image shape from the file's IHDR; `get_collate_fn()` gives the matching
+    `FileBatchCollate`, and the builder decodes both on the device. A file the worker cannot size (not a PNG, a palette, 16 bits)
+    is decoded here with `reader` and travels as a full decoded image; the crop is still taken on the device."""
 
     def __init__(self, data: List[Dict[str, Any]], config: Mapping[str, Any],
-                 reader: Optional[Callable[[str], np.ndarray]] = None) -> None:
+                 reader: Optional[Callable[[str], np.ndarray]] = None, item_form: str = "raw") -> None:
+        if item_form not in ITEM_FORMS:
+            raise ValueError(f"item_form must be one of {ITEM_FORMS}, not {item_form!r}")
+        self.item_form = item_form
         self.data = data
         self.config = config
         self.img_size = config["img_size"]
@@ -121,15 +139,51 @@ class FlameDataset(torch.utils.data.Dataset):
         return len(self.data)
 
     @classmethod
-    def from_config(cls, config: Mapping[str, Any], reader: Optional[Callable[[str], np.ndarray]] = None) -> "FlameDataset":
+    def from_config(cls, config: Mapping[str, Any], reader: Optional[Callable[[str], np.ndarray]] = None,
+                    item_form: str = "raw") -> "FlameDataset":
         with open(config["ann_path"]) as f:
             anno = json.load(f)
-        return cls(data=anno, config=config, reader=reader)
+        return cls(data=anno, config=config, reader=reader, item_form=item_form)
 
-    def get_collate_fn(self) -> "RawBatchCollate":
+    def get_collate_fn(self) -> Union["RawBatchCollate", "FileBatchCollate"]:
+        if self.item_form == "files":
+            return FileBatchCollate(self.img_size, self.resize_mode)
         return RawBatchCollate(self.img_size, self.resize_mode)
 
+    def _read_checked(self, idx: int, path: str) -> np.ndarray:
+        img = self.reader(path)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"item {idx} ({self.data[idx]['img_path']}): expected a uint8 RGB image [H,W,3], got {img.dtype} {img.shape}")
+        return img
+
+    def _file_item(self, idx: int) -> Dict[str, Any]:
+        from .png_reader import _header
+
+        anno = self.data[idx]
+        root = self.config.get("dataset_root", "")
+        path = os.path.join(root, anno["img_path"])
+        with open(path, "rb") as f:
+            png = f.read()
+        head = _header(png)
+        decoded = None
+        if head is None:  # the worker cannot size it: decoded here, cropped on the device
+            decoded = np.ascontiguousarray(self._read_checked(idx, path))
+            png, shape = b"", decoded.shape
+        else:
+            shape = (head[0], head[1], 3)
+        offset = tuple(0.1 * np.random.uniform(size=4) + 0.05)  # the same single draw as the raw form
+        x, y, w, h = ensure_bbox_boundaries(extend_bbox(np.array(anno["bbox"]), offset), shape[:2])
+        if w == 0 or h == 0:
+            raise ValueError(f"item {idx} ({anno['img_path']}): the bbox {anno['bbox']} crops an empty image ({w} x {h})")
+        with open(os.path.join(root, anno["annotation_path"]), "rb") as f:
+            text = f.read()
+        return {PNG: np.frombuffer(png, dtype=np.uint8), DECODED: decoded, ANNOTATION: np.frombuffer(text, dtype=np.uint8),
+                BBOX: np.array([x, y, w, h], dtype=np.int32), IMAGE_SHAPE: np.array(shape, dtype=np.int64),
+                SAMPLE_INDEX_KEY: idx, IMAGE_FILENAME_KEY: anno[self.filename_key]}
+
     def __getitem__(self, idx: int) -> Dict[str, Any]:
+        if self.item_form == "files":
+            return self._file_item(idx)
         anno = self.data[idx]
         root = self.config.get("dataset_root", "")
         img = self.reader(os.path.join(root, anno["img_path"]))
@@ -149,7 +203,12 @@ class FlameDataset(torch.utils.data.Dataset):
     def _load_mesh(mesh_path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The arrays of `_load_mesh` (flame_dataset.py:115-127); its model-view product runs on the device."""
         with open(mesh_path) as f:
-            data = json.load(f)
+            return FlameDataset._mesh_of(f)
+
+    @staticmethod
+    def _mesh_of(f) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`_load_mesh` on an open text file."""
+        data = json.load(f)
         vertices = np.ascontiguousarray(np.array(data["vertices"], dtype=np.float32).reshape(-1, 3))
         model_view = np.ascontiguousarray(np.array(data["model_view_matrix"], dtype=np.float32).reshape(4, 4))
         projection = np.ascontiguousarray(np.array(data["projection_matrix"], dtype=np.float32).reshape(4, 4))
@@ -212,9 +271,86 @@ class RawBatchCollate:
                 IMAGE_FILENAME_KEY: [it[IMAGE_FILENAME_KEY] for it in items]}
 
 
+class FileBatchCollate(RawBatchCollate):
+    """`RawBatchCollate` for the items of `FlameDataset(item_form="files")`: the same `None` dropping and refill. Everything is
+    a CPU tensor, so `DataLoader(pin_memory=True)` pins the batch whole:
+      png_files         uint8   every PNG file, each at a multiple of 16 bytes (png_reader._align), zero between them
+      png_table         int64 [B,5]   offset, size (0: the item came decoded), and the IHDR's height, width, channels
+      decoded_images    uint8   every image a worker had to decode (HWC RGB), each at a multiple of 16 bytes
+      decoded_table     int64 [B,2]   offset, size (0: the item is a PNG)
+      annotations       uint8   every annotation file, each at a multiple of 16 bytes
+      annotation_table  int64 [B,2]   offset, size
+      crop_descs        int64 [B,8]   dad3d_preprocess_images' rows for a crop read in place from the full image: the crop's byte
+                                      offset in its image (y W + x) 3 in column 0 (the builder adds the image's device address),
+                                      h, w, new_h, new_w, pad_top, pad_left, row stride W 3
+      frames, image_shape, INPUT_BBOX_KEY, SAMPLE_INDEX_KEY, IMAGE_FILENAME_KEY as in the raw form."""
+
+    @staticmethod
+    def _pack(arrays: Sequence[np.ndarray]) -> Tuple[torch.Tensor, np.ndarray]:
+        sizes = [int(a.size) for a in arrays]
+        table = np.zeros((len(arrays), 2), dtype=np.int64)
+        at = 0
+        for i, z in enumerate(sizes):
+            table[i] = (at, z)
+            at += (z + _ALIGN - 1) // _ALIGN * _ALIGN
+        packed = torch.zeros(at, dtype=torch.uint8)
+        flat = packed.numpy()
+        for (off, z), a in zip(table, arrays):
+            flat[off:off + z] = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        return packed, table
+
+    def __call__(self, batch: Sequence[Optional[Mapping[str, Any]]]) -> Dict[str, Any]:
+        from .png_reader import _header_of
+
+        n = len(batch)
+        items = [b for b in batch if b is not None]
+        if not items:
+            raise ValueError("every item of the batch is None")
+        items = items + items[: n - len(items)]
+        b = len(items)
+        none = np.zeros(0, dtype=np.uint8)
+        png_files, png_at = self._pack([it[PNG] for it in items])
+        decoded, decoded_table = self._pack([none if it.get(DECODED) is None else it[DECODED] for it in items])
+        annotations, annotation_table = self._pack([it[ANNOTATION] for it in items])
+        png_table = np.zeros((b, 5), dtype=np.int64)
+        png_table[:, :2] = png_at
+        descs = np.zeros((b, 8), dtype=np.int64)
+        frames = np.zeros((b, 8), dtype=np.int32)
+        for i, it in enumerate(items):
+            H, W = (int(v) for v in it[IMAGE_SHAPE][:2])
+            if png_table[i, 1]:
+                head = _header_of(bytes(it[PNG][:33]), int(png_table[i, 1]))
+                if head is None or head[:2] != (H, W):
+                    raise ValueError(f"item {it.get(SAMPLE_INDEX_KEY)}: the PNG's header does not give the item's {H} x {W} image")
+                png_table[i, 2:] = head
+            elif decoded_table[i, 1] != H * W * 3:
+                raise ValueError(f"item {it.get(SAMPLE_INDEX_KEY)}: neither a PNG nor a decoded {H} x {W} RGB image")
+            x, y, w, h = (int(v) for v in it[BBOX])
+            if w <= 0 or h <= 0 or x < 0 or y < 0 or x + w > W or y + h > H:
+                raise ValueError(f"item {it.get(SAMPLE_INDEX_KEY)}: bbox {(x, y, w, h)} does not lie in its {W} x {H} image")
+            nh, nw, top, left = self._geometry(h, w)
+            descs[i] = ((y * W + x) * 3, h, w, nh, nw, top, left, W * 3)
+            frames[i] = (H, x, y, w, h, top, left, 0)
+        stack = lambda k, dt: torch.from_numpy(np.stack([np.asarray(it[k], dtype=dt) for it in items]))  # noqa: E731
+        return {PNG_FILES: png_files, PNG_TABLE: torch.from_numpy(png_table), DECODED_IMAGES: decoded,
+                DECODED_TABLE: torch.from_numpy(decoded_table), ANNOTATIONS: annotations,
+                ANNOTATION_TABLE: torch.from_numpy(annotation_table), CROP_DESCS: torch.from_numpy(descs),
+                FRAMES: torch.from_numpy(frames), IMAGE_SHAPE: stack(IMAGE_SHAPE, np.int64), INPUT_BBOX_KEY: stack(BBOX, np.int32),
+                SAMPLE_INDEX_KEY: torch.tensor([int(it[SAMPLE_INDEX_KEY]) for it in items], dtype=torch.int64),
+                IMAGE_FILENAME_KEY: [it[IMAGE_FILENAME_KEY] for it in items]}
+
+
 class FlameBatchBuilder:
     """A raw batch (CPU, ideally pinned, or already on the device) -> (images [B,3,S,S] float32, targets), on the current
-    stream of `device`, with no host sync. `targets` holds what KeypointsDataMixin.get_input keeps (train/mixins.py:30-52):
+    stream of `device`, with no host sync. A file batch (`FileBatchCollate`) gives the same images and targets, to the bit, from
+    the files' bytes: upload, PNG decode to RGB on the device, crops read in place from the decoded images, the annotations
+    through `dad3d_annotation_parse`, then the same kernels. The file form waits for the device ONCE per batch: it reads the PNG
+    flags and the annotation status together (its small tables go up from pinned memory without blocking; a batch that is not
+    pinned blocks in its uploads, as in the raw form). An annotation with a nonzero status is parsed on the host with `_load_mesh`'s code from
+    the bytes still in the batch (which raises its own error for a bad file) and its rows are uploaded before
+    `dad3d_gt_keypoints` runs; a PNG the device flags is decoded by PIL. `last_fallbacks` counts, for the last call, the items
+    that took each: {"annotation_host", "png_host", "png_worker"} (None after a raw batch). A file batch already on the device
+    costs one more small copy back, of its tables. `targets` holds what KeypointsDataMixin.get_input keeps (train/mixins.py:30-52):
     TARGET_2D_LANDMARKS [B,K,2] (/ img_size), TARGET_LANDMARKS_HEATMAP [B,K,S/stride,S/stride] (uint8 by default, the
     dataset's bytes: losses.py fuses the / 255; "float" gives get_input's uint8 / 255), TARGET_3D_MODEL_VERTICES [B,N,3],
     TARGET_2D_FULL_LANDMARKS [B,N,2] (S pixels), TARGET_2D_LANDMARKS_PRESENCE bool [B,K], INPUT_BBOX_KEY int32 [B,4]; plus
@@ -252,12 +388,83 @@ class FlameBatchBuilder:
         import ctypes as C
 
         self._mean, self._std = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        self.n_verts = int(load_static()["faces"].max()) + 1  # the annotation's vertex count: the packaged FLAME topology's
+        self.last_fallbacks: Optional[Dict[str, int]] = None
+        self._png = None
+        self._range_flag = _lib.ANNOTATION_FLAG_RANGE
 
     def _up(self, t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         return t.to(self.device, dtype, non_blocking=True).contiguous()
 
+    def _from_files(self, raw: Mapping[str, Any]):
+        """The front of a file batch: (descs, frames, verts, mv, pm) on the device, as the raw form uploads them, and the owners of
+        the memory the descriptors point into. The caller holds those until `dad3d_preprocess_images` is enqueued: a block freed
+        before that launch could be handed to the very output the launch writes."""
+        import io
+
+        from .png_reader import PngDecoder
+
+        dev = self.device
+        if self._png is None:
+            self._png = PngDecoder(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        png_table, decoded_table, ann_table = (raw[k].cpu().numpy() for k in (PNG_TABLE, DECODED_TABLE, ANNOTATION_TABLE))
+        b, n = len(ann_table), self.n_verts
+        if png_table.shape != (b, 5) or decoded_table.shape != (b, 2) or ann_table.shape != (b, 2) or raw[CROP_DESCS].shape != (b, 8):
+            raise ValueError("inconsistent file batch: " + ", ".join(f"{k} {tuple(raw[k].shape)}" for k in
+                                                                     (PNG_TABLE, DECODED_TABLE, ANNOTATION_TABLE, CROP_DESCS)))
+        text = self._up(raw[ANNOTATIONS], torch.uint8)
+        offsets = self._up(raw[ANNOTATION_TABLE][:, 0], torch.int64)
+        sizes = self._up(raw[ANNOTATION_TABLE][:, 1], torch.int64)
+        decoded = self._up(raw[DECODED_IMAGES], torch.uint8)
+        pngs = [i for i in range(b) if png_table[i, 1]]  # the others came decoded
+        pending = self._png._launch_packed(raw[PNG_FILES], png_table[pngs, 0], png_table[pngs, 1], 3,
+                                           heads=[tuple(int(v) for v in png_table[i, 2:]) for i in pngs])
+        verts = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+        mv = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+        pm = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        if text.numel():
+            self._check(self._lib.dad3d_annotation_parse(text.data_ptr(), text.numel(), offsets.data_ptr(), sizes.data_ptr(), b, n,
+                                                         verts.data_ptr(), mv.data_ptr(), pm.data_ptr(), status.data_ptr(), dev.index, stream))
+        else:  # nothing but empty files: the host's parser says so
+            status.fill_(self._range_flag)
+        flags = [status] + ([pending.dev_flags, pending.dev_info] if pending.on_device else [])
+        got = torch.cat(flags).cpu().numpy()  # the one sync of the file form
+        images = pending.finish(got[b:b + len(pending.on_device)], got[b + len(pending.on_device):])
+        self.last_fallbacks = {"annotation_host": int((got[:b] != 0).sum()),
+                               "png_host": int((images.flags != 0).sum()),
+                               "png_worker": int((png_table[:, 1] == 0).sum())}
+        for i in np.nonzero(got[:b])[0]:  # the host's parser, from the bytes still in the batch
+            off, size = (int(v) for v in ann_table[i])
+            data = raw[ANNOTATIONS][off:off + size].cpu().numpy().tobytes()
+            v, m, p = FlameDataset._mesh_of(io.TextIOWrapper(io.BytesIO(data)))
+            if v.shape != (n, 3):
+                raise ValueError(f"item {i} of the batch: {v.shape[0]} vertices in the annotation, {n} expected")
+            verts[i], mv[i], pm[i] = (torch.from_numpy(t).to(dev) for t in (v, m, p))
+        tensors = dict(zip(pngs, images.tensors()))
+        bases = []
+        for i in range(b):
+            if i in tensors:
+                H, W = (int(v) for v in png_table[i, 2:4])
+                if tuple(tensors[i].shape) != (H, W, 3) or not tensors[i].is_contiguous():
+                    raise ValueError(f"item {i} of the batch decoded to {tuple(tensors[i].shape)}, not {(H, W, 3)}")
+                bases.append(tensors[i].data_ptr())
+            else:
+                bases.append(decoded.data_ptr() + int(decoded_table[i, 0]))
+        descs = raw[CROP_DESCS].to(dev, torch.int64, non_blocking=True)
+        descs = (descs.clone() if descs is raw[CROP_DESCS] else descs).contiguous()  # never edit the caller's batch
+        descs[:, 0] += torch.tensor(bases, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        return (descs, self._up(raw[FRAMES], torch.int32), verts, mv, pm), (pending, images, tensors, decoded)
+
     def __call__(self, raw: Mapping[str, Any]) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        dev, s = self.device, self.img_size
+        if ANNOTATIONS in raw:
+            front, owners = self._from_files(raw)
+            built = self._build(raw, *front)
+            del owners  # alive up to here: the preprocess launch that reads the decoded images is on the stream
+            return built
+        self.last_fallbacks = None
+        dev = self.device
         crops = self._up(raw[CROPS], torch.uint8)
         descs = raw[CROP_DESCS].to(dev, torch.int64, non_blocking=True)
         descs = (descs.clone() if descs is raw[CROP_DESCS] else descs).contiguous()  # never edit the caller's batch
@@ -269,6 +476,11 @@ class FlameBatchBuilder:
         if descs.shape != (b, 8) or frames.shape != (b, 8) or mv.shape != (b, 4, 4) or pm.shape != (b, 4, 4) or verts.shape[2] != 3:
             raise ValueError("inconsistent raw batch: " + ", ".join(f"{k} {tuple(raw[k].shape)}" for k in
                                                                     (CROP_DESCS, FRAMES, VERTICES, MODEL_VIEW, PROJECTION)))
+        return self._build(raw, descs, frames, verts, mv, pm)
+
+    def _build(self, raw, descs, frames, verts, mv, pm) -> Tuple[torch.Tensor, Dict[str, Any]]:
+        dev, s = self.device, self.img_size
+        b, n = verts.shape[:2]
         stream = torch.cuda.current_stream(dev).cuda_stream
         k = self.num_classes
         images = torch.empty((b, 3, s, s), dtype=torch.float32, device=dev)

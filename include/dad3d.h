@@ -773,6 +773,47 @@ DAD3D_EXPORT dad3d_status dad3d_json_parse_number_host(const uint8_t* text, cons
                                           uint64_t* bits_out, uint8_t* is_int_out, uint32_t* flags_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * DAD-3DHeads annotation files read on the device: what `FlameDataset._load_mesh` (model_training/data/flame_dataset.py:115-127) makes of
+ * `json.load` -- np.array(data["vertices"], float32) [n_verts,3], data["model_view_matrix"] and data["projection_matrix"] [4,4] -- for a
+ * batch of documents in ONE stream-ordered launch, one workgroup per document. All DEVICE pointers; the entry validates its arguments
+ * before any device work (-> DAD3D_E_INVALID), allocates nothing, takes no scratch and never synchronises.
+ *   text        n_bytes bytes, 16-byte aligned; document i is text[doc_offsets[i], doc_offsets[i] + doc_sizes[i]), its offset a multiple
+ *               of 16, its size < 2^31. A document outside `text` gets DAD3D_ANNOTATION_FLAG_RANGE and is not read.
+ *   vertices [B,n_verts,3], model_view [B,16], projection [B,16] float32; status [B] int32.
+ * Documents are parsed in isolation: whatever one holds, the outputs and status of the others are those of parsing them alone.
+ * status[i] == 0: the device validated every byte of document i and the three outputs are bit-equal to `_load_mesh` (every number token
+ * through the routine of dad3d_json_parse_number_host, then a round-to-nearest-even cast to float32; the int token `-0` is 0).
+ * status[i] != 0: DAD3D_ANNOTATION_FLAG_* bits; all three outputs of item i are NaN and the host parses the file. Status 0 requires:
+ *   - outside strings only space, tab, LF, CR, `{ } [ ] , :` and words (maximal runs of letters, digits, `+ - .`, at most
+ *     DAD3D_ANNOTATION_MAX_WORD_BYTES long): a word that starts with a digit or `-` is a number token the number routine does not flag
+ *     (else _FLAG_NUMBER), any other word is `true`, `false` or `null`;
+ *   - a quote opens or closes a string unless an odd run of backslashes stands in front of it (runs are counted up to
+ *     DAD3D_ANNOTATION_MAX_BACKSLASH_RUN; a longer one is flagged). Every string byte is 0x20 .. 0x7E and a backslash escapes one of
+ *     `" \ / b f n r t` only (else _FLAG_STRING);
+ *   - every significant token (`{ } [ ] , :`, a string, a word) is legal given its kind, the two tokens in front of it and its depth: `{`
+ *     is the first token and `}`, at depth 1, the last; no other `{` anywhere; at depth 1 `"key" : value` separated by commas, in arrays
+ *     values separated by commas; nothing trailing, doubled or missing; quotes and brackets balance (else _FLAG_GRAMMAR);
+ *   - among the keys at depth 1, "vertices", "model_view_matrix" and "projection_matrix" each appear exactly once, spelled plainly, no
+ *     depth-1 key holds a backslash, and no key appears twice: keys are compared by a 32-bit FNV-1a hash of their bytes, so two keys
+ *     that share a hash count as a repeat; a key is at most DAD3D_ANNOTATION_MAX_KEY_BYTES long and a document has at most
+ *     DAD3D_ANNOTATION_MAX_KEYS of them (else _FLAG_KEYS);
+ *   - "vertices" is an array of exactly n_verts arrays of exactly 3 number tokens, each matrix an array of 4 arrays of 4 (else
+ *     _FLAG_SHAPE). Other keys' values: numbers, true, false, null, strings, and arrays of those nested to any depth. */
+#define DAD3D_ANNOTATION_FLAG_GRAMMAR 0x1
+#define DAD3D_ANNOTATION_FLAG_KEYS 0x2
+#define DAD3D_ANNOTATION_FLAG_SHAPE 0x4
+#define DAD3D_ANNOTATION_FLAG_NUMBER 0x8
+#define DAD3D_ANNOTATION_FLAG_STRING 0x10
+#define DAD3D_ANNOTATION_FLAG_RANGE 0x20
+#define DAD3D_ANNOTATION_MAX_BACKSLASH_RUN 64
+#define DAD3D_ANNOTATION_MAX_WORD_BYTES 32
+#define DAD3D_ANNOTATION_MAX_KEY_BYTES 64
+#define DAD3D_ANNOTATION_MAX_KEYS 128
+DAD3D_EXPORT dad3d_status dad3d_annotation_parse(const uint8_t* text, int64_t n_bytes, const int64_t* doc_offsets, const int64_t* doc_sizes,
+                                    int batch, int n_verts, float* vertices, float* model_view, float* projection, int32_t* status,
+                                    int device, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FaceMeshPredictor._transform + _array_to_batch (predictor.py:80-95,195-203) for a batch of uint8 RGB images of ANY sizes
  * in one launch: LongestMaxSize (cv2.resize INTER_LINEAR, 8-bit fixed-point path) -> PadIfNeeded (centred, 0) -> Normalize
  * ((x - 255 mean) * (1 / (255 std)), float32) -> CHW. All DEVICE pointers:
