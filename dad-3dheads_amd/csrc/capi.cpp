@@ -1428,6 +1428,45 @@ dad3d_status dad3d_inflate_host(const uint8_t* const* ranges, const int64_t* ran
     return DAD3D_OK;
 }
 
+size_t dad3d_jpeg_decode_scratch_bytes(int64_t* desc, int batch, int32_t* grid) {
+    if (!desc || !grid || batch < 1 || batch > 65535) return 0;
+    int dims[DAD3D_JPEG_DECODE_GRID_INTS] = {0, 0, 0};
+    const size_t bytes = jpeg_decode_layout(reinterpret_cast<long long*>(desc), batch, dims);
+    for (int i = 0; i < DAD3D_JPEG_DECODE_GRID_INTS; ++i) grid[i] = dims[i];
+    return bytes;
+}
+
+dad3d_status dad3d_jpeg_decode(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, const int32_t* grid, uint8_t* out,
+                               size_t out_bytes, int32_t* flags, void* scratch, size_t scratch_bytes, int device, void* stream) {
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_jpeg_decode: batch %d outside 1 .. 65535", batch);
+    DAD3D_REQUIRE(files && desc && grid && out && flags && scratch, "dad3d_jpeg_decode: null argument");
+    DAD3D_REQUIRE(grid[0] >= 1 && grid[0] <= (1 << 22) && grid[1] >= 1 && grid[1] <= (1 << 22) && grid[2] >= 1 && grid[2] <= (1 << 28),
+                  "dad3d_jpeg_decode: a grid of %d segments, %d blocks, %d pixels (dad3d_jpeg_decode_scratch_bytes gives it)", grid[0], grid[1], grid[2]);
+    DAD3D_REQUIRE((long long)batch * ((grid[0] + 62) / 64) + (batch + 63) / 64 <= 0x7fffffffll, "dad3d_jpeg_decode: %d files of up to %d segments pass the grid",
+                  batch, grid[0]);
+    DAD3D_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && reinterpret_cast<uintptr_t>(desc) % 8 == 0,
+                  "dad3d_jpeg_decode: scratch must be 16-byte aligned, desc 8-byte aligned");
+    DAD3D_REQUIRE(scratch_bytes >= (size_t)batch * jpeg_decode_state_bytes(), "dad3d_jpeg_decode: %zu bytes of scratch for a batch of %d", scratch_bytes,
+                  batch);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JpegDecodeArgs a{files, files_bytes, reinterpret_cast<const long long*>(desc), batch, grid[0], grid[1], grid[2], out, out_bytes,
+                     flags, static_cast<unsigned char*>(scratch), scratch_bytes};
+    return launch_jpeg_decode(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t size, int channels, uint8_t* out, int64_t out_bytes, int32_t* h, int32_t* w,
+                                    int32_t* c, int32_t* flag) {
+    DAD3D_REQUIRE(size >= 0 && (file || size == 0) && h && w && c && flag && out_bytes >= 0, "dad3d_jpeg_decode_host: null or negative argument");
+    DAD3D_REQUIRE(channels == 0 || channels == 1 || channels == 3, "dad3d_jpeg_decode_host: %d channels (0 the file's own, 1, 3)", channels);
+    int hh = 0, ww = 0, cc = 0;
+    bool fits = true;
+    *flag = jpeg_decode_host(file, size, channels, out, out_bytes, &hh, &ww, &cc, &fits);
+    *h = hh, *w = ww, *c = cc;
+    DAD3D_REQUIRE(fits, "dad3d_jpeg_decode_host: a %d x %d x %d image does not fit %lld bytes", hh, ww, cc, (long long)out_bytes);
+    return DAD3D_OK;
+}
+
 size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes) {
     return n_bytes < 1 || n_bytes > 0x7fffffffLL ? 0 : json_parse_scratch_bytes(n_bytes);
 }

@@ -577,6 +577,24 @@ struct ZlibDecompressArgs {
     int32_t* flags;
 };
 dad3d_status launch_zlib_decompress(const ZlibDecompressArgs& a, hipStream_t s);
+// JPEG files read back (jpeg_decode.hip): scan, entropy decode per segment, IDCT per block, upsampling and colour per pixel
+struct JpegDecodeArgs {
+    const unsigned char* files;  // every file of the batch, at the offsets of the descriptor rows
+    size_t files_bytes;
+    const long long* desc;       // DEVICE [B][DAD3D_JPEG_DECODE_DESC_INTS]
+    int batch, max_segments, max_blocks, max_pixels;  // the grid dad3d_jpeg_decode_scratch_bytes gave
+    unsigned char* out;
+    size_t out_bytes;
+    int32_t* flags;              // [B] DAD3D_JPEG_DECODE_FLAG_*
+    unsigned char* scratch;      // jpeg_decode_layout: file states | per file: coefficients, planes, segment table
+    size_t scratch_bytes;
+};
+size_t jpeg_decode_layout(long long* desc_host, int batch, int* grid);
+size_t jpeg_decode_state_bytes();
+dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s);
+// host: one file through jpeg_entropy.hpp / jpeg_idct.hpp; returns the flag (out null: the header alone)
+int jpeg_decode_host(const unsigned char* file, long long size, int channels, unsigned char* out, long long out_bytes, int* h, int* w, int* c,
+                     bool* fits);
 // host: inflate.hpp on a list of byte ranges; returns the flag
 int inflate_host(const unsigned char* const* ranges, const long long* range_bytes, int n_ranges, unsigned char* out, long long capacity,
                  long long* length);

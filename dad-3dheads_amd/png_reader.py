@@ -111,6 +111,11 @@ class PngDecoder:
         as PIL's `convert` to L / LA / RGB / RGBA does. `force_general` sends every file through the serial inflate (for tests and
         the bench). One synchronisation: the flags. Packs the files the device will read into one pinned buffer (a file the host cannot size
         goes to PIL as it is), then `decode_packed`'s launches and finish."""
+        pending = self._launch(sources, channels, force_general)
+        return pending.finish(*pending.flags_on_host())
+
+    def _launch(self, sources: Sequence[Source], channels: Optional[int] = None, force_general: bool = False) -> "_PendingDecode":
+        """`decode` without its synchronisation: see `_launch_packed`."""
         if channels is not None and channels not in _MODE:
             raise ValueError(f"channels must be None or 1 .. 4, got {channels}")
         files = [_bytes_of(s) for s in sources]
@@ -127,7 +132,7 @@ class PngDecoder:
         pending = self._launch_packed(staged, offsets, [len(f) if h is not None else 0 for f, h in zip(files, heads)], channels, force_general,
                                       heads)
         pending.unstaged = {i: f for i, (f, h) in enumerate(zip(files, heads)) if h is None}
-        return pending.finish(*pending.flags_on_host())
+        return pending
 
     def decode_packed(self, buffer: Tensor, offsets: Sequence[int], sizes: Sequence[int], channels: Optional[int] = None,
                       force_general: bool = False, heads: Optional[Sequence] = None) -> PngImages:

@@ -717,6 +717,49 @@ DAD3D_EXPORT dad3d_status dad3d_inflate_host(const uint8_t* const* ranges, const
                                              int64_t capacity, int64_t* length, int32_t* flag);
 
 /* ---------------------------------------------------------------------------------------------
+ * Baseline JPEG files read back on the device, bit-equal to `PIL.Image.open` (libjpeg-turbo: the "islow" integer IDCT, "fancy"
+ * upsampling): Huffman-coded sequential files of 8-bit samples with one scan, grey or YCbCr at 4:4:4, 4:2:2 (2x1) or 4:2:0 (2x2),
+ * with or without restart markers, of any sizes in one call.
+ *   files   DEVICE: the bytes of every file, file b at files[desc[b][0] .. + desc[b][1])
+ *   desc    DEVICE [batch][DAD3D_JPEG_DECODE_DESC_INTS] int64: file offset, file bytes (below 2^31), height, width and components
+ *           (1 or 3) as the file's SOF0 states them (the caller has walked the markers up to SOF, nothing else, to size the
+ *           outputs), offset of the image in `out`, its row stride in bytes (at least width * out channels), out channels 1 or 3,
+ *           and four columns that dad3d_jpeg_decode_scratch_bytes fills: where the item's coefficients, planes and segment table
+ *           (and its capacity) lie in `scratch`
+ *   grid    HOST [DAD3D_JPEG_DECODE_GRID_INTS] int32 from dad3d_jpeg_decode_scratch_bytes: the most segments, blocks and pixels a
+ *           file of the batch may have, which size the launches
+ *   out     DEVICE: image b is [height][row stride] bytes from out[desc[b][5]], `width * out channels` of each row written; bytes
+ *           between and behind the rows, and behind an item, are left as they were
+ *   flags   DEVICE [batch] int32: 0, or why the item was not decoded -- DAD3D_JPEG_DECODE_FLAG_MALFORMED (a marker segment's
+ *           length, a table's validity, a missing table, SOF0 against the row, the restart markers' number or sequence, a
+ *           segment that needs a bit beyond its last byte or leaves a whole byte unread, a code no table assigns, a
+ *           coefficient index beyond 63, no EOI, or a row that points outside the buffers) and / or _UNSUPPORTED (a valid file
+ *           outside this decoder: progressive, extended, lossless, arithmetic coding, 12-bit samples, 16-bit tables, two or
+ *           four components, other sampling factors, several scans, DNL, an Adobe APP14, component ids other than 1 2 3 without
+ *           JFIF, fill bytes in front of a marker inside the scan, or values outside the 16 bits in front of and behind the
+ *           first IDCT pass, or outside -512 .. 511 behind the second, where libjpeg-turbo's vector code and its C code part).
+ *           The pixels of a flagged item are unspecified; the caller decodes it on the host. Nothing outside the item's own
+ *           places is read or written whatever the file holds.
+ * Out channels follow PIL's `convert`: grey is replicated, L = (19595 R + 38470 G + 7471 B + 32768) >> 16.
+ * dad3d_jpeg_decode_scratch_bytes is host-only: it reads columns 1 .. 4 of HOST rows, fills columns 8 .. 11 and `grid`, and returns
+ * the bytes of scratch (16-byte aligned), 0 for a row outside the limits. Four launches on `stream`, no allocation, no
+ * synchronisation: can be captured.
+ * dad3d_jpeg_decode_host runs the same routines on one file on the CPU, HOST pointers: channels 0 keeps the file's own; *h, *w, *c
+ * are set whenever the header was accepted; `out` may be NULL to read the header alone, and is otherwise [h][w][c] (DAD3D_E_INVALID
+ * where out_bytes is too small). *flag as above.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_JPEG_DECODE_DESC_INTS 12
+#define DAD3D_JPEG_DECODE_GRID_INTS 3
+#define DAD3D_JPEG_DECODE_FLAG_MALFORMED 0x1
+#define DAD3D_JPEG_DECODE_FLAG_UNSUPPORTED 0x2
+DAD3D_EXPORT size_t dad3d_jpeg_decode_scratch_bytes(int64_t* desc, int batch, int32_t* grid);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_decode(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, const int32_t* grid,
+                                            uint8_t* out, size_t out_bytes, int32_t* flags, void* scratch, size_t scratch_bytes, int device,
+                                            void* stream);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t size, int channels, uint8_t* out, int64_t out_bytes, int32_t* h,
+                                                 int32_t* w, int32_t* c, int32_t* flag);
+
+/* ---------------------------------------------------------------------------------------------
  * Reading JSON back: the large arrays of numbers of a document lifted into float64 on the device, with the doubles `json.load` makes
  * (dad_3dheads_benchmark/benchmark.py:177-180, the two `json.load` calls of `DADEvaluator.__call__`). The device lifts only what it has
  * validated and converted exactly; every other byte stays with the host parser, so a result can never differ from `json.load`.
