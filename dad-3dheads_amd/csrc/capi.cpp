@@ -1219,6 +1219,7 @@ dad3d_status dad3d_project_vertices(const float* vertices, const float* model_vi
                                     const float* frame, int batch, int nver, float* world_homo, float* xy,
                                     int32_t* xy_int, int device, void* stream) {
     DAD3D_REQUIRE(batch >= 0 && nver >= 0, "dad3d_project_vertices: bad argument");
+    DAD3D_REQUIRE(batch <= 65535, "dad3d_project_vertices: batch %d beyond the launch grid", batch);
     if (batch == 0 || nver == 0) return DAD3D_OK;
     DAD3D_REQUIRE(vertices && model_view && projection && frame, "dad3d_project_vertices: null input");
     DeviceGuard guard(device);
@@ -1754,6 +1755,8 @@ dad3d_status dad3d_eval_nearest(const float* query, const float* points, const i
     DAD3D_REQUIRE((flags & ~DAD3D_EVAL_SELF_EXCLUDE) == 0, "dad3d_eval_nearest: unknown flags 0x%x", flags);
     DAD3D_REQUIRE(query && points && min_dist2, "dad3d_eval_nearest: null argument");
     DAD3D_REQUIRE(batch <= 65535, "dad3d_eval_nearest: batch beyond the launch grid");
+    DAD3D_REQUIRE(!(flags & DAD3D_EVAL_SELF_EXCLUDE) || n_query == n_points,
+                  "dad3d_eval_nearest: DAD3D_EVAL_SELF_EXCLUDE needs the same set as query and points (Q %d, N %d)", n_query, n_points);
     DeviceGuard guard(device);
     DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
     EvalNearestArgs a{query, points, counts, similarity, min_dist2, knn_index, knn_dist2, batch, n_query, n_points, k,

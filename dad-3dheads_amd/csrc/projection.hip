@@ -5,9 +5,10 @@
 //     world = MV . [v; 1]          clip = P . world          xy = clip.xy / clip.w
 //     xy    = (x, H - y) - (crop_x, crop_y)                   xy_int = (int) xy   (visualize.py:22 `.astype(int)`)
 // One lane per vertex, matrices of the image in SGPR-uniform registers; a streaming kernel: 12 B in, 8 (+16 +8) B out
-// per vertex, HBM-bound. The arithmetic is projection_math.hpp's, shared with the training-batch kernel (train_batch.hip);
-// numpy's sgemm may fuse or reorder the products, so agreement with the reference is to fp32 rounding (tests: 1e-3 px at
-// image scale), not bitwise.
+// per vertex, HBM-bound. The arithmetic is projection_math.hpp's, shared with the training-batch kernel (train_batch.hip):
+// a fixed fp32 order that the tests hold to the bit against its NumPy restatement. numpy's own sgemm may fuse or reorder the
+// products, so agreement with the REFERENCE is to fp32 rounding (tests: 1e-3 px at image scale), not bitwise.
+// (int) of a non-finite or out-of-range xy is the gfx950 conversion's: NaN -> 0, saturating at INT32_MIN / INT32_MAX.
 #include "common.hpp"
 #include "projection_math.hpp"
 

@@ -372,7 +372,13 @@ DAD3D_EXPORT dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, 
  *   vertices [B,nver,3], model_view [B,4,4], projection [B,4,4] (row-major, as the annotation JSON stores them),
  *   frame [B,3] = (image height, crop_point_x, crop_point_y) -- zeros for no crop.
  * Outputs, each optional (NULL): world_homo [B,nver,4] = (MV . [v;1])^T, xy [B,nver,2] = (x/w, H - y/w) - crop,
- * xy_int [B,nver,2] = (int) xy. Agreement with the numpy reference is to fp32 rounding, not bitwise (sgemm order).
+ * xy_int [B,nver,2] = (int) xy: truncation toward zero; a NaN gives 0, +inf or a value >= 2^31 gives INT32_MAX, -inf or a
+ * value < -2^31 gives INT32_MIN (the gfx950 conversion saturates). A vertex with clip w = 0 or w < 0 is divided like any other
+ * (+-inf, NaN or a mirrored point), never clipped.
+ * The arithmetic is fixed: both 4x4 products are summed k = 0..3 in order in fp32 without fused multiply-adds, then one
+ * correctly rounded divide, flip and crop shift, so the outputs are reproducible to the bit (the tests hold them to a NumPy
+ * restatement of that order). It is numpy's own sgemm that may fuse or reorder the products: agreement with the numpy
+ * REFERENCE is therefore to fp32 rounding, not bitwise. batch > 65535 (the launch grid) -> DAD3D_E_INVALID before any device work.
  * --------------------------------------------------------------------------------------------- */
 DAD3D_EXPORT dad3d_status dad3d_project_vertices(const float* vertices, const float* model_view, const float* projection,
                                     const float* frame, int batch, int nver, float* world_homo, float* xy,
@@ -488,15 +494,23 @@ DAD3D_EXPORT dad3d_status dad3d_keypoint_errors(const float* pred, const float* 
  *     query [B,Q,3]; points [B,N,3]; counts [B] int32 or NULL: item b uses points[b, :counts[b]] (clamped to 0..N)
  *     similarity [B][13] = (s, R row-major 3x3, t) or NULL: every point is mapped to s * p . R + t (row vector) first
  *     flags: DAD3D_EVAL_SELF_EXCLUDE = query and points are the same set in the same order: point q is not a neighbour of
- *            query q
+ *            query q. Requires Q == N (else DAD3D_E_INVALID)
  *     min_dist2 [B,Q] (required); knn_index [B,Q,k] int32, knn_dist2 [B,Q,k]: the k nearest in ascending distance, ties to
  *     the lower index, -1 / +inf where fewer than k points exist (each optional, NULL)
+ *     Non-finite input: only a FINITE distance is ever reported. A point whose distance to the query is NaN or +inf (a NaN or
+ *     infinite coordinate, after the similarity) is skipped as if it were absent, and a query with a NaN or infinite coordinate
+ *     gets -1 / +inf at every rank (min_dist2 = +inf). Nothing propagates a NaN: where the reference's Chamfer mean would turn
+ *     NaN on a NaN vertex, the caller has to look for non-finite input itself. Rows past counts[b] are never read.
  * dad3d_eval_z5_ranks  benchmark.py:126-160 `calc_zn` / `zn` as the script computes it: for every anchor a (head-subset
  *   positions, HOST array anchors[n_anchors], n_anchors <= 8), all K head vertices ordered by fp32 distance to gt_head[a]
  *   (ties to the lower index, rank 0 included) = o_a, then
  *     counts[b][a] = #{ i < K : (g_z[i] >= g_z[o_a[i]]) == (w_z[i] >= w_z[o_a[i]]) }
  *     gt_head [B,K,3] (the GT world head subset TIMES -1, benchmark.py:155), pred_head [B,K,3], counts [B][n_anchors] int32,
  *     order [B][n_anchors][K] int32 (o_a) or NULL
+ *   Non-finite vertices: the sort key is the distance's bit pattern, then the index. +inf distances sort behind every finite
+ *   one (among themselves by index) and a NaN distance behind those, where a stable float64 argsort places them; SEVERAL NaN
+ *   distances order by their bit patterns (sign and payload) first, so not necessarily by index as that argsort would.
+ *   The z comparisons are IEEE: any comparison with a NaN z is false.
  * --------------------------------------------------------------------------------------------- */
 #define DAD3D_EVAL_SELF_EXCLUDE 0x1
 #define DAD3D_EVAL_MAX_K 8

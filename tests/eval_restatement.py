@@ -48,6 +48,64 @@ def write_golden_json(d, directory):
     return gt_path, sub_path
 
 
+# ---- lattice inputs: every fp32 product and partial sum of the scorer's kernels is exact on them ------------------------------
+# Coordinates are multiples of `step` = 1/8 with |x| <= 16; the similarity is s in {0.5, 1, 2, -1}, R a signed permutation and t a
+# multiple of 1/8 with |t| <= 16. Mapped points are then multiples of 1/16 below 48, differences multiples of 1/16 below 64,
+# and (qx-px)^2 + (qy-py)^2 + (qz-pz)^2 a multiple of 1/256 below 3 * 4096: d * 256 is an integer < 2^24. The fp32 kernel's
+# distances equal float64's whether or not the compiler fuses a multiply-add, exact ties are plentiful, and "ties to the lower
+# index" can be asserted without any exemption (test_eval_host.py checks this premise on the CPU).
+SIM_SCALES = (0.5, 1.0, 2.0, -1.0)
+
+
+def lattice_points(rng, n, span=16, step=1 / 8, batch=None):
+    """[n,3] (or [batch,n,3]) float32 points on the lattice step * Z^3 with |x| <= span."""
+    m = int(round(span / step))
+    shape = (n, 3) if batch is None else (batch, n, 3)
+    return (rng.integers(-m, m + 1, shape) * step).astype(np.float32)
+
+
+def lattice_similarity(rng, det=None):
+    """float32 [13] = (s, R row-major, t) of dad3d_eval_nearest: s of SIM_SCALES, R a signed permutation (det = +1 or -1 forced
+    with `det`: Procrustes with reflection="best" may return a reflection), t a multiple of 1/8 with |t| <= 16."""
+    r = np.zeros((3, 3))
+    r[np.arange(3), rng.permutation(3)] = rng.choice([-1.0, 1.0], 3)
+    if det is not None and np.linalg.det(r) * det < 0:
+        r[0] = -r[0]
+    return np.concatenate([[rng.choice(SIM_SCALES)], r.ravel(), rng.integers(-128, 129, 3) / 8]).astype(np.float32)
+
+
+def map_points(p, sim):
+    """s * p . R + t (row vector times R) in float64."""
+    p = np.asarray(p, np.float64)
+    if sim is None:
+        return p
+    sim = np.asarray(sim, np.float64)
+    with np.errstate(invalid="ignore"):  # inf * 0 of a non-finite point
+        return sim[0] * (p @ sim[1:10].reshape(3, 3)) + sim[10:13]
+
+
+def nearest_exact(q, p, k, self_exclude=False, sim=None):
+    """dad3d_eval_nearest for one item in float64: the k nearest points of every query by a stable argsort (ties to the lower
+    index) -> (index [Q,k] int32, squared distance [Q,k] float64), -1 / +inf where fewer than k points exist. The header's rule
+    for non-finite input: only a finite distance counts, a point at a NaN or infinite distance is absent."""
+    q, p = np.asarray(q, np.float64), map_points(p, sim)
+    idx = np.full((len(q), k), -1, np.int32)
+    dist = np.full((len(q), k), np.inf)
+    for s in range(0, len(q), 256):
+        with np.errstate(invalid="ignore"):
+            d = ((q[s:s + 256, None] - p[None]) ** 2).sum(-1)  # [chunk,N]
+        d[~np.isfinite(d)] = np.inf
+        if self_exclude:
+            rows = np.arange(s, min(s + 256, len(q)))
+            d[rows - s, rows] = np.inf
+        o = np.argsort(d, axis=1, kind="stable")[:, :k]
+        do = np.take_along_axis(d, o, 1)
+        kk = o.shape[1]
+        idx[s:s + 256, :kk] = np.where(np.isinf(do), -1, o)
+        dist[s:s + 256, :kk] = do
+    return idx, dist
+
+
 class Restatement:
     def __init__(self, faces, face_idx, b_coords, head_indices, face_indices):
         self.corners = np.asarray(faces, np.int64)[np.asarray(face_idx, np.int64)]  # [68,3]
@@ -118,6 +176,20 @@ class Restatement:
         w = np.asarray(pred_v, np.float32)[self.head]
         o, _ = self.anchor_order(g)
         return self.z5_counts(g, w, o).sum() / (len(self.head) * len(ANCHORS))
+
+    @staticmethod
+    def knn_agreement(g, w, idx):
+        """[K,k] bool: the README's Z5 comparison of vertex i with its neighbours idx[i] (the same `>=` as z5_counts)."""
+        gz, wz = np.asarray(g)[:, 2], np.asarray(w)[:, 2]
+        return (gz[:, None] >= gz[idx]) == (wz[:, None] >= wz[idx])
+
+    @staticmethod
+    def z5_knn(g, w, k=5):
+        """The README's Z5 as a count: every vertex against its k nearest OTHER vertices (float64 distances, stable order: ties
+        to the lower index). Z5 = count / (K * k). Needs K > k."""
+        idx, _ = nearest_exact(g, g, k, self_exclude=True)
+        assert (idx >= 0).all()
+        return int(Restatement.knn_agreement(g, w, idx).sum())
 
     def item(self, v, mv, p, bbox, height, pred):
         """The script's per-item metric values, NaN from the first one it cannot compute (its try/except)."""

@@ -94,6 +94,62 @@ def test_metrics_reached_rules():
     assert evaluation.metrics_reached(dict(full, N_landmarks_3d=np.zeros((5016, 3)).tolist()), 5017)[0] == 2
 
 
+def _f32_distances(q, p, sim):
+    """The kernel's arithmetic one fp32 operation at a time, left to right (csrc/mesh_eval.hip: the staging line and dist2)."""
+    q, p = q.astype(np.float32), p.astype(np.float32)
+    if sim is not None:
+        s, r, t = sim[0], sim[1:10].reshape(3, 3), sim[10:13]
+        p = np.stack([s * ((p[:, 0] * r[0, c] + p[:, 1] * r[1, c]) + p[:, 2] * r[2, c]) + t[c] for c in range(3)], 1)
+        assert p.dtype == np.float32
+    dx, dy, dz = (q[:, None, c] - p[None, :, c] for c in range(3))
+    d = (dx * dx + dy * dy) + dz * dz
+    assert d.dtype == np.float32
+    return d
+
+
+@pytest.mark.parametrize("span", [16, 2])
+def test_lattice_inputs_make_fp32_distances_exact(span):
+    """What lets the GPU tests ask for bit equality: on the generators' outputs, with and without the similarity, the fp32
+    distances equal float64's, d * 256 is an integer below 2^24 (so no product or partial sum was rounded, fused or not), and
+    exact ties are common."""
+    rng = np.random.default_rng(span)
+    q, p = er.lattice_points(rng, 300, span), er.lattice_points(rng, 3000, span)
+    assert q.dtype == np.float32 and np.abs(p).max() <= span and np.array_equal(p * 8, np.round(p * 8))
+    sims = [None, er.lattice_similarity(rng, det=-1), er.lattice_similarity(rng, det=1)] + [er.lattice_similarity(rng) for _ in range(8)]
+    for i, s in enumerate(er.SIM_SCALES):  # every scale, whatever the draw
+        sims[3 + i][0] = s
+    assert all(float(s[0]) in er.SIM_SCALES for s in sims[1:])
+    assert [round(float(np.linalg.det(s[1:10].reshape(3, 3).astype(np.float64)))) for s in sims[1:3]] == [-1, 1]
+    for sim in sims:
+        if sim is not None:
+            r = sim[1:10].reshape(3, 3).astype(np.float64)
+            assert np.array_equal(np.abs(r).sum(0), np.ones(3)) and np.array_equal(np.abs(r).sum(1), np.ones(3))
+            assert np.array_equal(sim[10:13] * 8, np.round(sim[10:13] * 8)) and np.abs(sim[10:13]).max() <= 16
+        d32 = _f32_distances(q, p, sim)
+        d64 = ((q.astype(np.float64)[:, None] - er.map_points(p, sim)[None]) ** 2).sum(-1)
+        assert np.array_equal(d32, d64)
+        assert np.array_equal(d64 * 256, np.round(d64 * 256)) and d64.max() * 256 < 2 ** 24
+    # the Z5 kernel's distances (no similarity, the set against itself) and the tie rate the exact tests rely on
+    idx, dist = er.nearest_exact(p, p, 9)
+    assert np.array_equal(np.take_along_axis(_f32_distances(p, p, None), idx, 1), dist)
+    assert (np.diff(dist, axis=1) == 0).any(1).mean() > (0.05 if span == 16 else 0.9)  # rows with a tie among their 9 nearest
+
+
+def test_nearest_exact_pads_and_breaks_ties_to_the_lower_index():
+    p = np.array([[0, 0, 0], [1, 0, 0], [1, 0, 0], [0, 2, 0]], np.float32)
+    idx, dist = er.nearest_exact(p[:1], p, 6)
+    assert idx.tolist() == [[0, 1, 2, 3, -1, -1]] and dist.tolist() == [[0, 1, 1, 4, np.inf, np.inf]]
+    idx, dist = er.nearest_exact(p, p, 2, self_exclude=True)
+    assert idx.tolist() == [[1, 2], [2, 0], [1, 0], [0, 1]] and dist[1:3, 0].tolist() == [0, 0]
+    idx, dist = er.nearest_exact(p, p[:0], 1)
+    assert (idx == -1).all() and np.isinf(dist).all()
+    p[1, 1] = np.nan  # a non-finite point is absent, a non-finite query finds nothing
+    idx, _ = er.nearest_exact(p, p, 2)
+    assert idx.tolist() == [[0, 2], [-1, -1], [2, 0], [3, 0]]
+    g = np.array([[0, 0, 0], [1, 0, 1], [0, 2, 2]], np.float32)  # distinct z: reversing it flips every comparison
+    assert er.Restatement.z5_knn(g, g, k=2) == 6 and er.Restatement.z5_knn(g, -g, k=2) == 0
+
+
 def test_eval_entries_reject_bad_arguments_without_a_gpu():
     lib = _lib.load()
     P = 1  # a non-null pointer value: validation fails before anything is dereferenced
@@ -102,10 +158,17 @@ def test_eval_entries_reject_bad_arguments_without_a_gpu():
         return lib.dad3d_eval_nearest(query, points, None, None, batch, q, n, k, flags, out, None, None, 0, None)
 
     for kw in (dict(batch=0), dict(q=0), dict(n=0), dict(batch=-1), dict(k=0), dict(k=9), dict(flags=4), dict(query=None),
-               dict(points=None), dict(out=None), dict(batch=70000)):
+               dict(points=None), dict(out=None), dict(batch=70000),
+               dict(flags=_lib.EVAL_SELF_EXCLUDE), dict(flags=_lib.EVAL_SELF_EXCLUDE, q=7, n=5)):  # "the same set": Q == N
         lib.dad3d_clear_error()
         assert nn(**kw) == _lib.E_INVALID, kw
-        assert lib.dad3d_last_error() != b""
+        # the argument check's own message: without a GPU a VALID call fails with the same status ("cannot select HIP device")
+        err = lib.dad3d_last_error()
+        assert b"dad3d_eval_nearest" in err and b"HIP device" not in err, (kw, err)
+        assert (b"SELF_EXCLUDE" in err) == (kw.get("flags") == _lib.EVAL_SELF_EXCLUDE), (kw, err)
+    lib.dad3d_clear_error()
+    assert lib.dad3d_project_vertices(P, P, P, P, 65536, 5, None, P, None, 0, None) == _lib.E_INVALID  # blockIdx.y carries the item
+    assert b"65536" in lib.dad3d_last_error()
     anchors = (np.ctypeslib.ctypes.c_int32 * 5)(1, 2, 3, 4, 5)
 
     def z5(batch=2, k=3669, anchors=anchors, n_anchors=5, g=P, w=P, counts=P):
@@ -115,5 +178,5 @@ def test_eval_entries_reject_bad_arguments_without_a_gpu():
                dict(counts=None), dict(anchors=None), dict(k=5)):  # K = 5: anchor 5 is out of range
         lib.dad3d_clear_error()
         assert z5(**kw) == _lib.E_INVALID, kw
-        assert lib.dad3d_last_error() != b""
+        assert b"dad3d_eval_z5_ranks" in lib.dad3d_last_error() and b"HIP device" not in lib.dad3d_last_error(), kw
     assert b"4096" in (lib.dad3d_clear_error(), z5(k=5000), lib.dad3d_last_error())[2]

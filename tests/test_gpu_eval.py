@@ -79,6 +79,225 @@ def test_nearest_self_exclusion_and_ties():
     assert idx_all.cpu().numpy()[0, 10, 0] == 10 and idx_all.cpu().numpy()[0, 400, 0] == 10
 
 
+# ---- exact: lattice inputs (eval_restatement.lattice_points) make every fp32 distance equal float64's, so the kernels are held
+# to the bit and to "ties to the lower index" with no near-tie exemption ---------------------------------------------------------
+def _dev(a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0", dtype)
+
+
+def _nearest_np(q, p, counts=None, sim=None, **kw):
+    out = evaluation.nearest(_dev(q), _dev(p), None if counts is None else _dev(np.asarray(counts, np.int32)),
+                             None if sim is None else _dev(sim), want_knn=True, **kw)
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def _assert_nearest_exact(got, q, p, k, counts=None, sim=None, self_exclude=False):
+    mind, idx, dist = got
+    for i in range(len(q)):
+        m = p.shape[1] if counts is None else min(max(int(counts[i]), 0), p.shape[1])
+        o, d = er.nearest_exact(q[i], p[i, :m], k, self_exclude, None if sim is None else sim[i])
+        assert np.array_equal(idx[i], o), (i, np.argwhere(idx[i] != o)[:5])
+        assert np.array_equal(dist[i], d), i
+        assert np.array_equal(mind[i], d[:, 0]), i
+
+
+# (k, N, Q, with a similarity): every k meets N = 1025 (one point past the LDS tile) and N < k (N == k for k = 1); the other N
+# and Q cross sparingly, with and without the similarity
+NEAREST_CASES = [(1, 1025, 257, True), (2, 1025, 257, True), (3, 1025, 257, True), (4, 1025, 257, True),
+                 (5, 1025, 257, True), (6, 1025, 257, True), (7, 1025, 257, True), (8, 1025, 257, True), (1, 1, 255, False),
+                 (2, 1, 1, True), (3, 1, 256, False), (4, 1, 257, True), (5, 1, 255, False), (6, 1, 1, True),
+                 (7, 1, 256, False), (8, 7, 257, True), (8, 1, 255, True), (4, 7, 256, True), (1, 7, 1, False),
+                 (5, 1023, 256, False), (1, 1024, 256, False), (8, 1024, 257, True), (2, 1023, 1, True),
+                 (3, 2049, 255, False), (1, 2049, 257, False), (6, 2049, 1, True), (7, 1024, 255, False)]
+
+
+@pytest.mark.parametrize("k,n,q,with_sim", NEAREST_CASES)
+def test_nearest_exact_on_lattice(k, n, q, with_sim):
+    rng = np.random.default_rng(1000 * k + n + q)
+    qs, ps = er.lattice_points(rng, q, batch=3), er.lattice_points(rng, n, batch=3)
+    sim = None
+    if with_sim:  # a reflection first: Procrustes may return one
+        sim = np.stack([er.lattice_similarity(rng, det=-1), er.lattice_similarity(rng), er.lattice_similarity(rng)])
+    _assert_nearest_exact(_nearest_np(qs, ps, sim=sim, k=k), qs, ps, k, sim=sim)
+
+
+def test_nearest_ragged_counts_are_clamped_and_rows_past_them_never_read():
+    rng = np.random.default_rng(77)
+    n, q, k = 1100, 257, 3
+    counts = np.array([0, -3, n + 5, 1024, 1025], np.int32)
+    qs, ps = er.lattice_points(rng, q, batch=5), er.lattice_points(rng, n, batch=5)
+    for i, c in enumerate(counts):
+        ps[i, max(int(c), 0):] = np.nan
+    sim = np.stack([er.lattice_similarity(rng) for _ in range(5)])
+    got = _nearest_np(qs, ps, counts, sim, k=k)
+    _assert_nearest_exact(got, qs, ps, k, counts, sim)
+    mind, idx, dist = got
+    assert (idx[:2] == -1).all() and np.isposinf(dist[:2]).all() and np.isposinf(mind[:2]).all()  # count 0 and below
+    assert idx[2].max() > 1025 and idx[3].max() <= 1023 and idx[4].max() <= 1024 and (idx[2:] >= 0).all()
+    assert np.isfinite(dist[2:]).all()
+
+
+@pytest.mark.parametrize("k", [1, 3])
+def test_nearest_duplicates_across_the_tile_edge_go_to_the_lower_index(k):
+    rng = np.random.default_rng(k)
+    ps = er.lattice_points(rng, 2100, batch=1)
+    ps[0, 1024] = ps[0, 2048] = ps[0, 1020]
+    qs = np.concatenate([ps[:, 1020:1021], ps[:, 1020:1021] + np.float32(0.125), er.lattice_points(rng, 254, batch=1)], 1)
+    got = _nearest_np(qs, ps, k=k)
+    _assert_nearest_exact(got, qs, ps, k)
+    assert got[1][0, 0].tolist() == [1020, 1024, 2048][:k] and (got[2][0, 0] == 0).all()
+    assert got[1][0, 1].tolist() == [1020, 1024, 2048][:k]  # the triple again, at a distance of 3/64
+
+
+@pytest.mark.parametrize("n", [1, 2, 1024, 1025, 2100])
+def test_nearest_self_exclusion_in_every_tile(n):
+    rng = np.random.default_rng(n)
+    ps = er.lattice_points(rng, n, batch=2)
+    if n >= 2:
+        ps[:, n - 1] = ps[:, 0]  # twins, in different tiles where there are two
+    if n > 1500:
+        ps[:, 1500] = ps[:, 1030]
+    got = _nearest_np(ps, ps, k=5, self_exclude=True)
+    _assert_nearest_exact(got, ps, ps, 5, self_exclude=True)
+    _, idx, dist = got
+    rows = np.arange(n)[None, :, None]
+    assert not (idx == rows).any() and not (idx[:, 1024:] == rows[:, 1024:]).any()  # rows past the first tile skip themselves too
+    if n == 1:
+        assert (idx == -1).all() and np.isposinf(dist).all() and np.isposinf(got[0]).all()
+    else:
+        assert (idx[:, 0, 0] == n - 1).all() and (idx[:, n - 1, 0] == 0).all() and (dist[:, [0, n - 1], 0] == 0).all()
+    if n > 1500:
+        assert (idx[:, 1030, 0] == 1500).all() and (idx[:, 1500, 0] == 1030).all() and (dist[:, [1030, 1500], 0] == 0).all()
+    # without the flag every point finds itself, or its lower twin
+    _, idx_all, _ = _nearest_np(ps, ps, k=1)
+    want = np.arange(n)
+    want[n - 1] = 0
+    if n > 1500:
+        want[1500] = 1030
+    assert np.array_equal(idx_all[..., 0], np.stack([want, want]))
+
+
+@pytest.mark.parametrize("with_sim", [False, True])
+def test_nearest_reports_only_finite_distances(with_sim):
+    """The rule of include/dad3d.h: a point at a NaN or infinite distance is skipped, a non-finite query gets -1 / +inf."""
+    rng = np.random.default_rng(31)
+    n, q, k = 1100, 300, 4
+    qs, ps = er.lattice_points(rng, q, batch=2), er.lattice_points(rng, n, batch=2)
+    ps[0, 5, 0] = ps[0, 1030, 2] = np.nan
+    ps[0, 1050, 1] = np.inf
+    ps[0, 7] = -np.inf
+    ps[1, :n - 2] = np.nan  # fewer finite points than k
+    qs[:, 3, 1] = np.nan
+    qs[:, 7, 0] = np.inf
+    sim = np.stack([er.lattice_similarity(rng), er.lattice_similarity(rng)]) if with_sim else None
+    got = _nearest_np(qs, ps, sim=sim, k=k)
+    _assert_nearest_exact(got, qs, ps, k, sim=sim)
+    mind, idx, dist = got
+    assert not np.isin(idx[0], [5, 7, 1030, 1050]).any() and (idx[0, [3, 7]] == -1).all() and np.isposinf(dist[0, [3, 7]]).all()
+    ok = np.setdiff1d(np.arange(q), [3, 7])
+    assert np.array_equal(np.sort(idx[1, ok], 1), np.tile([-1, -1, n - 2, n - 1], (len(ok), 1))) and not np.isnan(dist).any()
+    assert np.isposinf(mind[:, [3, 7]]).all() and np.isfinite(mind[:, ok]).all()
+
+
+Z5_SIZES = [1, 2, 3, 5, 8, 9, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096]
+
+
+def _z5_np(g, w, anchors):
+    counts, order = evaluation.z5_ranks(_dev(g), _dev(w), anchors=anchors, want_order=True)
+    return counts.cpu().numpy(), order.cpu().numpy()
+
+
+def _assert_z5_exact(g, w, anchors):
+    counts, order = _z5_np(g, w, anchors)
+    for j in range(len(g)):
+        with np.errstate(invalid="ignore"):
+            o, _ = er.Restatement.anchor_order(g[j], anchors)
+        assert np.array_equal(order[j], o), (j, anchors, np.argwhere(order[j] != o)[:5])
+        assert np.array_equal(counts[j], er.Restatement.z5_counts(g[j], w[j], o)), (j, anchors)
+
+
+def _z5_heads(rng, k):
+    """B = 3 head sets of falling span: most keys of the second tie, the third also repeats whole vertices."""
+    g = np.stack([er.lattice_points(rng, k, span) for span in (16, 2, 0.5)])
+    w = np.stack([er.lattice_points(rng, k, span) for span in (16, 2, 0.5)])
+    return g, w
+
+
+@pytest.mark.parametrize("k", Z5_SIZES)
+def test_z5_ranks_exact_on_lattice(k):
+    rng = np.random.default_rng(k)
+    g, w = _z5_heads(rng, k)
+    eight = tuple(int(a) % k for a in (k // 2, 0, k - 1, k // 2, 1, k // 3, 1023, 1024))  # one repeated, both ends
+    for anchors in [(0,), (k - 1,), eight] + ([evaluation.Z5_ANCHORS] if k > 5 else []):
+        _assert_z5_exact(g, w, anchors)
+
+
+@pytest.mark.parametrize("k", [9, 1025, 2049])
+def test_z5_ranks_non_finite_vertices_sort_last(k):
+    rng = np.random.default_rng(k)
+    g, w = _z5_heads(rng, k)
+    nan_at, inf_lo, inf_hi = k - 3, 0, k - 2  # none of them an anchor
+    g[0, nan_at, 0] = g[1, nan_at, 2] = np.nan
+    g[1:, inf_lo] = g[1:, inf_hi] = np.inf
+    w[2, 7, 2] = np.nan
+    anchors = evaluation.Z5_ANCHORS
+    _assert_z5_exact(g, w, anchors)
+    _, order = _z5_np(g, w, anchors)
+    assert (order[0, :, -1] == nan_at).all()  # the NaN takes the last rank
+    assert (order[1, :, -3:] == [inf_lo, inf_hi, nan_at]).all()  # the +inf pair by index behind every finite one, then the NaN
+    assert (order[2, :, -2:] == [inf_lo, inf_hi]).all()
+
+
+def test_z5_knn_on_lattice_equals_the_restatement(static):
+    """`evaluate_batch(z5="knn")` itself, its nearest call and its gather: an identity model-view makes the world mesh the
+    lattice mesh, and 2100 head positions in a shuffled order span three LDS tiles."""
+    rng = np.random.default_rng(2100)
+    b, n_head = 3, 2100
+    gt = np.stack([er.lattice_points(rng, 5023, span) for span in (16, 4, 1)])
+    pred = np.stack([er.lattice_points(rng, 5023, span) for span in (16, 4, 1)])
+    head = rng.permutation(5023)[:n_head]
+    eye = np.tile(np.eye(4, dtype=np.float32), (b, 1, 1))
+    kw = dict(landmarks=Landmarks68(static["faces"], device=torch.device("cuda", 0)), head_indices=_dev(head),
+              face_indices=_dev(np.arange(100)))
+    out = evaluation.evaluate_batch(_dev(gt), _dev(eye), _dev(eye), _dev(np.ones((b, 4))), _dev(np.zeros(b, np.float32)),
+                                    _dev(np.zeros((b, 68, 2), np.float32)), _dev(pred), _dev(np.full(b, 5023, np.int32)),
+                                    _dev(er.lattice_points(rng, 7, batch=b)), _dev(eye[:, :3, :3]), z5="knn", **kw)
+    z5 = out["z5"].cpu().numpy()
+    for i in range(b):
+        want = er.Restatement.z5_knn(-gt[i][head], pred[i][head])
+        count = z5[i] * n_head * 5
+        assert abs(count - round(count)) < 1e-6 and round(count) == want, (i, count, want)
+
+
+def test_z5_knn_on_goldens_matches_the_restatement(golden, restatement, static):
+    import train_batch_restatement as tbr
+
+    items = [0, 1, 2]
+    out = evaluation.evaluate_batch(*_batch_inputs(golden, items, static), **_kw(golden, static), z5="knn")
+    z5 = out["z5"].cpu().numpy()
+    head = restatement.head
+    n = len(head) * 5
+    for j, i in enumerate(items):
+        # the evaluator's GT frame: the fp32 k-ordered model-view product (test_gpu_projection.py holds the kernel to it)
+        g = -tbr.world(golden["gt_vertices"][i], golden["model_view"][i])[head, :3]
+        w = golden["pred_vertices"][i][head]
+        idx, d = er.nearest_exact(g, g, 6, self_exclude=True)  # one more: a tie at rank 5 shows
+        gap = np.diff(d, axis=1) <= NEAR_TIE * np.maximum(d[:, 1:], 1e-30)
+        tied = np.zeros_like(d, dtype=bool)
+        tied[:, 1:] |= gap
+        tied[:, :-1] |= gap
+        n_tied = int(tied[:, :5].sum())
+        want = int(restatement.knn_agreement(g, w, idx[:, :5]).sum())  # = Restatement.z5_knn(g, w), on the neighbours already found
+        count = z5[j] * n
+        print(f"item {i}: knn Z5 count {count:.6f}, float64 restatement {want}, near-tied entries {n_tied}")
+        assert n_tied <= 5
+        assert abs(count - round(count)) < 1e-6 and abs(round(count) - want) <= n_tied
+        # the kernel's own neighbours, outside those entries
+        _, got, _ = _nearest_np(g[None], g[None], k=5, self_exclude=True)
+        print(f"item {i}: kernel neighbours that differ from float64's: {int((got[0] != idx[:, :5]).sum())} (all among the near-tied)")
+        assert np.array_equal(got[0][~tied[:, :5]], idx[:, :5][~tied[:, :5]])
+
+
 @pytest.fixture(scope="module")
 def golden():
     return er.load_golden()
