@@ -1468,6 +1468,55 @@ dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t size, int chann
     return DAD3D_OK;
 }
 
+size_t dad3d_jpeg_max_bytes(int h, int w, int c, int subsampling) { return jpeg_encode_max_bytes(h, w, c, subsampling); }
+
+size_t dad3d_jpeg_encode_scratch_bytes(int batch, int h, int w, int c, int subsampling) {
+    return jpeg_encode_scratch_bytes(batch, h, w, c, subsampling);
+}
+
+static dad3d_status jpeg_encode_options_ok(const char* who, int h, int w, int c, int quality, int subsampling, int restart_interval) {
+    DAD3D_REQUIRE(c == 1 || c == 3, "%s: %d channels (1 grey, 3 RGB)", who, c);
+    DAD3D_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "%s: an image of %d x %d (1 .. 65535)", who, h, w);
+    DAD3D_REQUIRE(quality >= 1 && quality <= 100, "%s: quality %d outside 1 .. 100", who, quality);
+    DAD3D_REQUIRE(subsampling >= 0 && subsampling <= 2, "%s: subsampling %d (0 4:4:4, 1 4:2:2, 2 4:2:0)", who, subsampling);
+    DAD3D_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, "%s: a restart interval of %d MCUs (0 .. 65535)", who, restart_interval);
+    DAD3D_REQUIRE(jpeg_encode_max_bytes(h, w, c, subsampling) != 0, "%s: an image of %d x %d x %d has more than 2^22 blocks", who, h, w, c);
+    return DAD3D_OK;
+}
+
+dad3d_status dad3d_jpeg_encode(const uint8_t* images, int batch, int h, int w, int c, int quality, int subsampling, int restart_interval,
+                               uint8_t* out, size_t out_stride, int64_t* lengths, int32_t* flags, void* scratch, size_t scratch_bytes,
+                               int device, void* stream) {
+    const char* who = "dad3d_jpeg_encode";
+    DAD3D_REQUIRE(images && out && lengths && flags && scratch, "%s: null argument", who);
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "%s: batch %d outside 1 .. 65535", who, batch);
+    if (const dad3d_status st = jpeg_encode_options_ok(who, h, w, c, quality, subsampling, restart_interval)) return st;
+    const size_t worst = jpeg_encode_max_bytes(h, w, c, subsampling), need = jpeg_encode_scratch_bytes(batch, h, w, c, subsampling);
+    DAD3D_REQUIRE(out_stride >= worst, "%s: out_stride %zu is below the worst case of the shape (%zu bytes)", who, out_stride, worst);
+    DAD3D_REQUIRE(out_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "%s: out and out_stride must be 16-byte aligned", who);
+    DAD3D_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0 && (reinterpret_cast<uintptr_t>(lengths) & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(flags) & 3) == 0,
+                  "%s: lengths / flags / scratch are misaligned", who);
+    DAD3D_REQUIRE(scratch_bytes >= need, "%s: %zu bytes of scratch, %zu needed", who, scratch_bytes, need);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JpegEncodeArgs a{images, batch, h, w, c, quality, subsampling, restart_interval, out, out_stride, lengths, flags, scratch};
+    return launch_jpeg_encode(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_jpeg_encode_host(const uint8_t* image, int h, int w, int c, int quality, int subsampling, int restart_interval, uint8_t* out,
+                                    int64_t capacity, int64_t* length, int32_t* flag) {
+    const char* who = "dad3d_jpeg_encode_host";
+    DAD3D_REQUIRE(image && out && length && flag, "%s: null argument", who);
+    if (const dad3d_status st = jpeg_encode_options_ok(who, h, w, c, quality, subsampling, restart_interval)) return st;
+    DAD3D_REQUIRE(capacity >= (int64_t)jpeg_encode_max_bytes(h, w, c, subsampling), "%s: %lld bytes for a file of up to %zu", who,
+                  (long long)capacity, jpeg_encode_max_bytes(h, w, c, subsampling));
+    long long n = 0;
+    *flag = jpeg_encode_host(image, h, w, c, quality, subsampling, restart_interval, out, capacity, &n);
+    *length = n;
+    return DAD3D_OK;
+}
+
 size_t dad3d_json_parse_scratch_bytes(int64_t n_bytes) {
     return n_bytes < 1 || n_bytes > 0x7fffffffLL ? 0 : json_parse_scratch_bytes(n_bytes);
 }

@@ -595,6 +595,22 @@ dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s);
 // host: one file through jpeg_entropy.hpp / jpeg_idct.hpp; returns the flag (out null: the header alone)
 int jpeg_decode_host(const unsigned char* file, long long size, int channels, unsigned char* out, long long out_bytes, int* h, int* w, int* c,
                      bool* fits);
+// JPEG files written (jpeg_encode.hip): samples to coefficients per block, then per image the bits, byte stuffing and the framing
+struct JpegEncodeArgs {
+    const unsigned char* images;  // [B,h,w,c]
+    int batch, h, w, c, quality, subsampling, restart_interval;
+    unsigned char* out;           // [B][out_stride], 16-byte aligned rows
+    size_t out_stride;
+    int64_t* lengths;             // [B]
+    int32_t* flags;               // [B] DAD3D_JPEG_ENCODE_FLAG_*
+    void* scratch;                // jpeg_encode_scratch_bytes: coefficients [B][blocks][64] int16 | block records [B][blocks]
+};
+size_t jpeg_encode_max_bytes(int h, int w, int c, int subsampling);  // 0 for a shape outside the limits
+size_t jpeg_encode_scratch_bytes(int batch, int h, int w, int c, int subsampling);
+dad3d_status launch_jpeg_encode(const JpegEncodeArgs& a, hipStream_t s);
+// host: one image through jpeg_fdct.hpp / jpeg_huff_encode.hpp; returns the flag
+int jpeg_encode_host(const unsigned char* image, int h, int w, int c, int quality, int subsampling, int restart_interval, unsigned char* out,
+                     long long capacity, long long* length);
 // host: inflate.hpp on a list of byte ranges; returns the flag
 int inflate_host(const unsigned char* const* ranges, const long long* range_bytes, int n_ranges, unsigned char* out, long long capacity,
                  long long* length);

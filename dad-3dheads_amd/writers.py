@@ -15,6 +15,8 @@ and formatted here (`_json_item_host`). `JsonSaver`, `get_flame_params` and `fla
 
 Images (`ImageSaver` of the demo, demo_utils.py:122-127) are written as PNG: a uint8 CUDA batch is filtered, deflated and framed on
 the GPU (`PngEncoder`, csrc/png_encode.hip; `png_batch`, `save_png_batch`), a host image by PIL (`ImageSaver`).
+Where a lossy file is wanted -- photographs with overlays, renders over a background -- `JpegEncoder` (csrc/jpeg_encode.hip,
+DESIGN.md 4.20; `jpeg_batch`, `save_jpeg_batch`) writes baseline JPEG on the GPU with the bytes PIL writes for the same options.
 """
 from __future__ import annotations
 
@@ -650,6 +652,168 @@ def save_png_batch(images: Any, paths: Sequence[str], encoder: str = "auto") -> 
         blocks = _png_encoder_for(images).encode(images.detach()).to_host()
     else:
         blocks = _png_host_batch(images)
+    for block, path in zip(blocks, paths):
+        with open(path, "wb") as f:
+            f.write(block)
+
+
+def _jpeg_options(channels: int, height: int, width: int, quality: int = 75, subsampling: Optional[int] = None,
+                  restart_marker_rows: int = 0) -> Tuple[int, int, int, int]:
+    """(quality, subsampling, restart_marker_rows, restart interval in MCUs) as libjpeg takes them: `None` is PIL's default for the
+    mode (4:2:0 for RGB); grey has no subsampling; the interval is rows x MCUs per row, and a product above 65535, which libjpeg
+    would clamp, is refused."""
+    quality, rows = int(quality), int(restart_marker_rows)
+    subsampling = 0 if channels == 1 else 2 if subsampling is None else int(subsampling)
+    if channels not in (1, 3):
+        raise ValueError(f"JPEG: {channels} channels (1 grey, 3 RGB)")
+    if not 1 <= quality <= 100:
+        raise ValueError(f"JPEG: quality {quality} outside 1 .. 100")
+    if subsampling not in (0, 1, 2):
+        raise ValueError(f"JPEG: subsampling {subsampling} (0 4:4:4, 1 4:2:2, 2 4:2:0)")
+    if rows < 0:
+        raise ValueError(f"JPEG: restart_marker_rows {rows} is negative")
+    across = 2 if channels == 3 and subsampling else 1
+    mcus_per_row = ((int(width) + 7) // 8 + across - 1) // across
+    if rows * mcus_per_row > 65535:
+        raise ValueError(f"JPEG: restart_marker_rows {rows} x {mcus_per_row} MCUs per row passes the 65535 MCUs of a restart interval")
+    return quality, subsampling, rows, rows * mcus_per_row
+
+
+def _jpeg_host(image: np.ndarray, **options: Any) -> bytes:
+    """One image on the host with PIL: uint8 [H,W] or [H,W,1] (mode L) or [H,W,3] (RGB); `quality`, `subsampling`,
+    `restart_marker_rows` as `JpegEncoder` takes them."""
+    from PIL import Image
+
+    arr = np.ascontiguousarray(image)
+    if arr.ndim == 2:
+        arr = arr[:, :, None]
+    if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] not in (1, 3):
+        raise ValueError(f"image: expected uint8 [H,W,C] with C 1 or 3, got {arr.dtype} {arr.shape}")
+    quality, subsampling, rows, _ = _jpeg_options(arr.shape[2], arr.shape[0], arr.shape[1], **options)
+    buf = io.BytesIO()
+    if arr.shape[2] == 1:
+        Image.fromarray(arr[:, :, 0]).save(buf, "JPEG", quality=quality, restart_marker_rows=rows)
+    else:
+        Image.fromarray(arr).save(buf, "JPEG", quality=quality, subsampling=subsampling, restart_marker_rows=rows)
+    return buf.getvalue()
+
+
+class JpegData(_DeviceText):
+    """What `JpegEncoder.encode` returns: the JPEG files of `batch` images in HBM, the contract of `PngData`. A flagged item (the
+    encoder's own consistency check, or a flag the caller ORed in) is encoded on the host with PIL, which writes the same bytes."""
+
+    def __init__(self, encoder: "JpegEncoder", images: torch.Tensor, batch: int):
+        super().__init__(encoder, batch)
+        self.images = images
+
+    def _host_item(self, b: int) -> bytes:
+        e = self.formatter
+        return _jpeg_host(self.images[b].detach().cpu().numpy(), quality=e.quality, subsampling=e.subsampling,
+                          restart_marker_rows=e.restart_marker_rows)
+
+
+class JpegEncoder(_TextBuffers):
+    """A batch of uint8 images `[B,H,W,C]`, C = 1 (grey) or 3 (RGB), as baseline JPEG files made on the GPU (`dad3d_jpeg_encode`,
+    csrc/jpeg_encode.hip), byte-equal to `Image.fromarray(img).save(buf, "JPEG", quality=quality,
+    subsampling=subsampling, restart_marker_rows=restart_marker_rows)`. `subsampling` 0 / 1 / 2 is 4:4:4 / 4:2:2 / 4:2:0; `None` is
+    PIL's default for the mode. A restart marker per MCU row (`restart_marker_rows=1`) is what `jpeg_reader.JpegDecoder` reads in
+    parallel.
+
+    `reserve(batch)` allocates the device file buffer (`batch` rows of `dad3d_jpeg_max_bytes`), lengths, flags, scratch and one
+    pinned host buffer; `encode(images)` launches two kernels on the current stream with no allocation and no sync once the batch
+    fits (capturable in a graph); `JpegData.to_host()` brings the files over."""
+
+    def __init__(self, height: int, width: int, channels: int, quality: int = 75, subsampling: Optional[int] = None,
+                 restart_marker_rows: int = 0, device: Optional[int] = None):
+        self.height, self.width, self.channels = int(height), int(width), int(channels)
+        self.quality, self.subsampling, self.restart_marker_rows, self.restart_interval = _jpeg_options(
+            self.channels, self.height, self.width, quality, subsampling, restart_marker_rows)
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.torch_device = torch.device("cuda", self.device)
+        worst = self._lib.dad3d_jpeg_max_bytes(self.height, self.width, self.channels, self.subsampling)
+        if worst == 0:
+            raise ValueError(f"JpegEncoder: cannot encode images of {self.height} x {self.width} x {self.channels} (sides 1 .. 65535, at "
+                             "most 2^22 blocks)")
+        self.stride = (worst + 15) // 16 * 16
+        self.capacity = 0
+
+    def reserve(self, batch: int) -> None:
+        batch = max(int(batch), 1)
+        if batch <= self.capacity:
+            return
+        self._reserve_buffers(batch, self._lib.dad3d_jpeg_encode_scratch_bytes(batch, self.height, self.width, self.channels,
+                                                                                self.subsampling))
+
+    def encode(self, images: torch.Tensor, extra_flags: Optional[torch.Tensor] = None) -> JpegData:
+        """`images [B,H,W,C]` -> `JpegData`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
+        kernels: a non-zero entry sends that item to the host encoder."""
+        shape = (self.height, self.width, self.channels)
+        if (not isinstance(images, torch.Tensor) or images.device != self.torch_device or images.dtype != torch.uint8
+                or not images.is_contiguous() or images.ndim != 4 or tuple(images.shape[1:]) != shape):
+            raise ValueError(f"images: expected a contiguous uint8 tensor [B,{shape[0]},{shape[1]},{shape[2]}] on {self.torch_device}, got "
+                             f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))} on "
+                             f"{getattr(images, 'device', 'the host')}"
+                             + ("" if not isinstance(images, torch.Tensor) or images.is_contiguous() else " (not contiguous)"))
+        b = images.shape[0]
+        if b == 0:
+            self.reserve(1)
+            return JpegData(self, images, 0)
+        self.reserve(b)
+        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
+        _lib.check(self._lib.dad3d_jpeg_encode(images.data_ptr(), b, *shape, self.quality, self.subsampling, self.restart_interval,
+                                               self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
+                                               self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), self.device,
+                                               stream))
+        if extra_flags is not None:
+            self._flags[:b].bitwise_or_(extra_flags)
+        return JpegData(self, images, b)
+
+
+_jpeg_encoders: Dict[Tuple[int, int, int, int, int, int, int], JpegEncoder] = {}
+
+
+def _jpeg_encoder_for(images: torch.Tensor, **options: Any) -> JpegEncoder:
+    h, w, c = (int(v) for v in images.shape[1:])
+    quality, subsampling, rows, _ = _jpeg_options(c, h, w, **options)
+    key = (images.device.index, h, w, c, quality, subsampling, rows)
+    enc = _jpeg_encoders.get(key)
+    if enc is None:
+        enc = _jpeg_encoders[key] = JpegEncoder(h, w, c, quality, subsampling, rows, device=key[0])
+    return enc
+
+
+def _jpeg_on_device_path(images: Any) -> bool:
+    return (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.ndim == 4
+            and images.shape[3] in (1, 3) and images.shape[1] >= 1 and images.shape[2] >= 1 and images.is_contiguous())
+
+
+def _jpeg_host_batch(images: Any, **options: Any) -> List[bytes]:
+    arr = images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
+    return [_jpeg_host(a, **options) for a in arr]
+
+
+def jpeg_batch(images: Any, **options: Any) -> List[bytes]:
+    """`images [B,H,W,C]` uint8, C = 1 or 3 -> the bytes of one baseline JPEG file per image; `quality`, `subsampling` and
+    `restart_marker_rows` as `JpegEncoder` takes them. A contiguous uint8 CUDA tensor is encoded on the GPU; anything else (a numpy
+    array, a CPU tensor) by PIL on the host. Both write the same bytes."""
+    if _jpeg_on_device_path(images):
+        return [bytes(x) for x in _jpeg_encoder_for(images, **options).encode(images.detach()).to_host()]
+    return _jpeg_host_batch(images, **options)
+
+
+def save_jpeg_batch(images: Any, paths: Sequence[str], encoder: str = "auto", **options: Any) -> None:
+    """`images [B,H,W,C]` uint8 -> one `.jpg` per image. A contiguous uint8 CUDA tensor with C in {1, 3} is encoded on the GPU
+    (`JpegEncoder`; a flagged image is encoded here) and only the files cross to the host; a numpy array, a CPU tensor, a
+    non-contiguous tensor or `encoder="host"` takes the host path: one copy of the pixels, PIL per image. The bytes are the same."""
+    if encoder not in ("auto", "host"):
+        raise ValueError(f"encoder: expected 'auto' or 'host', got {encoder!r}")
+    assert len(images) == len(paths)
+    if encoder == "auto" and _jpeg_on_device_path(images):
+        blocks = _jpeg_encoder_for(images, **options).encode(images.detach()).to_host()
+    else:
+        blocks = _jpeg_host_batch(images, **options)
     for block, path in zip(blocks, paths):
         with open(path, "wb") as f:
             f.write(block)

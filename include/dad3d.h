@@ -774,6 +774,44 @@ DAD3D_EXPORT dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t si
                                                  int32_t* w, int32_t* c, int32_t* flag);
 
 /* ---------------------------------------------------------------------------------------------
+ * Images as baseline JPEG files made on the device, byte-equal to
+ *   PIL.Image.fromarray(img).save(buf, "JPEG", quality=q, subsampling=s, restart_marker_rows=r)
+ * with libjpeg-turbo behind PIL (mode RGB for c = 3, mode L for c = 1): its 16-bit fixed-point RGB -> YCbCr, edge replication, the
+ * h2v1 / h2v2 box filters with their alternating bias, the "islow" integer forward DCT, division by 8 Q rounded half away from zero,
+ * the standard Huffman tables, and libjpeg's order of header segments (SOI, JFIF APP0 with units 0 and density 1 x 1, a DQT per
+ * table, SOF0, a DHT per table, DRI when there is an interval, SOS).
+ *   images   DEVICE [batch,h,w,c] uint8, contiguous, c = 1 (grey) or 3 (RGB); h, w in 1 .. 65535 and at most 2^22 blocks per image
+ *   quality  1 .. 100: libjpeg's scaling of the Annex K tables, forced to baseline (1 .. 255)
+ *   subsampling  0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0; ignored for c = 1
+ *   restart_interval  MCUs between restart markers, 0 .. 65535, 0 for none (libjpeg's restart_in_rows is rows x MCUs per row; the
+ *            caller multiplies, and refuses a product above 65535 where libjpeg would clamp it)
+ *   out      DEVICE [batch][out_stride] bytes, 16-byte aligned; out_stride a multiple of 16, at least dad3d_jpeg_max_bytes(h, w, c,
+ *            subsampling). Item b's file is out[b * out_stride .. + lengths[b]); bytes behind it are left as they were
+ *   lengths  DEVICE [batch] int64   flags DEVICE [batch] int32   scratch DEVICE dad3d_jpeg_encode_scratch_bytes(..) bytes, 16-byte aligned
+ * dad3d_jpeg_max_bytes is a bound no file passes: the header (at most 629 bytes) + per block of the scan, dummy blocks included, twice
+ * 208 bytes -- a block's worst is a DC code of 11 bits with 11 value bits and 63 AC codes of 16 bits with 10 value bits each, 1660
+ * bits, rounded up to bytes per block so that the sum covers the padding of every interval, and byte stuffing (FF -> FF 00) at most
+ * doubles entropy bytes -- + 4 bytes per MCU (a restart marker behind every interval of the shortest interval, EOI behind the last;
+ * twice two bytes because the device checks each chunk against the row as if every byte of it were stuffed) + 16.
+ * flags[b] == 0 unless the encoder's own consistency check failed (DAD3D_JPEG_ENCODE_FLAG_INTERNAL: a coefficient outside baseline's
+ * categories, or a file that would pass its row; length 0, the caller encodes that item on the host). Two launches on `stream`, no
+ * allocation, no synchronisation: can be captured into a graph. Arguments (NULL, c not 1 or 3, h or w outside 1 .. 65535, more than
+ * 2^22 blocks, batch outside 1 .. 65535, quality outside 1 .. 100, subsampling outside 0 .. 2, an interval outside 0 .. 65535, a
+ * stride or scratch below what the shape needs, alignment) are validated before any device work -> DAD3D_E_INVALID. The *_max_bytes /
+ * *_scratch_bytes calls are host-only and return 0 for such a shape.
+ * dad3d_jpeg_encode_host runs the same routines on one image on the CPU, HOST pointers: the file goes to out[0 .. *length),
+ * capacity >= dad3d_jpeg_max_bytes; *flag as above.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_JPEG_ENCODE_FLAG_INTERNAL 0x1
+DAD3D_EXPORT size_t dad3d_jpeg_max_bytes(int h, int w, int c, int subsampling);
+DAD3D_EXPORT size_t dad3d_jpeg_encode_scratch_bytes(int batch, int h, int w, int c, int subsampling);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_encode(const uint8_t* images, int batch, int h, int w, int c, int quality, int subsampling,
+                                            int restart_interval, uint8_t* out, size_t out_stride, int64_t* lengths, int32_t* flags,
+                                            void* scratch, size_t scratch_bytes, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_encode_host(const uint8_t* image, int h, int w, int c, int quality, int subsampling, int restart_interval,
+                                                 uint8_t* out, int64_t capacity, int64_t* length, int32_t* flag);
+
+/* ---------------------------------------------------------------------------------------------
  * Reading JSON back: the large arrays of numbers of a document lifted into float64 on the device, with the doubles `json.load` makes
  * (dad_3dheads_benchmark/benchmark.py:177-180, the two `json.load` calls of `DADEvaluator.__call__`). The device lifts only what it has
  * validated and converted exactly; every other byte stays with the host parser, so a result can never differ from `json.load`.
