@@ -32,6 +32,8 @@ PNG_SEGMENT_BYTES, ZLIB_SECOND_DISTANCE, PNG_FLAG_INTERNAL, DEFLATE_HEADER_BYTES
 PNG_DECODE_DESC_INTS, ZLIB_DECODE_DESC_INTS, PNG_DECODE_INFO_SEGMENTED = 12, 4, 0x1
 PNG_DECODE_FLAG_MALFORMED, PNG_DECODE_FLAG_UNSUPPORTED, PNG_DECODE_FLAG_OVERFLOW = 0x1, 0x2, 0x4
 JPEG_DECODE_DESC_INTS, JPEG_DECODE_GRID_INTS, JPEG_DECODE_FLAG_MALFORMED, JPEG_DECODE_FLAG_UNSUPPORTED = 12, 3, 0x1, 0x2
+JPEG_DECODE_SYNC_DESC_INTS, JPEG_DECODE_SYNC_GRID_INTS = 16, 4
+JPEG_DECODE_SYNC_MODE_SEGMENTS, JPEG_DECODE_SYNC_MODE_VERIFIED, JPEG_DECODE_SYNC_MODE_SERIAL = 0, 1, 2
 JPEG_ENCODE_FLAG_INTERNAL = 0x1
 OVERLAY_MAX_COORD = 8192
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
@@ -169,6 +171,9 @@ SIGNATURES = {
     "dad3d_jpeg_decode_scratch_bytes": (C.c_size_t, [_P, _I, _P]),
     "dad3d_jpeg_decode": (_I, [_P, C.c_size_t, _P, _I, _P, _P, C.c_size_t, _P, _P, C.c_size_t, _I, _P]),
     "dad3d_jpeg_decode_host": (_I, [_P, C.c_int64, _I, _P, C.c_int64, _P, _P, _P, _P]),
+    "dad3d_jpeg_decode_sync_scratch_bytes": (C.c_size_t, [_P, _I, _P, _I]),
+    "dad3d_jpeg_decode_sync": (_I, [_P, C.c_size_t, _P, _I, _P, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
+    "dad3d_jpeg_decode_sync_host": (_I, [_P, C.c_int64, _I, _I, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "dad3d_jpeg_max_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "dad3d_jpeg_encode_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "dad3d_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),

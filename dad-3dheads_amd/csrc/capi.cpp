@@ -1468,6 +1468,55 @@ dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t size, int chann
     return DAD3D_OK;
 }
 
+size_t dad3d_jpeg_decode_sync_scratch_bytes(int64_t* desc, int batch, int32_t* grid, int piece_bytes) {
+    if (!desc || !grid || batch < 1 || batch > 65535) return 0;
+    int dims[DAD3D_JPEG_DECODE_SYNC_GRID_INTS] = {0, 0, 0, 0};
+    const size_t bytes = jpeg_decode_sync_layout(reinterpret_cast<long long*>(desc), batch, dims, piece_bytes);
+    for (int i = 0; i < DAD3D_JPEG_DECODE_SYNC_GRID_INTS; ++i) grid[i] = dims[i];
+    return bytes;
+}
+
+dad3d_status dad3d_jpeg_decode_sync(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, const int32_t* grid, int piece_bytes,
+                                    uint8_t* out, size_t out_bytes, int32_t* flags, int32_t* info, void* scratch, size_t scratch_bytes, int device,
+                                    void* stream) {
+    DAD3D_REQUIRE(piece_bytes >= 16 && piece_bytes <= 256 && (piece_bytes & (piece_bytes - 1)) == 0,
+                  "dad3d_jpeg_decode_sync: pieces of %d bytes (a power of two, 16 .. 256)", piece_bytes);
+    DAD3D_REQUIRE(batch >= 1 && batch <= 65535, "dad3d_jpeg_decode_sync: batch %d outside 1 .. 65535", batch);
+    DAD3D_REQUIRE(files && desc && grid && out && flags && info && scratch, "dad3d_jpeg_decode_sync: null argument");
+    DAD3D_REQUIRE(grid[0] >= 1 && grid[0] <= (1 << 22) && grid[1] >= 1 && grid[1] <= (1 << 22) && grid[2] >= 1 && grid[2] <= (1 << 28) && grid[3] >= 1 &&
+                      grid[3] <= (1 << 19),
+                  "dad3d_jpeg_decode_sync: a grid of %d segments, %d blocks, %d pixels, %d groups (dad3d_jpeg_decode_sync_scratch_bytes gives it)", grid[0],
+                  grid[1], grid[2], grid[3]);
+    DAD3D_REQUIRE((long long)batch * grid[0] <= 64ll * 0x7fffffffll, "dad3d_jpeg_decode_sync: %d files of up to %d segments pass the grid", batch,
+                  grid[0]);
+    DAD3D_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && reinterpret_cast<uintptr_t>(desc) % 8 == 0,
+                  "dad3d_jpeg_decode_sync: scratch must be 16-byte aligned, desc 8-byte aligned");
+    DAD3D_REQUIRE(scratch_bytes >= (size_t)batch * jpeg_decode_state_bytes(), "dad3d_jpeg_decode_sync: %zu bytes of scratch for a batch of %d",
+                  scratch_bytes, batch);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    JpegDecodeSyncArgs a{{files, files_bytes, reinterpret_cast<const long long*>(desc), batch, grid[0], grid[1], grid[2], out, out_bytes, flags,
+                          static_cast<unsigned char*>(scratch), scratch_bytes},
+                         piece_bytes, grid[3], info};
+    return launch_jpeg_decode_sync(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_jpeg_decode_sync_host(const uint8_t* file, int64_t size, int channels, int piece_bytes, uint8_t* out, int64_t out_bytes, int32_t* h,
+                                         int32_t* w, int32_t* c, int32_t* flag, int32_t* info) {
+    DAD3D_REQUIRE(size >= 0 && (file || size == 0) && h && w && c && flag && info && out_bytes >= 0,
+                  "dad3d_jpeg_decode_sync_host: null or negative argument");
+    DAD3D_REQUIRE(channels == 0 || channels == 1 || channels == 3, "dad3d_jpeg_decode_sync_host: %d channels (0 the file's own, 1, 3)", channels);
+    DAD3D_REQUIRE(piece_bytes >= 16 && piece_bytes <= 256 && (piece_bytes & (piece_bytes - 1)) == 0,
+                  "dad3d_jpeg_decode_sync_host: pieces of %d bytes (a power of two, 16 .. 256)", piece_bytes);
+    int hh = 0, ww = 0, cc = 0, what[4] = {0, 0, 0, 0};
+    bool fits = true;
+    *flag = jpeg_decode_host(file, size, channels, out, out_bytes, &hh, &ww, &cc, &fits, piece_bytes, what);
+    *h = hh, *w = ww, *c = cc;
+    for (int i = 0; i < 4; ++i) info[i] = what[i];
+    DAD3D_REQUIRE(fits, "dad3d_jpeg_decode_sync_host: a %d x %d x %d image does not fit %lld bytes", hh, ww, cc, (long long)out_bytes);
+    return DAD3D_OK;
+}
+
 size_t dad3d_jpeg_max_bytes(int h, int w, int c, int subsampling) { return jpeg_encode_max_bytes(h, w, c, subsampling); }
 
 size_t dad3d_jpeg_encode_scratch_bytes(int batch, int h, int w, int c, int subsampling) {

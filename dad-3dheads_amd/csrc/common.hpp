@@ -592,9 +592,20 @@ struct JpegDecodeArgs {
 size_t jpeg_decode_layout(long long* desc_host, int batch, int* grid);
 size_t jpeg_decode_state_bytes();
 dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s);
-// host: one file through jpeg_entropy.hpp / jpeg_idct.hpp; returns the flag (out null: the header alone)
+dad3d_status launch_jpeg_scan(const JpegDecodeArgs& a, hipStream_t s);    // the scan alone, and the IDCT and the colour launch alone:
+dad3d_status launch_jpeg_pixels(const JpegDecodeArgs& a, hipStream_t s);  // around the entropy stage of jpeg_decode_sync.hip
+// host: one file through jpeg_entropy.hpp / jpeg_idct.hpp; returns the flag (out null: the header alone). piece_bytes != 0: the
+// entropy stage of jpeg_sync.hpp, which fills info[4] (mode, pieces, groups, 0)
 int jpeg_decode_host(const unsigned char* file, long long size, int channels, unsigned char* out, long long out_bytes, int* h, int* w, int* c,
-                     bool* fits);
+                     bool* fits, int piece_bytes = 0, int* info = nullptr);
+// JPEG files read back, the entropy data of a file without restart markers decoded in pieces (jpeg_decode_sync.hip, jpeg_sync.hpp)
+struct JpegDecodeSyncArgs {
+    JpegDecodeArgs base;  // desc: DEVICE [B][DAD3D_JPEG_DECODE_DESC_INTS] and behind them [B][4]: the piece and group tables
+    int piece_bytes, max_groups;
+    int32_t* info;        // [B][4]
+};
+size_t jpeg_decode_sync_layout(long long* desc_host, int batch, int* grid, int piece_bytes);
+dad3d_status launch_jpeg_decode_sync(const JpegDecodeSyncArgs& a, hipStream_t s);
 // JPEG files written (jpeg_encode.hip): samples to coefficients per block, then per image the bits, byte stuffing and the framing
 struct JpegEncodeArgs {
     const unsigned char* images;  // [B,h,w,c]

@@ -14,6 +14,7 @@
 // A kernel leaves a file alone once its flag is set; the flags are the only words two lanes may both write (atomicOr).
 #include "common.hpp"
 #include "jpeg_idct.hpp"
+#include "jpeg_sync.hpp"
 
 namespace dad3d {
 namespace {
@@ -183,14 +184,15 @@ size_t jpeg_decode_layout(long long* desc, int batch, int* grid) {
 
 size_t jpeg_decode_state_bytes() { return sizeof(JpegFile); }
 
-dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s) {
+// the first and the last two of the four launches, which csrc/jpeg_decode_sync.hip puts around an entropy stage of its own
+dad3d_status launch_jpeg_scan(const JpegDecodeArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(a.batch), dim3(kWave), 0, s, a.files, a.files_bytes, a.desc, a.batch, a.out_bytes, a.scratch,
                        a.scratch_bytes, a.flags);
     DAD3D_HIP_TRY(hipGetLastError());
-    const int first_waves = (a.batch + kWave - 1) / kWave, more_waves = (a.max_segments - 1 + kWave - 1) / kWave;
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(first_waves + a.batch * more_waves), dim3(kWave), 0, s, a.files, a.desc, a.batch, first_waves,
-                       more_waves, a.scratch, a.flags);
-    DAD3D_HIP_TRY(hipGetLastError());
+    return DAD3D_OK;
+}
+
+dad3d_status launch_jpeg_pixels(const JpegDecodeArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((a.max_blocks + kWave - 1) / kWave, a.batch), dim3(kWave), 0, s, a.desc, a.scratch, a.flags);
     DAD3D_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3((a.max_pixels + kColourThreads - 1) / kColourThreads, a.batch), dim3(kColourThreads), 0, s, a.desc,
@@ -199,9 +201,20 @@ dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s) {
     return DAD3D_OK;
 }
 
-// one file on the CPU through the same headers; `out` may be null to read the header alone. Returns the flag.
+dad3d_status launch_jpeg_decode(const JpegDecodeArgs& a, hipStream_t s) {
+    const dad3d_status scanned = launch_jpeg_scan(a, s);
+    if (scanned != DAD3D_OK) return scanned;
+    const int first_waves = (a.batch + kWave - 1) / kWave, more_waves = (a.max_segments - 1 + kWave - 1) / kWave;
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(first_waves + a.batch * more_waves), dim3(kWave), 0, s, a.files, a.desc, a.batch, first_waves,
+                       more_waves, a.scratch, a.flags);
+    DAD3D_HIP_TRY(hipGetLastError());
+    return launch_jpeg_pixels(a, s);
+}
+
+// one file on the CPU through the same headers; `out` may be null to read the header alone. piece_bytes != 0: the entropy stage in
+// pieces, which fills info[4]. Returns the flag.
 int jpeg_decode_host(const unsigned char* file, long long size, int channels, unsigned char* out, long long out_bytes, int* h, int* w, int* c,
-                     bool* fits) {
+                     bool* fits, int piece_bytes, int* info) {
     JpegFile* F = new JpegFile();
     *h = *w = *c = 0, *fits = true;
     int flag = jpeg_parse_header(file, size, *F);
@@ -216,7 +229,10 @@ int jpeg_decode_host(const unsigned char* file, long long size, int channels, un
             short* coefs = new short[(size_t)blocks * 64];
             unsigned char* planes = new unsigned char[(size_t)blocks * 64];
             flag = jpeg_find_segments(file, size, *F, segs, cap);
-            for (int seg = 0; !flag && seg < F->nseg; ++seg) flag = jpeg_decode_segment(file, *F, seg, segs[seg], coefs);
+            if (!flag && piece_bytes)  // the entropy stage of csrc/jpeg_sync.hpp
+                flag = jpeg_sync_entropy_host(file, *F, segs, piece_bytes, coefs, info);
+            else
+                for (int seg = 0; !flag && seg < F->nseg; ++seg) flag = jpeg_decode_segment(file, *F, seg, segs[seg], coefs);
             const int total = flag ? 0 : jpeg_total_blocks(*F);
             for (int t = 0; !flag && t < total; ++t) {
                 const int comp = t < jpeg_component_base(*F, 1) ? 0 : t < jpeg_component_base(*F, 2) ? 1 : 2;

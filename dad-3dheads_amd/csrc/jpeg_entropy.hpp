@@ -271,7 +271,8 @@ struct JpegBits {
     }
 };
 
-DAD3D_HD int jpeg_symbol(JpegBits& in, const JpegHuff& t) {  // -1: a code no table assigns
+template <class Bits>  // JpegBits, or the reader of jpeg_sync.hpp that also knows where in the file it stands
+DAD3D_HD int jpeg_symbol(Bits& in, const JpegHuff& t) {  // -1: a code no table assigns
     const unsigned v = in.peek16();
     const unsigned quick = t.look[v >> 8];  // a code of eight bits or fewer: one read
     if (quick) {

@@ -203,14 +203,15 @@ class FaceMeshPredictor:
                             "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]})
         return results
 
-    def predict_files(self, sources: Sequence[Any], device_outputs: bool = False) -> List[Dict[str, Any]]:
+    def predict_files(self, sources: Sequence[Any], device_outputs: bool = False, jpeg_entropy: str = "segments") -> List[Dict[str, Any]]:
         """`predict_batch` fed with image files (paths or bytes, any sizes): PNG files and baseline JPEG files are decoded to RGB
         on the device (png_reader.PngDecoder, jpeg_reader.JpegDecoder, channels=3) and the decoded images go to the preprocess launch
         where they lie, so no decoded pixel crosses the bus. A source that starts FF D8 goes to the JPEG decoder, every other one
         to the PNG decoder; where both kinds are present their flags are read in one wait. A file a decoder flags (a progressive
         JPEG, a palette PNG, ...) is decoded by PIL on the host and uploaded. The result dicts are those of `predict_batch` on
         `np.asarray(Image.open(f).convert("RGB"))`, in the order of `sources`; what follows the preprocess launch is
-        `predict_batch`'s own code."""
+        `predict_batch`'s own code. `jpeg_entropy` is `JpegDecoder`'s `entropy`: "sync" decodes a JPEG file without restart markers
+        in pieces, to the same pixels."""
         from .jpeg_reader import SOI, JpegDecoder
         from .png_reader import PngDecoder, _bytes_of
 
@@ -220,13 +221,14 @@ class FaceMeshPredictor:
             decoded = PngDecoder(self.device).decode(files, channels=3).tensors()  # alive until the launch has consumed them
         else:
             pngs = [i for i in range(len(files)) if i not in set(jpegs)]
-            jpeg = JpegDecoder(self.device)._launch([files[i] for i in jpegs], 3)
+            jpeg = JpegDecoder(self.device, entropy=jpeg_entropy)._launch([files[i] for i in jpegs], 3)
             png = PngDecoder(self.device)._launch([files[i] for i in pngs], 3) if pngs else None
-            words = [t for t in ((jpeg.dev_flags,) + ((png.dev_flags, png.dev_info) if png else ())) if t is not None]
+            jpeg_words = jpeg.words()
+            words = [t for t in (tuple(jpeg_words) + ((png.dev_flags, png.dev_info) if png else ())) if t is not None]
             got = torch.cat(words).cpu().numpy() if words else np.zeros(0, np.int32)  # the one wait
-            nj, npng = len(jpeg.on_device), len(png.on_device) if png else 0
+            nj, npng = sum(t.numel() for t in jpeg_words), len(png.on_device) if png else 0
             decoded = [None] * len(files)
-            for i, t in zip(jpegs, jpeg.finish(got[:nj]).tensors()):
+            for i, t in zip(jpegs, jpeg.finish(*jpeg.split(got[:nj])).tensors()):
                 decoded[i] = t
             if png:
                 for i, t in zip(pngs, png.finish(got[nj:nj + npng], got[nj + npng:nj + 2 * npng]).tensors()):

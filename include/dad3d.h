@@ -774,6 +774,39 @@ DAD3D_EXPORT dad3d_status dad3d_jpeg_decode_host(const uint8_t* file, int64_t si
                                                  int32_t* w, int32_t* c, int32_t* flag);
 
 /* ---------------------------------------------------------------------------------------------
+ * dad3d_jpeg_decode with a second entropy stage: the same files, pixels and flags, but a file WITHOUT restart markers (DRI 0), which
+ * dad3d_jpeg_decode hands to a single lane, is cut into pieces of `piece_bytes` (a power of two, 16 .. 256) that are decoded side by
+ * side. Every piece first walks the Huffman codes from a guess; groups of 256 pieces hand their exit states forward until nothing
+ * changes (launch A), then once more from the exit of the group in front (launch B). A file is *verified* when every group's exit is
+ * the same behind both launches: its chain of states is then the serial walk's, and every piece decodes its own codes with all the
+ * checks of the serial walk. A file that is not verified is decoded by one lane inside the same call, so the result never depends on
+ * the guesses. A file with restart markers takes one lane per segment as in dad3d_jpeg_decode.
+ *   desc    DEVICE [batch * DAD3D_JPEG_DECODE_SYNC_DESC_INTS] int64: the batch's rows of DAD3D_JPEG_DECODE_DESC_INTS columns exactly
+ *           as dad3d_jpeg_decode takes them, and behind all of them [batch][4]: where the item's piece table and group table lie in
+ *           `scratch` and how many entries each holds. dad3d_jpeg_decode_sync_scratch_bytes fills these four and columns 8 .. 11.
+ *   grid    HOST [DAD3D_JPEG_DECODE_SYNC_GRID_INTS] int32: the three of dad3d_jpeg_decode and the most groups a file may have
+ *   info    DEVICE [batch][4] int32: mode, pieces, groups, 0. Mode DAD3D_JPEG_DECODE_SYNC_MODE_SEGMENTS (0): one lane per restart
+ *           segment; _VERIFIED (1): in pieces; _SERIAL (2): not verified, one lane. All 0 for an item the header scan has flagged.
+ *   files, out, flags, scratch as for dad3d_jpeg_decode; the flags are the same for every file whatever `piece_bytes`.
+ * A `piece_bytes` outside the rule gives DAD3D_E_INVALID before any device work (0 from dad3d_jpeg_decode_sync_scratch_bytes). Nine
+ * launches on `stream`, no allocation, no synchronisation: can be captured. Nothing outside the item's own places is read or written
+ * whatever the file holds.
+ * dad3d_jpeg_decode_sync_host runs the same routines on one file on the CPU, group after group, as dad3d_jpeg_decode_host does for
+ * dad3d_jpeg_decode; info is HOST [4] (all 0 while `out` is NULL or the header is flagged).
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_JPEG_DECODE_SYNC_DESC_INTS 16
+#define DAD3D_JPEG_DECODE_SYNC_GRID_INTS 4
+#define DAD3D_JPEG_DECODE_SYNC_MODE_SEGMENTS 0
+#define DAD3D_JPEG_DECODE_SYNC_MODE_VERIFIED 1
+#define DAD3D_JPEG_DECODE_SYNC_MODE_SERIAL 2
+DAD3D_EXPORT size_t dad3d_jpeg_decode_sync_scratch_bytes(int64_t* desc, int batch, int32_t* grid, int piece_bytes);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_decode_sync(const uint8_t* files, size_t files_bytes, const int64_t* desc, int batch, const int32_t* grid,
+                                                 int piece_bytes, uint8_t* out, size_t out_bytes, int32_t* flags, int32_t* info, void* scratch,
+                                                 size_t scratch_bytes, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_jpeg_decode_sync_host(const uint8_t* file, int64_t size, int channels, int piece_bytes, uint8_t* out,
+                                                      int64_t out_bytes, int32_t* h, int32_t* w, int32_t* c, int32_t* flag, int32_t* info);
+
+/* ---------------------------------------------------------------------------------------------
  * Images as baseline JPEG files made on the device, byte-equal to
  *   PIL.Image.fromarray(img).save(buf, "JPEG", quality=q, subsampling=s, restart_marker_rows=r)
  * with libjpeg-turbo behind PIL (mode RGB for c = 3, mode L for c = 1): its 16-bit fixed-point RGB -> YCbCr, edge replication, the
