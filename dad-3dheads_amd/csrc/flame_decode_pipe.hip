@@ -137,7 +137,12 @@ __device__ __forceinline__ void gemm_groups(const float* afrag, const float4 (&b
 // TO2D: `proj` is [B,V,2] (head_mesh.py:44-45 `to_2d`), else [B,V,3]. DAD3D_ZERO_ROTATION launches take the two-role kernel.
 // (Measured and dropped, profiles/r04_kernel_log.md: a launch of 33..64 images as ONE pass of four row blocks over both A images,
 // all eight waves finishing both half-blocks -- 13.2 us at B = 64 against 12.8 for the two-phase pipeline: every store of the
-// launch then leaves at the very end.)
+// launch then leaves at the very end. And profiles/r07_kernel_log.md: the LAST half-block as two row blocks of 16 images with a barrier
+// between them, rows 0..15 finished inside row block 1's GEMM and only rows 16..31 behind A(H - 1) -- bit-identical, 12.50 against 12.47 us
+// at B = 64 on top of the write-through landmark stores, 12.78 against 12.68 alone: the tail behind the last barrier is ~1.5 k cycles of
+// latency whether a lane finishes one vertex or two, and two chains of 104 dependent MFMAs are slower than one of 208 independent pairs.)
+// The two ends of a launch: nothing waits for data in front of the first barrier, and no store is left to the end-of-kernel write-back --
+// vertex stores, landmark slots and `translation z := 0` are all written through (flame_pipe_epilogue.hpp).
 // CHUNKED (models of few tiles: the landmark sub-model's 23 for the 445 list): the batch is cut into a.n_chunks chunks of a.chunk_half
 // half-blocks and a workgroup is one (tile, chunk) -- the kernel below on rows [b0, b0 + chunk) with every pointer moved there, so a
 // row's results are the bits of an unchunked launch. Workgroups w = tile * n_chunks + chunk are dealt to the XCDs in runs of a.wg_per_xcd
@@ -184,7 +189,14 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
     // 3d_vertices / projection leave as raw buffer stores: (uniform resource) + (32-bit byte offset of the lane) + immediate
     const __amdgpu_buffer_rsrc_t rs3 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.verts3d), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.proj), 0, 0x7fffffff, 0x00020000);
+    // (the landmark slots and `translation z := 0` leave as write-through stores too -- DAD3D_PIPE_LMK_STORE_AUX, flame_pipe_epilogue.hpp:
+    // no store of this kernel is left to the end-of-kernel write-back of the XCDs' L2s)
     cx.lx = reinterpret_cast<char*>(a.lmk_xy), cx.lp = reinterpret_cast<char*>(a.lmk_px);
+    // whether the launch has the two vertex outputs, as ONE opaque scalar word (bit 0 verts3d, bit 1 proj) tested where it is used: left
+    // to itself the compiler holds a 64-bit lane mask of each for the whole launch, and the scalar file is full -- the write-through stores
+    // took the CHUNKED instantiation from 3 SGPR spills to 5 without this (tests/test_kernel_resources.py allows 3). Timing: the same.
+    unsigned outs = __builtin_amdgcn_readfirstlane((a.verts3d ? 1u : 0u) | (a.proj ? 2u : 0u));
+    asm volatile("" : "+s"(outs));
     cx.lmk_next = a.lmk_next;
     cx.image_size = a.image_size;
     cx.zsign = (a.flags & DAD3D_FLIP_Z) ? -1.0f : 1.0f;
@@ -203,14 +215,14 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
             const float4 t = vt_lds[fu];
             const bool live = b < B && v0 + fu < a.n_verts;
             finish_vertex<TO2D, 0>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * fu], ot[3 * fu + 1], ot[3 * fu + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
-                                   live && a.verts3d != nullptr, live && a.proj != nullptr, live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
+                                   live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
         }
         if (fu < TV - 16) {
             const int j = fu + 16;
             const float4 t = vt_lds[j];
             const bool live = b < B && v0 + j < a.n_verts;
             finish_vertex<TO2D, 16>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * j], ot[3 * j + 1], ot[3 * j + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
-                                    live && a.verts3d != nullptr, live && a.proj != nullptr, live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
+                                    live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
         }
     };
 
@@ -353,7 +365,8 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
             c[5] = float4{raw2.z, 0.f, 0.f, 0.f};
             const int b = r * kRound + 32 * wave + lane;
             if ((a.flags & DAD3D_MUTATE_PARAMS) && tile == 0 && b < B)
-                a.params[(size_t)b * P + kNumBeta + 11] = 0.0f;  // translation z := 0 (head_mesh.py:41)
+                store_tz(a.params + ((unsigned)b * (unsigned)P + (unsigned)(kNumBeta + 11)));  // translation z := 0 (head_mesh.py:41), written through
+                                                                                              // (32-bit index: b P < b V, capi.cpp resolve_kernel)
         }
     };
     load_raw(0);  // with the stagers' requests, ahead of the basis: needed after seven groups
@@ -387,7 +400,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const bool live = b < B && vl[k];
-            live3[k] = live && a.verts3d != nullptr, livep[k] = live && a.proj != nullptr, livel[k] = live && nl > 0 && lh[k] >= 0;
+            live3[k] = live && (outs & 1u), livep[k] = live && (outs & 2u), livel[k] = live && nl > 0 && lh[k] >= 0;
         }
     };
     auto epi_fetch = [&](int k) {

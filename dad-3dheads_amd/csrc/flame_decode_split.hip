@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void split_params_kernel(SplitArgs a) {
         const float hh = a.image_size * 0.5f;
         *reinterpret_cast<float4*>(c + 16) = float4{G[7], G[8], s * hh, (tx + 1.0f) * hh};
         *reinterpret_cast<float4*>(c + 20) = float4{(ty + 1.0f) * hh, hh, 0.f, 0.f};
-        if ((a.flags & DAD3D_MUTATE_PARAMS) && live) prow[kNumBeta + 11] = 0.0f;  // translation z := 0 (head_mesh.py:41)
+        if ((a.flags & DAD3D_MUTATE_PARAMS) && live) store_tz(prow + kNumBeta + 11);  // translation z := 0 (head_mesh.py:41)
     }
 }
 
@@ -214,7 +214,8 @@ __global__ __launch_bounds__(256) void split_params_kernel(SplitArgs a) {
 // next behind B(p)), constants from ring slot (p - 2) & 7 (written next in window p + 4).
 // WB: the vertex stores write-back (L2 merges the seams, one write per line to HBM) instead of write-through: 3-6 % faster from ~600 (fp16x2) /
 // ~1000 (bf16x3) images up -- these kernels are energy-bound there -- and 10 % SLOWER at 256 (the dirty lines leave at the end of the launch);
-// the launcher chooses by batch size, the bits are the same.
+// the launcher chooses by batch size, the bits are the same. The landmark stores follow the vertex stores: write-through (DAD3D_PIPE_LMK_STORE_AUX)
+// unless WB.
 template <class S, bool TO2D, bool WB>
 __global__ __launch_bounds__(64 * (5 + S::kFinishers), (5 + S::kFinishers + 3) / 4) void flame_decode_split_kernel(SplitArgs a) {
     typedef typename S::vec8 vec8;
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(64 * (5 + S::kFinishers), (5 + S::kFinishers + 3) /
         const int b = (pb + q) * QB + g.i;
         const bool live = b < B && g.vlive && !((DAD3D_SPLIT_ABLATE & 256) && o.ox != 12345.678f);
         const unsigned row0 = (unsigned)((pb + q) * QB) * (unsigned)a.n_verts;  // (scalar)
-        vertex_store_at<TO2D, WB ? 0 : DAD3D_PIPE_STORE_AUX>(cx, rs3, rsp, o, __float_as_int(g.vt.z), __float_as_int(g.vt.w), live && a.verts3d != nullptr, live && a.proj != nullptr,
+        vertex_store_at<TO2D, WB ? 0 : DAD3D_PIPE_STORE_AUX, WB ? 0 : DAD3D_PIPE_LMK_STORE_AUX>(cx, rs3, rsp, o, __float_as_int(g.vt.z), __float_as_int(g.vt.w), live && a.verts3d != nullptr, live && a.proj != nullptr,
                               live && nl > 0 && __float_as_int(g.vt.z) >= 0, g.off3 + row0 * 12u, g.offp + row0 * kPB, (unsigned)b * nl);
     };
     auto finish_one = [&](int q, const Geo& g) {

@@ -13,6 +13,9 @@
 #ifndef DAD3D_PIPE_STORE_AUX  // cache policy of the vertex stores (buffer-op aux bits: 1 = sc0, 2 = nt, 16 = sc1). 2 = non-temporal: the
 #define DAD3D_PIPE_STORE_AUX 16 // outputs (105 KB per image) stream through the L2 instead of evicting the basis and piling up dirty lines
 #endif                          // for the end-of-kernel write-back: 21.95 / 38.2 against 23.5 / 40.7 us at B = 128 / 256 (plain stores)
+#ifndef DAD3D_PIPE_LMK_STORE_AUX  // cache policy of the landmark stores and of the `translation z := 0` store (0, 16 or 17): isolated 8-byte
+#define DAD3D_PIPE_LMK_STORE_AUX 16  // stores from workgroups on every XCD, so written back (0) every L2 ends the launch with partial dirty
+#endif                               // lines of one small array; 16 = sc1 writes them through as they are issued (profiles/r07_kernel_log.md)
 
 namespace dad3d {
 namespace pipe {
@@ -38,6 +41,42 @@ struct EpiCtx {  // uniform over the workgroup
     const int* lmk_next;
     float image_size, zsign;
 };
+// Stores that must not stay behind in an XCD's L2 as dirty lines for the end-of-kernel write-back, written with the policy AUX (the
+// buffer-op aux bits above: 16 = sc1, 17 = sc0 sc1, 0 = a plain write-back store). Not buffer stores: a resource is four scalar registers
+// held for the launch, and the pipelined kernel's scalar file is full -- two landmark resources took it from 2 SGPR spills to 6-7
+// (tests/test_kernel_resources.py allows 3). An agent-scope relaxed atomic store IS `global_store ... sc1` on gfx950 (system scope:
+// sc0 sc1) off the same base pointer and 32-bit lane offset as the plain store, 8 bytes in one instruction. The hardware takes the
+// 4-byte aligned address of a [.., 2] row of floats as it does for the plain store.
+template <int AUX>
+__device__ __forceinline__ void store_through(char* p, unsigned long long bits) {
+    static_assert(AUX == 0 || AUX == 16 || AUX == 17, "write-back, sc1 or sc0 sc1");
+    typedef unsigned long long u64u __attribute__((aligned(4)));
+    if constexpr (AUX == 0) *reinterpret_cast<u64u*>(p) = bits;
+    else if constexpr (AUX == 16) __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// `translation z := 0` of one params row (head_mesh.py:41), under the landmark stores' policy
+__device__ __forceinline__ void store_tz(float* p) {
+    if constexpr (DAD3D_PIPE_LMK_STORE_AUX == 0) *p = 0.0f;
+    else if constexpr (DAD3D_PIPE_LMK_STORE_AUX == 16) __hip_atomic_store(p, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_store(p, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// The landmark slots of one (vertex, image): (ox, oy) = its projection, lh / ln = the vertex's first slot and the slot chained after it
+// (duplicate indices in the landmark list: rare; the chain's loads wait, the rest does not), bnl = b * n_lmk. Byte offset (bnl + slot) * 8
+// < 2^31 (capi.cpp resolve_kernel).
+template <int AUX = DAD3D_PIPE_LMK_STORE_AUX>
+__device__ __forceinline__ void put_landmarks(const EpiCtx& cx, float ox, float oy, int lh, int ln, unsigned bnl) {
+    auto put = [&](int slot) {
+        const unsigned off = (bnl + (unsigned)slot) * 8u;
+        if (cx.lx) store_through<AUX>(cx.lx + off, __builtin_bit_cast(unsigned long long, f32x2{ox, oy}));
+        if (cx.lp) store_through<AUX>(cx.lp + off, __builtin_bit_cast(unsigned long long, u32x2{(unsigned)(int)ox, (unsigned)(int)oy}));  // numpy .astype(int): toward zero
+    };
+    put(lh);
+    if (ln >= 0) {
+        put(ln);
+        for (int slot = cx.lmk_next[ln]; slot >= 0; slot = cx.lmk_next[slot]) put(slot);
+    }
+}
 // One lane's vertex of one image. c0..c5 = the image's constants (D 9 | G 9 | s tx ty), (jx, jy, jz) = its jaw joint, (ex, ey, ez) =
 // v_posed of the vertex; W, w2 = sum of the five skinning weights, the jaw's; lh, ln = first landmark slot of the vertex, the slot
 // chained after it; st3 / stp / stl = store the 3-D vertex / the projection / landmarks (image inside the batch, vertex inside the
@@ -102,23 +141,12 @@ __device__ __forceinline__ void vertex_store(const EpiCtx& cx, __amdgpu_buffer_r
             else __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, f3u{o.ox, o.oy, o.oz}), rsp, (int)(vrow * 12u), 12 * VOFF, DAD3D_PIPE_STORE_AUX);
         }
     }
-    if (stl) {
-        auto put = [&](int slot) {
-            const unsigned off = (bnl + (unsigned)slot) * 8u;
-            if (cx.lx) *reinterpret_cast<f2u*>(cx.lx + off) = f2u{o.ox, o.oy};
-            if (cx.lp) *reinterpret_cast<i2u*>(cx.lp + off) = i2u{(int)o.ox, (int)o.oy};  // numpy .astype(int): toward zero
-        };
-        put(lh);
-        if (ln >= 0) {  // duplicate indices in the landmark list: the chain goes on
-            put(ln);
-            for (int slot = cx.lmk_next[ln]; slot >= 0; slot = cx.lmk_next[slot]) put(slot);
-        }
-    }
+    if (stl) put_landmarks(cx, o.ox, o.oy, lh, ln, bnl);
 }
 
-// vertex_store with the byte offsets of the vertex given (the split kernel keeps them per lane across phases) and the cache policy of the
-// vertex stores as a parameter (16 = sc1 write-through, 0 = write-back)
-template <bool TO2D, int AUX = DAD3D_PIPE_STORE_AUX>
+// vertex_store with the byte offsets of the vertex given (the split kernel keeps them per lane across phases) and the cache policies of the
+// vertex stores and of the landmark stores as parameters (16 = sc1 write-through, 0 = write-back)
+template <bool TO2D, int AUX = DAD3D_PIPE_STORE_AUX, int LAUX = DAD3D_PIPE_LMK_STORE_AUX>
 __device__ __forceinline__ void vertex_store_at(const EpiCtx& cx, __amdgpu_buffer_rsrc_t rs3, __amdgpu_buffer_rsrc_t rsp, const VertexOut& o, int lh, int ln, bool st3,
                                                 bool stp, bool stl, unsigned off3, unsigned offp, unsigned bnl) {
     if (st3) __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, f3u{o.rx, o.ry, o.rz}), rs3, (int)off3, 0, AUX);
@@ -126,18 +154,7 @@ __device__ __forceinline__ void vertex_store_at(const EpiCtx& cx, __amdgpu_buffe
         if (TO2D) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, f2u{o.ox, o.oy}), rsp, (int)offp, 0, AUX);
         else __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, f3u{o.ox, o.oy, o.oz}), rsp, (int)offp, 0, AUX);
     }
-    if (stl) {
-        auto put = [&](int slot) {
-            const unsigned off = (bnl + (unsigned)slot) * 8u;
-            if (cx.lx) *reinterpret_cast<f2u*>(cx.lx + off) = f2u{o.ox, o.oy};
-            if (cx.lp) *reinterpret_cast<i2u*>(cx.lp + off) = i2u{(int)o.ox, (int)o.oy};  // numpy .astype(int): toward zero
-        };
-        put(lh);
-        if (ln >= 0) {  // duplicate indices in the landmark list: the chain goes on
-            put(ln);
-            for (int slot = cx.lmk_next[ln]; slot >= 0; slot = cx.lmk_next[slot]) put(slot);
-        }
-    }
+    if (stl) put_landmarks<LAUX>(cx, o.ox, o.oy, lh, ln, bnl);
 }
 
 // PACKED = false: vertex_math_scalar + vertex_store above.
@@ -182,18 +199,7 @@ __device__ __forceinline__ void finish_vertex(const EpiCtx& cx, __amdgpu_buffer_
             }
         }
     }
-    if (stl) {
-        auto put = [&](int slot) {
-            const unsigned off = (bnl + (unsigned)slot) * 8u;
-            if (cx.lx) *reinterpret_cast<f2u*>(cx.lx + off) = f2u{ox, oy};
-            if (cx.lp) *reinterpret_cast<i2u*>(cx.lp + off) = i2u{(int)ox, (int)oy};  // numpy .astype(int): toward zero
-        };
-        put(lh);
-        if (ln >= 0) {  // duplicate indices in the landmark list: the chain goes on (rare; its loads wait, the rest does not)
-            put(ln);
-            for (int slot = cx.lmk_next[ln]; slot >= 0; slot = cx.lmk_next[slot]) put(slot);
-        }
-    }
+    if (stl) put_landmarks(cx, ox, oy, lh, ln, bnl);
 }
 
 }  // namespace pipe

@@ -13,5 +13,7 @@ $H $C $flags -x hip -c "$src" -o "$tmp/fd.o"
 $H $C $flags -x hip -c "${PIPE_SRC:-$S/flame_decode_pipe.hip}" -o "$tmp/fdp.o"  # PIPE_SRC: another revision of the pipelined kernel (e.g. `git show HEAD:...` into a file)
 $H $C $flags -fno-slp-vectorize -x hip -c "${SPLIT_SRC:-$S/flame_decode_split.hip}" -o "$tmp/fds.o"  # SPLIT_SRC: another revision of the bf16x3 split kernel
 $H $C $flags -DDAD3D_DIAG_SPIN_ENV -x hip -c "$S/capi.cpp" -o "$tmp/capi.o"
-$H --offload-arch=gfx950 -shared -fPIC -o "$root/tools/_variants/lib_$name.so" "$tmp/fd.o" "$tmp/fdp.o" "$tmp/fds.o" "$tmp/capi.o" "$S/flame_backward.o" "$S/sim3dr_kernels.o" "$S/projection.o" "$S/preprocess.o" "$S/mesh_losses.o" "$S/cnn_glue.o" "$S/sim3dr_compat.o"
+# every other object of the product library as the Makefile built it (its OBJS list, minus the four compiled above)
+others="$(cd "$S" && make -s -pn 2>/dev/null | sed -n 's/^OBJS *:= *//p' | head -1 | tr ' ' '\n' | grep -v -x -e flame_decode.o -e flame_decode_pipe.o -e flame_decode_split.o -e capi.o | sed "s|^|$S/|")"
+$H --offload-arch=gfx950 -shared -fPIC -o "$root/tools/_variants/lib_$name.so" "$tmp/fd.o" "$tmp/fdp.o" "$tmp/fds.o" "$tmp/capi.o" $others
 echo "built tools/_variants/lib_$name.so"
