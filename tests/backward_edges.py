@@ -1,5 +1,6 @@
 """Edge rows, the float64 statement and the per-row bars that the backward tests share (tests/test_backward_edges_host.py,
-tests/test_gpu_backward_edges.py, the tie cases of tests/test_gpu_autograd.py). Test infrastructure, not a conftest.
+tests/test_gpu_backward_edges.py, the tie cases of tests/test_gpu_autograd.py; tests/decode_layouts.py takes the rows, the joint
+sweep and the float64 statement for the forward on every constants layout). Test infrastructure, not a conftest.
 
 The float64 statement is `oracle.flame_ref` itself, unmodified, over a `FlameConstants` whose five float buffers are cast
 to double: torch promotes the oracle's own float32 zeros, so every product of the chain is a double product.
@@ -75,6 +76,28 @@ def edge_params():
     return [n for n, _ in rows], np.stack([p for _, p in rows]).astype(np.float32)
 
 
+FULL = {"shape": 300, "expression": 100, "jaw": 3, "rotation": 6, "eyeballs": 6, "neck": 3, "translation": 3, "scale": 1}
+EXTRA_JOINTS = (("eye0", 409), ("eye1", 412), ("neck", 415))  # where the full layout keeps the joints the shipped one lacks
+
+
+def joint_sweep(joints=EXTRA_JOINTS):
+    """(names, [N,422] float32) on the full layout (neck + eyeballs are inputs): `edge_params()`'s plain row with ordinary
+    neck / eyeball values, then each of `joints` (name, offset) in turn through zero, a denormal and ANGLES on AXIS, the other
+    joints at their ordinary values."""
+    base413 = edge_params()[1][0]
+    extra = (0.2 * np.random.default_rng(3).standard_normal(9)).astype(np.float32)
+    base = np.concatenate([base413[:409], extra, base413[409:]])
+    names, rows = ["unchanged"], [base]
+    for joint, at in joints:
+        for name, value in [("0", np.zeros(3, np.float32)), ("1e-40", np.full(3, 1e-40, np.float32))] + \
+                           [(n, axis_angle(a)) for n, a in ANGLES]:
+            row = base.copy()
+            row[at:at + 3] = value
+            names.append(f"{joint}_{name}")
+            rows.append(row)
+    return names, np.stack(rows)
+
+
 def oracle64(flame_consts):
     """The oracle's constants with the five float buffers in double: `flame_ref` then runs in float64 throughout."""
     f = ("v_template", "shapedirs", "posedirs", "j_regressor", "lbs_weights")
@@ -89,12 +112,13 @@ def weights(n, to_2d, seed=5):
     return torch.randn((n, 5023, 3), generator=gen), torch.randn((n, 5023, 2 if to_2d else 3), generator=gen)
 
 
-def oracle_grad(consts, params, wv, wp, zero_rot, to_2d, dtype):
-    """d/d(params) of (v . wv).sum() + 1e-2 (proj . wp).sum() through the oracle in `dtype` -> ([N,413] float64, value)."""
+def oracle_grad(consts, params, wv, wp, zero_rot, to_2d, dtype, layout=flame_ref.DEFAULT_CONSTS):
+    """d/d(params) of (v . wv).sum() + 1e-2 (proj . wp).sum() through the oracle in `dtype` -> ([N,P] float64, value).
+    `layout`: the FLAME constants dict the params rows are cut by (P = 413 for the shipped one)."""
     p = torch.as_tensor(params).to(dtype).clone().requires_grad_(True)
     q = p * 1.0  # the network output: a non-leaf that reprojected_vertices writes tz := 0 into
-    v = flame_ref.vertices_3d(consts, q, zero_rotation=zero_rot)
-    proj = flame_ref.reprojected_vertices(consts, q, to_2d=to_2d)
+    v = flame_ref.vertices_3d(consts, q, zero_rotation=zero_rot, consts=layout)
+    proj = flame_ref.reprojected_vertices(consts, q, to_2d=to_2d, consts=layout)
     value = (v * wv.to(dtype)).sum() + 1e-2 * (proj * wp.to(dtype)).sum()
     value.backward()
     return p.grad.double(), value.detach().double()

@@ -156,20 +156,9 @@ def test_chain_kernels_alone_on_the_edge_rows(hm, edge):
 def test_chain_kernels_sweep_neck_and_eyeballs(flame_model, static):
     """The full layout (neck + eyeballs are inputs): each of the three extra joints through zero, a denormal and the jaw's
     angles, the other joints at ordinary values."""
-    full = {"shape": 300, "expression": 100, "jaw": 3, "rotation": 6, "eyeballs": 6, "neck": 3, "translation": 3, "scale": 1}
-    mesh = HeadMesh(flame_config=full, flame_model=flame_model, static=static, device=0)
-    base413 = be.edge_params()[1][0]
-    extra = (0.2 * np.random.default_rng(3).standard_normal(9)).astype(np.float32)
-    base = np.concatenate([base413[:409], extra, base413[409:]])
-    names, rows = ["unchanged"], [base]
-    for joint, at in (("eye0", 409), ("eye1", 412), ("neck", 415)):
-        for name, value in [("0", np.zeros(3, np.float32)), ("1e-40", np.full(3, 1e-40, np.float32))] + \
-                           [(n, be.axis_angle(a)) for n, a in be.ANGLES]:
-            row = base.copy()
-            row[at:at + 3] = value
-            names.append(f"{joint}_{name}")
-            rows.append(row)
-    hold_chain("chain, full layout", mesh.flame, full, names, np.stack(rows))
+    mesh = HeadMesh(flame_config=be.FULL, flame_model=flame_model, static=static, device=0)
+    names, rows = be.joint_sweep()  # eye0, eye1, neck: the joints the shipped layout lacks
+    hold_chain("chain, full layout", mesh.flame, be.FULL, names, rows)
 
 
 def backward_through_the_c_abi(layer, params, flags, g_v3, g_pj):
