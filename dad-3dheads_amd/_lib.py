@@ -36,6 +36,9 @@ JPEG_DECODE_SYNC_DESC_INTS, JPEG_DECODE_SYNC_GRID_INTS = 16, 4
 JPEG_DECODE_SYNC_MODE_SEGMENTS, JPEG_DECODE_SYNC_MODE_VERIFIED, JPEG_DECODE_SYNC_MODE_SERIAL = 0, 1, 2
 JPEG_ENCODE_FLAG_INTERNAL = 0x1
 OVERLAY_MAX_COORD = 8192
+DTYPE_F16, DTYPE_BF16, HEATMAP_DTYPE_U8 = 1, 2, 3
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+POINTS_SRC_XY_F32, POINTS_SRC_YX_I32 = 0, 1
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -130,6 +133,8 @@ SIGNATURES = {
     "dad3d_preprocess_images": (_I, [_P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _I, _P]),
     "dad3d_nhwc_bias_act": (_I, [_P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
     "dad3d_nhwc_resize_sum": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_float), _I, _P]),
+    "dad3d_heatmap_argmax": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "dad3d_points_readjust": (_I, [_P, _I, _I, _I, _F, _F, _P, _I, _I, C.c_double, _P, _I, _P]),
     "dad3d_cube_region_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "dad3d_point_loss_terms": (_I, [_I]),
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),

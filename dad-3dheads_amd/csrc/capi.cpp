@@ -1711,6 +1711,37 @@ dad3d_status dad3d_nhwc_resize_sum(void* out, int n, int oh, int ow, int channel
     return launch_nhwc_resize_sum(out, n, oh, ow, channels, dtype, n_inputs, xs, hs, ws, weights, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_heatmap_argmax(const void* heatmap, int dtype, int batch, int channels, int h, int w, int layout, int sigmoid,
+                                  int32_t* yx_out, float* peak_out, int device, void* stream) {
+    const int es = dtype == DAD3D_DTYPE_F32 ? 4 : (dtype == DAD3D_DTYPE_F16 || dtype == DAD3D_DTYPE_BF16) ? 2 : dtype == DAD3D_HEATMAP_DTYPE_U8 ? 1 : 0;
+    DAD3D_REQUIRE(es, "dad3d_heatmap_argmax: unknown dtype %d", dtype);
+    DAD3D_REQUIRE(layout == DAD3D_LAYOUT_NCHW || layout == DAD3D_LAYOUT_NHWC, "dad3d_heatmap_argmax: unknown layout %d", layout);
+    DAD3D_REQUIRE(batch > 0 && channels > 0 && h > 0 && w > 0, "dad3d_heatmap_argmax: bad size (batch %d, channels %d, h %d, w %d)", batch,
+                  channels, h, w);
+    DAD3D_REQUIRE((int64_t)h * w <= (1 << 24), "dad3d_heatmap_argmax: a plane of %d x %d is beyond 2^24 positions", h, w);
+    DAD3D_REQUIRE((int64_t)batch * channels <= 0x7fffffff, "dad3d_heatmap_argmax: %d x %d planes are beyond the launch grid", batch, channels);
+    DAD3D_REQUIRE(!(sigmoid && dtype == DAD3D_HEATMAP_DTYPE_U8), "dad3d_heatmap_argmax: no sigmoid of a uint8 heatmap");
+    DAD3D_REQUIRE(heatmap && yx_out, "dad3d_heatmap_argmax: null argument");
+    DAD3D_REQUIRE(reinterpret_cast<uintptr_t>(heatmap) % es == 0, "dad3d_heatmap_argmax: the heatmap is not aligned to its %d-byte elements", es);
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    HeatmapArgmaxArgs a{heatmap, dtype, batch, channels, h, w, layout, sigmoid != 0, yx_out, peak_out, 1};
+    return launch_heatmap_argmax(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_points_readjust(const void* src, int src_kind, int batch, int n_points, float mul, float limit, const double* geometry,
+                                   int pad_left, int pad_top, double scale, int32_t* points_out, int device, void* stream) {
+    DAD3D_REQUIRE(src_kind == DAD3D_POINTS_SRC_XY_F32 || src_kind == DAD3D_POINTS_SRC_YX_I32, "dad3d_points_readjust: unknown src_kind %d", src_kind);
+    DAD3D_REQUIRE(batch > 0 && n_points > 0, "dad3d_points_readjust: bad size (batch %d, n_points %d)", batch, n_points);
+    DAD3D_REQUIRE((int64_t)batch * n_points * 2 <= 0x7fffffff, "dad3d_points_readjust: %d x %d points are beyond the launch grid", batch, n_points);
+    DAD3D_REQUIRE(src && points_out, "dad3d_points_readjust: null argument");
+    DAD3D_REQUIRE(geometry || (scale > 0.0 && scale <= 1.7976931348623157e308), "dad3d_points_readjust: the scale must be a positive finite number");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    PointsReadjustArgs a{src, src_kind, batch, n_points, mul, limit, geometry, pad_left, pad_top, scale, points_out};
+    return launch_points_readjust(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_cube_region_loss(const float* pred, const float* target, int batch, int n_verts,
                                     const int32_t* region_ptr, const int32_t* region_idx, const float* region_weight,
                                     int n_regions, const int32_t* vert_ptr, const int32_t* vert_region,

@@ -27,6 +27,16 @@ struct OpXor {
     __device__ static __forceinline__ T of(T a, T b) { return a ^ b; }
 };
 
+// argmax over (key, index) pairs packed into one 64-bit word by argmax_pack: the larger key wins, and among equal keys the
+// smaller index, so the result does not depend on the order of combination. 0 is below every packed pair of a key >= 1.
+struct OpArgmax {
+    __device__ static __forceinline__ unsigned long long of(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+};
+__device__ __forceinline__ unsigned long long argmax_pack(unsigned key, unsigned index) {
+    return (unsigned long long)key << 32 | (0xffffffffu - index);
+}
+__device__ __forceinline__ unsigned argmax_index(unsigned long long packed) { return 0xffffffffu - (unsigned)packed; }
+
 template <typename T>
 __device__ __forceinline__ T lane_xor(T v, int d) { return __shfl_xor(v, d, 64); }
 __device__ __forceinline__ unsigned long long lane_xor(unsigned long long v, int d) {  // two 32-bit shuffles

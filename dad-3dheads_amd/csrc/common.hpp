@@ -678,4 +678,24 @@ dad3d_status launch_nhwc_bias_act(void* y, const void* bias, const void* z, size
 dad3d_status launch_nhwc_resize_sum(void* out, int n, int oh, int ow, int channels, int dtype, int n_inputs, const void* const* xs,
                                     const int* hs, const int* ws, const float* weights, hipStream_t s);
 
+// heatmap peaks and the landmark readjustment (heatmap_points.hip): dtype = DAD3D_DTYPE_* or DAD3D_HEATMAP_DTYPE_U8, layout = DAD3D_LAYOUT_*
+struct HeatmapArgmaxArgs {
+    const void* heatmap;
+    int dtype, batch, channels, h, w, layout, sigmoid;
+    int32_t* yx;  // [B,C,2] (k // H, k % H)
+    float* peak;  // [B,C] or null
+    int n_split;  // set by the launcher: workgroups per channels-last image
+};
+dad3d_status launch_heatmap_argmax(const HeatmapArgmaxArgs& a, hipStream_t s);
+struct PointsReadjustArgs {
+    const void* src;  // src_kind 0: float32 (x, y); 1: int32 (row, col)
+    int src_kind, batch, n_points;
+    float mul, limit;
+    const double* geometry;  // [B,3] (pad_left, pad_top, scale) or null: the triple below
+    int pad_left, pad_top;
+    double scale;
+    int32_t* points;
+};
+dad3d_status launch_points_readjust(const PointsReadjustArgs& a, hipStream_t s);
+
 }  // namespace dad3d

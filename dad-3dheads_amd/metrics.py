@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from .heatmap_points import heatmap_peaks
 from .losses import _f32, heatmap_iou_terms
 
 __all__ = ["soft_iou", "keypoints_nme", "percentage_of_errors_below_IOD", "keypoint_errors", "SoftIoUMetric", "FailureRate",
@@ -209,8 +210,9 @@ class StepMetrics:
     the reference's log names (heatmap_iou, fr_2d_005, fr_2d_01, nme_2d, reproject_*, fr_3d_005, fr_3d_01, nme_3d) and
     accumulates every metric's state. `flame_indices` maps region names to vertex indices ("face" is used)."""
 
-    def __init__(self, head_mesh, flame_indices: Mapping[str, Any], img_size: int) -> None:
+    def __init__(self, head_mesh, flame_indices: Mapping[str, Any], img_size: int, stride: int = 2) -> None:
         self.head_mesh = head_mesh
+        self.stride = stride  # config["train"].get("stride", 2): the heatmap's pixel pitch in the image
         self.face = np.asarray(flame_indices["face"], dtype=np.int64)
         self.img_size = img_size
         self.iou_metric = SoftIoUMetric()
@@ -235,12 +237,14 @@ class StepMetrics:
         bbox = targets[INPUT_BBOX_KEY]
         if OUTPUT_2D_LANDMARKS in outputs.keys() or OUTPUT_LANDMARKS_HEATMAP in outputs.keys():
             res["heatmap_iou"] = self.iou_metric._update_logits(outputs[OUTPUT_LANDMARKS_HEATMAP], targets[TARGET_LANDMARKS_HEATMAP])
-            if OUTPUT_2D_LANDMARKS not in outputs.keys():
-                raise NotImplementedError("the heatmap-argmax branch of _get_keypoints_2d is not ported")
-            # outputs_2d = landmarks * img_size * presence, targets_2d = target * presence * img_size
-            vals = self.metrics_2d(outputs[OUTPUT_2D_LANDMARKS], targets[TARGET_2D_LANDMARKS], bbox,
-                                   presence=targets[TARGET_2D_LANDMARKS_PRESENCE], pred_scale=self.img_size,
-                                   target_scale=self.img_size)
+            # outputs_2d = _get_keypoints_2d * presence, targets_2d = target * presence * img_size
+            if OUTPUT_2D_LANDMARKS in outputs.keys():  # landmarks * img_size
+                pred, pred_scale = outputs[OUTPUT_2D_LANDMARKS], self.img_size
+            else:  # float(stride) * unravel_index(logits).flip(-1): the argmax of the logits, no sigmoid (flame_lightning_model.py:297)
+                pred = float(self.stride) * heatmap_peaks(outputs[OUTPUT_LANDMARKS_HEATMAP], sigmoid=False).flip(-1)
+                pred_scale = 1.0
+            vals = self.metrics_2d(pred, targets[TARGET_2D_LANDMARKS], bbox, presence=targets[TARGET_2D_LANDMARKS_PRESENCE],
+                                   pred_scale=pred_scale, target_scale=self.img_size)
             res.update(zip((n.format("2d") for n in self.metrics_2d.names), vals))
         params = outputs[OUTPUT_3DMM_PARAMS]
         projected = self.head_mesh.reprojected_vertices(params_3dmm=params, to_2d=True)

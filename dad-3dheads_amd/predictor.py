@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .head_mesh import HeadMesh
+from .heatmap_points import points_from_heatmap, points_from_landmarks
 from .resize_geometry import calculate_paddings, py3round  # noqa: F401  (public names of this module)
 
 # keys of the CNN's output dict (model_training/data/config.py:16-23: every constant's value is its own name)
@@ -118,15 +119,14 @@ class FaceMeshPredictor:
             return self.model(x)
 
     # -- postprocess (predictor.py:102-176,188-193) -------------------------------------------------------
-    def _landmarks_68(self, out: Dict[str, torch.Tensor]) -> Optional[np.ndarray]:
+    def _landmarks_68(self, out: Dict[str, torch.Tensor], geometry: Any) -> Optional[torch.Tensor]:
+        """The 68 points in the input frame, int32 `[B,68,2]` on the device, or None where the model has no 2-D output:
+        predictor.py:106-112,132-133,147-152 on the device (heatmap_points.py), with no host wait.
+        `geometry`: one (pad_left, pad_top, scale) triple or a float64 `[B,3]` device tensor of them."""
         if OUTPUT_2D_LANDMARKS in out:
-            return out[OUTPUT_2D_LANDMARKS].detach().cpu().numpy() * 256.0
+            return points_from_landmarks(out[OUTPUT_2D_LANDMARKS], geometry, self._img_size)
         if OUTPUT_LANDMARKS_HEATMAP in out:  # unravel_index(sigmoid(heatmap)).flip(-1) * stride (predictor.py:108-112)
-            hm = torch.sigmoid(out[OUTPUT_LANDMARKS_HEATMAP]).detach()
-            b, c, h, w = hm.shape
-            flat = hm.view(b, c, -1).argmax(-1)
-            yx = torch.stack((torch.div(flat, h, rounding_mode="trunc"), flat % h), dim=-1)
-            return float(self._stride) * yx.flip(-1).cpu().numpy()
+            return points_from_heatmap(out[OUTPUT_LANDMARKS_HEATMAP], geometry, self._img_size, self._stride, sigmoid=True)
         return None
 
     def _readjust_and_decode(self, params: torch.Tensor, pads_scale: torch.Tensor, device_outputs: bool):
@@ -167,43 +167,26 @@ class FaceMeshPredictor:
         res = {"3dmm_params": params, "3d_vertices": dec["verts3d"], "projected_vertices": dec["proj"]}
         if want_lmk:
             res["landmarks"] = dec["lmk_px"]
-        if OUTPUT_2D_LANDMARKS in out:  # predictor.py:147-152 on the device
-            # numpy promotes to float64 at the integer pad subtraction; same here so `astype(int)` truncates alike
-            pts = (out[OUTPUT_2D_LANDMARKS].detach().float() * 256.0).clamp_(0, self._img_size).double()
-            pts = (pts - torch.tensor([pads[2], pads[0]], device=self.device, dtype=torch.float64)) / scale
-            res["points"] = pts.to(torch.int32)
+        pts = self._landmarks_68(out, (pads[2], pads[0], scale))  # predictor.py:106-112,147-152 on the device
+        if pts is not None:
+            res["points"] = pts
         return res
 
-    def predict_batch(self, images: Sequence[np.ndarray], device_outputs: bool = False) -> List[Dict[str, Any]]:
-        """Batched predictor: list of HxWx3 uint8 RGB arrays (any sizes) -> list of the reference's result dicts."""
-        caches: List[Dict[str, Any]] = [{"input_shape": im.shape[:2]} for im in images]
+    def predict_batch(self, images: Sequence[np.ndarray], device_outputs: bool = False,
+                      points_on_device: bool = False) -> List[Dict[str, Any]]:
+        """Batched predictor: list of HxWx3 uint8 RGB arrays (any sizes) -> list of the reference's result dicts. With
+        `points_on_device` the `points` are int32 `[68,2]` device tensors; together with `device_outputs` the call makes no
+        host wait after the upload."""
         staged = []
         for im in images:
             if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
                 raise ValueError(f"expected uint8 RGB images [H,W,3], got {im.dtype} {im.shape}")
             staged.append(torch.from_numpy(np.ascontiguousarray(im)).to(self.device))
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.shape[1] * 3) for t in staged])
-        out = self.process(batch)
-        params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
-        geo = [self._geometry(c["input_shape"]) for c in caches]
-        pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
-        lm = self._landmarks_68(out)
-        if lm is None:  # `return {"3dmm_params": ...}` branch of predictor.py:144-145
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(),
-                                                             params.shape[0], pads_scale.data_ptr(), 0.0, 0.0, 1.0, stream))
-            params = params if device_outputs else params.cpu()
-            return [{"3dmm_params": params[i : i + 1]} for i in range(len(images))]
-        v3d, proj, params = self._readjust_and_decode(params, pads_scale, device_outputs)
-        results = []
-        for i, (pads, scale, _) in enumerate(geo):
-            pts = lm[i].clip(min=0, max=self._img_size) - np.array([[pads[2], pads[0]]])
-            pts = (pts / scale).astype(int)  # predictor.py:147-152
-            results.append({"points": np.reshape(pts, (-1, 2)), "projected_vertices": proj[i : i + 1],
-                            "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]})
-        return results
+        return self._results_of(batch, [im.shape[:2] for im in images], device_outputs, points_on_device)
 
-    def predict_files(self, sources: Sequence[Any], device_outputs: bool = False, jpeg_entropy: str = "segments") -> List[Dict[str, Any]]:
+    def predict_files(self, sources: Sequence[Any], device_outputs: bool = False, jpeg_entropy: str = "segments",
+                      points_on_device: bool = False) -> List[Dict[str, Any]]:
         """`predict_batch` fed with image files (paths or bytes, any sizes): PNG files and baseline JPEG files are decoded to RGB
         on the device (png_reader.PngDecoder, jpeg_reader.JpegDecoder, channels=3) and the decoded images go to the preprocess launch
         where they lie, so no decoded pixel crosses the bus. A source that starts FF D8 goes to the JPEG decoder, every other one
@@ -234,26 +217,26 @@ class FaceMeshPredictor:
                 for i, t in zip(pngs, png.finish(got[nj:nj + npng], got[nj + npng:nj + 2 * npng]).tensors()):
                     decoded[i] = t
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)) for t in decoded])
-        return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs)
+        return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs, points_on_device)
 
-    def _results_of(self, batch: torch.Tensor, shapes: Sequence[Tuple[int, int]], device_outputs: bool) -> List[Dict[str, Any]]:
+    def _results_of(self, batch: torch.Tensor, shapes: Sequence[Tuple[int, int]], device_outputs: bool,
+                    points_on_device: bool = False) -> List[Dict[str, Any]]:
         """What `predict_batch` does behind its preprocess launch, for images of the sizes `shapes` = [(h, w)]."""
+        geo = [self._geometry(s) for s in shapes]
+        # both uploads in front of the CNN. The points need the scale as the float64 it is (predictor.py:151); the params kernel reads float32
+        pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
+        geometry = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float64).to(self.device)
         out = self.process(batch)
         params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
-        geo = [self._geometry(s) for s in shapes]
-        pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
-        lm = self._landmarks_68(out)
-        if lm is None:
+        pts = self._landmarks_68(out, geometry)
+        if pts is None:  # `return {"3dmm_params": ...}` branch of predictor.py:144-145
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(),
                                                              params.shape[0], pads_scale.data_ptr(), 0.0, 0.0, 1.0, stream))
             params = params if device_outputs else params.cpu()
             return [{"3dmm_params": params[i : i + 1]} for i in range(len(shapes))]
         v3d, proj, params = self._readjust_and_decode(params, pads_scale, device_outputs)
-        results = []
-        for i, (pads, scale, _) in enumerate(geo):
-            pts = lm[i].clip(min=0, max=self._img_size) - np.array([[pads[2], pads[0]]])
-            pts = (pts / scale).astype(int)
-            results.append({"points": np.reshape(pts, (-1, 2)), "projected_vertices": proj[i : i + 1],
-                            "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]})
-        return results
+        if not points_on_device:
+            pts = pts.cpu().numpy().astype(int)  # one copy; `astype(int)` is the reference's dtype (predictor.py:152)
+        return [{"points": pts[i], "projected_vertices": proj[i : i + 1], "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]}
+                for i in range(len(shapes))]

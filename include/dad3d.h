@@ -970,6 +970,46 @@ DAD3D_EXPORT dad3d_status dad3d_nhwc_bias_act(void* y, const void* bias, const v
 DAD3D_EXPORT dad3d_status dad3d_nhwc_resize_sum(void* out, int n, int oh, int ow, int channels, int dtype, int n_inputs, const void* const* xs,
                                    const int* hs, const int* ws, const float* weights, int device, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * From the network's 2-D outputs to landmark points (csrc/heatmap_points.hip). All tensors are DEVICE pointers.
+ *
+ * dad3d_heatmap_argmax   `unravel_index` (model_training/model/utils.py:44-52) of a dense [B,C,H,W] heatmap: the argmax of
+ *   torch.sigmoid(heatmap) with sigmoid = 1 (predictor.py:108-112) or of the values themselves with sigmoid = 0
+ *   (train/flame_lightning_model.py:294-297). Every value is read once. NCHW is one launch; so is a channels-last image of
+ *   fewer than 512 pixels, and a larger one is split over workgroups that meet in yx_out (zeroed first, an atomic maximum of
+ *   packed pairs: order-free, so deterministic) with a second tiny launch that unpacks it in place.
+ *     dtype    DAD3D_DTYPE_F32 / _F16 / _BF16 or DAD3D_HEATMAP_DTYPE_U8 (the target heatmap of `get_2d_visuals`; no sigmoid)
+ *     layout   DAD3D_LAYOUT_NCHW: contiguous; DAD3D_LAYOUT_NHWC: channels-last, each pixel's C channels adjacent, pixels row-major
+ *     yx_out   int32 [B,C,2] = (k // H, k % H): the reference's own unravel (utils.py:50-51 divides by H, not W), kept for H != W
+ *     peak_out float32 [B,C] or NULL: the winning value (the sigmoid's value with sigmoid = 1, the byte's value for uint8)
+ *   k is torch.argmax's / np.argmax's flat index in [0, H*W): the smallest k whose value is NaN if there is one, else the smallest
+ *   k whose value equals the maximum; -0.0 == +0.0; an all -inf or all-equal plane gives 0. With sigmoid = 1 the values compared
+ *   are 1.0f / (1.0f + expf(-x)) in float32, rounded to nearest even to fp16 / bf16 for those inputs and compared there, so the
+ *   first saturated position wins (float32: every logit >= 16.636066 is 1.0), not the largest logit.
+ *   DAD3D_E_INVALID before any device work: a null heatmap or yx_out, a heatmap not aligned to its element, a size <= 0,
+ *   H*W > 2^24, B*C > 2^31 - 1, an unknown dtype or layout, sigmoid with uint8.
+ *
+ * dad3d_points_readjust  `readjust_landmarks_to_the_input_image` with the clip in front of it (predictor.py:132-133,147-152) for a
+ *   batch. src_kind 0: float32 [B,n,2] regressed (x, y); src_kind 1: int32 [B,n,2] (row, col) of dad3d_heatmap_argmax, flipped to
+ *   (x, y) here. Per coordinate, every step rounded on its own as numpy does: float32 v = src * mul (256.0 or float(stride));
+ *   clip to [0, limit] in float32; widen to float64; subtract the integer pad (pad_left for x, pad_top for y); divide by the
+ *   float64 scale (img_size / float(max_side)); truncate toward zero to int32 (saturating). +-inf are made finite by the clip; a NaN
+ *   gives INT32_MIN (numpy's cast is undefined there: this library's choice).
+ *     geometry   float64 [B,3] (pad_left, pad_top, scale) per image, or NULL: the one triple passed by value holds for the batch
+ *     points_out int32 [B,n,2] (x, y)
+ *   DAD3D_E_INVALID before any device work: a null src or points_out, a size <= 0, B*n*2 > 2^31 - 1, an unknown src_kind, and
+ *   without geometry a scale that is not a positive finite number. */
+#define DAD3D_HEATMAP_DTYPE_U8 3
+#define DAD3D_LAYOUT_NCHW 0
+#define DAD3D_LAYOUT_NHWC 1
+#define DAD3D_POINTS_SRC_XY_F32 0
+#define DAD3D_POINTS_SRC_YX_I32 1
+DAD3D_EXPORT dad3d_status dad3d_heatmap_argmax(const void* heatmap, int dtype, int batch, int channels, int h, int w, int layout, int sigmoid,
+                                  int32_t* yx_out, float* peak_out /* or NULL */, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_points_readjust(const void* src, int src_kind, int batch, int n_points, float mul, float limit,
+                                   const double* geometry /* or NULL */, int pad_left, int pad_top, double scale, int32_t* points_out,
+                                   int device, void* stream);
+
 /* Single-image HOST entry points with the argument lists of Sim3DR/lib/rasterize.h:84-100 (`bool` spelled
  * `int` for C). libdad3d_hip.so additionally exports the C++-linkage symbols `_get_tri_normal`,
  * `_get_ver_normal`, `_get_normal`, `_rasterize_triangles`, `_rasterize` with the reference's exact
