@@ -19,8 +19,8 @@
 //     T.[v;1] = sum_j w_j A_j [v;1] collapses to  W v + w_jaw (R_jaw - I)(v - J_jaw)  (W = sum of the weights): the
 //     translations of the other joints and the jaw's (J_jaw - J_neck) + (J_neck - J_root) + J_root chain cancel to fp32
 //     rounding (<= 2e-8 in model units; bar 5e-6, north star 1e-4). The other per-image constants (Rodrigues of the jaw,
-//     6-DoF rotation, scale, translation) are computed by the mma waves for 128 images at a time -- the first round inside
-//     the start-up bubble -- into an LDS ring.
+//     6-DoF rotation, scale, translation) are computed by the mma waves for 128 images at a time -- the first round in front
+//     of the first MFMA, among their basis requests -- into an LDS ring.
 //   * epilogue with the per-image constants in REGISTERS: lane (image i of the wave's 8, vertex group u) holds the image's 24
 //     constants for the half-block and the weights / landmark slots of its <= 3 vertices for the launch, so a (vertex, image)
 //     costs 3 LDS reads + ~30 VALU and leaves as one 12-byte and one 8-byte store (eight lanes = eight consecutive vertices
@@ -38,6 +38,9 @@
 #include "flame_math.hpp"
 #include "flame_pipe_epilogue.hpp"
 
+#ifndef DAD3D_PIPE_R0_AT  // constants round 0 sits behind this one of the mma waves' 26 basis requests (0..25), in all four waves at once.
+#define DAD3D_PIPE_R0_AT 1  // 12.27 / 12.29 / 12.31 us at B = 64 for 1 / 4 / 12 against 12.51 with the round inside the first GEMM; staggered
+#endif                      // over the waves (request 4 + 5 w) 12.53, a tie with the parent: profiles/r08_kernel_log.md section 3
 #ifndef DAD3D_PIPE_STAGER_PRIO  // s_setprio of the stager waves (the mma waves stay at 0). Their instructions are few and every
 #define DAD3D_PIPE_STAGER_PRIO 0  // one of them sits on a latency chain -- but priority 1 measured slower at every size (14.9 / 23.7 / 40.5 / 139.2
                                   // against 14.0 / 22.6 / 39.5 / 138.4 us at B = 64 / 128 / 256 / 1024, same call; 3: as 1)
@@ -72,6 +75,11 @@ struct Lds {
 __device__ __forceinline__ int lds_peek(lds_int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void wait_ge(lds_int* p, int target) {
     while (lds_peek(p) < target) __builtin_amdgcn_s_sleep(1);
+    asm volatile("" ::: "memory");  // the LDS reads this wait guards stay behind it (a wave's LDS operations execute in order)
+}
+__device__ __forceinline__ void wait_ge2(lds_int* p, int target, lds_int* q, int target_q) {  // two words, one LDS round trip per look
+    while ((int)(lds_peek(p) < target) | (int)(lds_peek(q) < target_q)) __builtin_amdgcn_s_sleep(1);
+    asm volatile("" ::: "memory");
 }
 __device__ __forceinline__ void arrive(lds_int* p, int lane) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have completed
@@ -103,7 +111,9 @@ __device__ __forceinline__ void gemm_groups(const float* afrag, const float4 (&b
 #pragma unroll
     for (int G = G0; G < G1; ++G) {
         if (FIRST && G + 1 == 8) wait_ge(parts + 1, 4);
-        if (FIRST && G + 1 == 16) wait_ge(parts + 2, 4 + RB / 2);  // four stagers and the mma waves that wrote the tail rows
+        // the last part of A(0): four stagers and the mma wave that wrote the tail rows. And constants round 0 of all four mma waves, for
+        // load_consts(0) behind this GEMM: written in front of group 7 at the latest, so the second word costs no LDS round trip of its own
+        if (FIRST && G + 1 == 16) wait_ge2(parts + 2, 4 + RB / 2, parts + 3, 4);
         if (G + 1 < KG) {
 #pragma unroll
             for (int m = 0; m < RB; ++m) an[m] = *reinterpret_cast<const float4*>(afrag + m * 16 * LD + 16 * (G + 1));
@@ -128,9 +138,12 @@ __device__ __forceinline__ void gemm_groups(const float* afrag, const float4 (&b
 
 }  // namespace
 
-// Barrier protocol (every wave of the workgroup executes exactly 1 + H phase barriers):
-//   B0      after the mma waves have written constants round 0 (wave 0 also the tail rows of A(0), inside the first GEMM)
+// Barrier protocol (every wave of the workgroup executes exactly 1 + H phase barriers: the start-up barrier and A(0 .. H - 1)):
+//   start   the stagers' requests for the first A image (the mma waves': for the params' tails of round 0) are in the load queue
 //   A(h)    after the mma waves have parked half-block h, the stagers have written A(h + 1) (and its tail rows)
+// Inside the first phase four arrival words in LDS stand for barriers: parts + 0 .. 2 = the three parts of A(0) are in LDS (the third
+// counts the four stagers and mma wave 0, which writes the tail rows k = 400..415), parts + 3 = constants round 0 is in LDS (the four
+// mma waves; read by the stagers before write_tail(1) and by the mma waves before load_consts(0)). Every arrival is unconditional.
 // Between A(h - 1) and A(h): mma waves [write a constants round,] multiply half-block h out of image h & 1 -- finishing half-block
 // h - 1 (accumulator tile (h - 1) & 1, constants already in registers) in the gaps -- park it in tile h & 1 and load its constants
 // into registers; stagers write image (h + 1) & 1 -- last read by GEMM(h - 1) -- and request the rows of half-block h + 2.
@@ -287,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
         arrive(parts, lane);
         stamp(7);
         // The second A image, NOW: a CU's requests come back in order, so what is asked for once the basis requests are queued comes
-        // back behind the whole basis stream -- asked for behind barrier B0 these rows arrived 1.5 k cycles after the mma waves had
+        // back behind the whole basis stream -- asked for ~8 k cycles into the launch these rows arrived 1.5 k cycles after the mma waves had
         // parked the first half-block. Here they interleave with the first basis requests and are back long before that. (In front of
         // the first barrier they would hold the basis back: 13.1 against 12.8 us at B = 64.)
         if (H > 1) load_rows(1, pre1);
@@ -298,7 +311,9 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
         // the tile's rows of the vertex table, for the last half-block (read behind the last barrier)
         if (fw == 3 && lane < TV) vt_lds[lane] = vt_row;
         stamp(2);
-        phase_barrier();  // B0: constants round 0 is in LDS
+        // constants round 0 is in LDS: write_tail(1) copies rows of it. This used to be a workgroup barrier, B0. (One half-block: nothing
+        // here reads the ring in front of A(0), and a wave polling LDS for thousands of cycles takes issue slots from the mma wave on its SIMD.)
+        if (H > 1) wait_ge(parts + 3, 4);
 #pragma unroll 1
         for (int h = 0; h < H; ++h) {
             if (h < 4) stamp(16 + 4 * h);
@@ -369,7 +384,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
                                                                                               // (32-bit index: b P < b V, capi.cpp resolve_kernel)
         }
     };
-    load_raw(0);  // with the stagers' requests, ahead of the basis: needed after seven groups
+    load_raw(0);  // with the stagers' requests, ahead of the basis: needed among the first basis requests
     float4 bq[KG];  // the wave's basis slice, resident for the launch
     // -- epilogue role: the wave finishes images [8 w, 8 w + 8) of every half-block; lane = (image ei, vertex group eu) walks the
     // vertices eu, eu + 8, eu + 16 of the tile. Their weights and landmark slots stay in registers for the launch.
@@ -421,7 +436,6 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
         if (G == 11) epi_finish(1), epi_fetch(2);
         if (G == 19) epi_finish(2);
     };
-    auto no_hook = [](int) {};
     const float* afrag0 = abuf + (lane & 15) * LD + 4 * (lane >> 4);
     float* const ot0 = otile + ((lane >> 4) * 4) * OS + wave * 16 + (lane & 15);
     // accumulators -> LDS tile [image][column]; D layout: row = (lane >> 4) * 4 + reg, column = lane & 15
@@ -443,10 +457,34 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
     // half-block 12.2 k cycles at that pace) nor for anybody's data: no wave waits for a load in front of the barrier above.
     // (in THIS order -- the requests come back in order and group 0 is what the first MFMA waits for; left alone, the scheduler
     // issued group 0 twenty-fifth)
+    // Constants round 0 sits INSIDE this issue loop, behind request DAD3D_PIPE_R0_AT: the params' tails were asked for in front of the
+    // barrier and are back first -- requests return in order -- and no MFMA streams yet, so the round's VALU work costs the matrix
+    // pipe nothing. The address unit does not run dry meanwhile: it serves the stagers' requests for the second A image, which
+    // otherwise queue between the basis requests until ~7 k cycles. (The round used to sit between groups 6 and 7 of the first GEMM,
+    // on the reading that it fills time the GEMM would spend waiting for the basis anyway. The stamps say the MFMA chain of all four
+    // waves stopped for ~1.4 k cycles there. What the move buys is less than that: the first MFMA now starts ~1.3 k cycles later and
+    // the GEMM behind it runs at ~300 cycles a group instead of ~320 + the stop -- the first half-block is parked ~0.3-0.5 k cycles
+    // earlier, the rest the basis stream takes back. profiles/r08_kernel_log.md.)
+    // A launch (or chunk) of ONE half-block has no second A image: nothing would feed the address unit during the round and every
+    // cycle of it would delay the basis, which is all such a launch waits for (landmark-only chunks 8.05 -> 8.34 us at 256 rows, B = 32
+    // 8.30 -> 8.37). There the round stays between groups 6 and 7 of the GEMM. Launch-uniform: a wave runs the round, and arrives, at
+    // exactly one of the two places.
+    const bool round0_early = H > 1;
+    auto round0 = [&]() {
+        stamp(1);
+        write_round(0, true);
+        if (wave == 0) arrive(parts + 2, lane);  // the tail rows of A(0)
+        arrive(parts + 3, lane);                 // "round 0 is in LDS": what barrier B0 used to say
+        stamp(4);
+    };
 #pragma unroll
     for (int G = 0; G < KG; ++G) {
         bq[G] = bsrc[(size_t)G * 256];
         __builtin_amdgcn_sched_barrier(0);
+        if (G == DAD3D_PIPE_R0_AT && round0_early) {
+            round0();
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     // the lanes' rows of the vertex table: weights and landmark slots, first used by the first epilogue -- behind the basis
     // (unconditional, from a clamped row: a branch around a load makes the wave wait for it on the spot; vl[k] gates every use)
@@ -455,24 +493,24 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
         const float4 t = a.vtab[min(v0 + eu + 8 * k, a.n_verts - 1)];
         vW[k] = t.x, vw2[k] = t.y, lh[k] = __float_as_int(t.z), ln[k] = __float_as_int(t.w);
     }
-    {   // the first half-block: A arrives in parts, the basis slice is still streaming into the registers. The constants of the
-        // first 128 images are computed between two of its groups: their ~250 instructions fill time the GEMM would spend waiting
-        // for the basis anyway, and nothing in front of the first MFMA waits for the params' tails.
+    {   // the first half-block: A arrives in parts, the basis slice is still streaming into the registers. Nothing but LDS reads and
+        // MFMAs: the constants of the first 128 images were written above, among the basis requests (one half-block: behind group 6).
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         float4 af[2];
         stamp(16);
-        gemm_groups<true, 0, 7, 2>(afrag0, bq, acc, af, parts, no_hook);
-        stamp(1);
-        write_round(0, true);
-        if (wave == 0) arrive(parts + 2, lane);
-        stamp(4);
-        phase_barrier();  // B0
-        gemm_groups<true, 7, KG, 2>(afrag0, bq, acc, af, parts, no_hook);
+        gemm_groups<true, 0, KG, 2>(afrag0, bq, acc, af, parts, [&](int G) {
+            if (G == 6 && !round0_early) {
+                // (the loaded values made opaque: left alone the compiler sees one computation at two places, hoists it in front of
+                // the first basis request -- behind a wait for the params' tails -- and every launch starts its basis stream late)
+                asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2), "+v"(raw_scale));
+                round0();
+            }
+        });
         stamp(2);
         park(0, acc);
         stamp(17);
     }
-    if (H > 1) load_consts(0);
+    if (H > 1) load_consts(0);  // (round 0 is in LDS: the GEMM waited for parts + 3 at group 16)
     phase_barrier();  // A(0)
     stamp(18);
 #pragma unroll 1
