@@ -154,6 +154,25 @@ inline void pipe_chunking(int n_tiles, int n_half, int* chunk_half, int* n_chunk
     *n_chunks = (n_half + *chunk_half - 1) / *chunk_half;
     *wg_per_xcd = (n_tiles * *n_chunks + 7) / 8;
 }
+// The kernel's `geom` argument (flame_decode_pipe.hip: one preloaded dword): the flags and a chunked launch's geometry in one word, a byte
+// each: flags | wg_per_xcd (<= 32) | n_chunks - 1 | n_tiles. pipe_chunking gives tiles x chunks <= 256 with at least two chunks: n_tiles <= 128,
+// but n_chunks up to 256 -- a sub-model of ONE tile (a landmark list of up to 20 vertices) whose n_half is a multiple of 256 -- hence the
+// "- 1". A launch that is not chunked sends the flags alone and reads n_chunks = 1, which is what PipeArgs says of it. (Bytes on purpose:
+// the kernel divides the workgroup number by n_chunks in front of its first address, and a divisor the compiler knows to be <= 256 takes
+// the short form of that division.)
+struct PipeGeom {
+    unsigned flags;
+    int wg_per_xcd, n_chunks, n_tiles;
+};
+constexpr bool pipe_geom_fits(int wg_per_xcd, int n_chunks, int n_tiles) {
+    return wg_per_xcd >= 0 && wg_per_xcd < 256 && n_chunks >= 1 && n_chunks <= 256 && n_tiles >= 0 && n_tiles < 256;
+}
+constexpr unsigned pipe_geom_word(unsigned flags, int wg_per_xcd, int n_chunks, int n_tiles) {
+    return (flags & 0xFFu) | (unsigned)wg_per_xcd << 8 | (unsigned)(n_chunks - 1) << 16 | (unsigned)n_tiles << 24;
+}
+constexpr PipeGeom pipe_geom_unpack(unsigned w) {
+    return PipeGeom{w & 0xFFu, (int)(w >> 8 & 0xFFu), (int)(w >> 16 & 0xFFu) + 1, (int)(w >> 24)};
+}
 dad3d_status launch_flame_decode_pipe(const PipeArgs& a, hipStream_t s);
 size_t flame_decode_pipe_lds_bytes();
 

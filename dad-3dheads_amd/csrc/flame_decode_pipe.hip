@@ -154,15 +154,45 @@ __device__ __forceinline__ void gemm_groups(const float* afrag, const float4 (&b
 // between them, rows 0..15 finished inside row block 1's GEMM and only rows 16..31 behind A(H - 1) -- bit-identical, 12.50 against 12.47 us
 // at B = 64 on top of the write-through landmark stores, 12.78 against 12.68 alone: the tail behind the last barrier is ~1.5 k cycles of
 // latency whether a lane finishes one vertex or two, and two chains of 104 dependent MFMAs are slower than one of 208 independent pairs.)
-// The two ends of a launch: nothing waits for data in front of the first barrier, and no store is left to the end-of-kernel write-back --
+// The two ends of a launch: nothing waits for data in front of the first barrier -- not for the kernel's own arguments either (below:
+// preloaded, and the rest read where a wave waits anyway) --, and no store is left to the end-of-kernel write-back --
 // vertex stores, landmark slots and `translation z := 0` are all written through (flame_pipe_epilogue.hpp).
 // CHUNKED (models of few tiles: the landmark sub-model's 23 for the 445 list): the batch is cut into a.n_chunks chunks of a.chunk_half
 // half-blocks and a workgroup is one (tile, chunk) -- the kernel below on rows [b0, b0 + chunk) with every pointer moved there, so a
 // row's results are the bits of an unchunked launch. Workgroups w = tile * n_chunks + chunk are dealt to the XCDs in runs of a.wg_per_xcd
 // (<= 32, one per CU); workgroup id -> XCD id % 8 is the observed placement (MI355X_MICROARCH.md, "for speed only"): the chunks of one
 // tile sit on one XCD (two at a run's end) and its basis slice crosses the fabric once or twice, not once per chunk.
+// Arguments: flat scalars in the order of first use, not one by-value struct -- the unit is built with -mllvm -amdgpu-kernarg-preload-count
+// (Makefile) and the first kPipePreloadDwords dwords of the kernarg segment arrive in SGPRs with the wave: everything the code in front of
+// the start-up barrier reads, so no wave starts with a scalar load from a kernarg slot that is fresh with every launch and a wait for it. The
+// compiler preloads scalar arguments only (a by-value struct: none) and whole arguments only, so the fourteen dwords are four pointers and
+// six words with no padding between them; 14 is what the hardware takes (16 user SGPRs, two of them the kernarg pointer). `span_half`: the
+// half-blocks a workgroup walks at most -- PipeArgs::n_half, CHUNKED PipeArgs::chunk_half (n_half is then the chunk's own). `geom`:
+// pipe_geom_word (common.hpp: the flags and a chunked launch's wg_per_xcd, n_chunks, n_tiles). The rest is one struct behind them, read from the kernarg segment by late_args() below. (The compiler keeps a prologue in
+// front of the entry that loads the preloaded range, for firmware that does not preload.) tests/test_decode_pipe_entry.py holds the
+// descriptor to this list. Measured: 11.85 against 12.19 us at B = 64 (profiles/r09_kernel_log.md).
+constexpr int kPipePreloadDwords = 14;  // params 2 | bpack 2 | vtab 2 | trace 2 | batch | n_verts | n_params | span_half | geom | n_lmk
+static_assert(4 * kPipePreloadDwords == 4 * sizeof(void*) + 6 * sizeof(int), "the preloaded range ends with n_lmk");
+struct PipeLateArgs {  // the arguments behind the preloaded range: one by-value struct, read where late_args() stands
+    const int* lmk_next;
+    float *verts3d, *proj, *lmk_xy;
+    int32_t* lmk_px;
+    float image_size;
+};
+static_assert((4 * kPipePreloadDwords) % alignof(PipeLateArgs) == 0, "`late` starts where the preloaded range ends: late_args() reads it there");
 template <bool TO2D, bool CHUNKED>
-__global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
+__global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(float* params, const float* bpack, const float4* vtab, unsigned long long* trace_buf, int batch,
+                                                                   int n_verts, int n_params, int span_half, unsigned geom, int n_lmk, PipeLateArgs late) {
+    // (dissolved by the compiler: the body below reads the launch's geometry under the names the host gives it. ORDER: lmk_next, verts3d, proj,
+    // lmk_xy, lmk_px and image_size are NOT set here -- late_args() sets them, and with them cx, rs3, rsp and outs; nothing may read any of
+    // those in front of a role's late_args() call. n_half and chunk_half both start as span_half: a chunked launch sends its chunk_half there and
+    // computes n_half below, any other launch never reads chunk_half. Rewritten on two fully initialised local structs the kernel is tidier
+    // and its chunked instantiation slower than the by-value struct at 2048 landmark-only rows -- profiles/r09_kernel_log.md section 3.)
+    PipeArgs a;
+    a.params = params, a.bpack = bpack, a.vtab = vtab, a.trace = trace_buf, a.n_params = n_params, a.batch = batch, a.n_half = span_half, a.n_verts = n_verts, a.n_lmk = n_lmk;
+    const PipeGeom g = pipe_geom_unpack(geom);
+    a.flags = g.flags, a.chunk_half = span_half, a.wg_per_xcd = g.wg_per_xcd, a.n_chunks = g.n_chunks, a.n_tiles = g.n_tiles;
+    // (`late` is read through the kernarg pointer in late_args(), not here: named here, its load would sit at the top of the kernel)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* abuf = smem + Lds::a_off;
     float* otile = smem + Lds::o_off;
@@ -174,17 +204,14 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
     // launch, no scratch. Made uniform with readfirstlane the branch turns scalar -- and 30-odd values turn into SGPRs with it: 7 spills
     // inside the loops instead of 2 outside them. tests/test_kernel_resources.py holds the line: scratch 0, VGPR spills 0.)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_id = blockIdx.x;
+    int tile_id = blockIdx.x, chunk_b0 = 0;
     if (CHUNKED) {
         const int w = (blockIdx.x & 7) * a.wg_per_xcd + (blockIdx.x >> 3);
         if ((int)(blockIdx.x >> 3) >= a.wg_per_xcd || w >= a.n_tiles * a.n_chunks) return;
         tile_id = w / a.n_chunks;
         const int b0 = (w % a.n_chunks) * a.chunk_half * HB;
+        chunk_b0 = b0;  // (the output pointers move there in late_args())
         a.params += (size_t)b0 * a.n_params;
-        if (a.verts3d) a.verts3d += (size_t)b0 * a.n_verts * 3;
-        if (a.proj) a.proj += (size_t)b0 * a.n_verts * (TO2D ? 2 : 3);
-        if (a.lmk_xy) a.lmk_xy += (size_t)b0 * a.n_lmk * 2;
-        if (a.lmk_px) a.lmk_px += (size_t)b0 * a.n_lmk * 2;
         a.batch = min(a.batch - b0, a.chunk_half * HB);
         a.n_half = (a.batch + HB - 1) / HB;
     }
@@ -198,20 +225,41 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
     stamp(0);
     if (tid < 4) __hip_atomic_store(parts + tid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const unsigned nl = (unsigned)a.n_lmk;
+    // What hangs on the arguments behind the preloaded range -- the output pointers, lmk_next, image_size -- is formed by late_args(): a scalar
+    // load of `late` through the kernarg pointer (a miss, ~450 cycles: the slot is fresh with every launch) and the wait for it, once per role
+    // and where the role waits anyway. In front of the role split it would put back what the preload takes away; as ONE load at the top with
+    // the wait further down its eleven registers live through both roles beside what is made of them: 10-12 SGPR spills.
     EpiCtx cx;
-    // 3d_vertices / projection leave as raw buffer stores: (uniform resource) + (32-bit byte offset of the lane) + immediate
-    const __amdgpu_buffer_rsrc_t rs3 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.verts3d), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.proj), 0, 0x7fffffff, 0x00020000);
-    // (the landmark slots and `translation z := 0` leave as write-through stores too -- DAD3D_PIPE_LMK_STORE_AUX, flame_pipe_epilogue.hpp:
-    // no store of this kernel is left to the end-of-kernel write-back of the XCDs' L2s)
-    cx.lx = reinterpret_cast<char*>(a.lmk_xy), cx.lp = reinterpret_cast<char*>(a.lmk_px);
-    // whether the launch has the two vertex outputs, as ONE opaque scalar word (bit 0 verts3d, bit 1 proj) tested where it is used: left
-    // to itself the compiler holds a 64-bit lane mask of each for the whole launch, and the scalar file is full -- the write-through stores
-    // took the CHUNKED instantiation from 3 SGPR spills to 5 without this (tests/test_kernel_resources.py allows 3). Timing: the same.
-    unsigned outs = __builtin_amdgcn_readfirstlane((a.verts3d ? 1u : 0u) | (a.proj ? 2u : 0u));
-    asm volatile("" : "+s"(outs));
-    cx.lmk_next = a.lmk_next;
-    cx.image_size = a.image_size;
+    __amdgpu_buffer_rsrc_t rs3, rsp;
+    unsigned outs = 0;
+    auto late_args = [&]() {
+        typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+        typedef const __attribute__((address_space(4))) PipeLateArgs* late_ptr;
+        kernarg_ptr kp = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));  // (opaque: otherwise the loads below are one load at the top of the kernel, and its values live through both roles)
+        const late_ptr lp = reinterpret_cast<late_ptr>(kp + 4 * kPipePreloadDwords);
+        a.lmk_next = lp->lmk_next, a.verts3d = lp->verts3d, a.proj = lp->proj, a.lmk_xy = lp->lmk_xy, a.lmk_px = lp->lmk_px, a.image_size = lp->image_size;
+        if (CHUNKED) {
+            const size_t b0 = (size_t)chunk_b0;
+            if (a.verts3d) a.verts3d += b0 * a.n_verts * 3;
+            if (a.proj) a.proj += b0 * a.n_verts * (TO2D ? 2 : 3);
+            if (a.lmk_xy) a.lmk_xy += b0 * a.n_lmk * 2;
+            if (a.lmk_px) a.lmk_px += b0 * a.n_lmk * 2;
+        }
+        // 3d_vertices / projection leave as raw buffer stores: (uniform resource) + (32-bit byte offset of the lane) + immediate
+        rs3 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.verts3d), 0, 0x7fffffff, 0x00020000);
+        rsp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.proj), 0, 0x7fffffff, 0x00020000);
+        // (the landmark slots and `translation z := 0` leave as write-through stores too -- DAD3D_PIPE_LMK_STORE_AUX, flame_pipe_epilogue.hpp:
+        // no store of this kernel is left to the end-of-kernel write-back of the XCDs' L2s)
+        cx.lx = reinterpret_cast<char*>(a.lmk_xy), cx.lp = reinterpret_cast<char*>(a.lmk_px);
+        // whether the launch has the two vertex outputs, as ONE opaque scalar word (bit 0 verts3d, bit 1 proj) tested where it is used: left
+        // to itself the compiler holds a 64-bit lane mask of each for the whole launch, and the scalar file is full -- the write-through stores
+        // took the CHUNKED instantiation from 3 SGPR spills to 5 without this (tests/test_kernel_resources.py allows 3). Timing: the same.
+        outs = __builtin_amdgcn_readfirstlane((a.verts3d ? 1u : 0u) | (a.proj ? 2u : 0u));
+        asm volatile("" : "+s"(outs));
+        cx.lmk_next = a.lmk_next;
+        cx.image_size = a.image_size;
+    };
     cx.zsign = (a.flags & DAD3D_FLIP_Z) ? -1.0f : 1.0f;
     float4* const vt_lds = reinterpret_cast<float4*>(smem + Lds::v_off);
     // The LAST half-block has no GEMM to ride in and nothing left to stage: all eight waves finish it, four images each, lane =
@@ -296,6 +344,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
         // CU's load queue, ahead of the 104 KB of basis they are about to ask for.
         phase_barrier();  // (and: the arrival words are zero)
         stamp(6);
+        late_args();  // (the wait hides behind the one for the first rows of A(0))
         write_a(0, 0, 4);
         arrive(parts, lane);
         stamp(7);
@@ -448,6 +497,9 @@ __global__ __launch_bounds__(512, 2) void flame_decode_pipe_kernel(PipeArgs a) {
     };
     const int n_rounds = (B + kRound - 1) / kRound;
 
+    // (here, where the mma waves are about to wait for the stagers anyway -- those reach the barrier ~1 k cycles later. Behind the basis requests
+    // the same scalar load sits under the basis stream and the headline LOSES 0.1 us against the by-value struct: profiles/r09_kernel_log.md)
+    late_args();
     stamp(6);
     phase_barrier();  // the stagers' requests for the first A image are in the load queue (and the arrival words are zero)
     stamp(7);
@@ -552,10 +604,19 @@ dad3d_status launch_flame_decode_pipe(const PipeArgs& a, hipStream_t s) {
     }
     // without a projection output the two instantiations differ in nothing that runs
     const bool to2d = (a.flags & DAD3D_TO_2D) || !a.proj;
-    if (a.chunk_half > 0 && to2d) {
-        hipLaunchKernelGGL((flame_decode_pipe_kernel<true, true>), dim3(8 * a.wg_per_xcd), dim3(512), lds, s, a);
-    } else if (to2d) hipLaunchKernelGGL((flame_decode_pipe_kernel<true, false>), dim3(a.n_tiles), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((flame_decode_pipe_kernel<false, false>), dim3(a.n_tiles), dim3(512), lds, s, a);
+    const bool chunked = a.chunk_half > 0 && to2d;
+    DAD3D_REQUIRE(!chunked || pipe_geom_fits(a.wg_per_xcd, a.n_chunks, a.n_tiles), "launch_flame_decode_pipe: chunk geometry %d x %d in runs of %d "
+                  "does not fit the kernel's geometry word", a.n_tiles, a.n_chunks, a.wg_per_xcd);  // (nothing pipe_chunking gives: tests/test_pipe_geom_word.py)
+    const unsigned geom = chunked ? pipe_geom_word(a.flags, a.wg_per_xcd, a.n_chunks, a.n_tiles) : pipe_geom_word(a.flags, 0, 1, 0);
+    const int span_half = chunked ? a.chunk_half : a.n_half;
+    const PipeLateArgs late{a.lmk_next, a.verts3d, a.proj, a.lmk_xy, a.lmk_px, a.image_size};
+#define DAD3D_PIPE_LAUNCH(TO2D_, CHUNKED_, GRID_)                                                                                              \
+    hipLaunchKernelGGL((flame_decode_pipe_kernel<TO2D_, CHUNKED_>), dim3(GRID_), dim3(512), lds, s, a.params, a.bpack, a.vtab, a.trace, a.batch, \
+                       a.n_verts, a.n_params, span_half, geom, a.n_lmk, late)
+    if (chunked) DAD3D_PIPE_LAUNCH(true, true, 8 * a.wg_per_xcd);
+    else if (to2d) DAD3D_PIPE_LAUNCH(true, false, a.n_tiles);
+    else DAD3D_PIPE_LAUNCH(false, false, a.n_tiles);
+#undef DAD3D_PIPE_LAUNCH
     DAD3D_HIP_TRY(hipGetLastError());
     return DAD3D_OK;
 }
