@@ -39,6 +39,9 @@ OVERLAY_MAX_COORD = 8192
 DTYPE_F16, DTYPE_BF16, HEATMAP_DTYPE_U8 = 1, 2, 3
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 POINTS_SRC_XY_F32, POINTS_SRC_YX_I32 = 0, 1
+BOX_DTYPE_I32, BOX_DTYPE_I64, BOX_DTYPE_F32, BOX_DTYPE_F64 = 0, 1, 2, 3
+PREPROCESS_OUT_F32_NCHW, PREPROCESS_OUT_F16_NHWC, PREPROCESS_OUT_BF16_NHWC = 0, 1, 2
+BOX_FLAG_EMPTY, BOX_FLAG_COLLAPSED, BOX_FLAG_RANGE = 0x1, 0x2, 0x4
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -135,6 +138,10 @@ SIGNATURES = {
     "dad3d_nhwc_resize_sum": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_float), _I, _P]),
     "dad3d_heatmap_argmax": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "dad3d_points_readjust": (_I, [_P, _I, _I, _I, _F, _F, _P, _I, _I, C.c_double, _P, _I, _P]),
+    "dad3d_preprocess_boxes": (_I, [_P, _I, _P, _I, _P, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, _P,
+                                    _I, _P]),
+    "dad3d_flame_readjust_params_frame": (_I, [_P, _P, _I, _P, _P]),
+    "dad3d_points_readjust_frame": (_I, [_P, _I, _I, _I, _F, _F, _P, _P, _I, _P]),
     "dad3d_cube_region_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "dad3d_point_loss_terms": (_I, [_I]),
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),

@@ -1742,6 +1742,52 @@ dad3d_status dad3d_points_readjust(const void* src, int src_kind, int batch, int
     return launch_points_readjust(a, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_preprocess_boxes(const int64_t* images, int n_images, const void* boxes, int box_dtype, const int32_t* image_index,
+                                    int n_boxes, const double* offset, int out_size, const float* mean, const float* std, int out_format,
+                                    void* out, int32_t* crops, double* geometry, int32_t* flags, int device, void* stream) {
+    DAD3D_REQUIRE(n_boxes >= 0 && n_boxes <= 65535 && out_size >= 1 && out_size <= 65535,
+                  "dad3d_preprocess_boxes: %d boxes / size %d outside the launch grid (65535)", n_boxes, out_size);
+    DAD3D_REQUIRE(box_dtype >= DAD3D_BOX_DTYPE_I32 && box_dtype <= DAD3D_BOX_DTYPE_F64, "dad3d_preprocess_boxes: unknown box_dtype %d", box_dtype);
+    DAD3D_REQUIRE(out_format >= DAD3D_PREPROCESS_OUT_F32_NCHW && out_format <= DAD3D_PREPROCESS_OUT_BF16_NHWC,
+                  "dad3d_preprocess_boxes: unknown out_format %d", out_format);
+    if (n_boxes == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(n_images >= 1 && n_images <= 65535, "dad3d_preprocess_boxes: %d images outside 1 .. 65535", n_images);
+    DAD3D_REQUIRE(images && boxes && image_index && mean && std && out && crops && geometry && flags, "dad3d_preprocess_boxes: null argument");
+    DAD3D_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "dad3d_preprocess_boxes: out must be 4-byte aligned");
+    PreprocessBoxesArgs a{};
+    if (offset) {
+        for (int k = 0; k < 4; ++k)
+            DAD3D_REQUIRE(offset[k] - offset[k] == 0.0, "dad3d_preprocess_boxes: offset[%d] is not finite", k);
+        a.has_offset = 1, a.left = offset[0], a.right = offset[1], a.top = offset[2], a.bottom = offset[3];
+    }
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    a.images = reinterpret_cast<const long long*>(images), a.n_images = n_images;
+    a.boxes = boxes, a.box_dtype = box_dtype, a.image_index = image_index, a.n_boxes = n_boxes;
+    a.out_size = out_size, a.out_format = out_format, a.out = out, a.crops = crops, a.geometry = geometry, a.flags = flags;
+    return launch_preprocess_boxes(a, mean, std, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_flame_readjust_params_frame(dad3d_flame* h, float* params, int batch, const double* geometry, void* stream) {
+    DAD3D_REQUIRE(h && batch >= 0, "dad3d_flame_readjust_params_frame: bad argument");
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(params && geometry, "dad3d_flame_readjust_params_frame: null argument");
+    DeviceGuard guard(h->device);
+    return launch_readjust_frame(params, batch, h->lay, geometry, h->image_size, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_points_readjust_frame(const void* src, int src_kind, int batch, int n_points, float mul, float limit, const double* geometry,
+                                         int32_t* points_out, int device, void* stream) {
+    DAD3D_REQUIRE(src_kind == DAD3D_POINTS_SRC_XY_F32 || src_kind == DAD3D_POINTS_SRC_YX_I32, "dad3d_points_readjust_frame: unknown src_kind %d", src_kind);
+    DAD3D_REQUIRE(batch > 0 && n_points > 0, "dad3d_points_readjust_frame: bad size (batch %d, n_points %d)", batch, n_points);
+    DAD3D_REQUIRE((int64_t)batch * n_points * 2 <= 0x7fffffff, "dad3d_points_readjust_frame: %d x %d points are beyond the launch grid", batch, n_points);
+    DAD3D_REQUIRE(src && points_out && geometry, "dad3d_points_readjust_frame: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    PointsReadjustArgs a{src, src_kind, batch, n_points, mul, limit, geometry, 0, 0, 1.0, points_out};
+    return launch_points_readjust_frame(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_cube_region_loss(const float* pred, const float* target, int batch, int n_verts,
                                     const int32_t* region_ptr, const int32_t* region_idx, const float* region_weight,
                                     int n_regions, const int32_t* vert_ptr, const int32_t* vert_region,

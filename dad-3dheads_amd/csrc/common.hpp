@@ -717,4 +717,26 @@ struct PointsReadjustArgs {
 };
 dad3d_status launch_points_readjust(const PointsReadjustArgs& a, hipStream_t s);
 
+// frames + bounding boxes -> network input, and a crop's results moved into its frame (preprocess_boxes.hip)
+struct PreprocessBoxesArgs {
+    const long long* images;  // [M][4] {address, h, w, row stride in bytes}
+    int n_images;
+    const void* boxes;  // [N][4] (x, y, w, h) of box_dtype
+    int box_dtype;
+    const int32_t* image_index;  // [N]
+    int n_boxes;
+    int has_offset;
+    double left, right, top, bottom;  // extend_bbox's factors
+    int out_size, out_format;
+    float3 mean255, inv_std255;
+    void* out;
+    int32_t* crops;    // [N][4]
+    double* geometry;  // [N][5] (pad_left, pad_top, scale, x, y)
+    int32_t* flags;    // [N]
+};
+dad3d_status launch_preprocess_boxes(PreprocessBoxesArgs a, const float mean[3], const float std[3], hipStream_t s);
+// geometry: [B][5] as above
+dad3d_status launch_readjust_frame(float* params, int batch, ParamLayout lay, const double* geometry, float img_size, hipStream_t s);
+dad3d_status launch_points_readjust_frame(const PointsReadjustArgs& a, hipStream_t s);  // a.geometry is [B][5]
+
 }  // namespace dad3d

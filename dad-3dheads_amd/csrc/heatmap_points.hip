@@ -26,6 +26,7 @@
 
 #include "collectives.hpp"
 #include "common.hpp"
+#include "points_math.hpp"
 
 namespace dad3d {
 namespace {
@@ -220,18 +221,9 @@ __global__ __launch_bounds__(256) void points_readjust_kernel(PointsReadjustArgs
     const int xy = i & 1, b = i / (2 * a.n_points);
     // (row, col) from the argmax is flipped to (x, y)
     const float s = a.src_kind == 0 ? static_cast<const float*>(a.src)[i] : (float)static_cast<const int32_t*>(a.src)[i ^ 1];
-    float v = s * a.mul;
-    v = v < 0.0f ? 0.0f : v;  // np.clip == minimum(maximum(v, 0), limit): a NaN passes through both
-    v = v > a.limit ? a.limit : v;
     double pad = xy == 0 ? a.pad_left : a.pad_top, scale = a.scale;  // the pads are integers held in float64
     if (a.geometry) pad = a.geometry[3 * b + xy], scale = a.geometry[3 * b + 2];
-    const double d = ((double)v - pad) / scale;
-    int out;
-    if (d != d) out = INT32_MIN;  // numpy's cast of a NaN is undefined: this project's choice
-    else if (d >= 2147483647.0) out = INT32_MAX;
-    else if (d <= -2147483648.0) out = INT32_MIN;
-    else out = (int)d;  // toward zero
-    a.points[i] = out;
+    a.points[i] = readjusted_coordinate(s, a.mul, a.limit, pad, scale);
 }
 
 template <typename T>

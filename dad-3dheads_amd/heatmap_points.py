@@ -60,8 +60,13 @@ def _readjust(src: Tensor, kind: int, mul: float, limit: float, geometry: Geomet
         triple = (int(geometry[0]), int(geometry[1]), float(geometry[2]))
     else:  # a list of triples: one upload
         geo = torch.tensor([[float(g[0]), float(g[1]), float(g[2])] for g in geometry], dtype=torch.float64).to(dev, non_blocking=True)
+    if geo is not None and tuple(geo.shape) == (b, 5):  # a crop's points in its frame: + (x, y) after the truncation
+        _lib.check(_lib.load().dad3d_points_readjust_frame(src.data_ptr(), kind, b, n, float(mul), float(limit), geo.data_ptr(), out.data_ptr(),
+                                                           dev.index or 0, torch.cuda.current_stream(dev).cuda_stream))
+        return out
     if geo is not None and tuple(geo.shape) != (b, 3):
-        raise ValueError(f"expected one (pad_left, pad_top, scale) triple or {b} of them, got {tuple(geo.shape)}")
+        raise ValueError(f"expected one (pad_left, pad_top, scale) triple, {b} of them or {b} rows (pad_left, pad_top, scale, x, y), "
+                         f"got {tuple(geo.shape)}")
     _lib.check(_lib.load().dad3d_points_readjust(src.data_ptr(), kind, b, n, float(mul), float(limit), None if geo is None else geo.data_ptr(),
                                                  triple[0], triple[1], triple[2], out.data_ptr(), dev.index or 0,
                                                  torch.cuda.current_stream(dev).cuda_stream))
@@ -71,7 +76,9 @@ def _readjust(src: Tensor, kind: int, mul: float, limit: float, geometry: Geomet
 def points_from_landmarks(lm: Tensor, geometry: Geometry, img_size: int) -> Tensor:
     """int32 CUDA `[B,n,2]`: `((lm * 256.0).clip(0, img_size) - (pad_left, pad_top)) / scale` truncated, as numpy evaluates it on
     the float32 landmarks `[B, 2n]` or `[B,n,2]` (predictor.py:132-133,147-152). `geometry` is one (pad_left, pad_top, scale)
-    triple for the batch, a list of one per image, or a float64 `[B,3]` tensor; the scale is `img_size / float(max_side)`."""
+    triple for the batch, a list of one per image, or a float64 `[B,3]` tensor; the scale is `img_size / float(max_side)`. A float64
+    `[B,5]` tensor (pad_left, pad_top, scale, x, y) is the geometry of crops (`dad3d_preprocess_boxes`): the integers (x, y), the
+    crop's origin in its frame, are added after the truncation."""
     if not lm.is_cuda or lm.ndim not in (2, 3) or lm.shape[-1] % 2:
         raise ValueError(f"expected CUDA landmarks [B,2n] or [B,n,2], got {tuple(lm.shape)} on {lm.device}")
     src = lm.detach().to(torch.float32).reshape(lm.shape[0], -1, 2).contiguous()

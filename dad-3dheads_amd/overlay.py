@@ -162,6 +162,43 @@ def _tables_from(table: Tensor):
     return tables_for
 
 
+# -- several heads per frame ---------------------------------------------------------------------------------------------------------
+def _by_frame(draw: Callable, predictions: Predictions, images: Images, image_index, out: Optional[Images], **kwargs):
+    """`draw(predictions, images, ...)` for predictions that name their frames: prediction k is drawn into `images[image_index[k]]`,
+    the heads of one frame in the order they come. Round r draws the r-th head of every frame that has one into the running
+    images, on the kernels `draw` launches anyway, so the bytes are those of one call per head on the running image (a loop over
+    the reference's demo_utils). A frame without heads is copied."""
+    items, form = _image_list(images)
+    if isinstance(predictions, dict):
+        raise ValueError("image_index: expected the list of per-head dicts that predict_boxes returns")
+    dicts = list(predictions)
+    index = np.asarray(image_index.cpu() if isinstance(image_index, Tensor) else image_index).reshape(-1).astype(np.int64)  # a tensor: one wait
+    if len(index) != len(dicts):
+        raise ValueError(f"image_index: {len(index)} entries for {len(dicts)} predictions")
+    if len(index) and not (0 <= index.min() and index.max() < len(items)):
+        raise ValueError(f"image_index: values outside 0 .. {len(items) - 1}")
+    heads: List[List[int]] = [[] for _ in items]
+    for k, i in enumerate(index):
+        heads[int(i)].append(k)
+    running = [t.clone() for t in items]
+    for r in range(max((len(h) for h in heads), default=0)):
+        frames = [i for i, h in enumerate(heads) if len(h) > r]
+        drawn = draw([dicts[heads[i][r]] for i in frames], [running[i] for i in frames], **kwargs)
+        for i, t in zip(frames, drawn):
+            running[i] = t
+    result = torch.stack(running) if form == "batch" else running[0] if form == "single" else running
+    if out is None:
+        return result
+    if form == "list":
+        if len(out) != len(items):
+            raise ValueError(f"out: {len(out)} tensors for {len(items)} images")
+        for o, t in zip(out, running):
+            o.copy_(t)
+    else:
+        out.copy_(result)
+    return out
+
+
 # -- the reference's surface --------------------------------------------------------------------------------------------------------
 def default_radius(h: int, w: int) -> int:
     return max(1, int(min(h, w) * 0.005))  # demo_utils.py:26
@@ -183,8 +220,11 @@ def draw_points(images: Images, points, radius: Optional[int] = None, color=POIN
     return _draw(images, out, _tables_from(table), launch)
 
 
-def draw_landmarks(predictions: Predictions, images: Images, out: Optional[Images] = None):
-    """demo_utils.py:32-34: the 68 predicted 2-D landmarks `predictions["points"]`."""
+def draw_landmarks(predictions: Predictions, images: Images, out: Optional[Images] = None, image_index=None):
+    """demo_utils.py:32-34: the 68 predicted 2-D landmarks `predictions["points"]`. With `image_index` (one frame number per
+    prediction, as `predict_boxes` returns them) prediction k is drawn into `images[image_index[k]]`, several heads of a frame in order."""
+    if image_index is not None:
+        return _by_frame(draw_landmarks, predictions, images, image_index, out)
     items, _ = _image_list(images)
     return draw_points(images, _field(predictions, "points", len(items), 2), out=out)
 
@@ -208,8 +248,11 @@ def landmark_indices(subset: str) -> np.ndarray:
     return _subset_ids(subset)
 
 
-def draw_3d_landmarks(predictions: Predictions, images: Images, subset: str = "191", out: Optional[Images] = None):
-    """demo_utils.py:37-47: discs at the projected vertices of a landmark subset."""
+def draw_3d_landmarks(predictions: Predictions, images: Images, subset: str = "191", out: Optional[Images] = None, image_index=None):
+    """demo_utils.py:37-47: discs at the projected vertices of a landmark subset. `image_index`: as in `draw_landmarks`."""
+    if image_index is not None:
+        landmark_indices(subset)
+        return _by_frame(draw_3d_landmarks, predictions, images, image_index, out, subset=subset)
     ids = landmark_indices(subset)
     items, _ = _image_list(images)
     verts = _field(predictions, "projected_vertices", len(items), 2)
@@ -278,11 +321,13 @@ def draw_segments(images: Images, points, edges, color=EDGE_COLOR, colors=None, 
     return _draw(images, out, _tables_from(table), launch)
 
 
-def draw_mesh(predictions: Predictions, images: Images, edges, out: Optional[Images] = None):
+def draw_mesh(predictions: Predictions, images: Images, edges, out: Optional[Images] = None, image_index=None):
     """demo_utils.py:50-65: the mesh's edges over `projected_vertices`, anti-aliased, EDGE_COLOR, in the list's order. Returns the
     line image, as the reference does (its `addWeighted` blend goes into a copy that is never returned; none is computed here).
     `edges`: the path of the reference's `head_edges.npy` / `face_edges.npy`, an integer array [E,2], an int32 CUDA tensor, or
-    `mesh_edges()`."""
+    `mesh_edges()`. `image_index`: as in `draw_landmarks`."""
+    if image_index is not None:
+        return _by_frame(draw_mesh, predictions, images, image_index, out, edges=edges)
     items, _ = _image_list(images)
     verts = _field(predictions, "projected_vertices", len(items), 2)
     return draw_segments(images, verts, edges, color=EDGE_COLOR, out=out)
@@ -356,10 +401,13 @@ def pose_points(rpy: RPY, h: int, w: int) -> np.ndarray:
     return np.array([centre] + ends + tips, dtype=np.int64)
 
 
-def draw_pose(predictions: Predictions, images: Images, out: Optional[Images] = None):
+def draw_pose(predictions: Predictions, images: Images, out: Optional[Images] = None, image_index=None):
     """demo_utils.py:68-94: the head's three axes as arrows from the image centre, colours (0,0,255), (0,255,0), (255,0,0) in
     that order, thickness `int(h * 0.005)` (ValueError where that is 0). An arrow is three solid segments: the shaft, then the two
-    tips from its end point. The angles come from `calculate_rpy`, which synchronises; the segment ends are float64 on the host."""
+    tips from its end point. The angles come from `calculate_rpy`, which synchronises; the segment ends are float64 on the host.
+    `image_index`: as in `draw_landmarks`; every head's arrows start at the centre of its frame, as the reference draws them."""
+    if image_index is not None:
+        return _by_frame(draw_pose, predictions, images, image_index, out)
     items, _ = _image_list(images)
     for t in items:
         pose_thickness(t.shape[0])

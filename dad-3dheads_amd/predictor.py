@@ -24,7 +24,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, boxes as _boxes
 from .head_mesh import HeadMesh
 from .heatmap_points import points_from_heatmap, points_from_landmarks
 from .resize_geometry import calculate_paddings, py3round  # noqa: F401  (public names of this module)
@@ -122,18 +122,28 @@ class FaceMeshPredictor:
     def _landmarks_68(self, out: Dict[str, torch.Tensor], geometry: Any) -> Optional[torch.Tensor]:
         """The 68 points in the input frame, int32 `[B,68,2]` on the device, or None where the model has no 2-D output:
         predictor.py:106-112,132-133,147-152 on the device (heatmap_points.py), with no host wait.
-        `geometry`: one (pad_left, pad_top, scale) triple or a float64 `[B,3]` device tensor of them."""
+        `geometry`: one (pad_left, pad_top, scale) triple, a float64 `[B,3]` device tensor of them, or the float64 `[B,5]` geometry of
+        crops (pad_left, pad_top, scale, x, y), whose points land in the frame."""
         if OUTPUT_2D_LANDMARKS in out:
             return points_from_landmarks(out[OUTPUT_2D_LANDMARKS], geometry, self._img_size)
         if OUTPUT_LANDMARKS_HEATMAP in out:  # unravel_index(sigmoid(heatmap)).flip(-1) * stride (predictor.py:108-112)
             return points_from_heatmap(out[OUTPUT_LANDMARKS_HEATMAP], geometry, self._img_size, self._stride, sigmoid=True)
         return None
 
-    def _readjust_and_decode(self, params: torch.Tensor, pads_scale: torch.Tensor, device_outputs: bool):
-        b = params.shape[0]
+    def _readjust(self, params: torch.Tensor, geometry: torch.Tensor) -> None:
+        """predictor.py:154-176 in place on the device. `geometry`: float32 `[B,3]` (pad_left, pad_top, scale) of whole images, or the
+        float64 `[B,5]` (pad_left, pad_top, scale, x, y) of crops, whose origin `adjust_3dmm_to_paddings` (head_mesh.py:48-60) adds."""
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(), b,
-                                                         pads_scale.data_ptr(), 0.0, 0.0, 1.0, stream))
+        if geometry.dtype == torch.float64:
+            assert tuple(geometry.shape) == (params.shape[0], 5) and geometry.is_contiguous()
+            _lib.check(self._lib.dad3d_flame_readjust_params_frame(self.head_mesh.flame._handle, params.data_ptr(), params.shape[0],
+                                                                   geometry.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(), params.shape[0],
+                                                             geometry.data_ptr(), 0.0, 0.0, 1.0, stream))
+
+    def _readjust_and_decode(self, params: torch.Tensor, pads_scale: torch.Tensor, device_outputs: bool):
+        self._readjust(params, pads_scale)
         out = self.head_mesh.decode(params, verts3d=True, proj=True, to_2d=True, landmarks=False, mutate=True)
         v3d, proj = out["verts3d"], out["proj"]
         if not device_outputs:
@@ -185,8 +195,113 @@ class FaceMeshPredictor:
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.shape[1] * 3) for t in staged])
         return self._results_of(batch, [im.shape[:2] for im in images], device_outputs, points_on_device)
 
+    # -- frames and bounding boxes (model_training/data/flame_dataset.py:96-99; csrc/preprocess_boxes.hip) -------------------------
+    def _input_format(self) -> int:
+        """What the preprocess launch writes for `self.model`: the fp16 / bf16 channels-last tensor `InferenceNet.forward` would
+        make of the float32 one (its cast and layout pass then find nothing to do), float32 planar for any other model."""
+        from .network import GraphedNet, InferenceNet
+
+        net = self.model.net if isinstance(self.model, GraphedNet) else self.model
+        if isinstance(net, InferenceNet) and net.dtype in (torch.bfloat16, torch.float16):
+            return _lib.PREPROCESS_OUT_BF16_NHWC if net.dtype == torch.bfloat16 else _lib.PREPROCESS_OUT_F16_NHWC
+        return _lib.PREPROCESS_OUT_F32_NCHW
+
+    def _stage_frames(self, frames: Sequence[Any]) -> List[torch.Tensor]:
+        """uint8 RGB frames as device tensors `[H,W,3]` with a unit pixel stride: an array is uploaded (once, however many boxes it
+        carries), a tensor on this device is read where it lies, whatever its row stride."""
+        staged = []
+        for f in frames:
+            if isinstance(f, np.ndarray):
+                if f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
+                    raise ValueError(f"expected uint8 RGB frames [H,W,3], got {f.dtype} {f.shape}")
+                staged.append(torch.from_numpy(np.ascontiguousarray(f)).to(self.device))
+            elif torch.is_tensor(f) and f.is_cuda:
+                if f.ndim != 3 or f.shape[2] != 3 or f.dtype != torch.uint8 or f.device != self.device:
+                    raise ValueError(f"expected uint8 RGB frames [H,W,3] on {self.device}, got {f.dtype} {tuple(f.shape)} on {f.device}")
+                staged.append(f if f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * f.shape[1] else f.contiguous())
+            else:
+                raise ValueError(f"expected numpy arrays or CUDA tensors, got {type(f).__name__}")
+            if staged[-1].shape[0] < 1 or staged[-1].shape[1] < 1:
+                raise ValueError(f"frame {len(staged) - 1} is empty: {tuple(staged[-1].shape)}")
+        return staged
+
+    def _preprocess_boxes_launch(self, frames: Sequence[torch.Tensor], boxes: torch.Tensor, image_index: torch.Tensor,
+                                 factors: Optional[Tuple[float, float, float, float]], out_format: int = _lib.PREPROCESS_OUT_F32_NCHW):
+        """One launch: device frames `[H,W,3]`, device boxes `[N,4]` (int32, int64, float32 or float64) and int32 `image_index [N]` ->
+        (network input, crops int32 `[N,4]`, geometry float64 `[N,5]`, flags int32 `[N]`), all on the device; nothing waits."""
+        n, s = boxes.shape[0], self._img_size
+        table = torch.tensor([[t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)] for t in frames], dtype=torch.int64).to(self.device)
+        dtype = {_lib.PREPROCESS_OUT_F32_NCHW: torch.float32, _lib.PREPROCESS_OUT_F16_NHWC: torch.float16,
+                 _lib.PREPROCESS_OUT_BF16_NHWC: torch.bfloat16}[out_format]
+        layout = torch.contiguous_format if out_format == _lib.PREPROCESS_OUT_F32_NCHW else torch.channels_last
+        out = torch.empty((n, 3, s, s), dtype=dtype, device=self.device, memory_format=layout)
+        crops = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        geometry = torch.empty((n, 5), dtype=torch.float64, device=self.device)
+        flags = torch.empty((n,), dtype=torch.int32, device=self.device)
+        mean, std = (C.c_float * 3)(*_MEAN), (C.c_float * 3)(*_STD)
+        offset = None if factors is None else (C.c_double * 4)(*factors)
+        box_dtype = {torch.int32: _lib.BOX_DTYPE_I32, torch.int64: _lib.BOX_DTYPE_I64, torch.float32: _lib.BOX_DTYPE_F32,
+                     torch.float64: _lib.BOX_DTYPE_F64}[boxes.dtype]
+        assert boxes.is_contiguous() and image_index.is_contiguous() and image_index.dtype == torch.int32
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.dad3d_preprocess_boxes(table.data_ptr(), len(frames), boxes.data_ptr(), box_dtype, image_index.data_ptr(), n,
+                                                    offset, s, mean, std, out_format, out.data_ptr(), crops.data_ptr(),
+                                                    geometry.data_ptr(), flags.data_ptr(), self.cuda_id, stream))
+        return out, crops, geometry, flags
+
+    def predict_boxes(self, frames: Sequence[Any], boxes: Any, image_index: Any = None, offset: Any = 0.1,
+                      device_outputs: bool = False, points_on_device: bool = False) -> List[Dict[str, Any]]:
+        """The heads of frames from bounding boxes, in the frames' coordinates: one result dict per box, in box order, with the
+        keys and shapes of `predict_batch` plus `"bbox"` (the crop used, int32 `[4]` as (x, y, w, h)), `"image_index"` and
+        `"flags"` (`_lib.BOX_FLAG_*`). No detector is part of this: the boxes are the caller's.
+
+        `frames`: uint8 RGB numpy arrays or CUDA tensors `[H,W,3]` of any sizes; a tensor is read where it lies, with any row
+        stride. `boxes` as (x, y, w, h): on the host a list with one `[k_i,4]` array per frame, or one `[N,4]` array with
+        `image_index [N]`; or a CUDA tensor `[N,4]` with a CUDA `image_index`. `offset`: what `extend_bbox` takes (one value,
+        (w, h) or (left, right, top, bottom)), or None for the boxes as they are.
+
+        Every box becomes the crop the network was trained on -- `extend_bbox`, `ensure_bbox_boundaries` -- and the crops go through
+        the predictor's preprocessing in ONE launch that reads them in place (`dad3d_preprocess_boxes`); behind the CNN the params
+        are moved into the frame as `adjust_3dmm_to_paddings(params, [y, _, x, _])` does it and the points get (x, y) added, so
+        `projected_vertices`, `points` and `3dmm_params` are the frame's; `3d_vertices` do not depend on the frame.
+
+        A host box that the kernel would flag raises ValueError before anything is launched. Device boxes are never looked at on
+        the host: flagged rows come back with their flags and with finite, meaningless values, and with `device_outputs` and
+        `points_on_device` nothing waits for the device (`bbox`, `image_index` and `flags` are then device tensors too)."""
+        return self._predict_boxes_staged(self._stage_frames(frames), boxes, image_index, offset, device_outputs, points_on_device)
+
+    def _predict_boxes_staged(self, frames: List[torch.Tensor], boxes: Any, image_index: Any, offset: Any, device_outputs: bool,
+                              points_on_device: bool) -> List[Dict[str, Any]]:
+        factors = _boxes.offset_factors(offset)
+        if torch.is_tensor(boxes):
+            if not boxes.is_cuda or boxes.ndim != 2 or boxes.shape[1] != 4 or boxes.dtype == torch.bool or boxes.is_complex():
+                raise ValueError(f"boxes: expected a CUDA tensor [N,4] of numbers, got {boxes.dtype} {tuple(boxes.shape)} on {boxes.device}")
+            if not torch.is_tensor(image_index) or not image_index.is_cuda or tuple(image_index.shape) != (boxes.shape[0],) \
+                    or image_index.is_floating_point():
+                raise ValueError("image_index: device boxes need a CUDA integer tensor [N]")
+            known = (torch.int32, torch.int64, torch.float32, torch.float64)
+            dev_boxes = (boxes if boxes.dtype in known else boxes.to(torch.float64)).to(self.device).contiguous()
+            dev_index = image_index.to(self.device, torch.int32).contiguous()
+        else:
+            flat, index = _boxes.flatten_boxes(len(frames), boxes, image_index)
+            _boxes.check_boxes([tuple(t.shape[:2]) for t in frames], flat, index, factors, self._img_size)  # ValueError, nothing launched
+            dev_boxes, dev_index = torch.from_numpy(flat).to(self.device), torch.from_numpy(index).to(self.device)
+        if dev_boxes.shape[0] == 0:
+            return []
+        batch, crops, geometry, flags = self._preprocess_boxes_launch(frames, dev_boxes, dev_index, factors, self._input_format())
+        results = self._results_from(batch, geometry, geometry, device_outputs, points_on_device)
+        if device_outputs and points_on_device:  # no wait: the side outputs stay where they are
+            for i, r in enumerate(results):
+                r.update({"bbox": crops[i], "image_index": dev_index[i], "flags": flags[i]})
+        else:
+            side = torch.cat([crops, dev_index[:, None], flags[:, None]], dim=1).cpu().numpy()  # one copy
+            for i, r in enumerate(results):
+                r.update({"bbox": side[i, :4].copy(), "image_index": int(side[i, 4]), "flags": int(side[i, 5])})
+        return results
+
     def predict_files(self, sources: Sequence[Any], device_outputs: bool = False, jpeg_entropy: str = "segments",
-                      points_on_device: bool = False) -> List[Dict[str, Any]]:
+                      points_on_device: bool = False, boxes: Any = None, image_index: Any = None,
+                      offset: Any = 0.1) -> List[Dict[str, Any]]:
         """`predict_batch` fed with image files (paths or bytes, any sizes): PNG files and baseline JPEG files are decoded to RGB
         on the device (png_reader.PngDecoder, jpeg_reader.JpegDecoder, channels=3) and the decoded images go to the preprocess launch
         where they lie, so no decoded pixel crosses the bus. A source that starts FF D8 goes to the JPEG decoder, every other one
@@ -194,7 +309,8 @@ class FaceMeshPredictor:
         JPEG, a palette PNG, ...) is decoded by PIL on the host and uploaded. The result dicts are those of `predict_batch` on
         `np.asarray(Image.open(f).convert("RGB"))`, in the order of `sources`; what follows the preprocess launch is
         `predict_batch`'s own code. `jpeg_entropy` is `JpegDecoder`'s `entropy`: "sync" decodes a JPEG file without restart markers
-        in pieces, to the same pixels."""
+        in pieces, to the same pixels. With `boxes` (and `image_index`, `offset`) the files are frames and the call is `predict_boxes`
+        on them."""
         from .jpeg_reader import SOI, JpegDecoder
         from .png_reader import PngDecoder, _bytes_of
 
@@ -216,6 +332,8 @@ class FaceMeshPredictor:
             if png:
                 for i, t in zip(pngs, png.finish(got[nj:nj + npng], got[nj + npng:nj + 2 * npng]).tensors()):
                     decoded[i] = t
+        if boxes is not None:  # the decoded frames stay on the device; the crops are read from them in place
+            return self._predict_boxes_staged(self._stage_frames(decoded), boxes, image_index, offset, device_outputs, points_on_device)
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)) for t in decoded])
         return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs, points_on_device)
 
@@ -226,17 +344,22 @@ class FaceMeshPredictor:
         # both uploads in front of the CNN. The points need the scale as the float64 it is (predictor.py:151); the params kernel reads float32
         pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
         geometry = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float64).to(self.device)
+        return self._results_from(batch, pads_scale, geometry, device_outputs, points_on_device)
+
+    def _results_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor, device_outputs: bool,
+                      points_on_device: bool) -> List[Dict[str, Any]]:
+        """The CNN and everything behind it. `pads_scale` is what `_readjust` takes and `geometry` what `_landmarks_68` takes: for
+        crops both are the float64 `[B,5]` geometry of `dad3d_preprocess_boxes`."""
+        n = batch.shape[0]
         out = self.process(batch)
         params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
         pts = self._landmarks_68(out, geometry)
         if pts is None:  # `return {"3dmm_params": ...}` branch of predictor.py:144-145
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.dad3d_flame_readjust_params(self.head_mesh.flame._handle, params.data_ptr(),
-                                                             params.shape[0], pads_scale.data_ptr(), 0.0, 0.0, 1.0, stream))
+            self._readjust(params, pads_scale)
             params = params if device_outputs else params.cpu()
-            return [{"3dmm_params": params[i : i + 1]} for i in range(len(shapes))]
+            return [{"3dmm_params": params[i : i + 1]} for i in range(n)]
         v3d, proj, params = self._readjust_and_decode(params, pads_scale, device_outputs)
         if not points_on_device:
             pts = pts.cpu().numpy().astype(int)  # one copy; `astype(int)` is the reference's dtype (predictor.py:152)
         return [{"points": pts[i], "projected_vertices": proj[i : i + 1], "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]}
-                for i in range(len(shapes))]
+                for i in range(n)]

@@ -1010,6 +1010,61 @@ DAD3D_EXPORT dad3d_status dad3d_points_readjust(const void* src, int src_kind, i
                                    const double* geometry /* or NULL */, int pad_left, int pad_top, double scale, int32_t* points_out,
                                    int device, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The heads of a frame from bounding boxes (csrc/preprocess_boxes.hip): DAD-3DNet was trained on crops made by a box widened by
+ * about 10 % (model_training/data/flame_dataset.py:96-99), and its results are wanted in the frame's coordinates. No detector is
+ * part of this library: the boxes are the caller's.
+ *
+ * dad3d_preprocess_boxes  ONE launch from frames and boxes to the network's input. DEVICE pointers except `offset`, `mean`, `std`:
+ *     images      int64 [M][4]: {address of the frame's first byte (uint8 RGB, HWC, unit pixel stride), h, w, row stride in bytes}
+ *     boxes       [N][4] (x, y, w, h) of box_dtype (DAD3D_BOX_DTYPE_*); every value is widened exactly to float64
+ *     image_index int32 [N]: the frame of each box
+ *     offset      HOST (left, right, top, bottom), the factors of `extend_bbox`, or NULL for none
+ *     out         out_format DAD3D_PREPROCESS_OUT_F32_NCHW: float32 [N,3,S,S], the bits of dad3d_preprocess_images on the copied crop;
+ *                 _F16_NHWC / _BF16_NHWC: [N,S,S,3] of that dtype, the float32 values rounded to nearest even, i.e. the memory of
+ *                 `float32_result.to(dtype).contiguous(memory_format=torch.channels_last)`. 4-byte aligned.
+ *     crops       int32 [N][4]: the (x, y, w, h) used
+ *     geometry    float64 [N][5]: pad_left, pad_top, scale, x, y
+ *     flags       int32 [N]: DAD3D_BOX_FLAG_*
+ *   Per box, on the device: with an offset `extend_bbox` (data/utils.py:73-103) in float64 -- x - w*left, y - h*top,
+ *   w*((1.0 + right) + left), h*((1.0 + top) + bottom), each truncated toward zero to int32 -- and without one the truncation alone;
+ *   `ensure_bbox_boundaries` (data/utils.py:106-115) in integers; then the predictor's geometry on the crop's (h, w)
+ *   (predictor.py:117-123): scale = S / float(max(h, w)), new = rint(dim * scale) (half to even: py3round), calculate_paddings;
+ *   then LongestMaxSize -> PadIfNeeded -> Normalize -> CHW as dad3d_preprocess_images does them, the crop read in place. The crop's
+ *   edges are the resize's borders: no pixel outside the crop is read.
+ *     DAD3D_BOX_FLAG_EMPTY      the crop's w or h is <= 0 after the boundary rule
+ *     DAD3D_BOX_FLAG_COLLAPSED  new_h or new_w is 0 (a 1 x 1000 crop: py3round(0.256) = 0)
+ *     DAD3D_BOX_FLAG_RANGE      a value of the box (before or after extend_bbox) that is not finite or whose magnitude is >= 2^30, an
+ *                               image_index outside [0, M), a frame with a null address or a side outside [1, 2^30); crops = 0
+ *   A flagged box divides nothing, reads no pixel, gets the all-padding image (normalised zeros) and geometry (0, 0, 1, 0, 0).
+ *   DAD3D_E_INVALID before any device work: a null pointer, N or M or S outside 1 .. 65535 (N == 0 returns DAD3D_OK), an unknown
+ *   box_dtype or out_format, an offset that is not finite, `out` not 4-byte aligned.
+ *
+ * dad3d_flame_readjust_params_frame  dad3d_flame_readjust_params on rows of that float64 geometry [B][5] (scale and pads converted
+ *   to float32, as torch.tensor(.., dtype=float32) converts them), followed by HeadMesh.adjust_3dmm_to_paddings(params, [y, _, x, _])
+ *   (head_mesh.py:48-60): t + (float32([x, y, 0]) * 2) / img_size, each operation rounded once. The decode of these params gives
+ *   `projected_vertices` in the frame's pixels. With x = y = 0 the bits of dad3d_flame_readjust_params.
+ *
+ * dad3d_points_readjust_frame  dad3d_points_readjust with that geometry [B][5]: (x, y) is added as an integer after the reference's
+ *   truncation (predictor.py:150-152), saturating. With x = y = 0 the bits of dad3d_points_readjust. */
+#define DAD3D_BOX_DTYPE_I32 0
+#define DAD3D_BOX_DTYPE_I64 1
+#define DAD3D_BOX_DTYPE_F32 2
+#define DAD3D_BOX_DTYPE_F64 3
+#define DAD3D_PREPROCESS_OUT_F32_NCHW 0
+#define DAD3D_PREPROCESS_OUT_F16_NHWC 1
+#define DAD3D_PREPROCESS_OUT_BF16_NHWC 2
+#define DAD3D_BOX_FLAG_EMPTY 0x1
+#define DAD3D_BOX_FLAG_COLLAPSED 0x2
+#define DAD3D_BOX_FLAG_RANGE 0x4
+DAD3D_EXPORT dad3d_status dad3d_preprocess_boxes(const int64_t* images, int n_images, const void* boxes, int box_dtype,
+                                    const int32_t* image_index, int n_boxes, const double* offset /* HOST [4] or NULL */, int out_size,
+                                    const float* mean, const float* std, int out_format, void* out, int32_t* crops, double* geometry,
+                                    int32_t* flags, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_flame_readjust_params_frame(dad3d_flame* h, float* params, int batch, const double* geometry, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_points_readjust_frame(const void* src, int src_kind, int batch, int n_points, float mul, float limit,
+                                         const double* geometry, int32_t* points_out, int device, void* stream);
+
 /* Single-image HOST entry points with the argument lists of Sim3DR/lib/rasterize.h:84-100 (`bool` spelled
  * `int` for C). libdad3d_hip.so additionally exports the C++-linkage symbols `_get_tri_normal`,
  * `_get_ver_normal`, `_get_normal`, `_rasterize_triangles`, `_rasterize` with the reference's exact
