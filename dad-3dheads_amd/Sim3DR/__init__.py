@@ -3,4 +3,5 @@
 `Mesh` the reference has no counterpart for."""
 from .Sim3DR import get_normal, rasterize, rasterize_triangles, render_texture  # noqa: F401
 from .lighting import RenderPipeline  # noqa: F401
+from .frames import DeviceFrames, frame_table  # noqa: F401
 from .mesh import Mesh  # noqa: F401

@@ -13,6 +13,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib
+from .frames import DeviceFrames
 
 
 def _chk(t: Tensor, dtype, ndim: int, name: str, dev: torch.device) -> Tensor:
@@ -124,6 +125,70 @@ class Mesh:
         _lib.check(self._lib.dad3d_mesh_rasterize(self._handle, img.data_ptr(), v.data_ptr(), col.data_ptr(), dptr,
                                                   b, h, w, c, float(alpha), int(reverse), self._stream()))
         return img
+
+    # -- heads into frames --------------------------------------------------------------------------
+    def _frames_args(self, frames, vertices: Tensor, image_index):
+        v = self._verts(vertices)
+        dev = self.torch_device
+        fr = frames if isinstance(frames, DeviceFrames) else DeviceFrames(frames, dev)
+        if fr.device.device != dev:
+            raise ValueError(f"frames: on {fr.device.device}, the mesh on {dev}")
+        if isinstance(image_index, Tensor) and image_index.is_cuda:
+            idx = _chk(image_index, torch.int32, 1, "image_index", dev)  # used as it is: never read on the host
+        else:
+            idx = torch.as_tensor(np.asarray(image_index, dtype=np.int32).reshape(-1)).to(dev)
+        if idx.shape[0] != v.shape[0]:
+            raise ValueError(f"image_index: {idx.shape[0]} entries for {v.shape[0]} heads")
+        if v.shape[0] > _lib.FRAME_MAX_COUNT:
+            raise ValueError(f"vertices: {v.shape[0]} heads, at most {_lib.FRAME_MAX_COUNT}")
+        # without frames the C entries have nothing to do and write no flags: every index is outside [0, 0)
+        flags = torch.empty(v.shape[0], dtype=torch.int32, device=dev) if len(fr) else torch.full((v.shape[0],), _lib.FRAME_FLAG_INDEX,
+                                                                                                   dtype=torch.int32, device=dev)
+        return fr, v, idx, flags
+
+    def rasterize_frames(self, frames, vertices: Tensor, colors: Tensor, image_index, reverse: bool = False) -> Tensor:
+        """Head k drawn into `frames[image_index[k]]`, for all heads of the call in one chain of launches: per frame what
+        `Sim3DR.rasterize(vertices[k], triangles, colors[k], bg=frame)` gives when called for the frame's heads in ascending k --
+        every head with a z-buffer of its own, so a later head paints over an earlier one wherever it covers.
+
+        frames: a list of uint8 CUDA tensors `[H,W,3]` of any sizes and row strides (views included), one `[B,H,W,3]` tensor, or a
+        `DeviceFrames` built from either (its table is uploaded once: what a graph capture needs); written in place. vertices,
+        colors `[N,nver,3]` float32 (frame pixel x, pixel y, depth; colours in [0,1]). image_index: an int32 CUDA tensor `[N]`, used
+        as it is, or a host sequence, uploaded. -> int32 CUDA `flags [N]`: 0 drawn, `_lib.FRAME_FLAG_INDEX` no such frame,
+        `_lib.FRAME_FLAG_CAPACITY` the head did not fit the list pool of 4 * ntri * N entries (it holds every call whose on-screen
+        triangle boxes are at most 64 x 64 pixels); a flagged head changes no byte. Async on the current stream, no host wait."""
+        fr, v, idx, flags = self._frames_args(frames, vertices, image_index)
+        col = self._verts(colors, "colors")
+        if col.shape[0] != v.shape[0]:
+            raise ValueError("colors: batch mismatch")
+        _lib.check(self._lib.dad3d_mesh_rasterize_frames(self._handle, fr.device.data_ptr(), fr.host.ctypes.data, len(fr), v.data_ptr(),
+                                                         col.data_ptr(), idx.data_ptr(), v.shape[0], int(bool(reverse)), flags.data_ptr(),
+                                                         self._stream()))
+        return flags
+
+    def render_frames(self, frames, vertices: Tensor, image_index, reverse: bool = False, light_out: Optional[Tensor] = None,
+                      ambient: float = 0.3, directional: float = 0.6, specular: float = 0.1, specular_exp: float = 5,
+                      color_ambient: Sequence[float] = (1, 1, 1), color_directional: Sequence[float] = (1, 1, 1),
+                      light_pos: Sequence[float] = (0, 0, 5), view_pos: Sequence[float] = (0, 0, 5)) -> Tensor:
+        """`rasterize_frames` with RenderPipeline's light (lighting.py:37-71, texture=None) as the colours: the light of every head
+        as `phong_light(vertices, None)` computes it (into `light_out`, allocated when None), then the frames chain. -> flags."""
+        fr, v, idx, flags = self._frames_args(frames, vertices, image_index)
+        light = torch.empty_like(v) if light_out is None else self._verts(light_out, "light_out")
+        if light.shape[0] != v.shape[0]:
+            raise ValueError("light_out: batch mismatch")
+        cfg = _lib.LightC(float(ambient), float(directional), float(specular), float(specular_exp),
+                          (C.c_float * 3)(*color_ambient), (C.c_float * 3)(*color_directional),
+                          (C.c_float * 3)(*light_pos), (C.c_float * 3)(*view_pos))
+        _lib.check(self._lib.dad3d_mesh_render_frames(self._handle, fr.device.data_ptr(), fr.host.ctypes.data, len(fr), v.data_ptr(),
+                                                      light.data_ptr(), idx.data_ptr(), v.shape[0], C.byref(cfg),
+                                                      _lib.RENDER_REVERSE if reverse else 0, flags.data_ptr(), self._stream()))
+        return flags
+
+    def frames_scratch_bytes(self) -> int:
+        """Bytes of device scratch the handle holds for the frames chain (0 before the first call); it only ever grows."""
+        n = C.c_size_t()
+        _lib.check(self._lib.dad3d_mesh_frames_scratch_bytes(self._handle, C.byref(n)))
+        return int(n.value)
 
     def rasterize_triangles(self, vertices: Tensor, h: int, w: int, depth: Optional[Tensor] = None):
         v = self._verts(vertices)

@@ -42,6 +42,8 @@ POINTS_SRC_XY_F32, POINTS_SRC_YX_I32 = 0, 1
 BOX_DTYPE_I32, BOX_DTYPE_I64, BOX_DTYPE_F32, BOX_DTYPE_F64 = 0, 1, 2, 3
 PREPROCESS_OUT_F32_NCHW, PREPROCESS_OUT_F16_NHWC, PREPROCESS_OUT_BF16_NHWC = 0, 1, 2
 BOX_FLAG_EMPTY, BOX_FLAG_COLLAPSED, BOX_FLAG_RANGE = 0x1, 0x2, 0x4
+FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0x2, 4096, 65535
+RENDER_REVERSE, RENDER_CLEAR = 1, 2
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -127,6 +129,9 @@ SIGNATURES = {
     "dad3d_mesh_phong_light": (_I, [_P, _P, _P, _P, _I, C.POINTER(LightC), _P]),
     "dad3d_mesh_normal_phong_light": (_I, [_P, _P, _P, _P, _I, C.POINTER(LightC), _P]),
     "dad3d_mesh_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(LightC), _I, _P]),
+    "dad3d_mesh_rasterize_frames": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "dad3d_mesh_render_frames": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.POINTER(LightC), _I, _P, _P]),
+    "dad3d_mesh_frames_scratch_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
     "dad3d_mesh_normal_plan": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "dad3d_mesh_debug_trace": (_I, [_P, _P]),
     "dad3d_mesh_set_texcoords": (_I, [_P, _P, _I, _I, _P]),

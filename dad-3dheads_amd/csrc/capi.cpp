@@ -938,8 +938,38 @@ struct dad3d_mesh {
         raster_batch = batch, raster_h = h, raster_w = w;
         return DAD3D_OK;
     }
+    void* d_frames = nullptr;  // scratch of the frames chain (sim3dr_frames.hip), grown on demand like d_raster; needs no initialisation
+    size_t frames_bytes = 0;
+    dad3d_status frames_scratch(int n_frames, int n_heads, int total_tiles) {
+        const size_t need = frames_scratch_bytes(ntri, n_frames, n_heads, total_tiles);
+        if (need <= frames_bytes) return DAD3D_OK;
+        DAD3D_HIP_TRY(hipDeviceSynchronize());
+        if (d_frames) (void)hipFree(d_frames);
+        d_frames = nullptr;
+        frames_bytes = 0;
+        DAD3D_HIP_TRY(hipMalloc(&d_frames, need));
+        frames_bytes = need;
+        return DAD3D_OK;
+    }
     MeshDev dev() const { return MeshDev{d_tri, d_adj_ptr, d_adj_face, d_adj_tri, ntri, nver}; }
 };
+
+// the checks the two frames entries share, all on the host; *total_tiles = 0: nothing to do
+static dad3d_status frames_arguments(const char* who, dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                     const float* vertices, const float* colors, const int32_t* image_index, int n_heads, int32_t* flags,
+                                     int* total_tiles) {
+    *total_tiles = 0;
+    DAD3D_REQUIRE(m && n_frames >= 0 && n_heads >= 0, "%s: bad argument", who);
+    DAD3D_REQUIRE(n_frames <= DAD3D_FRAME_MAX_COUNT && n_heads <= DAD3D_FRAME_MAX_COUNT, "%s: %d frames and %d heads, at most %d each", who,
+                  n_frames, n_heads, DAD3D_FRAME_MAX_COUNT);
+    if (n_heads == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(image_index && flags, "%s: null buffer", who);
+    if (n_frames == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(frames && frames_host && (m->ntri == 0 || (vertices && colors)), "%s: null buffer", who);
+    DAD3D_REQUIRE(m->ntri <= 65535 && 4ll * m->ntri * n_heads < (1ll << 31), "%s: %d triangles and %d heads exceed 65535 triangles or 2^31 list entries",
+                  who, m->ntri, n_heads);
+    return frames_check_shapes(who, frames_host, n_frames, total_tiles);
+}
 
 extern "C" {
 
@@ -1079,7 +1109,7 @@ dad3d_status dad3d_mesh_create(const int32_t* tri, int ntri, int nver, int devic
 void dad3d_mesh_destroy(dad3d_mesh* m) {
     if (!m) return;
     DeviceGuard guard(m->device);
-    for (void* p : {(void*)m->d_tri, (void*)m->d_adj_ptr, (void*)m->d_adj_face, (void*)m->d_adj_tri, m->d_raster, (void*)m->d_tex_tri[0],
+    for (void* p : {(void*)m->d_tri, (void*)m->d_adj_ptr, (void*)m->d_adj_face, (void*)m->d_adj_tri, m->d_raster, m->d_frames, (void*)m->d_tex_tri[0],
                     (void*)m->d_tex_tri[1]})
         if (p) (void)hipFree(p);
     for (int k = 0; k < kNormalChunkings; ++k)
@@ -1144,6 +1174,44 @@ dad3d_status dad3d_mesh_render(dad3d_mesh* m, uint8_t* image, const float* verti
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
     return launch_rasterize(m->dev(), m->nc, m->d_raster, m->d_trace, image, vertices, light, depth, nullptr, nullptr, batch, h, w, 3,
                             flags, 0, cfg, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_mesh_rasterize_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames, const float* vertices,
+                                         const float* colors, const int32_t* image_index, int n_heads, int reverse, int32_t* flags, void* stream) {
+    int total_tiles = 0;
+    if (dad3d_status st = frames_arguments("dad3d_mesh_rasterize_frames", m, frames, frames_host, n_frames, vertices, colors, image_index, n_heads,
+                                           flags, &total_tiles))
+        return st;
+    if (total_tiles == 0) return DAD3D_OK;  // no frames or no heads
+    DeviceGuard guard(m->device);
+    if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
+    return launch_rasterize_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, colors, image_index, n_heads, reverse ? 1 : 0,
+                                   flags, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_mesh_render_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames, const float* vertices,
+                                      float* light, const int32_t* image_index, int n_heads, const dad3d_light* cfg, int render_flags,
+                                      int32_t* flags, void* stream) {
+    DAD3D_REQUIRE(cfg, "dad3d_mesh_render_frames: bad argument");
+    DAD3D_REQUIRE(!(render_flags & ~DAD3D_RENDER_REVERSE),
+                  "dad3d_mesh_render_frames: render flags %d: only DAD3D_RENDER_REVERSE (a frame is the caller's picture: no DAD3D_RENDER_CLEAR)", render_flags);
+    int total_tiles = 0;
+    if (dad3d_status st = frames_arguments("dad3d_mesh_render_frames", m, frames, frames_host, n_frames, vertices, light, image_index, n_heads, flags,
+                                           &total_tiles))
+        return st;
+    if (total_tiles == 0) return DAD3D_OK;
+    DeviceGuard guard(m->device);
+    if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
+    // the light of every head, flagged or not, as dad3d_mesh_normal_phong_light computes it; then it is the colours
+    if (dad3d_status st = launch_phong(m->dev(), m->nc, light, vertices, nullptr, nullptr, n_heads, *cfg, static_cast<hipStream_t>(stream))) return st;
+    return launch_rasterize_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, light, image_index, n_heads,
+                                   render_flags & DAD3D_RENDER_REVERSE, flags, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_mesh_frames_scratch_bytes(dad3d_mesh* m, size_t* bytes) {
+    DAD3D_REQUIRE(m && bytes, "dad3d_mesh_frames_scratch_bytes: bad argument");
+    *bytes = m->frames_bytes;
+    return DAD3D_OK;
 }
 
 dad3d_status dad3d_mesh_rasterize_triangles(dad3d_mesh* m, const float* vertices, float* depth, int32_t* tri_buf,

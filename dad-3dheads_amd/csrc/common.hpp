@@ -336,6 +336,12 @@ dad3d_status launch_render_texture(const MeshDev& m, void* scratch, void* image,
                                    int tex_h, int tex_w, int tex_c, int nearest, hipStream_t s);
 dad3d_status launch_phong(const MeshDev& m, const NormalChunksDev* nc, float* light, const float* vertices, const float* normals,
                           float* normals_out, int batch, const dad3d_light& cfg, hipStream_t s);
+// Heads into frames (sim3dr_frames.hip). frames_check_shapes: the host copy of the frame table against the limits, *total_tiles =
+// the 64 x 64 tiles of all frames; nothing touches the device. scratch: frames_scratch_bytes(..) bytes, no initialisation needed.
+dad3d_status frames_check_shapes(const char* who, const int64_t* frames_host, int n_frames, int* total_tiles);
+size_t frames_scratch_bytes(int ntri, int n_frames, int n_heads, int total_tiles);
+dad3d_status launch_rasterize_frames(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles, const float* vertices,
+                                     const float* colors, const int32_t* image_index, int n_heads, int reverse, int32_t* flags, hipStream_t s);
 
 // matrix projection (flame_dataset.py:115-141): frame = [B][3] (image height, crop x, crop y)
 dad3d_status launch_project_vertices(const float* vertices, const float* model_view, const float* projection,

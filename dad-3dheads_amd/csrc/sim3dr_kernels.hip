@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "sim3dr_math.hpp"
 
 #ifndef DAD3D_NT_ABLATE  // diagnostics: 1 no face pass, 2 no table gathers, 4 no staging, 8 no normalisation
 #define DAD3D_NT_ABLATE 0
@@ -39,59 +40,8 @@ namespace dad3d {
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// exact-arithmetic helpers
+// exact-arithmetic helpers (the raster's own: sim3dr_math.hpp)
 // ------------------------------------------------------------------------------------------------
-// (int) of a float as x86-64 cvttss2si (what `(int) ceil(..)` compiles to in the reference build).
-__device__ __forceinline__ int f2i_x86(float f) {
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
-}
-__device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }  // std::min
-__device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }  // std::max
-
-struct TriSetup {  // pixel-independent part of get_point_weight / is_point_in_tri
-    float x0, y0, ax, ay, bx, by, d00, d01, d11, inv;
-};
-
-__device__ __forceinline__ TriSetup tri_setup(float x0, float y0, float x1, float y1, float x2, float y2) {
-    TriSetup t;
-    t.x0 = x0;
-    t.y0 = y0;
-    t.ax = x2 - x0;  // v0 = p2 - p0
-    t.ay = y2 - y0;
-    t.bx = x1 - x0;  // v1 = p1 - p0
-    t.by = y1 - y0;
-    t.d00 = t.ax * t.ax + t.ay * t.ay;
-    t.d01 = t.ax * t.bx + t.ay * t.by;
-    t.d11 = t.bx * t.bx + t.by * t.by;
-    const float den = t.d00 * t.d11 - t.d01 * t.d01;
-    t.inv = (den == 0.0f) ? 0.0f : 1.0f / den;
-    return t;
-}
-
-// TriSetup from the corners and the stored inv: the expressions of tri_setup without its division, so the same bits
-__device__ __forceinline__ TriSetup setup_from_corners(float x0, float y0, float x1, float y1, float x2, float y2, float inv) {
-    TriSetup t;
-    t.x0 = x0;
-    t.y0 = y0;
-    t.ax = x2 - x0;
-    t.ay = y2 - y0;
-    t.bx = x1 - x0;
-    t.by = y1 - y0;
-    t.d00 = t.ax * t.ax + t.ay * t.ay;
-    t.d01 = t.ax * t.bx + t.ay * t.by;
-    t.d11 = t.bx * t.bx + t.by * t.by;
-    t.inv = inv;
-    return t;
-}
-
-__device__ __forceinline__ void tri_uv(const TriSetup& t, float px, float py, float& u, float& v) {
-    const float cx = px - t.x0, cy = py - t.y0;  // v2 = p - p0
-    const float d02 = t.ax * cx + t.ay * cy;
-    const float d12 = t.bx * cx + t.by * cy;
-    u = (t.d11 * d02 - t.d01 * d12) * t.inv;
-    v = (t.d00 * d12 - t.d01 * d02) * t.inv;
-}
-
 __device__ __forceinline__ void face_cross(const float* vb, int i0, int i1, int i2, float n[3]) {
     const float ax = vb[3 * i0], ay = vb[3 * i0 + 1], az = vb[3 * i0 + 2];
     const float e1x = vb[3 * i1] - ax, e1y = vb[3 * i1 + 1] - ay, e1z = vb[3 * i1 + 2] - az;
@@ -865,12 +815,6 @@ struct TriLane {  // one triangle as a lane carries it: setup, corner depths, bo
 __device__ __forceinline__ void divmod_small(int n, int d, float rcp_d, int& q, int& r) {  // rcp_d = v_rcp_f32(d)
     q = (int)(((float)n + 0.5f) * rcp_d);
     r = n - q * d;
-}
-
-// orderable(z) for a z that is not NaN: one shift, one or, one xor
-__device__ __forceinline__ unsigned depth_order_number(float z) {
-    const int u = __float_as_int(z + 0.0f);  // -0 -> +0
-    return (unsigned)u ^ ((unsigned)(u >> 31) | 0x80000000u);
 }
 
 // MODE 0: _rasterize (strictly-interior test, colour output)   MODE 1: _rasterize_triangles

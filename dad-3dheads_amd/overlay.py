@@ -1,6 +1,7 @@
 """The demo's overlays on the GPU: `demo_utils.py`'s `draw_points`, `draw_landmarks`, `draw_3d_landmarks`, `draw_mesh` and `draw_pose`
 for batches of uint8 images that stay on the device (csrc/overlay.hip; the outputs `68_landmarks`, `191_landmarks`, `445_landmarks`,
-`head_mesh`, `face_mesh` and `pose` of the reference's demo.py).
+`head_mesh`, `face_mesh` and `pose` of the reference's demo.py), and `draw_heads`: the heads of `predict_boxes` as shaded or PNCC surfaces
+in their frames, all frames and heads in one raster chain (csrc/sim3dr_frames.hip).
 
 `images` is a CUDA uint8 tensor `[B,H,W,3]`, one image `[H,W,3]`, or a list of `[H,W,3]` tensors of any sizes (one launch per
 distinct shape). The result has the form of the input and is a new tensor: an input is only drawn into when it is passed as `out=`.
@@ -197,6 +198,85 @@ def _by_frame(draw: Callable, predictions: Predictions, images: Images, image_in
     else:
         out.copy_(result)
     return out
+
+
+def _head_index(dicts: Sequence[Dict[str, object]], image_index, device: torch.device):
+    """The frame number of every head for `Mesh.rasterize_frames`: a CUDA int32 tensor where the values lie on the device (never
+    read here), a host array otherwise. `image_index=None`: the `"image_index"` of the dicts."""
+    values = [d["image_index"] for d in dicts] if image_index is None else image_index
+    if isinstance(values, Tensor):
+        return values.to(device, torch.int32).reshape(-1) if values.is_cuda else values.numpy().reshape(-1).astype(np.int32)
+    values = list(values)
+    if values and all(isinstance(v, Tensor) and v.is_cuda for v in values):
+        return torch.stack([v.reshape(()) for v in values]).to(device, torch.int32)
+    return np.asarray([int(v) for v in values], dtype=np.int32)
+
+
+_renderers: Dict[Tuple[int, str], object] = {}  # (id of the head mesh, mode) -> PNCCEstimator | Mesh; the head mesh is kept alive with it
+
+
+def draw_heads(predictions: Predictions, frames: Images, mode: str = "shaded", image_index=None, out: Optional[Images] = None,
+               head_mesh=None):
+    """The heads of `predict_boxes` / `predict_files(.., boxes=)` drawn into their frames as surfaces: `mode="shaded"` the whole FLAME
+    mesh under RenderPipeline's default light, `mode="pncc"` the ear-less face subset in its colour codes (pncc_estimator.py). The
+    dicts' `3dmm_params` are already in frame coordinates; they are stacked and decoded once (`proj`, z flipped, as
+    `PNCCEstimator.render_batch` does), and all heads of all frames go through one `Mesh.render_frames` / `rasterize_frames` chain:
+    head k into `frames[image_index[k]]`, a later head of a frame over an earlier one, as a loop over `Sim3DR.rasterize(.., bg=frame)`
+    paints them. `image_index=None`: the dicts' own. A head whose index names no frame is not drawn. With device values nothing is
+    read on the host. `frames` as for the other overlays; the result has their form and is a copy unless `out=` is given (`out` may be
+    `frames` itself). `head_mesh`: the predictor's `HeadMesh` (None: a new one, which needs the FLAME model file)."""
+    if mode not in ("shaded", "pncc"):
+        raise ValueError(f"mode: 'shaded' or 'pncc', got {mode!r}")
+    items, form = _image_list(frames)
+    for t in items:
+        if not t.is_cuda:
+            raise ValueError("frames: expected CUDA tensors (the heads are drawn on the GPU; there is no CPU fallback)")
+    if isinstance(predictions, dict):
+        raise ValueError("predictions: expected the list of per-head dicts that predict_boxes returns")
+    dicts = list(predictions)
+    if out is None:
+        target = frames.clone() if form != "list" else [t.clone() for t in items]
+    else:
+        target = out
+        if form == "list":
+            if len(out) != len(items):
+                raise ValueError(f"out: {len(out)} tensors for {len(items)} frames")
+            for o, t in zip(out, items):
+                if o.shape != t.shape or o.dtype != torch.uint8 or o.device != t.device:
+                    raise ValueError("out: expected uint8 tensors of the frames' shapes on their device")
+                if o is not t:
+                    o.copy_(t)
+        else:
+            if not isinstance(out, Tensor) or out.shape != frames.shape or out.dtype != torch.uint8 or out.device != frames.device:
+                raise ValueError("out: expected a uint8 tensor of the frames' shape on their device")
+            if out is not frames:
+                out.copy_(frames)
+    if not dicts or not items:
+        return target
+    device = items[0].device
+    if head_mesh is None:
+        from .head_mesh import HeadMesh
+        head_mesh = HeadMesh(device=device.index)
+    params = _field(dicts, "3dmm_params", len(dicts), 1).to(device, torch.float32).contiguous()
+    index = _head_index(dicts, image_index, device)
+    if len(index) != len(dicts):
+        raise ValueError(f"image_index: {len(index)} entries for {len(dicts)} predictions")
+    draw_into = target if form == "list" else target if form == "batch" else [target]
+    key = (id(head_mesh), mode)
+    if mode == "pncc":
+        if key not in _renderers:
+            from .pncc import PNCCEstimator
+            _renderers[key] = PNCCEstimator(head_mesh=head_mesh)
+        _renderers[key].render_frames(params, draw_into, index, mutate=False)
+    else:
+        flame = head_mesh.flame
+        if key not in _renderers:
+            from .Sim3DR.mesh import Mesh
+            _renderers[key] = (Mesh(np.ascontiguousarray(np.asarray(flame.faces), dtype=np.int32),
+                                    int(np.asarray(flame.flame_model.v_template).shape[0]), device=flame.device_index), head_mesh)
+        verts = flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=False)["proj"]
+        _renderers[key][0].render_frames(draw_into, verts, index)
+    return target
 
 
 # -- the reference's surface --------------------------------------------------------------------------------------------------------

@@ -65,6 +65,14 @@ class PNCCEstimator:
                     self.colors.astype(np.float32), with_background)
 
     # -- MI355X-native batched entry ----------------------------------------------------------------------
+    def _device_mesh(self) -> Mesh:
+        flame = self.head_mesh.flame
+        if self._mesh is None:
+            self._mesh = Mesh(self.faces_wo_back_remapped.astype(np.int32), int(np.asarray(flame.flame_model.v_template).shape[0]),
+                              device=flame.device_index)
+            self._colors_dev = torch.from_numpy(self.colors.astype(np.float32)).to(flame.torch_device)
+        return self._mesh
+
     def render_batch(self, params: Tensor, bg: Optional[Tensor] = None, size: Optional[Tuple[int, int]] = None,
                      mutate: bool = True) -> Tensor:
         """`params [B,413]` fp32 on the GPU -> uint8 `[B,H,W,3]` PNCC images on the GPU. `bg` (rendered into, like
@@ -72,10 +80,7 @@ class PNCCEstimator:
         the z flip, raster of the ear-less face subset with the colour codes."""
         flame = self.head_mesh.flame
         dev = flame.torch_device
-        if self._mesh is None:
-            self._mesh = Mesh(self.faces_wo_back_remapped.astype(np.int32), int(np.asarray(flame.flame_model.v_template).shape[0]),
-                              device=flame.device_index)
-            self._colors_dev = torch.from_numpy(self.colors.astype(np.float32)).to(dev)
+        self._device_mesh()
         b = params.shape[0]
         if bg is None:
             h, w = size if size is not None else (self.img_size, self.img_size)
@@ -83,3 +88,14 @@ class PNCCEstimator:
         verts = flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=mutate)["proj"]
         colors = self._colors_dev[None].expand(b, -1, -1).contiguous()
         return self._mesh.rasterize(verts, colors, bg)
+
+    def render_frames(self, params: Tensor, frames, image_index, mutate: bool = True) -> Tensor:
+        """The PNCC of several heads drawn into their frames: `params [N,413]` fp32 on the GPU, in frame coordinates (what
+        `predict_boxes` returns), head k into `frames[image_index[k]]` -- a list of uint8 CUDA `[H,W,3]` tensors of any sizes, one
+        `[B,H,W,3]` tensor or a `Sim3DR.frames.DeviceFrames`, written in place. The decode of `render_batch`, then
+        `Mesh.rasterize_frames` with the colour codes: a later head of a frame paints over an earlier one. -> int32 CUDA flags [N]
+        (`Mesh.rasterize_frames`); `image_index` as a CUDA tensor is never read on the host."""
+        mesh = self._device_mesh()
+        verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=mutate)["proj"]
+        colors = self._colors_dev[None].expand(params.shape[0], -1, -1).contiguous()
+        return mesh.rasterize_frames(frames, verts, colors, image_index)

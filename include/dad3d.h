@@ -328,6 +328,47 @@ enum { DAD3D_RENDER_REVERSE = 1, DAD3D_RENDER_CLEAR = 2 };
 DAD3D_EXPORT dad3d_status dad3d_mesh_render(dad3d_mesh* m, uint8_t* image, const float* vertices, float* light, float* depth, int batch,
                                int h, int w, const dad3d_light* cfg, int flags, void* stream);
 
+/* Several heads into their frames in one chain of seven launches: the loop `for k: frame[image_index[k]] = Sim3DR.rasterize(
+ * vertices[k], triangles, colors[k], bg=frame[image_index[k]], reverse=reverse)` (Sim3DR/Sim3DR.py:14-29 around _rasterize,
+ * rasterize_kernel.cpp:219-292) for frames of any sizes, and with dad3d_mesh_render_frames RenderPipeline.__call__
+ * (lighting.py:37-71, texture=None) per head. Every call of that loop has a z-buffer of its own starting at -1e8, so a later
+ * head paints over an earlier one wherever it covers a pixel, also where it lies behind; within a head: strict-interior test,
+ * `>` depth test, ties to the lowest triangle index, (unsigned char) truncation. A frame without heads is not written, and a
+ * pixel no head covers is not written. alpha == 1 and three channels only; no depth output.
+ *   frames       DEVICE int64 [n_frames][4], the table of dad3d_preprocess_boxes: {address of the first byte, h, w, row stride in
+ *                bytes}; uint8 RGB pixels, HWC, unit pixel stride. The stride may exceed 3 * w; neither it nor the address need be
+ *                aligned: pixels are written as single bytes, and no byte outside [row, row + 3 * w) of a row is touched.
+ *   frames_host  HOST copy of the same table: shapes are checked and the scratch is sized from it, before any device work
+ *   vertices     DEVICE [n_heads,nver,3] fp32 (frame pixel x, pixel y, depth); colors / light [n_heads,nver,3] fp32
+ *   image_index  DEVICE int32 [n_heads], in any order; never read on the host
+ *   flags        DEVICE int32 [n_heads], written: 0 = drawn; DAD3D_FRAME_FLAG_INDEX = image_index outside [0, n_frames);
+ *                DAD3D_FRAME_FLAG_CAPACITY = the head did not fit the list pool. A flagged head is not drawn at all and changes
+ *                no byte of any frame.
+ * List pool: every (64 x 64 tile, triangle) pair a head touches takes one entry of a pool of 4 * ntri * n_heads; heads take
+ * theirs in ascending order, and a head that no longer fits is dropped whole. A triangle whose box inside the frame is at most
+ * 64 x 64 pixels touches at most 2 x 2 tiles, so a call in which every such box is that small always fits.
+ * dad3d_mesh_render_frames: `light` [n_heads,nver,3] receives the Phong light of every head (the arithmetic of
+ * dad3d_mesh_normal_phong_light: per-head norm_vertices bounds and normals), which is then the colours; one launch more.
+ * `render_flags`: DAD3D_RENDER_REVERSE; DAD3D_RENDER_CLEAR is DAD3D_E_INVALID (a frame is the caller's picture).
+ * Scratch: owned by the handle, bounded by n_heads * ntri, n_frames and the tile total of the frames (about 24 * ntri bytes a
+ * head and 12 bytes a tile), allocated on first use and on growth -- that call synchronises the device. A call whose scratch
+ * is large enough allocates nothing, does not synchronise and can be captured into a graph. One handle serves one stream at a time.
+ * Limits: at most DAD3D_FRAME_MAX_TILES tiles a frame, less than 2^24 tiles in all, n_frames and n_heads at most
+ * DAD3D_FRAME_MAX_COUNT each, ntri at most 65535 and 4 * ntri * n_heads < 2^31; beyond them DAD3D_E_INVALID with a message.
+ * n_frames == 0 or n_heads == 0: nothing to do, DAD3D_OK. Every argument check happens before any device work. */
+#define DAD3D_FRAME_FLAG_INDEX 1
+#define DAD3D_FRAME_FLAG_CAPACITY 2
+#define DAD3D_FRAME_MAX_TILES 4096
+#define DAD3D_FRAME_MAX_COUNT 65535
+DAD3D_EXPORT dad3d_status dad3d_mesh_rasterize_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                                      const float* vertices, const float* colors, const int32_t* image_index, int n_heads,
+                                                      int reverse, int32_t* flags, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_mesh_render_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                                   const float* vertices, float* light, const int32_t* image_index, int n_heads,
+                                                   const dad3d_light* cfg, int render_flags, int32_t* flags, void* stream);
+/* Read-only: the bytes of device scratch the handle holds for the two entries above (0 before the first call). */
+DAD3D_EXPORT dad3d_status dad3d_mesh_frames_scratch_bytes(dad3d_mesh* m, size_t* bytes);
+
 /* Batched `_render_texture_core` (rasterize_kernel.cpp:358-463, declared in rasterize.h:102-109; the reference's Cython binding
  * comments it out): a head drawn with a texture instead of per-vertex colours. Two launches: the geometry kernel of
  * dad3d_mesh_rasterize (same boxes), then a tile kernel with
