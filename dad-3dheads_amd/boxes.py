@@ -1,6 +1,7 @@
 """Bounding boxes on the host: the argument forms of `FaceMeshPredictor.predict_boxes` and the rule `dad3d_preprocess_boxes` applies
 to every box on the device (csrc/preprocess_boxes.hip), restated with `dataset.extend_bbox` / `ensure_bbox_boundaries` and
-`resize_geometry`, so that a box the kernel would flag is refused before anything is launched. Pure numpy: no GPU, no library."""
+`resize_geometry`, so that a box the kernel would flag is refused before anything is launched; and `next_boxes`, the rule by which
+`dad3d_boxes_from_heads` (csrc/track_boxes.hip) takes the boxes of the next call from the heads of this one. Pure numpy: no GPU, no library."""
 from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple, Union
@@ -85,6 +86,62 @@ def crop_and_flags(box, image: int, shapes: Sequence[Tuple[int, int]], factors: 
         return crop, _lib.BOX_FLAG_EMPTY
     new_h, new_w, _, _ = longest_max_size(int(crop[3]), int(crop[2]), img_size)
     return crop, (_lib.BOX_FLAG_COLLAPSED if new_h == 0 or new_w == 0 else 0)
+
+
+def next_boxes(proj, shapes: Sequence[Tuple[int, int]], image_index, prev_flags=None, subset=None, min_side: int = 1,
+               min_visible: float = 0.5) -> Tuple[np.ndarray, np.ndarray]:
+    """The boxes of the next call from the projected vertices of this one: `dad3d_boxes_from_heads` (csrc/track_boxes.hip,
+    include/dad3d.h) on the host, rule for rule. `proj` float32 `[N,V,>=2]` (x, y first), `shapes` the frames' (h, w), `image_index
+    [N]`, `prev_flags [N]` the flags of the call that produced `proj` (or None), `subset` vertex indices to bound (None: all; duplicates
+    allowed) -> (int32 `[N,4]` boxes as (x, y, w, h), int32 `[N]` of `_lib.TRACK_FLAG_*`). Any flag zeroes the box, which the next
+    `crop_and_flags` flags EMPTY: a lost head stays lost in its slot until the caller writes a fresh box there.
+
+    `min_side=1` asks for no more than "not empty" and `min_visible=0.5` for most of the head's box still in the frame; both are
+    design choices, not measurements, and the caller's to set."""
+    proj = np.asarray(proj)
+    if proj.ndim != 3 or proj.shape[2] < 2 or proj.shape[1] < 1 or proj.dtype != np.float32:
+        raise ValueError(f"proj: expected float32 [N,V,2] or [N,V,3], got {proj.dtype} {proj.shape}")
+    n, n_verts = proj.shape[:2]
+    index = np.asarray(image_index).reshape(-1)
+    previous = None if prev_flags is None else np.asarray(prev_flags).reshape(-1)
+    if len(index) != n or (previous is not None and len(previous) != n):
+        raise ValueError(f"image_index / prev_flags: expected {n} entries")
+    if int(min_side) < 0 or not 0.0 <= float(min_visible) <= 1.0:  # false for a NaN
+        raise ValueError(f"min_side {min_side} is negative or min_visible {min_visible} is outside [0, 1]")
+    picked = None if subset is None else np.asarray(subset).reshape(-1).astype(np.int64)
+    if picked is not None and len(picked) == 0:
+        raise ValueError("subset: no index (None selects all vertices)")
+    boxes, flags = np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+    for i in range(n):
+        if previous is not None and previous[i] != 0:
+            flags[i] = _lib.TRACK_FLAG_PREVIOUS
+            continue
+        image = int(index[i])
+        if not 0 <= image < len(shapes) or not all(0 < int(s) < 2 ** 30 for s in shapes[image][:2]) \
+                or (picked is not None and not np.all((picked >= 0) & (picked < n_verts))):
+            flags[i] = _lib.TRACK_FLAG_RANGE
+            continue
+        xy = proj[i, :, :2] if picked is None else proj[i, picked, :2]
+        if not np.all(np.isfinite(xy)):
+            flags[i] = _lib.TRACK_FLAG_NONFINITE
+            continue
+        lo, hi = xy.min(axis=0), xy.max(axis=0)  # float32, exact
+        if not (np.all(np.abs(lo) < RANGE) and np.all(np.abs(hi) < RANGE)):
+            flags[i] = _lib.TRACK_FLAG_RANGE
+            continue
+        x0, y0 = (int(v) for v in np.floor(lo))
+        x1, y1 = (int(v) for v in np.ceil(hi))
+        w, h = x1 - x0, y1 - y0
+        frame_h, frame_w = (int(s) for s in shapes[image][:2])
+        if min(w, h) < int(min_side):
+            flags[i] |= _lib.TRACK_FLAG_SMALL
+        if w * h != 0:
+            inter = max(0, min(x1, frame_w) - max(x0, 0)) * max(0, min(y1, frame_h) - max(y0, 0))
+            if float(inter) < float(min_visible) * float(w * h):  # Python's float(int) rounds to nearest even, as the conversion on the device
+                flags[i] |= _lib.TRACK_FLAG_OUTSIDE
+        if not flags[i]:
+            boxes[i] = (x0, y0, w, h)
+    return boxes, flags
 
 
 def check_boxes(shapes: Sequence[Tuple[int, int]], flat: np.ndarray, index: np.ndarray, factors, img_size: int) -> None:

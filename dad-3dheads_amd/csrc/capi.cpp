@@ -1856,6 +1856,26 @@ dad3d_status dad3d_points_readjust_frame(const void* src, int src_kind, int batc
     return launch_points_readjust_frame(a, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_boxes_from_heads(const float* proj, int n_heads, int n_verts, int64_t head_stride, int vertex_stride, const int32_t* subset,
+                                    int n_subset, const int64_t* frames, int n_frames, const int32_t* image_index, const int32_t* prev_flags,
+                                    int min_side, double min_visible, int32_t* boxes, int32_t* flags, int device, void* stream) {
+    DAD3D_REQUIRE(n_heads >= 0 && n_heads <= 65535, "dad3d_boxes_from_heads: %d heads outside the launch grid (65535)", n_heads);
+    DAD3D_REQUIRE(n_verts >= 1 && n_verts <= 65535, "dad3d_boxes_from_heads: %d vertices outside 1 .. 65535", n_verts);
+    DAD3D_REQUIRE(vertex_stride >= 2, "dad3d_boxes_from_heads: a vertex stride of %d floats holds no (x, y)", vertex_stride);
+    DAD3D_REQUIRE((subset == nullptr) == (n_subset == 0), "dad3d_boxes_from_heads: a subset and its count go together (NULL and 0 for all vertices)");
+    DAD3D_REQUIRE(n_subset >= 0 && n_subset <= 65535, "dad3d_boxes_from_heads: %d subset indices outside 1 .. 65535", n_subset);
+    DAD3D_REQUIRE(min_side >= 0, "dad3d_boxes_from_heads: min_side %d is negative", min_side);
+    DAD3D_REQUIRE(min_visible >= 0.0 && min_visible <= 1.0, "dad3d_boxes_from_heads: min_visible %g is outside [0, 1]", min_visible);  // false for a NaN
+    if (n_heads == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(n_frames >= 1 && n_frames <= 65535, "dad3d_boxes_from_heads: %d frames outside 1 .. 65535", n_frames);
+    DAD3D_REQUIRE(proj && frames && image_index && boxes && flags, "dad3d_boxes_from_heads: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    TrackBoxesArgs a{proj, n_heads, n_verts, (long long)head_stride, vertex_stride, subset, n_subset, reinterpret_cast<const long long*>(frames),
+                     n_frames, image_index, prev_flags, min_side, min_visible, boxes, flags};
+    return launch_boxes_from_heads(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_cube_region_loss(const float* pred, const float* target, int batch, int n_verts,
                                     const int32_t* region_ptr, const int32_t* region_idx, const float* region_weight,
                                     int n_regions, const int32_t* vert_ptr, const int32_t* vert_region,

@@ -745,4 +745,23 @@ dad3d_status launch_preprocess_boxes(PreprocessBoxesArgs a, const float mean[3],
 dad3d_status launch_readjust_frame(float* params, int batch, ParamLayout lay, const double* geometry, float img_size, hipStream_t s);
 dad3d_status launch_points_readjust_frame(const PointsReadjustArgs& a, hipStream_t s);  // a.geometry is [B][5]
 
+// the projected vertices of a call's heads -> the boxes of the next call (track_boxes.hip)
+struct TrackBoxesArgs {
+    const float* proj;  // head i's vertex v at proj + i*head_stride + v*vertex_stride: x at +0, y at +1
+    int n_heads, n_verts;
+    long long head_stride;
+    int vertex_stride;
+    const int32_t* subset;  // [n_subset] vertex indices, or null: all
+    int n_subset;
+    const long long* frames;  // [M][4] {address, h, w, row stride in bytes}
+    int n_frames;
+    const int32_t* image_index;  // [N]
+    const int32_t* prev_flags;   // [N] or null
+    int min_side;
+    double min_visible;
+    int32_t* boxes;  // [N][4] (x, y, w, h)
+    int32_t* flags;  // [N]
+};
+dad3d_status launch_boxes_from_heads(const TrackBoxesArgs& a, hipStream_t s);
+
 }  // namespace dad3d

@@ -225,12 +225,19 @@ class FaceMeshPredictor:
                 raise ValueError(f"frame {len(staged) - 1} is empty: {tuple(staged[-1].shape)}")
         return staged
 
+    def _frames_table(self, frames: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The int64 `[M,4]` device table {address, h, w, row stride in bytes} of `dad3d_preprocess_boxes` and `dad3d_boxes_from_heads`."""
+        return torch.tensor([[t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)] for t in frames], dtype=torch.int64).to(self.device)
+
     def _preprocess_boxes_launch(self, frames: Sequence[torch.Tensor], boxes: torch.Tensor, image_index: torch.Tensor,
-                                 factors: Optional[Tuple[float, float, float, float]], out_format: int = _lib.PREPROCESS_OUT_F32_NCHW):
+                                 factors: Optional[Tuple[float, float, float, float]], out_format: int = _lib.PREPROCESS_OUT_F32_NCHW,
+                                 table: Optional[torch.Tensor] = None):
         """One launch: device frames `[H,W,3]`, device boxes `[N,4]` (int32, int64, float32 or float64) and int32 `image_index [N]` ->
-        (network input, crops int32 `[N,4]`, geometry float64 `[N,5]`, flags int32 `[N]`), all on the device; nothing waits."""
+        (network input, crops int32 `[N,4]`, geometry float64 `[N,5]`, flags int32 `[N]`), all on the device; nothing waits.
+        `table`: the frames' table where the caller has it already."""
         n, s = boxes.shape[0], self._img_size
-        table = torch.tensor([[t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)] for t in frames], dtype=torch.int64).to(self.device)
+        if table is None:
+            table = self._frames_table(frames)
         dtype = {_lib.PREPROCESS_OUT_F32_NCHW: torch.float32, _lib.PREPROCESS_OUT_F16_NHWC: torch.float16,
                  _lib.PREPROCESS_OUT_BF16_NHWC: torch.bfloat16}[out_format]
         layout = torch.contiguous_format if out_format == _lib.PREPROCESS_OUT_F32_NCHW else torch.channels_last
@@ -288,8 +295,9 @@ class FaceMeshPredictor:
             dev_boxes, dev_index = torch.from_numpy(flat).to(self.device), torch.from_numpy(index).to(self.device)
         if dev_boxes.shape[0] == 0:
             return []
-        batch, crops, geometry, flags = self._preprocess_boxes_launch(frames, dev_boxes, dev_index, factors, self._input_format())
-        results = self._results_from(batch, geometry, geometry, device_outputs, points_on_device)
+        batched = self._predict_boxes_batched(frames, dev_boxes, dev_index, factors)
+        crops, flags = batched["bbox"], batched["flags"]
+        results = self._rows_of(batched, device_outputs, points_on_device)
         if device_outputs and points_on_device:  # no wait: the side outputs stay where they are
             for i, r in enumerate(results):
                 r.update({"bbox": crops[i], "image_index": dev_index[i], "flags": flags[i]})
@@ -350,16 +358,117 @@ class FaceMeshPredictor:
                       points_on_device: bool) -> List[Dict[str, Any]]:
         """The CNN and everything behind it. `pads_scale` is what `_readjust` takes and `geometry` what `_landmarks_68` takes: for
         crops both are the float64 `[B,5]` geometry of `dad3d_preprocess_boxes`."""
-        n = batch.shape[0]
+        return self._rows_of(self._batched_from(batch, pads_scale, geometry), device_outputs, points_on_device)
+
+    def _batched_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """`_results_from` before the results are cut into rows: the device tensors `3dmm_params [N,413]` and, where the model has a
+        2-D output, `points [N,68,2]` int32, `projected_vertices [N,5023,2]` and `3d_vertices [N,5023,3]`. Nothing waits."""
         out = self.process(batch)
         params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
         pts = self._landmarks_68(out, geometry)
         if pts is None:  # `return {"3dmm_params": ...}` branch of predictor.py:144-145
             self._readjust(params, pads_scale)
-            params = params if device_outputs else params.cpu()
+            return {"3dmm_params": params}
+        v3d, proj, params = self._readjust_and_decode(params, pads_scale, True)
+        return {"points": pts, "projected_vertices": proj, "3d_vertices": v3d, "3dmm_params": params}
+
+    @staticmethod
+    def _rows_of(batched: Dict[str, torch.Tensor], device_outputs: bool, points_on_device: bool) -> List[Dict[str, Any]]:
+        """One result dict per row of `_batched_from`'s tensors, copied to the host first unless the caller keeps them on the device."""
+        params = batched["3dmm_params"] if device_outputs else batched["3dmm_params"].cpu()
+        n = params.shape[0]
+        if "points" not in batched:
             return [{"3dmm_params": params[i : i + 1]} for i in range(n)]
-        v3d, proj, params = self._readjust_and_decode(params, pads_scale, device_outputs)
+        pts, proj, v3d = batched["points"], batched["projected_vertices"], batched["3d_vertices"]
+        if not device_outputs:
+            v3d, proj = v3d.cpu(), proj.cpu()
         if not points_on_device:
             pts = pts.cpu().numpy().astype(int)  # one copy; `astype(int)` is the reference's dtype (predictor.py:152)
         return [{"points": pts[i], "projected_vertices": proj[i : i + 1], "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]}
                 for i in range(n)]
+
+    def _predict_boxes_batched(self, frames: List[torch.Tensor], dev_boxes: torch.Tensor, dev_index: torch.Tensor,
+                               factors: Optional[Tuple[float, float, float, float]], table: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """What stands behind `predict_boxes`, uncut: `_batched_from`'s device tensors in frame coordinates plus `bbox [N,4]` (the
+        crops used), `flags [N]` and `image_index [N]`, int32. Staged frames, device boxes and index; nothing waits."""
+        batch, crops, geometry, flags = self._preprocess_boxes_launch(frames, dev_boxes, dev_index, factors, self._input_format(), table)
+        batched = self._batched_from(batch, geometry, geometry)
+        batched.update({"bbox": crops, "flags": flags, "image_index": dev_index})
+        return batched
+
+    def next_boxes(self, results_or_proj: Any, frames: Sequence[Any], image_index: Any = None, prev_flags: Any = None, subset: Any = None,
+                   min_side: int = 1, min_visible: float = 0.5):
+        """The boxes of the next `predict_boxes` call from the heads of this one, the tracking step of 3DDFA_V2: each head's box is the
+        integer bounds of its projected vertices (`subset`: vertex indices, None for all 5023, the head box the dataset's `bbox` and
+        the training crop are about), zeroed and flagged `_lib.TRACK_FLAG_*` where the head is lost -- see `boxes.next_boxes` for
+        the rule. -> (boxes int32 `[N,4]` as (x, y, w, h), flags int32 `[N]`).
+
+        `results_or_proj`: the list of dicts `predict_boxes` returned (`image_index` and `prev_flags` then default to the dicts' own
+        `image_index` and `flags`), or `projected_vertices` stacked as `[N,V,2]` / `[N,V,3]`. `frames`: the frames (only their sizes
+        matter: arrays, tensors or (h, w) pairs). Device values go through ONE launch (`dad3d_boxes_from_heads`) and nothing waits
+        for the device; host values go through the same rule in numpy. Give the boxes to the next call with the same `image_index`:
+        a zeroed box comes back flagged `BOX_FLAG_EMPTY`, and with that flag as `prev_flags` the head stays lost until it gets a
+        fresh box from the caller's detector."""
+        if isinstance(results_or_proj, (list, tuple)):
+            dicts = list(results_or_proj)
+            if not dicts:
+                return np.zeros((0, 4), np.int32), np.zeros(0, np.int32)
+            if image_index is None:
+                image_index = [d["image_index"] for d in dicts]
+            if prev_flags is None:
+                prev_flags = [d["flags"] for d in dicts]
+            proj = torch.cat([d["projected_vertices"] for d in dicts])
+            on_device = proj.is_cuda
+            image_index, prev_flags = (torch.stack([v.reshape(()) for v in seq])  # the dicts' 0-d device values: gathered on the device
+                                       if on_device and isinstance(seq, list) and all(torch.is_tensor(v) and v.is_cuda for v in seq) else seq
+                                       for seq in (image_index, prev_flags))
+        else:
+            proj = results_or_proj
+            on_device = torch.is_tensor(proj) and proj.is_cuda
+        if image_index is None:
+            raise ValueError("image_index: needed with projected vertices (the result dicts carry their own)")
+        if not on_device:
+            shapes = [tuple(int(s) for s in (f.shape[:2] if hasattr(f, "shape") else f[:2])) for f in frames]
+            host = [None if v is None else v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in (image_index, prev_flags, subset)]
+            proj = proj.numpy() if torch.is_tensor(proj) else np.asarray(proj)
+            return _boxes.next_boxes(np.ascontiguousarray(proj, dtype=np.float32), shapes, host[0], host[1], host[2], min_side, min_visible)
+        # the kernel reads no pixel: a frame given by its size alone gets a placeholder address, which only says that the frame exists
+        table = torch.tensor([[f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)] if torch.is_tensor(f) else
+                              [1, *(int(s) for s in (f.shape[:2] if hasattr(f, "shape") else f[:2])), 0] for f in frames], dtype=torch.int64).to(self.device)
+        n = proj.shape[0]
+        out_boxes = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        out_flags = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self._boxes_from_heads_launch(proj, table, self._dev_int32(image_index, n, "image_index"),
+                                      None if prev_flags is None else self._dev_int32(prev_flags, n, "prev_flags"),
+                                      None if subset is None else self._dev_int32(subset, None, "subset"), min_side, min_visible, out_boxes, out_flags)
+        return out_boxes, out_flags
+
+    def _dev_int32(self, values: Any, n: Optional[int], name: str) -> torch.Tensor:
+        """Integers as a contiguous int32 tensor `[n]` on this device: a tensor is converted where it lies, host values are uploaded."""
+        t = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values).reshape(-1).astype(np.int32))
+        if t.is_floating_point() or t.ndim != 1 or (n is not None and t.shape[0] != n):
+            raise ValueError(f"{name}: expected integers [{'K' if n is None else n}], got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device, torch.int32).contiguous()
+
+    def _boxes_from_heads_launch(self, proj: torch.Tensor, table: torch.Tensor, image_index: torch.Tensor, prev_flags: Optional[torch.Tensor],
+                                 subset: Optional[torch.Tensor], min_side: int, min_visible: float, out_boxes: torch.Tensor,
+                                 out_flags: torch.Tensor) -> None:
+        """`dad3d_boxes_from_heads` on the current stream: `proj` float32 `[N,V,2|3]` on this device with a unit last stride (any
+        head and vertex strides), int32 device vectors, the frames' table; writes `out_boxes [N,4]` and `out_flags [N]` in place."""
+        if proj.ndim != 3 or proj.shape[2] not in (2, 3) or proj.dtype != torch.float32 or proj.device != self.device:
+            raise ValueError(f"projected vertices: expected float32 [N,V,2] or [N,V,3] on {self.device}, got {proj.dtype} {tuple(proj.shape)}")
+        if proj.shape[0] and (proj.stride(2) != 1 or proj.stride(1) < 2 or proj.stride(0) < 0):
+            proj = proj.contiguous()
+        n, v = proj.shape[:2]
+        assert out_boxes.is_contiguous() and out_boxes.dtype == torch.int32 and tuple(out_boxes.shape) == (n, 4)
+        assert out_flags.is_contiguous() and out_flags.dtype == torch.int32 and tuple(out_flags.shape) == (n,)
+        for t, shape in ((image_index, (n,)), (prev_flags, (n,)), (subset, None)):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and t.ndim == 1
+                                 and (shape is None or tuple(t.shape) == shape)), (t.dtype, tuple(t.shape))
+        assert table.dtype == torch.int64 and table.is_contiguous() and table.ndim == 2 and table.shape[1] == 4
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.dad3d_boxes_from_heads(proj.data_ptr(), n, v, proj.stride(0), proj.stride(1),
+                                                    None if subset is None else subset.data_ptr(), 0 if subset is None else subset.shape[0],
+                                                    table.data_ptr(), table.shape[0], image_index.data_ptr(),
+                                                    None if prev_flags is None else prev_flags.data_ptr(), int(min_side), float(min_visible),
+                                                    out_boxes.data_ptr(), out_flags.data_ptr(), self.cuda_id, stream))

@@ -1,0 +1,141 @@
+"""Heads tracked from frame to frame on the device, as 3DDFA_V2 (the project Sim3DR comes from) tracks them: detect once, then take
+each frame's box from the previous frame's fit. `HeadTracker.step` is `predict_boxes` on the boxes it holds on the device followed
+by ONE launch (`dad3d_boxes_from_heads`, csrc/track_boxes.hip) from the heads' projected vertices to the boxes of the next step,
+so a video loop never waits for the device.
+
+A head is lost explicitly and stays lost: the launch zeroes the box of a head it flags (`_lib.TRACK_FLAG_*`: not finite, out of
+range, too small, mostly outside its frame), the next `predict_boxes` flags the zero box `BOX_FLAG_EMPTY` without reading a pixel,
+and that flag comes back as `TRACK_FLAG_PREVIOUS` at every later step, until `reseed` writes a box that the caller's detector found.
+Slots are fixed by `start`: nothing is compacted, merged or smoothed, and no detector is part of this."""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import boxes as _boxes
+
+
+class HeadTracker:
+    def __init__(self, predictor, offset: Any = 0.1, subset: Any = None, min_side: int = 1, min_visible: float = 0.5):
+        """`predictor`: a `FaceMeshPredictor`. `offset`: what `predict_boxes` widens every box by. `subset`: the vertex indices whose
+        bounds are a head's next box (an index list such as the face or head lists of the metrics; None: all vertices, the head box
+        the dataset's `bbox` and the training crop are about). `min_side`, `min_visible`: see `boxes.next_boxes`. Nothing is launched here."""
+        self.predictor = predictor
+        self._factors = _boxes.offset_factors(offset)
+        self._offset = offset
+        if int(min_side) < 0 or not 0.0 <= float(min_visible) <= 1.0:
+            raise ValueError(f"min_side {min_side} is negative or min_visible {min_visible} is outside [0, 1]")
+        self.min_side, self.min_visible = int(min_side), float(min_visible)
+        self._subset_host = None
+        if subset is not None:
+            ids = (subset.cpu().numpy() if torch.is_tensor(subset) else np.asarray(subset)).reshape(-1)
+            if ids.size == 0 or ids.dtype.kind not in "iu":
+                raise ValueError(f"subset: expected a list of vertex indices, got {ids.dtype} {ids.shape}")
+            self._subset_host = ids.astype(np.int32)
+        self._subset: Optional[torch.Tensor] = None
+        self._n_frames: Optional[int] = None
+        self._boxes: Optional[torch.Tensor] = None        # int32 [N,4]: the boxes of the next step
+        self._index: Optional[torch.Tensor] = None        # int32 [N]: every slot's frame, fixed by start
+        self._track_flags: Optional[torch.Tensor] = None  # int32 [N]: TRACK_FLAG_* of the last step
+
+    @property
+    def n_slots(self) -> int:
+        return 0 if self._boxes is None else int(self._boxes.shape[0])
+
+    def start(self, frames: Sequence[Any], boxes: Any, image_index: Any = None) -> None:
+        """Fixes the slots: one per box, in box order, each in the frame its `image_index` names, and the number of frames of
+        every later `step`. `boxes` and `image_index` in the forms `predict_boxes` takes them. A host box that `predict_boxes`
+        would refuse raises ValueError here; device boxes are never looked at on the host (a flagged one is a slot that starts
+        lost). The boxes are held as int32, converted toward zero, which is what the tracker's own boxes are."""
+        device = self.predictor.device
+        if torch.is_tensor(boxes):
+            if boxes.ndim != 2 or boxes.shape[1] != 4 or boxes.dtype == torch.bool or boxes.is_complex():
+                raise ValueError(f"boxes: expected a tensor [N,4] of numbers, got {boxes.dtype} {tuple(boxes.shape)}")
+            if not torch.is_tensor(image_index) or tuple(image_index.shape) != (boxes.shape[0],) or image_index.is_floating_point():
+                raise ValueError("image_index: device boxes need an integer tensor [N]")
+            dev_boxes = boxes.to(device, torch.int32).contiguous().clone()
+            dev_index = image_index.to(device, torch.int32).contiguous().clone()
+        else:
+            flat, index = _boxes.flatten_boxes(len(frames), boxes, image_index)
+            shapes = [tuple(int(s) for s in f.shape[:2]) for f in frames]
+            _boxes.check_boxes(shapes, flat, index, self._factors, self.predictor._img_size)  # ValueError, nothing launched
+            dev_boxes = torch.from_numpy(flat.astype(np.int32)).to(device)
+            dev_index = torch.from_numpy(index).to(device)
+        self._n_frames = len(frames)
+        self._boxes, self._index = dev_boxes, dev_index
+        self._track_flags = torch.zeros(dev_boxes.shape[0], dtype=torch.int32, device=device)
+        self._subset = None if self._subset_host is None else torch.from_numpy(self._subset_host).to(device)
+
+    def step(self, frames: Sequence[Any]) -> List[Dict[str, Any]]:
+        """One frame set of the video: `predict_boxes(frames, <the held boxes>, device_outputs=True, points_on_device=True)`, then the
+        boxes of the next step from these heads, written over the held ones. -> `predict_boxes`'s result dicts, one per slot, all
+        values on the device, plus `"track_flags"` (`_lib.TRACK_FLAG_*` of the box this head gave). `"image_index"` is the slot's
+        frame for a live head and -1 for a flagged one (box flags or track flags), so `overlay.draw_heads` and `Mesh.render_frames`,
+        which skip a head that names no frame, do not draw a lost head's meaningless values. The frames may change size from step
+        to step; their number is `start`'s. Nothing here waits for the device."""
+        if self._boxes is None:
+            raise ValueError("step: call start(frames, boxes) first")
+        if len(frames) != self._n_frames:
+            raise ValueError(f"step: {len(frames)} frames, but start fixed {self._n_frames}")
+        pred = self.predictor
+        if self.n_slots == 0:
+            return []
+        staged = pred._stage_frames(frames)
+        table = pred._frames_table(staged)
+        batched = pred._predict_boxes_batched(staged, self._boxes, self._index, self._factors, table)
+        if "projected_vertices" not in batched:
+            raise ValueError("step: the predictor's model has no 2-D output, so there are no projected vertices to take boxes from")
+        flags = batched["flags"]
+        pred._boxes_from_heads_launch(batched["projected_vertices"], table, self._index, flags, self._subset, self.min_side, self.min_visible,
+                                      self._boxes, self._track_flags)
+        track = self._track_flags.clone()  # the results keep this step's flags when the next step writes its own
+        drawn = torch.where((flags | track) != 0, torch.full_like(self._index, -1), self._index)
+        results = pred._rows_of(batched, True, True)
+        for i, r in enumerate(results):
+            r.update({"bbox": batched["bbox"][i], "image_index": drawn[i], "flags": flags[i], "track_flags": track[i]})
+        return results
+
+    def reseed(self, slots: Any, boxes: Any) -> None:
+        """Fresh boxes `[K,4]` for the slots `[K]` that the caller's detector found again: they are the slots' boxes at the next
+        step, and the slots' flags are cleared. Host or device arguments; device arguments are never read on the host, so their
+        slot numbers are the caller's to keep inside 0 .. n_slots - 1 (host ones outside raise ValueError)."""
+        if self._boxes is None:
+            raise ValueError("reseed: call start(frames, boxes) first")
+        device = self._boxes.device
+        if torch.is_tensor(slots):
+            if slots.is_floating_point() or slots.ndim != 1:
+                raise ValueError(f"slots: expected integers [K], got {slots.dtype} {tuple(slots.shape)}")
+            if not slots.is_cuda and slots.numel() and not (0 <= int(slots.min()) and int(slots.max()) < self.n_slots):
+                raise ValueError(f"slots: values outside 0 .. {self.n_slots - 1}")
+            dev_slots = slots.to(device, torch.int64)
+        else:
+            ids = np.asarray(slots).reshape(-1)
+            if ids.size and (ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() >= self.n_slots):
+                raise ValueError(f"slots: expected integers in 0 .. {self.n_slots - 1}, got {ids.tolist()}")
+            dev_slots = torch.from_numpy(ids.astype(np.int64)).to(device)
+        fresh = boxes if torch.is_tensor(boxes) else torch.from_numpy(np.asarray(boxes, dtype=np.float64).reshape(-1, 4).astype(np.int32))
+        if fresh.ndim != 2 or tuple(fresh.shape) != (dev_slots.shape[0], 4) or fresh.dtype == torch.bool or fresh.is_complex():
+            raise ValueError(f"boxes: expected [{dev_slots.shape[0]},4] numbers, got {fresh.dtype} {tuple(fresh.shape)}")
+        if dev_slots.shape[0] == 0:
+            return
+        # slot numbers given on the device were never seen on the host: one outside the slots goes to a spare row and moves nothing
+        n = self.n_slots
+        rows = torch.where((dev_slots >= 0) & (dev_slots < n), dev_slots, torch.full_like(dev_slots, n))
+        spare = torch.zeros((1, 4), dtype=torch.int32, device=device)
+        self._boxes.copy_(torch.cat([self._boxes, spare]).index_copy_(0, rows, fresh.to(device, torch.int32))[:n])
+        self._track_flags.copy_(torch.cat([self._track_flags, spare[0, :1]]).index_fill_(0, rows, 0)[:n])
+
+    def boxes(self) -> torch.Tensor:
+        """int32 `[N,4]` on the device: the boxes (x, y, w, h) the next step will use, zero for a lost slot. The tracker's own buffer."""
+        if self._boxes is None:
+            raise ValueError("boxes: call start(frames, boxes) first")
+        return self._boxes
+
+    def lost(self) -> torch.Tensor:
+        """int32 `[N]` on the device: the `_lib.TRACK_FLAG_*` of every slot after the last step, 0 for a slot that is tracked. A
+        caller reads it when it chooses to wait, for instance every few frames before it runs its detector."""
+        if self._track_flags is None:
+            raise ValueError("lost: call start(frames, boxes) first")
+        return self._track_flags

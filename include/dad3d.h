@@ -1106,6 +1106,50 @@ DAD3D_EXPORT dad3d_status dad3d_flame_readjust_params_frame(dad3d_flame* h, floa
 DAD3D_EXPORT dad3d_status dad3d_points_readjust_frame(const void* src, int src_kind, int batch, int n_points, float mul, float limit,
                                          const double* geometry, int32_t* points_out, int device, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tracking heads from frame to frame (csrc/track_boxes.hip): the boxes of the next call from the projected vertices of this one,
+ * as 3DDFA_V2 tracks (detect once, then each frame's box from the previous frame's fit). Still no detector: the first boxes, and the
+ * boxes of a head that was lost, are the caller's.
+ *
+ * dad3d_boxes_from_heads  ONE launch, one workgroup per head. DEVICE pointers:
+ *     proj         float32: head i's vertex v at proj + i*head_stride + v*vertex_stride (strides in floats), x at +0 and y at +1;
+ *                  vertex_stride >= 2, so [N,V,2] and [N,V,3] both work
+ *     subset       int32 [n_subset]: the vertex indices to bound, duplicates allowed; or NULL / 0 for all n_verts
+ *     frames       int64 [n_frames][4], the table of dad3d_preprocess_boxes: {address, h, w, row stride in bytes}; no pixel is read
+ *     image_index  int32 [N]: the frame of each head
+ *     prev_flags   int32 [N] or NULL: the flags of the call that produced proj (DAD3D_BOX_FLAG_*, or whatever the caller joins to them)
+ *     boxes        int32 [N][4] (x, y, w, h), written
+ *     flags        int32 [N]: DAD3D_TRACK_FLAG_*, written
+ *   Per head, in this order; the first of 1 - 3 that holds is the head's only flag:
+ *     1. DAD3D_TRACK_FLAG_PREVIOUS   prev_flags[i] != 0. No vertex of that head is read.
+ *     2. DAD3D_TRACK_FLAG_RANGE      image_index[i] outside [0, n_frames); a frame with a null address or a side outside [1, 2^30)
+ *                                    (the conditions of DAD3D_BOX_FLAG_RANGE); a subset index outside [0, n_verts)
+ *     3. DAD3D_TRACK_FLAG_NONFINITE  a selected x or y is a NaN or +-inf, wherever it stands. Otherwise xmin, xmax, ymin, ymax are
+ *                                    float32 values (min and max do not round), and DAD3D_TRACK_FLAG_RANGE again if one of them has a
+ *                                    magnitude >= 2^30.
+ *     4. x0 = floor(xmin), y0 = floor(ymin), x1 = ceil(xmax), y1 = ceil(ymax); the box is (x0, y0, x1 - x0, y1 - y0). It is NOT
+ *        clipped to the frame: `extend_bbox` and `ensure_bbox_boundaries` do that in the next dad3d_preprocess_boxes.
+ *     5. DAD3D_TRACK_FLAG_SMALL      min(w, h) < min_side
+ *     6. DAD3D_TRACK_FLAG_OUTSIDE    double(inter) < min_visible * double(w * h), with inter the area of the box cut with
+ *                                    [0, W) x [0, H), both areas in int64: one product, no division. Not evaluated where w * h == 0.
+ *        5 and 6 may both be set.
+ *   Any flag zeroes the head's box: (0, 0, 0, 0), which the next dad3d_preprocess_boxes flags DAD3D_BOX_FLAG_EMPTY without reading a
+ *   pixel; passed on as prev_flags, that flag keeps the head PREVIOUS in its slot until the caller writes a fresh box there.
+ *   (`ensure_bbox_boundaries` alone does not empty a box that lies outside its frame: (-50, -50, 20, 20) becomes the crop
+ *   (0, 0, 24, 24) in the frame's corner.)
+ *   DAD3D_E_INVALID before any device work: a null proj, frames, image_index, boxes or flags; n_heads, n_verts or n_frames outside
+ *   1 .. 65535 (n_heads == 0 returns DAD3D_OK), n_subset outside 1 .. 65535 with a subset, a subset without a count or a count without
+ *   a subset; vertex_stride < 2; min_side < 0; min_visible outside [0, 1] or a NaN. */
+#define DAD3D_TRACK_FLAG_PREVIOUS 0x1
+#define DAD3D_TRACK_FLAG_RANGE 0x2
+#define DAD3D_TRACK_FLAG_NONFINITE 0x4
+#define DAD3D_TRACK_FLAG_SMALL 0x8
+#define DAD3D_TRACK_FLAG_OUTSIDE 0x10
+DAD3D_EXPORT dad3d_status dad3d_boxes_from_heads(const float* proj, int n_heads, int n_verts, int64_t head_stride, int vertex_stride,
+                                    const int32_t* subset /* or NULL */, int n_subset, const int64_t* frames, int n_frames,
+                                    const int32_t* image_index, const int32_t* prev_flags /* or NULL */, int min_side,
+                                    double min_visible, int32_t* boxes, int32_t* flags, int device, void* stream);
+
 /* Single-image HOST entry points with the argument lists of Sim3DR/lib/rasterize.h:84-100 (`bool` spelled
  * `int` for C). libdad3d_hip.so additionally exports the C++-linkage symbols `_get_tri_normal`,
  * `_get_ver_normal`, `_get_normal`, `_rasterize_triangles`, `_rasterize` with the reference's exact
