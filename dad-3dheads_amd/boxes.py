@@ -1,7 +1,9 @@
 """Bounding boxes on the host: the argument forms of `FaceMeshPredictor.predict_boxes` and the rule `dad3d_preprocess_boxes` applies
 to every box on the device (csrc/preprocess_boxes.hip), restated with `dataset.extend_bbox` / `ensure_bbox_boundaries` and
 `resize_geometry`, so that a box the kernel would flag is refused before anything is launched; and `next_boxes`, the rule by which
-`dad3d_boxes_from_heads` (csrc/track_boxes.hip) takes the boxes of the next call from the heads of this one. Pure numpy: no GPU, no library."""
+`dad3d_boxes_from_heads` (csrc/track_boxes.hip) takes the boxes of the next call from the heads of this one; and `suppress_duplicates`,
+the rule by which `dad3d_track_suppress_duplicates` (csrc/track_steady.hip) drops the later of two slots on one head. Pure numpy: no GPU,
+no library."""
 from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple, Union
@@ -142,6 +144,42 @@ def next_boxes(proj, shapes: Sequence[Tuple[int, int]], image_index, prev_flags=
         if not flags[i]:
             boxes[i] = (x0, y0, w, h)
     return boxes, flags
+
+
+def suppress_duplicates(boxes, flags, image_index, merge_iou: float) -> Tuple[np.ndarray, np.ndarray]:
+    """Two slots on one head: `dad3d_track_suppress_duplicates` (csrc/track_steady.hip, include/dad3d.h) on the host, rule for rule.
+    `boxes` int32 `[N,4]` as (x, y, w, h) and `flags [N]` as `next_boxes` left them, `image_index [N]` -> copies of both with every
+    duplicate flagged `_lib.TRACK_FLAG_DUPLICATE` and zeroed. A slot takes part only if its flags are 0 and both sides are positive.
+    Walking upward, slot j is a duplicate if a KEPT earlier slot of the same frame overlaps it with `inter > 0` and
+    `float(inter) >= merge_iou * float(union)`, areas as integers: greedy, so a slot that was suppressed suppresses nobody, and the
+    lower slot wins -- an arbitrary but fixed choice, since which of two converged slots is the right one cannot be known without
+    appearance. Any number of slots: `_lib.TRACK_MAX_SLOTS` is the kernel's limit (its LDS), not the rule's."""
+    out_boxes = np.array(boxes, dtype=np.int32).reshape(-1, 4)
+    out_flags = np.array(flags, dtype=np.int32).reshape(-1)
+    index = np.asarray(image_index).reshape(-1)
+    n = len(out_boxes)
+    if len(out_flags) != n or len(index) != n:
+        raise ValueError(f"flags / image_index: expected {n} entries")
+    iou = float(merge_iou)
+    if not 0.0 < iou <= 1.0:  # false for a NaN
+        raise ValueError(f"merge_iou {merge_iou} is outside (0, 1]")
+    kept = []  # (frame, x0, y0, x1, y1, area) in Python's integers
+    for j in range(n):
+        x, y, w, h = (int(v) for v in out_boxes[j])
+        if out_flags[j] != 0 or w <= 0 or h <= 0:
+            continue
+        frame, x1, y1, area = int(index[j]), x + w, y + h, w * h
+        for f, ax0, ay0, ax1, ay1, a_area in kept:
+            if f != frame:
+                continue
+            inter = max(0, min(ax1, x1) - max(ax0, x)) * max(0, min(ay1, y1) - max(ay0, y))
+            if inter > 0 and float(inter) >= iou * float(a_area + area - inter):  # float(int) rounds to nearest even, as the device's conversion
+                out_boxes[j] = 0
+                out_flags[j] = _lib.TRACK_FLAG_DUPLICATE
+                break
+        else:
+            kept.append((frame, x, y, x1, y1, area))
+    return out_boxes, out_flags
 
 
 def check_boxes(shapes: Sequence[Tuple[int, int]], flat: np.ndarray, index: np.ndarray, factors, img_size: int) -> None:

@@ -1876,6 +1876,35 @@ dad3d_status dad3d_boxes_from_heads(const float* proj, int n_heads, int n_verts,
     return launch_boxes_from_heads(a, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_one_euro_rows(const float* x, int64_t x_stride, float* out, int64_t out_stride, int n, int d, const int32_t* flags,
+                                 const float* min_cutoff, const float* beta, float rate, float two_pi_dt, float alpha_d, float* state_x,
+                                 float* state_dx, int32_t* age, int device, void* stream) {
+    DAD3D_REQUIRE(d >= 1 && n >= 0, "dad3d_one_euro_rows: bad size (n %d, d %d)", n, d);
+    DAD3D_REQUIRE(x_stride >= d && out_stride >= d, "dad3d_one_euro_rows: a row stride (%lld, %lld) is below d = %d", (long long)x_stride,
+                  (long long)out_stride, d);
+    for (float v : {rate, two_pi_dt, alpha_d})  // false for a NaN
+        DAD3D_REQUIRE(v > 0.0f && v - v == 0.0f, "dad3d_one_euro_rows: the scalar %g is not finite and positive", (double)v);
+    DAD3D_REQUIRE(alpha_d <= 1.0f, "dad3d_one_euro_rows: alpha_d %g is above 1", (double)alpha_d);
+    if (n == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(x && out && min_cutoff && beta && state_x && state_dx && age, "dad3d_one_euro_rows: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    OneEuroArgs a{x, (long long)x_stride, out, (long long)out_stride, n, d, flags, min_cutoff, beta, rate, two_pi_dt, alpha_d, state_x, state_dx, age};
+    return launch_one_euro_rows(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_track_suppress_duplicates(int32_t* boxes, int32_t* flags, const int32_t* image_index, int n, double merge_iou, int device,
+                                             void* stream) {
+    DAD3D_REQUIRE(merge_iou > 0.0 && merge_iou <= 1.0, "dad3d_track_suppress_duplicates: merge_iou %g is outside (0, 1]", merge_iou);  // false for a NaN
+    DAD3D_REQUIRE(n >= 0 && n <= DAD3D_TRACK_MAX_SLOTS, "dad3d_track_suppress_duplicates: %d slots outside 0 .. %d", n, DAD3D_TRACK_MAX_SLOTS);
+    if (n == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(boxes && flags && image_index, "dad3d_track_suppress_duplicates: null argument");
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    SuppressDuplicatesArgs a{boxes, flags, image_index, n, merge_iou};
+    return launch_suppress_duplicates(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_cube_region_loss(const float* pred, const float* target, int batch, int n_verts,
                                     const int32_t* region_ptr, const int32_t* region_idx, const float* region_weight,
                                     int n_regions, const int32_t* vert_ptr, const int32_t* vert_region,

@@ -764,4 +764,27 @@ struct TrackBoxesArgs {
 };
 dad3d_status launch_boxes_from_heads(const TrackBoxesArgs& a, hipStream_t s);
 
+// steady tracks (track_steady.hip): the One-Euro filter over the rows of a matrix, and the suppression of duplicate slots
+struct OneEuroArgs {
+    const float* x;  // row i at x + i*x_stride
+    long long x_stride;
+    float* out;  // may be x itself (then with x's stride)
+    long long out_stride;
+    int n, d;
+    const int32_t* flags;                 // [N] or null
+    const float *min_cutoff, *beta;       // [D]
+    float rate, two_pi_dt, alpha_d;       // the host's three scalars
+    float *state_x, *state_dx;            // [N][D], contiguous
+    int32_t* age;                         // [N]
+};
+dad3d_status launch_one_euro_rows(const OneEuroArgs& a, hipStream_t s);
+struct SuppressDuplicatesArgs {
+    int32_t* boxes;  // [N][4] (x, y, w, h), in place
+    int32_t* flags;  // [N], in place
+    const int32_t* image_index;  // [N]
+    int n;  // 1 .. DAD3D_TRACK_MAX_SLOTS
+    double merge_iou;
+};
+dad3d_status launch_suppress_duplicates(const SuppressDuplicatesArgs& a, hipStream_t s);
+
 }  // namespace dad3d

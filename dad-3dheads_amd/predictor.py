@@ -360,12 +360,25 @@ class FaceMeshPredictor:
         crops both are the float64 `[B,5]` geometry of `dad3d_preprocess_boxes`."""
         return self._rows_of(self._batched_from(batch, pads_scale, geometry), device_outputs, points_on_device)
 
-    def _batched_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def _batched_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor,
+                      params_hook: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """`_results_from` before the results are cut into rows: the device tensors `3dmm_params [N,413]` and, where the model has a
-        2-D output, `points [N,68,2]` int32, `projected_vertices [N,5023,2]` and `3d_vertices [N,5023,3]`. Nothing waits."""
+        2-D output, `points [N,68,2]` int32, `projected_vertices [N,5023,2]` and `3d_vertices [N,5023,3]`. Nothing waits.
+        `params_hook` (private, for `tracking.HeadTracker`): called with the readjusted params `[N,413]` between `_readjust` and the
+        decode, it returns the params to decode (a contiguous float32 device tensor; the argument itself, changed in place, is
+        fine), so the decode still runs once; `3dmm_params_raw` is then the readjusted rows as the hook received them. The points
+        come from the network's 2-D head and do not pass the hook."""
         out = self.process(batch)
         params = out[OUTPUT_3DMM_PARAMS].detach().to(self.device, torch.float32).contiguous().clone()
         pts = self._landmarks_68(out, geometry)
+        if params_hook is not None:
+            if pts is None:  # nothing to decode for: the hook's state is not advanced for a result its caller cannot use
+                raise ValueError("params_hook: the predictor's model has no 2-D output, so there is no decode to stand in front of")
+            self._readjust(params, pads_scale)
+            raw = params.clone()
+            params = params_hook(params)
+            dec = self.head_mesh.decode(params, verts3d=True, proj=True, to_2d=True, landmarks=False, mutate=True)
+            return {"points": pts, "projected_vertices": dec["proj"], "3d_vertices": dec["verts3d"], "3dmm_params": params, "3dmm_params_raw": raw}
         if pts is None:  # `return {"3dmm_params": ...}` branch of predictor.py:144-145
             self._readjust(params, pads_scale)
             return {"3dmm_params": params}
@@ -388,16 +401,18 @@ class FaceMeshPredictor:
                 for i in range(n)]
 
     def _predict_boxes_batched(self, frames: List[torch.Tensor], dev_boxes: torch.Tensor, dev_index: torch.Tensor,
-                               factors: Optional[Tuple[float, float, float, float]], table: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                               factors: Optional[Tuple[float, float, float, float]], table: Optional[torch.Tensor] = None,
+                               params_hook: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """What stands behind `predict_boxes`, uncut: `_batched_from`'s device tensors in frame coordinates plus `bbox [N,4]` (the
-        crops used), `flags [N]` and `image_index [N]`, int32. Staged frames, device boxes and index; nothing waits."""
+        crops used), `flags [N]` and `image_index [N]`, int32. Staged frames, device boxes and index; nothing waits.
+        `params_hook(params, flags)`: `_batched_from`'s hook, given the rows' box flags too."""
         batch, crops, geometry, flags = self._preprocess_boxes_launch(frames, dev_boxes, dev_index, factors, self._input_format(), table)
-        batched = self._batched_from(batch, geometry, geometry)
+        batched = self._batched_from(batch, geometry, geometry, None if params_hook is None else (lambda p: params_hook(p, flags)))
         batched.update({"bbox": crops, "flags": flags, "image_index": dev_index})
         return batched
 
     def next_boxes(self, results_or_proj: Any, frames: Sequence[Any], image_index: Any = None, prev_flags: Any = None, subset: Any = None,
-                   min_side: int = 1, min_visible: float = 0.5):
+                   min_side: int = 1, min_visible: float = 0.5, merge_iou: Optional[float] = None):
         """The boxes of the next `predict_boxes` call from the heads of this one, the tracking step of 3DDFA_V2: each head's box is the
         integer bounds of its projected vertices (`subset`: vertex indices, None for all 5023, the head box the dataset's `bbox` and
         the training crop are about), zeroed and flagged `_lib.TRACK_FLAG_*` where the head is lost -- see `boxes.next_boxes` for
@@ -408,7 +423,13 @@ class FaceMeshPredictor:
         matter: arrays, tensors or (h, w) pairs). Device values go through ONE launch (`dad3d_boxes_from_heads`) and nothing waits
         for the device; host values go through the same rule in numpy. Give the boxes to the next call with the same `image_index`:
         a zeroed box comes back flagged `BOX_FLAG_EMPTY`, and with that flag as `prev_flags` the head stays lost until it gets a
-        fresh box from the caller's detector."""
+        fresh box from the caller's detector.
+
+        `merge_iou` in (0, 1]: of two boxes of one frame that overlap by at least this IoU the later one is flagged
+        `TRACK_FLAG_DUPLICATE` and zeroed (`boxes.suppress_duplicates`; one more launch for device values, which takes at most
+        `_lib.TRACK_MAX_SLOTS` heads -- the kernel's limit; host values have none). None: no box is compared with another."""
+        if merge_iou is not None and not 0.0 < float(merge_iou) <= 1.0:
+            raise ValueError(f"merge_iou {merge_iou} is outside (0, 1]")
         if isinstance(results_or_proj, (list, tuple)):
             dicts = list(results_or_proj)
             if not dicts:
@@ -431,17 +452,33 @@ class FaceMeshPredictor:
             shapes = [tuple(int(s) for s in (f.shape[:2] if hasattr(f, "shape") else f[:2])) for f in frames]
             host = [None if v is None else v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in (image_index, prev_flags, subset)]
             proj = proj.numpy() if torch.is_tensor(proj) else np.asarray(proj)
-            return _boxes.next_boxes(np.ascontiguousarray(proj, dtype=np.float32), shapes, host[0], host[1], host[2], min_side, min_visible)
+            found = _boxes.next_boxes(np.ascontiguousarray(proj, dtype=np.float32), shapes, host[0], host[1], host[2], min_side, min_visible)
+            return found if merge_iou is None else _boxes.suppress_duplicates(found[0], found[1], host[0], merge_iou)
         # the kernel reads no pixel: a frame given by its size alone gets a placeholder address, which only says that the frame exists
         table = torch.tensor([[f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)] if torch.is_tensor(f) else
                               [1, *(int(s) for s in (f.shape[:2] if hasattr(f, "shape") else f[:2])), 0] for f in frames], dtype=torch.int64).to(self.device)
         n = proj.shape[0]
         out_boxes = torch.empty((n, 4), dtype=torch.int32, device=self.device)
         out_flags = torch.empty((n,), dtype=torch.int32, device=self.device)
-        self._boxes_from_heads_launch(proj, table, self._dev_int32(image_index, n, "image_index"),
+        if merge_iou is not None and n > _lib.TRACK_MAX_SLOTS:
+            raise ValueError(f"merge_iou: {n} heads are more than the {_lib.TRACK_MAX_SLOTS} the duplicate rule compares in one launch")
+        dev_index = self._dev_int32(image_index, n, "image_index")
+        self._boxes_from_heads_launch(proj, table, dev_index,
                                       None if prev_flags is None else self._dev_int32(prev_flags, n, "prev_flags"),
                                       None if subset is None else self._dev_int32(subset, None, "subset"), min_side, min_visible, out_boxes, out_flags)
+        if merge_iou is not None:
+            self._suppress_duplicates_launch(out_boxes, out_flags, dev_index, merge_iou)
         return out_boxes, out_flags
+
+    def _suppress_duplicates_launch(self, boxes: torch.Tensor, flags: torch.Tensor, image_index: torch.Tensor, merge_iou: float) -> None:
+        """`dad3d_track_suppress_duplicates` on the current stream, in place on `boxes` int32 `[N,4]` and `flags [N]` as
+        `_boxes_from_heads_launch` left them: one launch, nothing is read on the host."""
+        n = boxes.shape[0]
+        for t, shape in ((boxes, (n, 4)), (flags, (n,)), (image_index, (n,))):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape, (t.dtype, tuple(t.shape))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.dad3d_track_suppress_duplicates(boxes.data_ptr(), flags.data_ptr(), image_index.data_ptr(), n, float(merge_iou),
+                                                             self.cuda_id, stream))
 
     def _dev_int32(self, values: Any, n: Optional[int], name: str) -> torch.Tensor:
         """Integers as a contiguous int32 tensor `[n]` on this device: a tensor is converted where it lies, host values are uploaded."""

@@ -6,7 +6,15 @@ so a video loop never waits for the device.
 A head is lost explicitly and stays lost: the launch zeroes the box of a head it flags (`_lib.TRACK_FLAG_*`: not finite, out of
 range, too small, mostly outside its frame), the next `predict_boxes` flags the zero box `BOX_FLAG_EMPTY` without reading a pixel,
 and that flag comes back as `TRACK_FLAG_PREVIOUS` at every later step, until `reseed` writes a box that the caller's detector found.
-Slots are fixed by `start`: nothing is compacted, merged or smoothed, and no detector is part of this."""
+Slots are fixed by `start`: nothing is compacted, and no detector is part of this.
+
+Two options, both off by default, steady the loop with one more launch each and still no host wait. `steady` (a
+`steady.SteadyConfig`) passes every slot's 3DMM row through a One-Euro filter between the CNN and the decode, in frame coordinates
+(crop-space params of different crops do not compare), so the vertices, the projected vertices and with them the next crop are
+steadied too; the filter's state is per slot and restarts with the slot. `points` come from the network's 2-D head and stay
+unfiltered. `merge_iou` flags the later of two slots that converged on one head `TRACK_FLAG_DUPLICATE` and zeroes its box
+(`boxes.suppress_duplicates`): it is then lost like any other lost slot. Which of the two is "right" cannot be known without
+appearance; the lower slot wins."""
 from __future__ import annotations
 
 from typing import Any, Dict, List, Optional, Sequence
@@ -14,14 +22,24 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import boxes as _boxes
+from . import _lib, boxes as _boxes
+from .steady import OneEuroFilter, SteadyConfig
 
 
 class HeadTracker:
-    def __init__(self, predictor, offset: Any = 0.1, subset: Any = None, min_side: int = 1, min_visible: float = 0.5):
+    def __init__(self, predictor, offset: Any = 0.1, subset: Any = None, min_side: int = 1, min_visible: float = 0.5,
+                 steady: Optional[SteadyConfig] = None, merge_iou: Optional[float] = None):
         """`predictor`: a `FaceMeshPredictor`. `offset`: what `predict_boxes` widens every box by. `subset`: the vertex indices whose
         bounds are a head's next box (an index list such as the face or head lists of the metrics; None: all vertices, the head box
-        the dataset's `bbox` and the training crop are about). `min_side`, `min_visible`: see `boxes.next_boxes`. Nothing is launched here."""
+        the dataset's `bbox` and the training crop are about). `min_side`, `min_visible`: see `boxes.next_boxes`. `steady`: a
+        `steady.SteadyConfig` to filter the params with, or None. `merge_iou` in (0, 1]: the IoU from which two slots of one frame
+        are one head, or None. With both None every result is what it is without them. Nothing is launched here."""
+        if steady is not None and not isinstance(steady, SteadyConfig):
+            raise ValueError(f"steady: expected a steady.SteadyConfig or None, got {type(steady).__name__}")
+        if merge_iou is not None and not 0.0 < float(merge_iou) <= 1.0:  # false for a NaN
+            raise ValueError(f"merge_iou {merge_iou} is outside (0, 1]")
+        self.steady, self.merge_iou = steady, None if merge_iou is None else float(merge_iou)
+        self._filter: Optional[OneEuroFilter] = None
         self.predictor = predictor
         self._factors = _boxes.offset_factors(offset)
         self._offset = offset
@@ -63,18 +81,31 @@ class HeadTracker:
             _boxes.check_boxes(shapes, flat, index, self._factors, self.predictor._img_size)  # ValueError, nothing launched
             dev_boxes = torch.from_numpy(flat.astype(np.int32)).to(device)
             dev_index = torch.from_numpy(index).to(device)
+        if self.merge_iou is not None and dev_boxes.shape[0] > _lib.TRACK_MAX_SLOTS:
+            raise ValueError(f"start: {dev_boxes.shape[0]} slots are more than the {_lib.TRACK_MAX_SLOTS} that merge_iou compares in one launch")
         self._n_frames = len(frames)
         self._boxes, self._index = dev_boxes, dev_index
         self._track_flags = torch.zeros(dev_boxes.shape[0], dtype=torch.int32, device=device)
         self._subset = None if self._subset_host is None else torch.from_numpy(self._subset_host).to(device)
+        self._filter = None
+        if self.steady is not None and dev_boxes.shape[0]:
+            min_cutoff, beta = self.steady.expand(self.predictor.head_mesh.flame_constants)
+            self._filter = OneEuroFilter(dev_boxes.shape[0], len(min_cutoff), min_cutoff, beta, self.steady.d_cutoff, device)
 
-    def step(self, frames: Sequence[Any]) -> List[Dict[str, Any]]:
+    def step(self, frames: Sequence[Any], dt: Optional[float] = None) -> List[Dict[str, Any]]:
         """One frame set of the video: `predict_boxes(frames, <the held boxes>, device_outputs=True, points_on_device=True)`, then the
         boxes of the next step from these heads, written over the held ones. -> `predict_boxes`'s result dicts, one per slot, all
         values on the device, plus `"track_flags"` (`_lib.TRACK_FLAG_*` of the box this head gave). `"image_index"` is the slot's
         frame for a live head and -1 for a flagged one (box flags or track flags), so `overlay.draw_heads` and `Mesh.render_frames`,
         which skip a head that names no frame, do not draw a lost head's meaningless values. The frames may change size from step
-        to step; their number is `start`'s. Nothing here waits for the device."""
+        to step; their number is `start`'s. Nothing here waits for the device.
+
+        With `steady`: `dt` is the time since the last step in seconds (None: `1 / steady.rate`). `"3dmm_params"` is the filtered
+        row (with tz := 0 from the decode, as without the filter), `"3d_vertices"`, `"projected_vertices"` and the next boxes come
+        from it, and the new key `"3dmm_params_raw"` is the readjusted row before the filter (its tz as the network gave it). A row
+        whose box is flagged passes unfiltered and restarts its track. `"points"` are the network's 2-D head's and are not
+        filtered. The filter works in frame coordinates: if the frames change size (another video, another scale), call `reset()`.
+        With `merge_iou`: a duplicate slot has `TRACK_FLAG_DUPLICATE` in `"track_flags"`, so `"image_index"` -1."""
         if self._boxes is None:
             raise ValueError("step: call start(frames, boxes) first")
         if len(frames) != self._n_frames:
@@ -84,17 +115,25 @@ class HeadTracker:
             return []
         staged = pred._stage_frames(frames)
         table = pred._frames_table(staged)
-        batched = pred._predict_boxes_batched(staged, self._boxes, self._index, self._factors, table)
+        hook = None
+        if self._filter is not None:
+            step_dt = self.steady.dt if dt is None else float(dt)
+            hook = lambda params, box_flags: self._filter.step(params, box_flags, step_dt, out=params)  # noqa: E731  in place
+        batched = pred._predict_boxes_batched(staged, self._boxes, self._index, self._factors, table, params_hook=hook)
         if "projected_vertices" not in batched:
             raise ValueError("step: the predictor's model has no 2-D output, so there are no projected vertices to take boxes from")
         flags = batched["flags"]
         pred._boxes_from_heads_launch(batched["projected_vertices"], table, self._index, flags, self._subset, self.min_side, self.min_visible,
                                       self._boxes, self._track_flags)
+        if self.merge_iou is not None:
+            pred._suppress_duplicates_launch(self._boxes, self._track_flags, self._index, self.merge_iou)
         track = self._track_flags.clone()  # the results keep this step's flags when the next step writes its own
         drawn = torch.where((flags | track) != 0, torch.full_like(self._index, -1), self._index)
         results = pred._rows_of(batched, True, True)
         for i, r in enumerate(results):
             r.update({"bbox": batched["bbox"][i], "image_index": drawn[i], "flags": flags[i], "track_flags": track[i]})
+            if hook is not None:
+                r["3dmm_params_raw"] = batched["3dmm_params_raw"][i : i + 1]
         return results
 
     def reseed(self, slots: Any, boxes: Any) -> None:
@@ -126,6 +165,23 @@ class HeadTracker:
         spare = torch.zeros((1, 4), dtype=torch.int32, device=device)
         self._boxes.copy_(torch.cat([self._boxes, spare]).index_copy_(0, rows, fresh.to(device, torch.int32))[:n])
         self._track_flags.copy_(torch.cat([self._track_flags, spare[0, :1]]).index_fill_(0, rows, 0)[:n])
+        if self._filter is not None:
+            self._filter.reset(rows)  # a fresh box is a fresh track: the slot's next sample passes unfiltered
+
+    def reset(self) -> None:
+        """Every slot's filter track restarts at the next step (nothing else changes; without `steady` nothing happens). For a
+        caller whose frames change size between steps: the filter's state is in the old frames' coordinates. No host wait."""
+        if self._filter is not None:
+            self._filter.reset()
+
+    def age(self) -> torch.Tensor:
+        """int32 `[N]` on the device: how many samples each slot's filter track has seen (0: it restarts at the next step; it stops
+        counting at 2^30). The filter's own buffer; ValueError without `steady`."""
+        if self._boxes is None:
+            raise ValueError("age: call start(frames, boxes) first")
+        if self._filter is None:
+            raise ValueError("age: the tracker was built without steady")
+        return self._filter.age
 
     def boxes(self) -> torch.Tensor:
         """int32 `[N,4]` on the device: the boxes (x, y, w, h) the next step will use, zero for a lost slot. The tracker's own buffer."""

@@ -1150,6 +1150,67 @@ DAD3D_EXPORT dad3d_status dad3d_boxes_from_heads(const float* proj, int n_heads,
                                     const int32_t* image_index, const int32_t* prev_flags /* or NULL */, int min_side,
                                     double min_visible, int32_t* boxes, int32_t* flags, int device, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Steady tracks (csrc/track_steady.hip): two per-slot rules over state that stays on the device, each ONE launch, each held bit
+ * for bit to its numpy statement (steady.one_euro_rows, boxes.suppress_duplicates). The unit is built with -ffp-contract=off.
+ *
+ * dad3d_one_euro_rows  A One-Euro filter (Casiez, Roussel, Vogel 2012) over the rows of a float32 matrix [n,d]. DEVICE pointers:
+ *     x           float32: row i at x + i*x_stride (strides in floats, >= d)
+ *     out         float32: row i at out + i*out_stride, written. out may be x itself with x's stride (in place); any other overlap
+ *                 is undefined
+ *     flags       int32 [n] or NULL: a row whose flag is not 0 is meaningless (DAD3D_BOX_FLAG_*, DAD3D_TRACK_FLAG_*)
+ *     min_cutoff, beta   float32 [d]: the filter's two constants per column
+ *     state_x, state_dx  float32 [n][d], contiguous: the last output and the last filtered derivative, read and written
+ *     age         int32 [n]: the number of samples a row's track has seen, read and written; 0 starts a track
+ *   The rule is stated on three float32 scalars that the HOST computes once per call from dt in float64 and rounds once:
+ *     rate = 1/dt,  two_pi_dt = 2 pi dt,  alpha_d = r_d / (r_d + 1) with r_d = 2 pi d_cutoff dt
+ *   Per row i, in this order:
+ *     1. flags != NULL && flags[i] != 0:  out[i,:] = x[i,:], age[i] = 0, the state rows stay as they are. The track restarts.
+ *     2. some x[i,c] is a NaN or an infinity:  the same as 1.
+ *     3. age[i] <= 0:  out = x, state_x = x, state_dx = +0.0, age = 1.
+ *     4. otherwise per element, in float32, every operation rounded once (xp = state_x, dxp = state_dx):
+ *            dx  = (x - xp) * rate
+ *            dxh = dxp + alpha_d * (dx - dxp)
+ *            fc  = min_cutoff[c] + beta[c] * fabsf(dxh)
+ *            r   = two_pi_dt * fc
+ *            a   = r / (r + 1.0f)              (the correctly rounded quotient, denormals kept)
+ *            out = xp + a * (x - xp)
+ *        then state_x = out, state_dx = dxh, age = min(age + 1, 2^30).
+ *     5. if some out[i,c] or dxh of 4 is not finite (x - xp can overflow; inf / inf is a NaN), the row restarts as in 3 instead.
+ *        The state therefore never holds a NaN or an infinity that the kernel wrote.
+ *   DAD3D_E_INVALID before any launch, and nothing is written: d < 1; n < 0; a stride below d; rate, two_pi_dt or alpha_d not finite
+ *   or not positive; alpha_d > 1; then (n == 0 returns DAD3D_OK with no launch) a null x, out, min_cutoff, beta, state_x, state_dx
+ *   or age.
+ *
+ * dad3d_track_suppress_duplicates  Two slots that converged on one head: the later one is flagged and zeroed. In place on what
+ * dad3d_boxes_from_heads left. DEVICE pointers:
+ *     boxes        int32 [n][4] (x, y, w, h), read and written
+ *     flags        int32 [n]: DAD3D_TRACK_FLAG_*, read and written
+ *     image_index  int32 [n]: the frame of each slot; any values, compared for equality only
+ *   A slot takes part only if flags == 0 and w > 0 and h > 0. Walk j upward: slot j is a duplicate if some KEPT earlier slot i < j
+ *   (one that takes part and is no duplicate itself) has image_index[i] == image_index[j] and
+ *       inter > 0  and  double(inter) >= merge_iou * double(union)
+ *   with all areas in int64: inter from the int64 minimum and maximum of the corners (x, y, x + w, y + h),
+ *   union = w_i*h_i + w_j*h_j - inter (two int32 sides cannot overflow that sum); one product, no division. A duplicate gets
+ *   flags = DAD3D_TRACK_FLAG_DUPLICATE and the box (0, 0, 0, 0); no other word is written. The rule is greedy, not "any overlap":
+ *   a slot suppressed by i suppresses nobody. The lower slot wins; that choice is arbitrary but fixed (which of two converged slots
+ *   is the right one cannot be known without appearance).
+ *   n <= DAD3D_TRACK_MAX_SLOTS: one workgroup holds the pair bits in LDS. The allocation is static and sized for the cap whatever
+ *   n is -- 1024^2 / 8 bytes of bits plus 20 KiB of staged boxes and frame numbers, 151 552 bytes of the CU's 160 KiB -- so a
+ *   launch of 64 slots occupies as much LDS as one of 1024; it is one workgroup either way.
+ *   DAD3D_E_INVALID before any launch: merge_iou not finite or outside (0, 1]; n < 0 or n > DAD3D_TRACK_MAX_SLOTS; then (n == 0
+ *   returns DAD3D_OK) a null boxes, flags or image_index. */
+#define DAD3D_TRACK_MAX_SLOTS 1024
+/* Parenthesised on purpose: this bit is set by dad3d_track_suppress_duplicates alone. The five plain DAD3D_TRACK_FLAG_* above are
+ * the complete set dad3d_boxes_from_heads writes, and are counted as such. */
+#define DAD3D_TRACK_FLAG_DUPLICATE (0x20)
+DAD3D_EXPORT dad3d_status dad3d_one_euro_rows(const float* x, int64_t x_stride, float* out, int64_t out_stride, int n, int d,
+                                 const int32_t* flags /* or NULL */, const float* min_cutoff, const float* beta, float rate,
+                                 float two_pi_dt, float alpha_d, float* state_x, float* state_dx, int32_t* age, int device,
+                                 void* stream);
+DAD3D_EXPORT dad3d_status dad3d_track_suppress_duplicates(int32_t* boxes, int32_t* flags, const int32_t* image_index, int n,
+                                 double merge_iou, int device, void* stream);
+
 /* Single-image HOST entry points with the argument lists of Sim3DR/lib/rasterize.h:84-100 (`bool` spelled
  * `int` for C). libdad3d_hip.so additionally exports the C++-linkage symbols `_get_tri_normal`,
  * `_get_ver_normal`, `_get_normal`, `_rasterize_triangles`, `_rasterize` with the reference's exact
