@@ -57,7 +57,6 @@ PNG, DECODED, ANNOTATION = "png", "decoded", "annotation"
 PNG_FILES, PNG_TABLE, DECODED_IMAGES, DECODED_TABLE, ANNOTATIONS, ANNOTATION_TABLE = ("png_files", "png_table", "decoded_images",
                                                                                       "decoded_table", "annotations", "annotation_table")
 ITEM_FORMS = ("raw", "files")
-_ALIGN = 16  # png_reader._align's and dad3d_annotation_parse's
 
 
 def read_as_rgb(path: str) -> np.ndarray:
@@ -274,7 +273,7 @@ class RawBatchCollate:
 class FileBatchCollate(RawBatchCollate):
     """`RawBatchCollate` for the items of `FlameDataset(item_form="files")`: the same `None` dropping and refill. Everything is
     a CPU tensor, so `DataLoader(pin_memory=True)` pins the batch whole:
-      png_files         uint8   every PNG file, each at a multiple of 16 bytes (png_reader._align), zero between them
+      png_files         uint8   every PNG file, each at a multiple of 16 bytes (_packed_files.pack), zero between them
       png_table         int64 [B,5]   offset, size (0: the item came decoded), and the IHDR's height, width, channels
       decoded_images    uint8   every image a worker had to decode (HWC RGB), each at a multiple of 16 bytes
       decoded_table     int64 [B,2]   offset, size (0: the item is a PNG)
@@ -287,17 +286,9 @@ class FileBatchCollate(RawBatchCollate):
 
     @staticmethod
     def _pack(arrays: Sequence[np.ndarray]) -> Tuple[torch.Tensor, np.ndarray]:
-        sizes = [int(a.size) for a in arrays]
-        table = np.zeros((len(arrays), 2), dtype=np.int64)
-        at = 0
-        for i, z in enumerate(sizes):
-            table[i] = (at, z)
-            at += (z + _ALIGN - 1) // _ALIGN * _ALIGN
-        packed = torch.zeros(at, dtype=torch.uint8)
-        flat = packed.numpy()
-        for (off, z), a in zip(table, arrays):
-            flat[off:off + z] = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
-        return packed, table
+        from ._packed_files import pack
+
+        return pack(arrays)  # not pinned: `DataLoader(pin_memory=True)` pins the batch whole
 
     def __call__(self, batch: Sequence[Optional[Mapping[str, Any]]]) -> Dict[str, Any]:
         from .png_reader import _header_of
@@ -402,6 +393,7 @@ class FlameBatchBuilder:
         before that launch could be handed to the very output the launch writes."""
         import io
 
+        from ._packed_files import read_back
         from .png_reader import PngDecoder
 
         dev = self.device
@@ -429,13 +421,12 @@ class FlameBatchBuilder:
                                                          verts.data_ptr(), mv.data_ptr(), pm.data_ptr(), status.data_ptr(), dev.index, stream))
         else:  # nothing but empty files: the host's parser says so
             status.fill_(self._range_flag)
-        flags = [status] + ([pending.dev_flags, pending.dev_info] if pending.on_device else [])
-        got = torch.cat(flags).cpu().numpy()  # the one sync of the file form
-        images = pending.finish(got[b:b + len(pending.on_device)], got[b + len(pending.on_device):])
-        self.last_fallbacks = {"annotation_host": int((got[:b] != 0).sum()),
+        (got,), (words,) = read_back([pending], [status])  # the one sync of the file form
+        images = pending.finish(*words)
+        self.last_fallbacks = {"annotation_host": int((got != 0).sum()),
                                "png_host": int((images.flags != 0).sum()),
                                "png_worker": int((png_table[:, 1] == 0).sum())}
-        for i in np.nonzero(got[:b])[0]:  # the host's parser, from the bytes still in the batch
+        for i in np.nonzero(got)[0]:  # the host's parser, from the bytes still in the batch
             off, size = (int(v) for v in ann_table[i])
             data = raw[ANNOTATIONS][off:off + size].cpu().numpy().tobytes()
             v, m, p = FlameDataset._mesh_of(io.TextIOWrapper(io.BytesIO(data)))

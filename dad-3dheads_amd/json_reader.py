@@ -22,6 +22,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._packed_files import cuda_device
 
 PLACEHOLDER_KEY = "__dad3d_device_array__"
 _PLACEHOLDER_BYTES = PLACEHOLDER_KEY.encode("ascii")
@@ -217,10 +218,7 @@ def load(source: Union[str, os.PathLike, bytes, bytearray, memoryview], device: 
 
     Raises `json.JSONDecodeError` for a malformed document, as `json.loads` does. A document that holds the placeholder key, or is
     2 GiB or larger, is parsed on the host alone."""
-    _lib.require_gpu()
-    if device is None:
-        device = torch.cuda.current_device()
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = cuda_device(device)
     pinned = _read(source)
     n = pinned.numel()
     data = pinned.numpy().tobytes() if n <= MAX_BYTES else None

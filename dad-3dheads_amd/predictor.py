@@ -319,10 +319,11 @@ class FaceMeshPredictor:
         `predict_batch`'s own code. `jpeg_entropy` is `JpegDecoder`'s `entropy`: "sync" decodes a JPEG file without restart markers
         in pieces, to the same pixels. With `boxes` (and `image_index`, `offset`) the files are frames and the call is `predict_boxes`
         on them."""
+        from ._packed_files import bytes_of, read_back
         from .jpeg_reader import SOI, JpegDecoder
-        from .png_reader import PngDecoder, _bytes_of
+        from .png_reader import PngDecoder
 
-        files = [_bytes_of(s) for s in sources]
+        files = [bytes_of(s) for s in sources]
         jpegs = [i for i, f in enumerate(files) if f[:2] == SOI]
         if not jpegs:
             decoded = PngDecoder(self.device).decode(files, channels=3).tensors()  # alive until the launch has consumed them
@@ -330,16 +331,11 @@ class FaceMeshPredictor:
             pngs = [i for i in range(len(files)) if i not in set(jpegs)]
             jpeg = JpegDecoder(self.device, entropy=jpeg_entropy)._launch([files[i] for i in jpegs], 3)
             png = PngDecoder(self.device)._launch([files[i] for i in pngs], 3) if pngs else None
-            jpeg_words = jpeg.words()
-            words = [t for t in (tuple(jpeg_words) + ((png.dev_flags, png.dev_info) if png else ())) if t is not None]
-            got = torch.cat(words).cpu().numpy() if words else np.zeros(0, np.int32)  # the one wait
-            nj, npng = sum(t.numel() for t in jpeg_words), len(png.on_device) if png else 0
             decoded = [None] * len(files)
-            for i, t in zip(jpegs, jpeg.finish(*jpeg.split(got[:nj])).tensors()):
-                decoded[i] = t
-            if png:
-                for i, t in zip(pngs, png.finish(got[nj:nj + npng], got[nj + npng:nj + 2 * npng]).tensors()):
-                    decoded[i] = t
+            for pending, words, where in zip((jpeg, png), read_back([jpeg, png])[1], (jpegs, pngs)):  # the one wait
+                if pending is not None:
+                    for i, t in zip(where, pending.finish(*words).tensors()):
+                        decoded[i] = t
         if boxes is not None:  # the decoded frames stay on the device; the crops are read from them in place
             return self._predict_boxes_staged(self._stage_frames(decoded), boxes, image_index, offset, device_outputs, points_on_device)
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)) for t in decoded])

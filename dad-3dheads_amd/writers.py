@@ -17,10 +17,10 @@ Images (`ImageSaver` of the demo, demo_utils.py:122-127) are written as PNG: a u
 the GPU (`PngEncoder`, csrc/png_encode.hip; `png_batch`, `save_png_batch`), a host image by PIL (`ImageSaver`).
 Where a lossy file is wanted -- photographs with overlays, renders over a background -- `JpegEncoder` (csrc/jpeg_encode.hip,
 DESIGN.md 4.20; `jpeg_batch`, `save_jpeg_batch`) writes baseline JPEG on the GPU with the bytes PIL writes for the same options.
+Both are `_ImageEncoder`: one argument check, one encode body, one cache, one device-path predicate and one write loop.
 """
 from __future__ import annotations
 
-import ctypes as C
 import io
 import json
 import os
@@ -86,6 +86,24 @@ class JsonSaver:
             json.dump(flame_params, out)
 
 
+def _check_batch(name: str, t: Any, dtype: torch.dtype, shape: Tuple[int, ...], device: torch.device) -> None:
+    """ValueError unless `t` is a contiguous `dtype` tensor [B, *shape] on `device`."""
+    if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or not t.is_contiguous() or t.ndim != len(shape) + 1
+            or tuple(t.shape[1:]) != tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous {str(dtype)[6:]} tensor [B,{','.join(str(v) for v in shape)}] on {device}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', 'the host')}"
+                         + ("" if not isinstance(t, torch.Tensor) or t.is_contiguous() else " (not contiguous)"))
+
+
+def _write_blocks(blocks: Sequence[Any], paths: Sequence[str], tail: bytes = b"") -> None:
+    """One file per block of bytes, each with `tail` behind it."""
+    for block, path in zip(blocks, paths):
+        with open(path, "wb") as f:
+            f.write(block)
+            if tail:
+                f.write(tail)
+
+
 class _DeviceText:
     """Text of `batch` items in a formatter's HBM buffer. Item b's bytes are `text[b, :lengths[b]]` (byte offset `b * stride` of
     the buffer); `flags[b] != 0` marks an item the kernel left to the host (`_host_item`). The buffers belong to the formatter:
@@ -138,7 +156,19 @@ class _DeviceText:
 
 class _TextBuffers:
     """The buffers of a device text formatter: `capacity` rows of `stride` bytes of text, lengths and flags, the kernels' scratch
-    and the pinned host side of the copy."""
+    and the pinned host side of the copy. A subclass sets `stride` and gives `_scratch_bytes_for(batch)`."""
+
+    def __init__(self, device: Optional[int] = None):
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.torch_device = torch.device("cuda", self.device)
+        self.capacity = 0
+
+    def reserve(self, batch: int) -> None:
+        batch = max(int(batch), 1)
+        if batch > self.capacity:
+            self._reserve_buffers(batch, self._scratch_bytes_for(batch))
 
     def _reserve_buffers(self, batch: int, scratch_bytes: int) -> None:
         dev = self.torch_device
@@ -174,28 +204,16 @@ class ObjFormatter(_TextBuffers):
     takes them) gives `face_text`, the constant block behind every mesh's vertices."""
 
     def __init__(self, n_verts: int, faces: Optional[np.ndarray] = None, device: Optional[int] = None):
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.device = torch.cuda.current_device() if device is None else int(device)
-        self.torch_device = torch.device("cuda", self.device)
+        super().__init__(device)
         self.n_verts = int(n_verts)
         self.stride = (self.n_verts * _lib.OBJ_MAX_LINE_BYTES + 15) // 16 * 16
         self.face_text = b"" if faces is None else _face_block(np.asarray(faces) + 1.0).encode("ascii")
-        self.capacity = 0
 
-    def reserve(self, batch: int) -> None:
-        batch = max(int(batch), 1)
-        if batch <= self.capacity:
-            return
-        self._reserve_buffers(batch, self._lib.dad3d_obj_format_scratch_bytes(batch, self.n_verts))
+    def _scratch_bytes_for(self, batch: int) -> int:
+        return self._lib.dad3d_obj_format_scratch_bytes(batch, self.n_verts)
 
     def format(self, vertices: torch.Tensor) -> ObjText:
-        if (not isinstance(vertices, torch.Tensor) or vertices.device != self.torch_device or vertices.dtype != torch.float32
-                or not vertices.is_contiguous() or vertices.ndim != 3 or tuple(vertices.shape[1:]) != (self.n_verts, 3)):
-            raise ValueError(f"vertices: expected a contiguous float32 tensor [B,{self.n_verts},3] on {self.torch_device}, got "
-                             f"{getattr(vertices, 'dtype', type(vertices))} {tuple(getattr(vertices, 'shape', ()))} on "
-                             f"{getattr(vertices, 'device', 'the host')}"
-                             + ("" if not isinstance(vertices, torch.Tensor) or vertices.is_contiguous() else " (not contiguous)"))
+        _check_batch("vertices", vertices, torch.float32, (self.n_verts, 3), self.torch_device)
         b = vertices.shape[0]
         self.reserve(b)
         stream = torch.cuda.current_stream(self.torch_device).cuda_stream
@@ -234,10 +252,7 @@ def obj_text_batch(vertices: torch.Tensor, faces_1based: np.ndarray) -> List[byt
 
 
 def _write_obj_files(blocks: Sequence[Any], face_text: bytes, paths: Sequence[str]) -> None:
-    for block, path in zip(blocks, paths):
-        with open(path, "wb") as f:
-            f.write(block)
-            f.write(face_text)
+    _write_blocks(blocks, paths, face_text)
 
 
 def save_obj_batch(vertices: torch.Tensor, faces: np.ndarray, paths: Sequence[str], formatter: str = "auto") -> None:
@@ -408,22 +423,18 @@ class JsonFormatter(_TextBuffers):
     and no sync once the batch fits (capturable in a graph); `JsonText.to_host()` brings the bytes over."""
 
     def __init__(self, template: JsonTemplate, device: Optional[int] = None):
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(device)
         if template.n_slots < 1:
             raise ValueError("JsonFormatter: a template without numbers is a constant: template.render([])")
-        self.device = torch.cuda.current_device() if device is None else int(device)
-        self.torch_device = torch.device("cuda", self.device)
         self.template, self.n_slots, self.stride = template, template.n_slots, template.stride
         self._image = template.device_image(self.torch_device)
         self._offsets = np.ascontiguousarray(template.offsets)
-        self.capacity = 0
 
-    def reserve(self, batch: int) -> None:
-        batch = max(int(batch), 1)
-        if batch <= self.capacity:
-            return
-        self._reserve_buffers(batch, self._lib.dad3d_json_format_scratch_bytes(batch, self.n_slots))
+    def _scratch_bytes_for(self, batch: int) -> int:
+        return self._lib.dad3d_json_format_scratch_bytes(batch, self.n_slots)
+
+    def _reserve_buffers(self, batch: int, scratch_bytes: int) -> None:
+        super()._reserve_buffers(batch, scratch_bytes)
         self._staging = torch.zeros((batch, self.n_slots), dtype=torch.float32, device=self.torch_device)
 
     def staging(self, batch: int) -> torch.Tensor:
@@ -433,24 +444,17 @@ class JsonFormatter(_TextBuffers):
     def format(self, values: torch.Tensor, host_item=None, extra_flags: Optional[torch.Tensor] = None) -> JsonText:
         """`values [B,n_slots]` -> `JsonText`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
         kernels: a non-zero entry sends that item to `host_item(b)`."""
-        if (not isinstance(values, torch.Tensor) or values.device != self.torch_device or values.dtype != torch.float32
-                or not values.is_contiguous() or values.ndim != 2 or values.shape[1] != self.n_slots):
-            raise ValueError(f"values: expected a contiguous float32 tensor [B,{self.n_slots}] on {self.torch_device}, got "
-                             f"{getattr(values, 'dtype', type(values))} {tuple(getattr(values, 'shape', ()))} on "
-                             f"{getattr(values, 'device', 'the host')}"
-                             + ("" if not isinstance(values, torch.Tensor) or values.is_contiguous() else " (not contiguous)"))
+        _check_batch("values", values, torch.float32, (self.n_slots,), self.torch_device)
         b = values.shape[0]
-        if b == 0:
-            self.reserve(1)
-            return JsonText(self, values, 0, host_item)
         self.reserve(b)
-        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
-        _lib.check(self._lib.dad3d_json_format_values(values.data_ptr(), b, self.n_slots, self._image.data_ptr(), self._offsets.ctypes.data,
-                                                      self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
-                                                      self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(),
-                                                      self.device, stream))
-        if extra_flags is not None:
-            self._flags[:b].bitwise_or_(extra_flags)
+        if b:
+            stream = torch.cuda.current_stream(self.torch_device).cuda_stream
+            _lib.check(self._lib.dad3d_json_format_values(values.data_ptr(), b, self.n_slots, self._image.data_ptr(), self._offsets.ctypes.data,
+                                                          self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
+                                                          self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(),
+                                                          self.device, stream))
+            if extra_flags is not None:
+                self._flags[:b].bitwise_or_(extra_flags)
         return JsonText(self, values, b, host_item)
 
 
@@ -506,9 +510,7 @@ def save_flame_params_batch(params: torch.Tensor, paths: Sequence[str], formatte
         raise ValueError(f"formatter: expected 'auto' or 'host', got {formatter!r}")
     assert params.ndim == 2 and params.shape[0] == len(paths)
     if formatter == "auto" and _params_on_device_path(params, FLAME_CONSTS):
-        for block, path in zip(_format_flame_params(params, FLAME_CONSTS).to_host(), paths):
-            with open(path, "wb") as f:
-                f.write(block)
+        _write_blocks(_format_flame_params(params, FLAME_CONSTS).to_host(), paths)
         return
     saver = JsonSaver()
     for row, path in zip(flame_params_batch(params), paths):
@@ -548,113 +550,125 @@ class ImageSaver:
             f.write(_png_host(np.asarray(image)))
 
 
-class PngData(_DeviceText):
-    """What `PngEncoder.encode` returns: the PNG files of `batch` images in HBM, the contract of `ObjText`. A flagged item (the
-    encoder's own consistency check, or a flag the caller ORed in) is encoded on the host with PIL."""
+class _ImageData(_DeviceText):
+    """What an image encoder's `encode` returns: the files of `batch` images in HBM, the contract of `ObjText`. A flagged item (the
+    encoder's own consistency check, or a flag the caller ORed in) is encoded on the host with PIL, with the encoder's options."""
 
-    def __init__(self, encoder: "PngEncoder", images: torch.Tensor, batch: int):
+    def __init__(self, encoder: "_ImageEncoder", images: torch.Tensor, batch: int):
         super().__init__(encoder, batch)
         self.images = images
 
     def _host_item(self, b: int) -> bytes:
-        return _png_host(self.images[b].detach().cpu().numpy())
+        return self.formatter._host_encode(self.images[b].detach().cpu().numpy(), **self.formatter.options)
 
 
-class PngEncoder(_TextBuffers):
-    """A batch of uint8 images `[B,H,W,C]`, C = 1..4, as PNG files made on the GPU (`dad3d_png_encode`, csrc/png_encode.hip,
-    DESIGN.md 4.15): row filters, deflate per segment of `_lib.PNG_SEGMENT_BYTES` with Huffman tables built on the device, CRC-32
-    and Adler-32. Lossless; the bytes are this encoder's own.
+PngData = JpegData = _ImageData
 
-    `reserve(batch)` allocates the device file buffer (`batch` rows of `dad3d_png_max_bytes`), lengths, flags, scratch and one
-    pinned host buffer; `encode(images)` launches three kernels on the current stream with no allocation and no sync once the
-    batch fits (capturable in a graph); `PngData.to_host()` brings the files over."""
+
+class _ImageEncoder(_TextBuffers):
+    """A batch of uint8 images `[B,H,W,C]` as files made on the GPU. `reserve(batch)` allocates the device file buffer (`batch` rows
+    of the format's worst case), lengths, flags, scratch and one pinned host buffer; `encode(images)` launches on the current stream
+    with no allocation and no sync once the batch fits (capturable in a graph); `to_host()` of what it returns brings the files
+    over. A format gives `_CHANNELS` (the channel counts it takes), `_LIMITS` (for the error text), `options` (what its host
+    encoder takes besides the image), `_key_options`, `_max_bytes`, `_scratch_bytes_for`, `_launch` and `_host_encode`."""
+
+    options: Dict[str, Any] = {}
 
     def __init__(self, height: int, width: int, channels: int, device: Optional[int] = None):
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.device = torch.cuda.current_device() if device is None else int(device)
-        self.torch_device = torch.device("cuda", self.device)
+        super().__init__(device)
         self.height, self.width, self.channels = int(height), int(width), int(channels)
-        worst = self._lib.dad3d_png_max_bytes(self.height, self.width, self.channels)
+        worst = self._max_bytes()
         if worst == 0:
-            raise ValueError(f"PngEncoder: cannot encode images of {self.height} x {self.width} x {self.channels} (1..4 channels, a "
-                             "filtered stream below 2^31 bytes)")
+            raise ValueError(f"{type(self).__name__}: cannot encode images of {self.height} x {self.width} x {self.channels} ({self._LIMITS})")
         self.stride = (worst + 15) // 16 * 16
-        self.capacity = 0
 
-    def reserve(self, batch: int) -> None:
-        batch = max(int(batch), 1)
-        if batch <= self.capacity:
-            return
-        self._reserve_buffers(batch, self._lib.dad3d_png_scratch_bytes(batch, self.height, self.width, self.channels))
+    @staticmethod
+    def _key_options(channels: int, height: int, width: int) -> tuple:
+        """The constructor's arguments behind `channels`, as the options of a `*_batch` call give them."""
+        return ()
 
-    def encode(self, images: torch.Tensor, extra_flags: Optional[torch.Tensor] = None) -> PngData:
-        """`images [B,H,W,C]` -> `PngData`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
+    def encode(self, images: torch.Tensor, extra_flags: Optional[torch.Tensor] = None) -> _ImageData:
+        """`images [B,H,W,C]` -> the files. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
         kernels: a non-zero entry sends that item to the host encoder."""
-        shape = (self.height, self.width, self.channels)
-        if (not isinstance(images, torch.Tensor) or images.device != self.torch_device or images.dtype != torch.uint8
-                or not images.is_contiguous() or images.ndim != 4 or tuple(images.shape[1:]) != shape):
-            raise ValueError(f"images: expected a contiguous uint8 tensor [B,{shape[0]},{shape[1]},{shape[2]}] on {self.torch_device}, got "
-                             f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))} on "
-                             f"{getattr(images, 'device', 'the host')}"
-                             + ("" if not isinstance(images, torch.Tensor) or images.is_contiguous() else " (not contiguous)"))
+        _check_batch("images", images, torch.uint8, (self.height, self.width, self.channels), self.torch_device)
         b = images.shape[0]
-        if b == 0:
-            self.reserve(1)
-            return PngData(self, images, 0)
         self.reserve(b)
-        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
-        _lib.check(self._lib.dad3d_png_encode(images.data_ptr(), b, *shape, self._text.data_ptr(), self._text.stride(0),
-                                              self._lengths.data_ptr(), self._flags.data_ptr(), self._scratch.data_ptr(),
-                                              self._scratch.numel(), self.device, stream))
-        if extra_flags is not None:
-            self._flags[:b].bitwise_or_(extra_flags)
-        return PngData(self, images, b)
+        if b:
+            _lib.check(self._launch(images, b, torch.cuda.current_stream(self.torch_device).cuda_stream))
+            if extra_flags is not None:
+                self._flags[:b].bitwise_or_(extra_flags)
+        return _ImageData(self, images, b)
 
 
-_png_encoders: Dict[Tuple[int, int, int, int], PngEncoder] = {}
+class PngEncoder(_ImageEncoder):
+    """`_ImageEncoder` for PNG, C = 1..4 (`dad3d_png_encode`, csrc/png_encode.hip, DESIGN.md 4.15, three kernels): row filters,
+    deflate per segment of `_lib.PNG_SEGMENT_BYTES` with Huffman tables built on the device, CRC-32 and Adler-32. Lossless; the
+    bytes are this encoder's own."""
+
+    _CHANNELS = (1, 2, 3, 4)
+    _LIMITS = "1..4 channels, a filtered stream below 2^31 bytes"
+
+    def _max_bytes(self) -> int:
+        return self._lib.dad3d_png_max_bytes(self.height, self.width, self.channels)
+
+    def _scratch_bytes_for(self, batch: int) -> int:
+        return self._lib.dad3d_png_scratch_bytes(batch, self.height, self.width, self.channels)
+
+    def _launch(self, images: torch.Tensor, b: int, stream: int) -> int:
+        return self._lib.dad3d_png_encode(images.data_ptr(), b, self.height, self.width, self.channels, self._text.data_ptr(),
+                                          self._text.stride(0), self._lengths.data_ptr(), self._flags.data_ptr(), self._scratch.data_ptr(),
+                                          self._scratch.numel(), self.device, stream)
+
+    @staticmethod
+    def _host_encode(image: np.ndarray, **options: Any) -> bytes:
+        return _png_host(image, **options)
 
 
-def _png_encoder_for(images: torch.Tensor) -> PngEncoder:
-    key = (images.device.index, int(images.shape[1]), int(images.shape[2]), int(images.shape[3]))
-    enc = _png_encoders.get(key)
+_encoders: Dict[tuple, _ImageEncoder] = {}
+
+
+def _encoder_for(cls, images: torch.Tensor, **options: Any) -> _ImageEncoder:
+    """One encoder of the format `cls` per (device, h, w, c, *options)."""
+    h, w, c = (int(v) for v in images.shape[1:])
+    key = (cls, images.device.index, h, w, c) + cls._key_options(c, h, w, **options)
+    enc = _encoders.get(key)
     if enc is None:
-        enc = _png_encoders[key] = PngEncoder(*key[1:], device=key[0])
+        enc = _encoders[key] = cls(*key[2:], device=key[1])
     return enc
 
 
-def _png_on_device_path(images: Any) -> bool:
+def _image_on_device_path(images: Any, channels: Sequence[int]) -> bool:
     return (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.ndim == 4
-            and 1 <= images.shape[3] <= 4 and images.shape[1] >= 1 and images.shape[2] >= 1 and images.is_contiguous())
+            and images.shape[3] in channels and images.shape[1] >= 1 and images.shape[2] >= 1 and images.is_contiguous())
 
 
-def _png_host_batch(images: Any) -> List[bytes]:
+def _image_files(cls, images: Any, encoder: str, **options: Any) -> Sequence[Any]:
+    """One file per image in the format of `cls`: from the GPU for a contiguous uint8 CUDA batch (unless `encoder="host"`), else
+    from the format's host encoder, image by image."""
+    if encoder == "auto" and _image_on_device_path(images, cls._CHANNELS):
+        return _encoder_for(cls, images, **options).encode(images.detach()).to_host()
     arr = images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
-    return [_png_host(a) for a in arr]
+    return [cls._host_encode(a, **options) for a in arr]
+
+
+def _save_image_files(cls, images: Any, paths: Sequence[str], encoder: str, **options: Any) -> None:
+    if encoder not in ("auto", "host"):
+        raise ValueError(f"encoder: expected 'auto' or 'host', got {encoder!r}")
+    assert len(images) == len(paths)
+    _write_blocks(_image_files(cls, images, encoder, **options), paths)
 
 
 def png_batch(images: Any) -> List[bytes]:
     """`images [B,H,W,C]` uint8 -> the bytes of one PNG file per image. A contiguous uint8 CUDA tensor is encoded on the GPU;
     anything else (a numpy array, a CPU tensor) by PIL on the host. The files differ in bytes and decode to the same pixels."""
-    if _png_on_device_path(images):
-        return [bytes(x) for x in _png_encoder_for(images).encode(images.detach()).to_host()]
-    return _png_host_batch(images)
+    return [bytes(x) for x in _image_files(PngEncoder, images, "auto")]
 
 
 def save_png_batch(images: Any, paths: Sequence[str], encoder: str = "auto") -> None:
     """`images [B,H,W,C]` uint8 -> one `.png` per image. A contiguous uint8 CUDA tensor is encoded on the GPU (`PngEncoder`; a
     flagged image is encoded here) and only the files cross to the host; a numpy array, a CPU tensor, a non-contiguous tensor or
     `encoder="host"` takes the host path: one copy of the pixels, PIL per image."""
-    if encoder not in ("auto", "host"):
-        raise ValueError(f"encoder: expected 'auto' or 'host', got {encoder!r}")
-    assert len(images) == len(paths)
-    if encoder == "auto" and _png_on_device_path(images):
-        blocks = _png_encoder_for(images).encode(images.detach()).to_host()
-    else:
-        blocks = _png_host_batch(images)
-    for block, path in zip(blocks, paths):
-        with open(path, "wb") as f:
-            f.write(block)
+    _save_image_files(PngEncoder, images, paths, encoder)
 
 
 def _jpeg_options(channels: int, height: int, width: int, quality: int = 75, subsampling: Optional[int] = None,
@@ -698,125 +712,59 @@ def _jpeg_host(image: np.ndarray, **options: Any) -> bytes:
     return buf.getvalue()
 
 
-class JpegData(_DeviceText):
-    """What `JpegEncoder.encode` returns: the JPEG files of `batch` images in HBM, the contract of `PngData`. A flagged item (the
-    encoder's own consistency check, or a flag the caller ORed in) is encoded on the host with PIL, which writes the same bytes."""
+class JpegEncoder(_ImageEncoder):
+    """`_ImageEncoder` for baseline JPEG, C = 1 (grey) or 3 (RGB) (`dad3d_jpeg_encode`, csrc/jpeg_encode.hip, DESIGN.md 4.20, two
+    kernels), byte-equal to `Image.fromarray(img).save(buf, "JPEG", quality=quality, subsampling=subsampling,
+    restart_marker_rows=restart_marker_rows)`. `subsampling` 0 / 1 / 2 is 4:4:4 / 4:2:2 / 4:2:0; `None` is PIL's default for the
+    mode. A restart marker per MCU row (`restart_marker_rows=1`) is what `jpeg_reader.JpegDecoder` reads in parallel. A flagged
+    item goes to PIL, which writes the same bytes."""
 
-    def __init__(self, encoder: "JpegEncoder", images: torch.Tensor, batch: int):
-        super().__init__(encoder, batch)
-        self.images = images
-
-    def _host_item(self, b: int) -> bytes:
-        e = self.formatter
-        return _jpeg_host(self.images[b].detach().cpu().numpy(), quality=e.quality, subsampling=e.subsampling,
-                          restart_marker_rows=e.restart_marker_rows)
-
-
-class JpegEncoder(_TextBuffers):
-    """A batch of uint8 images `[B,H,W,C]`, C = 1 (grey) or 3 (RGB), as baseline JPEG files made on the GPU (`dad3d_jpeg_encode`,
-    csrc/jpeg_encode.hip), byte-equal to `Image.fromarray(img).save(buf, "JPEG", quality=quality,
-    subsampling=subsampling, restart_marker_rows=restart_marker_rows)`. `subsampling` 0 / 1 / 2 is 4:4:4 / 4:2:2 / 4:2:0; `None` is
-    PIL's default for the mode. A restart marker per MCU row (`restart_marker_rows=1`) is what `jpeg_reader.JpegDecoder` reads in
-    parallel.
-
-    `reserve(batch)` allocates the device file buffer (`batch` rows of `dad3d_jpeg_max_bytes`), lengths, flags, scratch and one
-    pinned host buffer; `encode(images)` launches two kernels on the current stream with no allocation and no sync once the batch
-    fits (capturable in a graph); `JpegData.to_host()` brings the files over."""
+    _CHANNELS = (1, 3)
+    _LIMITS = "sides 1 .. 65535, at most 2^22 blocks"
 
     def __init__(self, height: int, width: int, channels: int, quality: int = 75, subsampling: Optional[int] = None,
                  restart_marker_rows: int = 0, device: Optional[int] = None):
-        self.height, self.width, self.channels = int(height), int(width), int(channels)
         self.quality, self.subsampling, self.restart_marker_rows, self.restart_interval = _jpeg_options(
-            self.channels, self.height, self.width, quality, subsampling, restart_marker_rows)
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.device = torch.cuda.current_device() if device is None else int(device)
-        self.torch_device = torch.device("cuda", self.device)
-        worst = self._lib.dad3d_jpeg_max_bytes(self.height, self.width, self.channels, self.subsampling)
-        if worst == 0:
-            raise ValueError(f"JpegEncoder: cannot encode images of {self.height} x {self.width} x {self.channels} (sides 1 .. 65535, at "
-                             "most 2^22 blocks)")
-        self.stride = (worst + 15) // 16 * 16
-        self.capacity = 0
+            int(channels), int(height), int(width), quality, subsampling, restart_marker_rows)
+        self.options = {"quality": self.quality, "subsampling": self.subsampling, "restart_marker_rows": self.restart_marker_rows}
+        super().__init__(height, width, channels, device)
 
-    def reserve(self, batch: int) -> None:
-        batch = max(int(batch), 1)
-        if batch <= self.capacity:
-            return
-        self._reserve_buffers(batch, self._lib.dad3d_jpeg_encode_scratch_bytes(batch, self.height, self.width, self.channels,
-                                                                                self.subsampling))
+    @staticmethod
+    def _key_options(channels: int, height: int, width: int, **options: Any) -> tuple:
+        return _jpeg_options(channels, height, width, **options)[:3]
 
-    def encode(self, images: torch.Tensor, extra_flags: Optional[torch.Tensor] = None) -> JpegData:
-        """`images [B,H,W,C]` -> `JpegData`. `extra_flags` (int32 [B] on the device) is ORed into the items' flags behind the
-        kernels: a non-zero entry sends that item to the host encoder."""
-        shape = (self.height, self.width, self.channels)
-        if (not isinstance(images, torch.Tensor) or images.device != self.torch_device or images.dtype != torch.uint8
-                or not images.is_contiguous() or images.ndim != 4 or tuple(images.shape[1:]) != shape):
-            raise ValueError(f"images: expected a contiguous uint8 tensor [B,{shape[0]},{shape[1]},{shape[2]}] on {self.torch_device}, got "
-                             f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))} on "
-                             f"{getattr(images, 'device', 'the host')}"
-                             + ("" if not isinstance(images, torch.Tensor) or images.is_contiguous() else " (not contiguous)"))
-        b = images.shape[0]
-        if b == 0:
-            self.reserve(1)
-            return JpegData(self, images, 0)
-        self.reserve(b)
-        stream = torch.cuda.current_stream(self.torch_device).cuda_stream
-        _lib.check(self._lib.dad3d_jpeg_encode(images.data_ptr(), b, *shape, self.quality, self.subsampling, self.restart_interval,
-                                               self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
-                                               self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), self.device,
-                                               stream))
-        if extra_flags is not None:
-            self._flags[:b].bitwise_or_(extra_flags)
-        return JpegData(self, images, b)
+    def _max_bytes(self) -> int:
+        return self._lib.dad3d_jpeg_max_bytes(self.height, self.width, self.channels, self.subsampling)
 
+    def _scratch_bytes_for(self, batch: int) -> int:
+        return self._lib.dad3d_jpeg_encode_scratch_bytes(batch, self.height, self.width, self.channels, self.subsampling)
 
-_jpeg_encoders: Dict[Tuple[int, int, int, int, int, int, int], JpegEncoder] = {}
+    def _launch(self, images: torch.Tensor, b: int, stream: int) -> int:
+        return self._lib.dad3d_jpeg_encode(images.data_ptr(), b, self.height, self.width, self.channels, self.quality, self.subsampling,
+                                           self.restart_interval, self._text.data_ptr(), self._text.stride(0), self._lengths.data_ptr(),
+                                           self._flags.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), self.device, stream)
+
+    @staticmethod
+    def _host_encode(image: np.ndarray, **options: Any) -> bytes:
+        return _jpeg_host(image, **options)
 
 
 def _jpeg_encoder_for(images: torch.Tensor, **options: Any) -> JpegEncoder:
-    h, w, c = (int(v) for v in images.shape[1:])
-    quality, subsampling, rows, _ = _jpeg_options(c, h, w, **options)
-    key = (images.device.index, h, w, c, quality, subsampling, rows)
-    enc = _jpeg_encoders.get(key)
-    if enc is None:
-        enc = _jpeg_encoders[key] = JpegEncoder(h, w, c, quality, subsampling, rows, device=key[0])
-    return enc
-
-
-def _jpeg_on_device_path(images: Any) -> bool:
-    return (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.ndim == 4
-            and images.shape[3] in (1, 3) and images.shape[1] >= 1 and images.shape[2] >= 1 and images.is_contiguous())
-
-
-def _jpeg_host_batch(images: Any, **options: Any) -> List[bytes]:
-    arr = images.detach().cpu().numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
-    return [_jpeg_host(a, **options) for a in arr]
+    return _encoder_for(JpegEncoder, images, **options)
 
 
 def jpeg_batch(images: Any, **options: Any) -> List[bytes]:
     """`images [B,H,W,C]` uint8, C = 1 or 3 -> the bytes of one baseline JPEG file per image; `quality`, `subsampling` and
     `restart_marker_rows` as `JpegEncoder` takes them. A contiguous uint8 CUDA tensor is encoded on the GPU; anything else (a numpy
     array, a CPU tensor) by PIL on the host. Both write the same bytes."""
-    if _jpeg_on_device_path(images):
-        return [bytes(x) for x in _jpeg_encoder_for(images, **options).encode(images.detach()).to_host()]
-    return _jpeg_host_batch(images, **options)
+    return [bytes(x) for x in _image_files(JpegEncoder, images, "auto", **options)]
 
 
 def save_jpeg_batch(images: Any, paths: Sequence[str], encoder: str = "auto", **options: Any) -> None:
     """`images [B,H,W,C]` uint8 -> one `.jpg` per image. A contiguous uint8 CUDA tensor with C in {1, 3} is encoded on the GPU
     (`JpegEncoder`; a flagged image is encoded here) and only the files cross to the host; a numpy array, a CPU tensor, a
     non-contiguous tensor or `encoder="host"` takes the host path: one copy of the pixels, PIL per image. The bytes are the same."""
-    if encoder not in ("auto", "host"):
-        raise ValueError(f"encoder: expected 'auto' or 'host', got {encoder!r}")
-    assert len(images) == len(paths)
-    if encoder == "auto" and _jpeg_on_device_path(images):
-        blocks = _jpeg_encoder_for(images, **options).encode(images.detach()).to_host()
-    else:
-        blocks = _jpeg_host_batch(images, **options)
-    for block, path in zip(blocks, paths):
-        with open(path, "wb") as f:
-            f.write(block)
+    _save_image_files(JpegEncoder, images, paths, encoder, **options)
 
 
 class _ZlibData(_DeviceText):
@@ -834,19 +782,19 @@ class _ZlibCompressor(_TextBuffers):
     """The deflate of `PngEncoder` on plain byte rows `[B,n]`: one zlib stream per row (`dad3d_zlib_compress`)."""
 
     def __init__(self, n: int, device: int):
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.device, self.torch_device, self.n = int(device), torch.device("cuda", int(device)), int(n)
+        super().__init__(device)
+        self.n = int(n)
         worst = self._lib.dad3d_zlib_max_bytes(self.n)
         if worst == 0:
             raise ValueError(f"zlib_compress_batch: rows of {self.n} bytes (1 .. 2^31 - 1)")
         self.stride = (worst + 15) // 16 * 16
-        self.capacity = 0
+
+    def _scratch_bytes_for(self, batch: int) -> int:
+        return self._lib.dad3d_zlib_scratch_bytes(batch, self.n)
 
     def compress(self, data: torch.Tensor) -> _ZlibData:
         b = data.shape[0]
-        if b > self.capacity:
-            self._reserve_buffers(b, self._lib.dad3d_zlib_scratch_bytes(b, self.n))
+        self.reserve(b)
         stream = torch.cuda.current_stream(self.torch_device).cuda_stream
         _lib.check(self._lib.dad3d_zlib_compress(data.data_ptr(), b, self.n, self._text.data_ptr(), self._text.stride(0),
                                                  self._lengths.data_ptr(), self._flags.data_ptr(), self._scratch.data_ptr(),

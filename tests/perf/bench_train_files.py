@@ -153,7 +153,7 @@ def bench(b, iters, st, root):
     torch.cuda.synchronize()
     assert not status.any().item(), status
     pending = decoder._launch_packed(up["png_files"], png_table[:, 0], png_table[:, 1], 3, heads=heads)
-    full_images = pending.finish(*pending.flags_on_host()).tensors()
+    full_images = pending.finish(*pending.words_on_host()).tensors()
     descs = up["crop_descs"].clone()
     descs[:, 0] += torch.tensor([t.data_ptr() for t in full_images], dtype=torch.int64).to(dev)
 

@@ -206,20 +206,32 @@ def test_decode_packed():
     assert np.array_equal(neighbours.tensors()[0].cpu().numpy(), pil_array(files[0], 1))
 
 
-def test_decode_packed_contract_errors_raise_before_any_launch():
-    f = jpeg(picture((8, 8, 3), 4), quality=90)
+def png_file():
+    buf = io.BytesIO()
+    Image.fromarray(picture((8, 8, 3), 4)).save(buf, "PNG")
+    return buf.getvalue()
+
+
+@pytest.mark.parametrize("kind", ["jpeg", "png"])
+def test_decode_packed_contract_errors_raise_before_any_launch(kind):
+    from dad_3dheads_amd import png_reader
+
+    f, decoder, no_mode = {"jpeg": (jpeg(picture((8, 8, 3), 4), quality=90), jpeg_reader.JpegDecoder(0), 2),
+                           "png": (png_file(), png_reader.PngDecoder(0), 5)}[kind]
     buffer = torch.zeros(align(len(f)) + 16, dtype=torch.uint8)
-    decoder = jpeg_reader.JpegDecoder(0)
+    buffer[:len(f)] = torch.from_numpy(np.frombuffer(f, dtype=np.uint8).copy())
     for bad in (lambda: decoder.decode_packed(buffer, [8], [len(f)]),  # an offset that is no multiple of 16
                 lambda: decoder.decode_packed(buffer, [16], [len(f) + 16]),  # past the end
                 lambda: decoder.decode_packed(buffer, [0, 16], [len(f)]),  # offsets and sizes of different lengths
                 lambda: decoder.decode_packed(buffer, [-16], [len(f)]),
                 lambda: decoder.decode_packed(buffer.to(torch.int8), [0], [len(f)]),
                 lambda: decoder.decode_packed(buffer.view(2, -1), [0], [len(f)]),
-                lambda: decoder.decode_packed(buffer, [0], [len(f)], channels=2),
-                lambda: decoder.decode_packed(buffer, [0], [len(f)], heads=[])):
+                lambda: decoder.decode_packed(buffer, [0], [len(f)], channels=no_mode),
+                lambda: decoder.decode_packed(buffer, [0], [len(f)], heads=[]),
+                lambda: decoder.decode_packed(buffer.numpy(), [0], [len(f)])):  # not a tensor
         with pytest.raises(ValueError):
             bad()
+    assert decoder.decode_packed(buffer, [0], [len(f)]).flags.tolist() == [0]  # and the call the bad ones are one step away from
 
 
 def test_load_jpeg_batch():
