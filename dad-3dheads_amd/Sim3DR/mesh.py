@@ -6,6 +6,7 @@ All methods take a leading batch dimension; nothing is copied to the host.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -46,10 +47,11 @@ class Mesh:
         h = C.c_void_p()
         _lib.check(self._lib.dad3d_mesh_create(tri.ctypes.data, self.ntri, self.nver, self.device_index, C.byref(h)))
         self._handle = h
+        self._owner_pid = os.getpid()
 
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
-        if h:
+        if h and getattr(self, "_owner_pid", None) == os.getpid():  # a forked child does not own the device state (see FLAMELayer.__del__)
             try:
                 self._lib.dad3d_mesh_destroy(h)
             except Exception:

@@ -166,6 +166,7 @@ class FLAMELayer(torch.nn.Module):
         handle = C.c_void_p()
         _lib.check(lib.dad3d_flame_create(C.byref(model_c), C.byref(consts_c), float(image_size), self.device_index, C.byref(handle)))
         self._handle = handle
+        self._owner_pid = os.getpid()
         self._lib = lib
         self.n_params = lib.dad3d_flame_num_params(handle)
         self.n_landmarks = 0
@@ -175,7 +176,7 @@ class FLAMELayer(torch.nn.Module):
         # plain dict access: nn.Module.__setattr__ is not safe to call while the interpreter shuts down
         h = self.__dict__.get("_handle")
         self.__dict__["_handle"] = None
-        if h:
+        if h and self.__dict__.get("_owner_pid") == os.getpid():  # a forked child (a DataLoader worker whose collector meets the parent's garbage) does not own the device state: it frees nothing
             try:
                 self._lib.dad3d_flame_destroy(h)
             except Exception:

@@ -88,6 +88,7 @@ class RcclAllGather:
             raise RuntimeError("RcclAllGather needs a GPU")
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.comm = C.c_void_p()
+        self._owner_pid = os.getpid()
         # Every rank must enter ncclCommInitRank or none: a rank that cannot even load the library would leave the others
         # waiting in it for ever. Agree on that first, through the group that exists (object collectives: any backend).
         try:
@@ -202,6 +203,8 @@ class RcclAllGather:
 
     def __del__(self):
         if sys.is_finalizing():  # HIP / RCCL may already be gone: a native crash there is not an exception
+            return
+        if getattr(self, "_owner_pid", None) != os.getpid():  # a forked child does not own the communicator (see FLAMELayer.__del__)
             return
         try:
             self.destroy()

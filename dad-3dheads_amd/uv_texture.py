@@ -104,13 +104,14 @@ class UVMap:
         _lib.check(self._lib.dad3d_uvmap_create(f.ctypes.data, len(f), int(n_verts), texel.ctypes.data, verts.ctypes.data,
                                                 bary.ctypes.data, len(texel), s, self.device, C.byref(handle)))
         self._handle = handle
+        self._owner_pid = os.getpid()
         self.size = s
         self.n_verts = int(n_verts)
 
     def __del__(self):
         h = self.__dict__.get("_handle")
         self.__dict__["_handle"] = None
-        if h:
+        if h and self.__dict__.get("_owner_pid") == os.getpid():  # a forked child does not own the device state (see FLAMELayer.__del__)
             try:
                 self._lib.dad3d_uvmap_destroy(h)
             except Exception:

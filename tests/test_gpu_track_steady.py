@@ -11,35 +11,17 @@ import pytest
 import torch
 
 from dad_3dheads_amd import _lib, boxes, steady
+from guarded import SENTINEL_F, Guarded
 
 pytestmark = pytest.mark.gpu
 
 P, DUP, EMPTY = _lib.TRACK_FLAG_PREVIOUS, _lib.TRACK_FLAG_DUPLICATE, _lib.BOX_FLAG_EMPTY
 F, NAN, INF = np.float32, float("nan"), float("inf")
-GUARD = 8
-SENTINEL_F, SENTINEL_I = F(-7777.0), -7777
 CAP = _lib.TRACK_MAX_SLOTS
 
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-class Guarded:
-    """A device buffer of 32-bit words between guard words, all filled with a sentinel: `body` is the part a kernel may write."""
-
-    def __init__(self, words, dtype):
-        self.sentinel = SENTINEL_F if dtype == torch.float32 else SENTINEL_I
-        self.all = torch.full((words + 2 * GUARD,), float(self.sentinel) if dtype == torch.float32 else self.sentinel, dtype=dtype, device="cuda")
-        self.body = self.all[GUARD:GUARD + words]
-
-    def ptr(self):
-        return self.body.data_ptr()
-
-    def host(self):
-        got = self.all.cpu().numpy()
-        assert (got[:GUARD] == self.sentinel).all() and (got[-GUARD:] == self.sentinel).all(), "a guard word was written"
-        return got[GUARD:-GUARD]
 
 
 # ---- 1. the filter kernel ------------------------------------------------------------------------------------------------------

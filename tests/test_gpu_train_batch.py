@@ -68,11 +68,16 @@ def test_batch_against_golden_and_oracle(z, st, name, tmp_path):
         assert np.abs(sub_px[i] - z[p + "subset_px"][i]).max() <= tol, (name, i)
         assert np.abs(full[i, ::int(z["full_stride"])] - z[p + "full"][i]).max() <= tol, (name, i)
         assert np.abs(t[TL][i].cpu().numpy() - z[p + "landmarks"][i]).max() <= tol / 256, (name, i)
-    # presence: equal, except points within 1e-3 px of a crop edge (the golden's recorded margin)
+    # ... and every geometric target equals the restatement of the kernel's fixed order to the bit (tests/test_gpu_gt_keypoints.py
+    # holds the entry itself to it; here it is the builder's tables, uploads and frame rows that are held)
     pres = t[TP].cpu().numpy()
-    edge = z[p + "margin"] <= 1e-3
-    assert np.array_equal(pres[~edge], z[p + "presence"][~edge])
-    assert edge.sum() <= 12, edge.sum()
+    kw = dict(zip(("corners", "weights"), rs.lmk68_tables(st))) if str(z[p + "subset"]) == "68" else {"index": st["lmk_445"]}
+    for i, it in enumerate(items):
+        want = rs.chain(it["vertices"], it["model_view"], it["projection"], (it["image_shape"][0], *it["bbox"]), 256, str(z[p + "mode"]), **kw)
+        for what, got, ref in zip(("full", "subset_px", "landmarks", "presence"), (full[i], sub_px[i], t[TL][i].cpu().numpy(), pres[i]), want):
+            assert got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got.view(np.uint8), ref.view(np.uint8)), (name, i, what)
+    # presence: the golden's on every point, the ones on a crop edge included
+    assert np.array_equal(pres, z[p + "presence"])
     # heatmaps: byte-equal to the restated reference coder (tests/train_objective_restatement.encode) on the kernel's own
     # subset and presence ...
     import train_objective_restatement as tors
@@ -86,26 +91,48 @@ def test_batch_against_golden_and_oracle(z, st, name, tmp_path):
     assert builder.coder.num_classes == heat.shape[1]
 
 
+def _oracle_image(img, mode, mean, std):
+    """The preprocessing oracle's network input of one crop, as test_batch_against_golden_and_oracle states it."""
+    if mode == "resize":
+        small = pp.resize_linear_u8(img, 256, 256)
+        m = np.array(mean, np.float32) * np.float32(255)
+        den = np.reciprocal(np.array(std, np.float32) * np.float32(255), dtype=np.float32)
+        return np.transpose((small.astype(np.float32) - m) * den, (2, 0, 1))
+    return pp.transform(img, 256, mean, std)
+
+
 def test_double_transform_bit_equal(st):
     """Identity matrices, H = 0, crop corner 0: the kernel's crop-pixel points are the fed points (x, -y) exactly, so the
-    float64 keypoint transform meets the restatement bit for bit, for both modes and odd crop shapes."""
+    float64 keypoint transform meets the restatement bit for bit, for both modes and odd crop shapes; so do the 68 landmarks, their
+    normalised form and their presence, and the images of these shapes are the preprocessing oracle's."""
     rng = np.random.default_rng(5)
+    kw = dict(zip(("corners", "weights"), rs.lmk68_tables(st)))
     for mode in ("longest_max_size", "resize"):
         items = []
         for i, (h, w) in enumerate([(1, 300), (255, 257), (256, 256), (611, 97), (3, 1)]):
             xy = (rng.uniform(-0.2, 1.2, (rs.N_VERTS, 2)) * (w, h)).astype(np.float32)
             verts = np.stack([xy[:, 0], -xy[:, 1], rng.uniform(-1, 1, rs.N_VERTS).astype(np.float32)], -1).astype(np.float32)
-            items.append({"image": np.zeros((h, w, 3), np.uint8), "bbox": np.array([0, 0, w, h], np.int32),
+            items.append({"image": rs.image(40 + i, h, w), "bbox": np.array([0, 0, w, h], np.int32),
                           "image_shape": np.array([0, w, 3]), "vertices": verts, "model_view": np.eye(4, dtype=np.float32),
                           "projection": np.eye(4, dtype=np.float32), "SAMPLE_INDEX_KEY": i, "IMAGE_FILENAME_KEY": str(i)})
         cfg = {"img_size": 256, "stride": 4, "num_classes": 68, "keypoints": {"2d_subset_name": "multipie_keypoints"},
                "transform": {"resize_mode": mode}}
-        _, t = FlameBatchBuilder(cfg, 0)(RawBatchCollate(256, mode)(items))
-        full = t[TF].cpu().numpy()
+        builder = FlameBatchBuilder(cfg, 0)
+        images, t = builder(RawBatchCollate(256, mode)(items))
+        mean, std = NORMALIZE[builder.normalize]
+        full, sub_px, norm, pres = t[TF].cpu().numpy(), builder.last_subset_px.cpu().numpy(), t[TL].cpu().numpy(), t[TP].cpu().numpy()
+        present = 0
         for i, it in enumerate(items):
             h, w = it["image"].shape[:2]
+            assert it["image"].any() and np.array_equal(images[i].cpu().numpy(), _oracle_image(it["image"], mode, mean, std)), (mode, i)
             ref = rs.albu_keypoints(np.stack([it["vertices"][:, 0], -it["vertices"][:, 1]], -1), h, w, 256, mode)
             assert np.array_equal(full[i].view(np.uint32), ref.view(np.uint32)), (mode, i)
+            want = rs.chain(it["vertices"], it["model_view"], it["projection"], (0, 0, 0, w, h), 256, mode, **kw)
+            assert np.array_equal(want[0].view(np.uint32), ref.view(np.uint32))
+            for what, got, r in zip(("subset_px", "subset_norm", "presence"), (sub_px[i], norm[i], pres[i]), want[1:]):
+                assert got.dtype == r.dtype and got.shape == r.shape and np.array_equal(got.view(np.uint8), r.view(np.uint8)), (mode, i, what)
+            present += int(pres[i].sum())
+        assert 0 < present < pres.size  # the landmarks fall on both sides of the crops' edges
 
 
 def test_batch_of_one_equals_batch_of_64(z, st, tmp_path):

@@ -6,6 +6,8 @@ the seeded scenes the golden, the tests and the benchmark share. Never reads the
   presence       0 < x < w and 0 < y < h in crop pixels (:167-170)
   albu_keypoints albumentations 1.0.0 LongestMaxSize + PadIfNeeded / Resize on "xy" keypoints, float64 as under the pinned
                  numpy 1.22 (np.float32 * Python float is float64 there), rounded to fp32 once (:189-190)
+  chain          the whole of gt_keypoints_kernel in its fixed order; a subset id outside [0, nver) gives a NaN row, absent
+  chain64        the same chain in float64 with no fp32 rounding: the plain high-precision reference
 """
 from __future__ import annotations
 
@@ -31,8 +33,17 @@ def world(vertices: np.ndarray, model_view: np.ndarray) -> np.ndarray:
     return _mat_points(model_view, np.concatenate([v, np.ones_like(v[:, :1])], 1))
 
 
+def rows(world_h: np.ndarray, ids) -> np.ndarray:
+    """world_h[ids], with a NaN row for every id outside [0, nver): the kernel reads nothing there (include/dad3d.h)."""
+    ids = np.asarray(ids, np.int64)
+    ok = (ids >= 0) & (ids < len(world_h))
+    out = np.full(ids.shape + (4,), np.nan, world_h.dtype)
+    out[ok] = world_h[ids[ok]]
+    return out
+
+
 def landmarks68(world_h: np.ndarray, corners: np.ndarray, weights: np.ndarray) -> np.ndarray:
-    tri = world_h[:, :3][corners]  # [68,3 corners,3]
+    tri = rows(world_h, corners)[..., :3]  # [68,3 corners,3]
     w = weights.astype(np.float32)
     xyz = (tri[:, 0] * w[:, 0, None] + tri[:, 1] * w[:, 1, None]) + tri[:, 2] * w[:, 2, None]
     return np.concatenate([xyz, np.ones_like(xyz[:, :1])], 1).astype(np.float32)
@@ -60,14 +71,45 @@ def albu_keypoints(xy: np.ndarray, h: int, w: int, size: int, mode: str) -> np.n
 
 
 def chain(vertices, model_view, projection, frame, size, mode, index=None, corners=None, weights=None):
-    """One item: frame = (image height, crop x, y, w, h) -> (full [N,2], subset_px [K,2], subset_norm [K,2], presence [K])."""
+    """One item: frame = (image height, crop x, y, w, h) -> (full [N,2], subset_px [K,2], subset_norm [K,2], presence [K]).
+    A subset id outside [0, N) gives a NaN row that is absent; with neither index nor corners the subset is empty."""
     height, cx, cy, w, h = (int(v) for v in frame[:5])
     wh = world(vertices, model_view)
-    sub = landmarks68(wh, corners, weights) if index is None else wh[np.asarray(index)]
-    xy_sub, xy_full = project(sub, projection, height, cx, cy), project(wh, projection, height, cx, cy)
-    pres = presence(xy_sub, w, h)
-    sub_px = albu_keypoints(xy_sub, h, w, size, mode)
-    return albu_keypoints(xy_full, h, w, size, mode), sub_px, (sub_px / np.float32(size)).astype(np.float32), pres
+    if index is None and corners is None:
+        sub = wh[:0]
+    else:
+        sub = landmarks68(wh, corners, weights) if index is None else rows(wh, index)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        xy_sub, xy_full = project(sub, projection, height, cx, cy), project(wh, projection, height, cx, cy)
+        pres = presence(xy_sub, w, h)
+        sub_px = albu_keypoints(xy_sub, h, w, size, mode)
+        return albu_keypoints(xy_full, h, w, size, mode), sub_px, (sub_px / np.float32(size)).astype(np.float32), pres
+
+
+def chain64(vertices, model_view, projection, frame, size, mode, index=None, corners=None, weights=None):
+    """`chain` in float64 throughout, nothing rounded to fp32 on the way: the plain high-precision reference. Float64 outputs."""
+    height, cx, cy, w, h = (int(v) for v in frame[:5])
+    v = np.asarray(vertices, np.float64)
+    wh = np.concatenate([v, np.ones_like(v[:, :1])], 1) @ np.asarray(model_view, np.float64).T
+    if index is None and corners is None:
+        sub = wh[:0]
+    elif index is None:
+        xyz = (rows(wh, corners)[..., :3] * np.asarray(weights, np.float64)[:, :, None]).sum(1)
+        sub = np.concatenate([xyz, np.ones_like(xyz[:, :1])], 1)
+    else:
+        sub = rows(wh, index)
+    out = []
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for pts in (wh, sub):
+            c = pts @ np.asarray(projection, np.float64).T
+            xy = np.stack([c[:, 0] / c[:, 3] - cx, (height - c[:, 1] / c[:, 3]) - cy], -1)
+            if mode == "longest_max_size":
+                _, _, top, left = longest_max_size(h, w, size)
+                out.append((xy, xy * (size / max(h, w)) + (left, top)))
+            else:
+                out.append((xy, xy * (size / w, size / h)))
+        (_, full), (xy_sub, sub_px) = out
+        return full, sub_px, sub_px / size, presence(xy_sub, w, h)
 
 
 # ---- seeded scenes ------------------------------------------------------------------------------------------------------
