@@ -264,6 +264,37 @@ class Mesh:
             _lib.TEX_INDEX_REFERENCE if indexing == "reference" else _lib.TEX_INDEX_CORNER, self._stream()))
         return img
 
+    def render_texture_frames(self, frames, vertices: Tensor, textures: Tensor, image_index, mapping: str = "bilinear",
+                              indexing: str = "corner") -> Tensor:
+        """Textured heads through the frames chain: per frame, in ascending head order, `frame = (unsigned char)
+        _render_texture_core(image=float(frame), vertices[k], .., textures[k], a fresh depth buffer at -1e8)` -- a later head paints
+        over an earlier one wherever it covers a pixel, an uncovered pixel is not written.
+
+        frames, vertices, image_index and the returned flags as for `rasterize_frames`. textures `[N,th,tw,tc]` (head k samples
+        texture k) or one shared `[th,tw,tc]`, float32 or uint8, tc >= 3 (the first three channels are used). mapping "bilinear" |
+        "nearest", indexing "corner" | "reference" as for `render_texture`. The two-pixel border band of `render_texture` is taken on
+        each frame's own size (reference behaviour, kept; it only matters for a head whose triangle boxes reach the frame's outer
+        two pixels). No `reverse`. Async on the current stream, no host wait."""
+        fr, v, idx, flags = self._frames_args(frames, vertices, image_index)
+        if mapping not in ("bilinear", "nearest"):
+            raise ValueError(f"mapping: 'bilinear' or 'nearest', got {mapping!r}")
+        if indexing not in ("corner", "reference"):
+            raise ValueError(f"indexing: 'corner' or 'reference', got {indexing!r}")
+        dtypes = {torch.float32: _lib.DTYPE_F32, torch.uint8: _lib.DTYPE_U8}
+        tex = textures
+        if not isinstance(tex, Tensor) or tex.dtype not in dtypes or tex.ndim not in (3, 4) or not tex.is_contiguous() or tex.device != self.torch_device:
+            raise ValueError(f"textures: expected a contiguous float32 or uint8 tensor with 3 or 4 dims on {self.torch_device}, got "
+                             f"{getattr(tex, 'dtype', type(tex))} {tuple(getattr(tex, 'shape', ()))} on {getattr(tex, 'device', None)}")
+        if tex.ndim == 4 and tex.shape[0] != v.shape[0]:
+            raise ValueError(f"textures: {tex.shape[0]} textures for {v.shape[0]} heads")
+        th, tw, tc = tex.shape[-3:]
+        _lib.check(self._lib.dad3d_mesh_render_texture_frames(
+            self._handle, fr.device.data_ptr(), fr.host.ctypes.data, len(fr), v.data_ptr(), tex.data_ptr(), dtypes[tex.dtype],
+            int(tex.ndim == 4), th, tw, tc, 0 if mapping == "nearest" else 1,
+            _lib.TEX_INDEX_REFERENCE if indexing == "reference" else _lib.TEX_INDEX_CORNER, idx.data_ptr(), v.shape[0], flags.data_ptr(),
+            self._stream()))
+        return flags
+
     # -- lighting ----------------------------------------------------------------------------------
     def phong_light(self, vertices: Tensor, normals: Optional[Tensor] = None, ambient: float = 0.3, directional: float = 0.6,
                     specular: float = 0.1, specular_exp: float = 5, color_ambient: Sequence[float] = (1, 1, 1),

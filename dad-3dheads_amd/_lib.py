@@ -46,6 +46,7 @@ TRACK_FLAG_PREVIOUS, TRACK_FLAG_RANGE, TRACK_FLAG_NONFINITE, TRACK_FLAG_SMALL, T
 TRACK_FLAG_DUPLICATE, TRACK_MAX_SLOTS = 0x20, 1024
 FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0x2, 4096, 65535
 RENDER_REVERSE, RENDER_CLEAR = 1, 2
+BAKE_FLAG_INDEX = 0x1
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -133,6 +134,7 @@ SIGNATURES = {
     "dad3d_mesh_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(LightC), _I, _P]),
     "dad3d_mesh_rasterize_frames": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "dad3d_mesh_render_frames": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.POINTER(LightC), _I, _P, _P]),
+    "dad3d_mesh_render_texture_frames": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "dad3d_mesh_frames_scratch_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
     "dad3d_mesh_normal_plan": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "dad3d_mesh_debug_trace": (_I, [_P, _P]),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "dad3d_uvmap_size": (_I, [_P]),
     "dad3d_uvmap_vertex_normals": (_I, [_P, _P, _P, _I, _P]),
     "dad3d_uvmap_bake": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dad3d_uvmap_bake_frames": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
     "dad3d_obj_format_scratch_bytes": (C.c_size_t, [_I, _I]),
     "dad3d_obj_format_vertices": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
     "dad3d_json_format_scratch_bytes": (C.c_size_t, [_I, _I]),

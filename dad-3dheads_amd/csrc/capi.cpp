@@ -1208,6 +1208,36 @@ dad3d_status dad3d_mesh_render_frames(dad3d_mesh* m, const int64_t* frames, cons
                                    render_flags & DAD3D_RENDER_REVERSE, flags, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_mesh_render_texture_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames, const float* vertices,
+                                              const void* texture, int texture_dtype, int texture_batched, int tex_h, int tex_w, int tex_c,
+                                              int mapping_type, int indexing, const int32_t* image_index, int n_heads, int32_t* flags, void* stream) {
+    const char* who = "dad3d_mesh_render_texture_frames";
+    // the scalar arguments and the host table first: a bad one is refused before the handle is looked at or any device work starts
+    DAD3D_REQUIRE(texture_dtype == DAD3D_DTYPE_F32 || texture_dtype == DAD3D_DTYPE_U8, "%s: the texture is float32 (DAD3D_DTYPE_F32) or uint8 (DAD3D_DTYPE_U8)", who);
+    DAD3D_REQUIRE(tex_h >= 1 && tex_w >= 1 && tex_c >= 1 && (size_t)tex_h * tex_w * tex_c < (1ull << 31), "%s: texture of %d x %d x %d", who, tex_h, tex_w, tex_c);
+    DAD3D_REQUIRE(tex_c >= 3, "%s: a frame has three channels, tex_c = %d", who, tex_c);
+    DAD3D_REQUIRE(indexing == DAD3D_TEX_INDEX_CORNER || indexing == DAD3D_TEX_INDEX_REFERENCE, "%s: unknown indexing mode %d", who, indexing);
+    DAD3D_REQUIRE(n_frames >= 0 && n_heads >= 0, "%s: bad argument", who);
+    DAD3D_REQUIRE(n_frames <= DAD3D_FRAME_MAX_COUNT && n_heads <= DAD3D_FRAME_MAX_COUNT, "%s: %d frames and %d heads, at most %d each", who,
+                  n_frames, n_heads, DAD3D_FRAME_MAX_COUNT);
+    int total_tiles = 0;
+    if (n_frames > 0 && n_heads > 0 && frames_host)
+        if (dad3d_status st = frames_check_shapes(who, frames_host, n_frames, &total_tiles)) return st;
+    DAD3D_REQUIRE(m, "%s: null handle", who);
+    if (dad3d_status st = frames_arguments(who, m, frames, frames_host, n_frames, vertices, vertices, image_index, n_heads, flags, &total_tiles)) return st;
+    if (total_tiles == 0) return DAD3D_OK;  // no frames or no heads
+    if (m->ntri > 0) {
+        DAD3D_REQUIRE(texture, "%s: null buffer", who);
+        DAD3D_REQUIRE(m->d_tex_tri[DAD3D_TEX_INDEX_CORNER], "%s: no texture coordinates attached (dad3d_mesh_set_texcoords)", who);
+        DAD3D_REQUIRE(m->d_tex_tri[indexing], "%s: reference indexing needs tex_coords rows of 3 floats, one for every vertex a triangle names", who);
+    }
+    DeviceGuard guard(m->device);
+    if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
+    return launch_render_texture_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, m->d_tex_tri[indexing], texture,
+                                        texture_dtype == DAD3D_DTYPE_U8, texture_batched ? (size_t)tex_h * tex_w * tex_c : 0, tex_h, tex_w, tex_c,
+                                        mapping_type == 0, image_index, n_heads, flags, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_mesh_frames_scratch_bytes(dad3d_mesh* m, size_t* bytes) {
     DAD3D_REQUIRE(m && bytes, "dad3d_mesh_frames_scratch_bytes: bad argument");
     *bytes = m->frames_bytes;
@@ -2189,6 +2219,34 @@ dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* ver
     UvBakeArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, images, hw, texture,
                  batch, m->nver, m->size, h, w, kUvBakeChunk};
     return launch_uv_bake(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices, const double* normals,
+                                     const int64_t* frames, const int64_t* frames_host, int n_frames, const int32_t* image_index, int n_heads,
+                                     int32_t* flags, void* stream) {
+    const char* who = "dad3d_uvmap_bake_frames";
+    // the scalars and the host table first: a bad one is refused before the handle is looked at or any device work starts
+    DAD3D_REQUIRE(n_frames >= 0 && n_heads >= 0, "%s: negative count (%d frames, %d heads)", who, n_frames, n_heads);
+    DAD3D_REQUIRE(n_heads <= 65535, "%s: %d heads, beyond the launch grid of 65535", who, n_heads);
+    DAD3D_REQUIRE(n_frames == 0 || frames_host, "%s: null host frame table", who);
+    // the shapes as frames_check_shapes reads them, without the raster chain's tile limits: nothing here works in tiles
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t addr = frames_host[4 * (size_t)f], h = frames_host[4 * (size_t)f + 1], w = frames_host[4 * (size_t)f + 2],
+                      stride = frames_host[4 * (size_t)f + 3];
+        DAD3D_REQUIRE(addr != 0, "%s: frame %d has no address", who, f);
+        DAD3D_REQUIRE(h >= 1 && w >= 1 && h <= INT32_MAX && w <= INT32_MAX, "%s: frame %d is %lld x %lld pixels", who, f, (long long)h, (long long)w);
+        DAD3D_REQUIRE(stride >= 3 * w, "%s: frame %d has a row stride of %lld bytes for %lld pixels of 3 bytes", who, f, (long long)stride,
+                      (long long)w);
+    }
+    DAD3D_REQUIRE(m, "%s: null handle", who);
+    if (n_heads == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(texture && image_index && flags && ((vertices && normals) || m->n_cand == 0), "%s: null buffer", who);
+    DAD3D_REQUIRE(n_frames == 0 || frames, "%s: null device frame table", who);
+    DeviceGuard guard(m->device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", m->device);
+    UvBakeFramesArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, reinterpret_cast<const long long*>(frames), image_index,
+                       texture, score, flags, n_heads, n_frames, m->nver, m->size};
+    return launch_uv_bake_frames(a, static_cast<hipStream_t>(stream));
 }
 
 static dad3d_status overlay_checked(const char* who, const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points,

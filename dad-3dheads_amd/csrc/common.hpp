@@ -342,6 +342,12 @@ dad3d_status frames_check_shapes(const char* who, const int64_t* frames_host, in
 size_t frames_scratch_bytes(int ntri, int n_frames, int n_heads, int total_tiles);
 dad3d_status launch_rasterize_frames(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles, const float* vertices,
                                      const float* colors, const int32_t* image_index, int n_heads, int reverse, int32_t* flags, hipStream_t s);
+// Textured heads into frames (sim3dr_frames_texture.hip): the same lists, then a tile kernel with _render_texture_core's pixel test and
+// resolve. tex_tri as for launch_render_texture; tex_head_stride = elements between two heads' textures, 0 for one shared texture.
+dad3d_status launch_render_texture_frames(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles,
+                                          const float* vertices, const float4* tex_tri, const void* texture, int texture_u8, size_t tex_head_stride,
+                                          int tex_h, int tex_w, int tex_c, int nearest, const int32_t* image_index, int n_heads, int32_t* flags,
+                                          hipStream_t s);
 
 // matrix projection (flame_dataset.py:115-141): frame = [B][3] (image height, crop x, crop y)
 dad3d_status launch_project_vertices(const float* vertices, const float* model_view, const float* projection,
@@ -402,29 +408,7 @@ struct EvalZ5Args {
 dad3d_status launch_eval_nearest(const EvalNearestArgs& a, hipStream_t s);
 dad3d_status launch_eval_z5(const EvalZ5Args& a, hipStream_t s);
 
-// the reference demo's UV-texture bake (uv_texture.hip), float64 like its NumPy
-struct UvNormalArgs {
-    const int* adj_ptr;   // [V+1] CSR rows: the faces of a vertex, ascending face index, each face once
-    const int4* adj;      // [adj_ptr[V]] {corner 0, corner 1, corner 2, how often the face names the vertex}
-    const float* vertices;  // [B,V,3]
-    double* normals;        // [B,V,3]
-    int batch, n_verts;
-};
-struct UvBakeArgs {
-    const int* texel_ptr;     // [S*S+1] CSR rows: the candidates of a texel, DESCENDING candidate index
-    const int* cand_verts;    // [n,3] in texel-list order
-    const double* cand_bary;  // [n,3] in texel-list order
-    const float* vertices;    // [B,V,3]
-    const double* normals;    // [B,V,3]
-    const uint8_t* images;    // [B,h,w,3]
-    const int* hw;            // [B,2] per-item (height, width) inside the padded h x w, or null
-    uint8_t* texture;         // [B,S,S,3], every byte written
-    int batch, n_verts, size, h, w, chunk;
-};
-constexpr int kUvBakeChunk = 8;  // images per bake workgroup: the table is read once per chunk
-int uv_bake_grid_y(int batch, int chunk);
-dad3d_status launch_uv_vertex_normals(const UvNormalArgs& a, hipStream_t s);
-dad3d_status launch_uv_bake(const UvBakeArgs& a, hipStream_t s);
+// the UV-texture bake (uv_texture.hip, uv_texture_frames.hip): uv_texture.hpp, included below, outside this namespace
 
 // the demo's overlays (overlay.hip): segments and discs over a per-image point table, drawn per pixel
 struct OverlaySegmentsArgs {
@@ -788,3 +772,5 @@ struct SuppressDuplicatesArgs {
 dad3d_status launch_suppress_duplicates(const SuppressDuplicatesArgs& a, hipStream_t s);
 
 }  // namespace dad3d
+
+#include "uv_texture.hpp"

@@ -28,44 +28,11 @@
 
 #include "collectives.hpp"
 #include "common.hpp"
+#include "sim3dr_frames.hpp"
 #include "sim3dr_math.hpp"
 
 namespace dad3d {
 namespace {
-
-constexpr int kFrameTileShift = 6;
-constexpr int kFrameTile = 1 << kFrameTileShift;  // 64 x 64 u64 keys = 32 KiB of LDS
-constexpr int kFrameThreads = 256;
-constexpr int kFrameWaves = kFrameThreads / 64;
-constexpr int kPlanThreads = 1024;
-constexpr int kPlanWaves = kPlanThreads / 64;
-constexpr int kWaveBoxPixels = 32;  // a box of more pixels inside the tile is walked by the whole wave, not by its own lane
-
-struct FrameScratch {
-    int* frame_base;       // [M + 1]   first tile of a frame; clamped to the host's tile total
-    unsigned* need;        // [N]       (tile, triangle) entries of a head
-    uint2* tri_box;        // [N][ntri] tile box of a triangle: tx0 | tx1 << 16, ty0 | ty1 << 16; tx0 > tx1: off screen
-    unsigned* tile_count;  // [T]       entries of a tile (counted, then counted again as the write cursor)
-    unsigned* tile_off;    // [T + 1]   first pool entry of a tile
-    unsigned* items;       // [T]       the non-empty tiles
-    unsigned* n_items;     // [1]
-    unsigned* pool;        // [pool_entries]  head << 16 | triangle
-    unsigned pool_entries;
-    int total_tiles;       // T, from the host's copy of the shapes
-};
-
-struct FrameShape {
-    int h, w, tiles_x, tiles;  // tiles == 0: not a frame the chain draws into
-};
-__device__ __forceinline__ FrameShape frame_shape(const long long* frames, int f) {
-    const long long h = frames[4 * (size_t)f + 1], w = frames[4 * (size_t)f + 2];
-    FrameShape s{0, 0, 0, 0};
-    if (h < 1 || w < 1 || h > INT_MAX - kFrameTile || w > INT_MAX - kFrameTile) return s;
-    const long long tx = (w + kFrameTile - 1) >> kFrameTileShift, ty = (h + kFrameTile - 1) >> kFrameTileShift;
-    if (tx * ty > DAD3D_FRAME_MAX_TILES) return s;
-    s.h = (int)h, s.w = (int)w, s.tiles_x = (int)tx, s.tiles = (int)(tx * ty);
-    return s;
-}
 
 __global__ __launch_bounds__(kFrameThreads) void frames_setup_kernel(FrameScratch sc, const long long* frames, int n_frames, int n_heads) {
     __shared__ int red[kFrameWaves];
@@ -211,23 +178,14 @@ struct FrameTileArgs {
 
 __global__ __launch_bounds__(kFrameThreads) void frames_tile_kernel(FrameTileArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned long long keys[kFrameTile * kFrameTile];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const unsigned n_items = *a.sc.n_items;
-    const size_t head_floats = (size_t)a.m.nver * 3;
+    const size_t head_floats = (size_t)a.m.nver * 3;  // the resolve's
     for (unsigned item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int g = (int)a.sc.items[item];
-        // the frame of tile g: the last f with frame_base[f] <= g (frames without tiles share a base with their successor)
-        int lo = 0, hi = a.n_frames;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (a.sc.frame_base[mid] <= g) lo = mid;
-            else hi = mid;
-        }
-        const int f = lo;
-        const FrameShape fs = frame_shape(a.frames, f);
-        const int tile = g - a.sc.frame_base[f];
-        const int px0 = (tile % fs.tiles_x) * kFrameTile, py0 = (tile / fs.tiles_x) * kFrameTile;
-        const int px1 = min(px0 + kFrameTile, fs.w) - 1, py1 = min(py0 + kFrameTile, fs.h) - 1;
+        const FrameTile ft = frame_tile(a.sc, a.frames, a.n_frames, g);
+        const FrameShape& fs = ft.fs;
+        const int f = ft.f, px0 = ft.px0, py0 = ft.py0, px1 = ft.px1, py1 = ft.py1;
         for (int p = tid; p < kFrameTile * kFrameTile; p += kFrameThreads) keys[p] = 0ull;  // 0: no fragment (a head's keys start at 1 << 48)
         __syncthreads();
 
@@ -243,56 +201,7 @@ __global__ __launch_bounds__(kFrameThreads) void frames_tile_kernel(FrameTileArg
             (void)__hip_atomic_fetch_max(&keys[(y - py0) * kFrameTile + (x - px0)], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         };
 
-        const unsigned n_list = a.sc.tile_count[g], off = a.sc.tile_off[g];
-        for (unsigned base = (unsigned)(tid & ~63); base < n_list; base += kFrameThreads) {
-            const unsigned i = base + lane;
-            const bool have = i < n_list;
-            const unsigned e = have ? a.sc.pool[off + i] : 0u;
-            const unsigned k = e >> 16, t = e & 0xffffu;
-            float x0 = 0.f, y0 = 0.f, z0 = 0.f, x1 = 0.f, y1 = 0.f, z1 = 0.f, x2 = 0.f, y2 = 0.f, z2 = 0.f;
-            int bx0 = 1, bx1 = 0, by0 = 1, by1 = 0;
-            if (have) {
-                const float* vb = a.vertices + k * head_floats;
-                const int i0 = a.m.tri[3 * t], i1 = a.m.tri[3 * t + 1], i2 = a.m.tri[3 * t + 2];
-                x0 = vb[3 * i0], y0 = vb[3 * i0 + 1], z0 = vb[3 * i0 + 2];
-                x1 = vb[3 * i1], y1 = vb[3 * i1 + 1], z1 = vb[3 * i1 + 2];
-                x2 = vb[3 * i2], y2 = vb[3 * i2 + 1], z2 = vb[3 * i2 + 2];
-                // the box of rasterize_kernel.cpp:246-254 (as frames_box computed it), then clipped to this tile
-                bx0 = max(max(f2i_x86(ceilf(std_min(x0, std_min(x1, x2)))), 0), px0);
-                bx1 = min(min(f2i_x86(floorf(std_max(x0, std_max(x1, x2)))), fs.w - 1), px1);
-                by0 = max(max(f2i_x86(ceilf(std_min(y0, std_min(y1, y2)))), 0), py0);
-                by1 = min(min(f2i_x86(floorf(std_max(y0, std_max(y1, y2)))), fs.h - 1), py1);
-            }
-            const bool ok = have && bx0 <= bx1 && by0 <= by1;
-            const int area = ok ? (bx1 - bx0 + 1) * (by1 - by0 + 1) : 0;
-            const bool big = area > kWaveBoxPixels;
-            const unsigned long long key_hi = (unsigned long long)(k + 1) << 48;
-            const unsigned key_lo = 0xFFFEu - t;
-            if (ok && !big) {
-                const TriSetup ts = tri_setup(x0, y0, x1, y1, x2, y2);
-                for (int y = by0; y <= by1; ++y)
-                    for (int x = bx0; x <= bx1; ++x) test_pixel(ts, z0, z1, z2, key_hi, key_lo, x, y);
-            }
-            unsigned long long todo = __ballot(big);
-            while (todo) {  // wave-uniform: one large box at a time, all 64 lanes on its pixels
-                const int j = __builtin_ctzll(todo);
-                todo &= todo - 1;
-                auto bf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
-                auto bi = [&](int v) { return __builtin_amdgcn_readlane(v, j); };
-                const TriSetup ts = tri_setup(bf(x0), bf(y0), bf(x1), bf(y1), bf(x2), bf(y2));
-                const float wz0 = bf(z0), wz1 = bf(z1), wz2 = bf(z2);
-                const unsigned we = (unsigned)bi((int)e);
-                const unsigned long long wkey_hi = (unsigned long long)((we >> 16) + 1) << 48;
-                const unsigned wkey_lo = 0xFFFEu - (we & 0xffffu);
-                const int wx0 = bi(bx0), wy0 = bi(by0), bw = bi(bx1) - wx0 + 1, warea = bi(area);
-                const float rcp_bw = __builtin_amdgcn_rcpf((float)bw);
-                for (int p = lane; p < warea; p += 64) {
-                    // exact p / bw for p < 4096, bw <= 64: (p + 0.5) / bw is at least 1 / 128 away from an integer, the product's error < 1e-3
-                    const int py = (int)(((float)p + 0.5f) * rcp_bw), px = p - py * bw;
-                    test_pixel(ts, wz0, wz1, wz2, wkey_hi, wkey_lo, wx0 + px, wy0 + py);
-                }
-            }
-        }
+        walk_frame_tile(a.m, a.sc, a.vertices, g, ft, test_pixel);
         __syncthreads();
 
         // resolve: every won pixel is shaded once from its winner and written with three byte stores
@@ -325,26 +234,6 @@ __global__ __launch_bounds__(kFrameThreads) void frames_tile_kernel(FrameTileArg
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct FrameLayout {
-    size_t frame_base, need, tri_box, tile_count, tile_off, items, n_items, pool, total;
-    unsigned pool_entries;
-    FrameLayout(int ntri, int n_frames, int n_heads, int total_tiles) {
-        // 4 * ntri * N entries: a triangle whose clipped box is at most 64 x 64 pixels touches at most 2 x 2 tiles
-        pool_entries = (unsigned)std::min<unsigned long long>(4ull * (unsigned)ntri * (unsigned)n_heads, 0x7fffffffull);
-        frame_base = 0;
-        need = align256(frame_base + ((size_t)n_frames + 1) * sizeof(int));
-        tri_box = align256(need + (size_t)n_heads * sizeof(unsigned));
-        tile_count = align256(tri_box + (size_t)n_heads * ntri * sizeof(uint2));
-        tile_off = align256(tile_count + (size_t)total_tiles * sizeof(unsigned));
-        items = align256(tile_off + ((size_t)total_tiles + 1) * sizeof(unsigned));
-        n_items = align256(items + (size_t)total_tiles * sizeof(unsigned));
-        pool = align256(n_items + sizeof(unsigned));
-        total = align256(pool + (size_t)pool_entries * sizeof(unsigned));
-    }
-};
-
 }  // namespace
 
 dad3d_status frames_check_shapes(const char* who, const int64_t* frames_host, int n_frames, int* total_tiles) {
@@ -370,8 +259,8 @@ size_t frames_scratch_bytes(int ntri, int n_frames, int n_heads, int total_tiles
     return FrameLayout(ntri, n_frames, n_heads, total_tiles).total;
 }
 
-dad3d_status launch_rasterize_frames(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles, const float* vertices,
-                                     const float* colors, const int32_t* image_index, int n_heads, int reverse, int32_t* flags, hipStream_t s) {
+dad3d_status build_frame_lists(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles, const float* vertices,
+                               const int32_t* image_index, int n_heads, int32_t* flags, hipStream_t s, FrameScratch* lists, int* tile_blocks) {
     static int cus = 0;  // the same for every device of the node (one GPU model)
     if (!cus) {
         int dev = 0, n = 0;
@@ -400,9 +289,20 @@ dad3d_status launch_rasterize_frames(const MeshDev& m, void* scratch, const int6
     hipLaunchKernelGGL(frames_bin_kernel<0>, tri_grid, dim3(kFrameThreads), 0, s, m.ntri, sc, table, image_index, flags);
     hipLaunchKernelGGL(frames_scan_kernel, dim3(1), dim3(kPlanThreads), 0, s, sc);
     hipLaunchKernelGGL(frames_bin_kernel<1>, tri_grid, dim3(kFrameThreads), 0, s, m.ntri, sc, table, image_index, flags);
-    // five workgroups of 32 KiB a CU; the grid is sized by the host's tile count, the items by the device's list
-    const FrameTileArgs a{m, sc, table, n_frames, vertices, colors, reverse};
-    hipLaunchKernelGGL(frames_tile_kernel, dim3(std::min(total_tiles, 5 * cus)), dim3(kFrameThreads), 0, s, a);
+    DAD3D_HIP_TRY(hipGetLastError());
+    *lists = sc;
+    *tile_blocks = std::min(total_tiles, 5 * cus);  // five workgroups of 32 KiB a CU; the grid is sized by the host's tile count
+    return DAD3D_OK;
+}
+
+dad3d_status launch_rasterize_frames(const MeshDev& m, void* scratch, const int64_t* frames, int n_frames, int total_tiles, const float* vertices,
+                                     const float* colors, const int32_t* image_index, int n_heads, int reverse, int32_t* flags, hipStream_t s) {
+    FrameScratch sc;
+    int tile_blocks = 0;
+    if (dad3d_status st = build_frame_lists(m, scratch, frames, n_frames, total_tiles, vertices, image_index, n_heads, flags, s, &sc, &tile_blocks)) return st;
+    // the items come from the device's list
+    const FrameTileArgs a{m, sc, reinterpret_cast<const long long*>(frames), n_frames, vertices, colors, reverse};
+    hipLaunchKernelGGL(frames_tile_kernel, dim3(tile_blocks), dim3(kFrameThreads), 0, s, a);
     DAD3D_HIP_TRY(hipGetLastError());
     return DAD3D_OK;
 }

@@ -17,13 +17,14 @@
 // to the correctly rounded sequences (v_div_scale/v_div_fmas/v_div_fixup; v_rsq_f64 with the Newton-Raphson refinement and
 // fix-up), so the normals are bit-equal to the float64 restatement.
 #include "common.hpp"
+#include "uv_texture.hpp"
 
 namespace dad3d {
 namespace {
 
 constexpr int kNormThreads = 256;
-constexpr int kBakeThreads = 256;
-constexpr int kBakeTexels = 4;  // texels per lane: 12 output bytes, three dword stores
+constexpr int kBakeThreads = kUvBakeThreads;
+constexpr int kBakeTexels = kUvBakeTexels;
 
 __global__ __launch_bounds__(kNormThreads) void vertex_normals_kernel(UvNormalArgs a) {
     const int v = blockIdx.x * kNormThreads + threadIdx.x;
@@ -47,46 +48,20 @@ __global__ __launch_bounds__(kNormThreads) void vertex_normals_kernel(UvNormalAr
     o[0] = sx / norm, o[1] = sy / norm, o[2] = sz / norm;
 }
 
-struct Cand {
-    int v0, v1, v2;
-    double w0, w1, w2;
-};
-
-__device__ __forceinline__ Cand load_cand(const UvBakeArgs& a, int j) {
-    const int* v = a.cand_verts + (size_t)j * 3;
-    const double* w = a.cand_bary + (size_t)j * 3;
-    return Cand{v[0], v[1], v[2], w[0], w[1], w[2]};
-}
-
-// The source pixel of candidate c on image b, or -1 where it is skipped (back-facing or outside the strict bounds).
-__device__ __forceinline__ int sample(const UvBakeArgs& a, const Cand& c, const float* vb, const double* nb, const uint8_t* img,
-                                      int h, int w) {
-    const double nz = (nb[c.v0 * 3 + 2] * c.w0 + nb[c.v1 * 3 + 2] * c.w1) + nb[c.v2 * 3 + 2] * c.w2;
-    const double ndv = -nz;
-    if (ndv < 0.0) return -1;  // -0.0 and NaN pass, as in the reference
-    const double px = ((double)vb[c.v0 * 3] * c.w0 + (double)vb[c.v1 * 3] * c.w1) + (double)vb[c.v2 * 3] * c.w2;
-    const double py = ((double)vb[c.v0 * 3 + 1] * c.w0 + (double)vb[c.v1 * 3 + 1] * c.w1) + (double)vb[c.v2 * 3 + 1] * c.w2;
-    const double rx = rint(px), ry = rint(py);  // np.round: half to even
-    // compared as doubles: NaN and +-inf fail here, where NumPy's astype(int) turns them into INT64_MIN
-    if (!(rx > 0.0 && rx < (double)w && ry > 0.0 && ry < (double)h)) return -1;
-    const uint8_t* p = img + ((size_t)(int)ry * a.w + (int)rx) * 3;
-    return p[0] | (p[1] << 8) | (p[2] << 16);
-}
-
 __global__ __launch_bounds__(kBakeThreads) void bake_kernel(UvBakeArgs a) {
     const int n_tex = a.size * a.size;
     const int t0 = (blockIdx.x * kBakeThreads + threadIdx.x) * kBakeTexels;
     if (t0 >= n_tex) return;
     const int nt = min(kBakeTexels, n_tex - t0);
     int beg[kBakeTexels], end[kBakeTexels];
-    Cand first[kBakeTexels];
+    UvCand first[kBakeTexels];
 #pragma unroll
     for (int k = 0; k < kBakeTexels; ++k) {
         beg[k] = end[k] = 0;
-        first[k] = Cand{0, 0, 0, 0.0, 0.0, 0.0};
+        first[k] = UvCand{0, 0, 0, 0.0, 0.0, 0.0};
         if (k < nt) {
             beg[k] = a.texel_ptr[t0 + k], end[k] = a.texel_ptr[t0 + k + 1];
-            if (beg[k] < end[k]) first[k] = load_cand(a, beg[k]);
+            if (beg[k] < end[k]) first[k] = uv_load_cand(a.cand_verts, a.cand_bary, beg[k]);
         }
     }
     const int b1 = min(a.batch, (int)(blockIdx.y + 1) * a.chunk);
@@ -96,13 +71,15 @@ __global__ __launch_bounds__(kBakeThreads) void bake_kernel(UvBakeArgs a) {
         const float* vb = a.vertices + (size_t)b * a.n_verts * 3;
         const double* nb = a.normals + (size_t)b * a.n_verts * 3;
         const uint8_t* img = a.images + (size_t)b * a.h * a.w * 3;
+        auto pixel_at = [&](int y, int x) { return img + ((size_t)y * a.w + x) * 3; };
+        double ndv;
         unsigned rgb[kBakeTexels];
 #pragma unroll
         for (int k = 0; k < kBakeTexels; ++k) {
             int px = -1;
             if (beg[k] < end[k]) {
-                px = sample(a, first[k], vb, nb, img, h, w);
-                for (int j = beg[k] + 1; px < 0 && j < end[k]; ++j) px = sample(a, load_cand(a, j), vb, nb, img, h, w);
+                px = uv_sample(first[k], vb, nb, h, w, pixel_at, ndv);
+                for (int j = beg[k] + 1; px < 0 && j < end[k]; ++j) px = uv_sample(uv_load_cand(a.cand_verts, a.cand_bary, j), vb, nb, h, w, pixel_at, ndv);
             }
             rgb[k] = px < 0 ? 0u : (unsigned)px;
         }

@@ -216,7 +216,7 @@ _renderers: Dict[Tuple[int, str], object] = {}  # (id of the head mesh, mode) ->
 
 
 def draw_heads(predictions: Predictions, frames: Images, mode: str = "shaded", image_index=None, out: Optional[Images] = None,
-               head_mesh=None):
+               head_mesh=None, textures=None, creator=None, mapping: str = "bilinear"):
     """The heads of `predict_boxes` / `predict_files(.., boxes=)` drawn into their frames as surfaces: `mode="shaded"` the whole FLAME
     mesh under RenderPipeline's default light, `mode="pncc"` the ear-less face subset in its colour codes (pncc_estimator.py). The
     dicts' `3dmm_params` are already in frame coordinates; they are stacked and decoded once (`proj`, z flipped, as
@@ -224,9 +224,21 @@ def draw_heads(predictions: Predictions, frames: Images, mode: str = "shaded", i
     head k into `frames[image_index[k]]`, a later head of a frame over an earlier one, as a loop over `Sim3DR.rasterize(.., bg=frame)`
     paints them. `image_index=None`: the dicts' own. A head whose index names no frame is not drawn. With device values nothing is
     read on the host. `frames` as for the other overlays; the result has their form and is a copy unless `out=` is given (`out` may be
-    `frames` itself). `head_mesh`: the predictor's `HeadMesh` (None: a new one, which needs the FLAME model file)."""
-    if mode not in ("shaded", "pncc"):
-        raise ValueError(f"mode: 'shaded' or 'pncc', got {mode!r}")
+    `frames` itself). `head_mesh`: the predictor's `HeadMesh` (None: a new one, which needs the FLAME model file).
+    `mode="textured"`: every head with its own texture, `textures` a `[N,S,S,3]` tensor (one shared `[S,S,3]` works too) or a
+    `uv_texture.TextureAccumulator` (slot k for head k), through `creator.render_frames` (`creator`: the `UVTextureCreator` that holds
+    the texture coordinates; None: the accumulator's), sampled `mapping="bilinear"` or `"nearest"`."""
+    if mode not in ("shaded", "pncc", "textured"):
+        raise ValueError(f"mode: 'shaded', 'pncc' or 'textured', got {mode!r}")
+    if mode != "textured" and (textures is not None or creator is not None):
+        raise ValueError(f"textures / creator: only with mode='textured', got mode={mode!r}")
+    if mode == "textured":
+        if textures is None:
+            raise ValueError("mode='textured' needs textures= (a tensor or a TextureAccumulator)")
+        if creator is None:
+            creator = getattr(textures, "creator", None)
+        if creator is None:
+            raise ValueError("mode='textured' with a texture tensor needs creator= (the UVTextureCreator with the texture coordinates)")
     items, form = _image_list(frames)
     for t in items:
         if not t.is_cuda:
@@ -254,6 +266,13 @@ def draw_heads(predictions: Predictions, frames: Images, mode: str = "shaded", i
     if not dicts or not items:
         return target
     device = items[0].device
+    if mode == "textured":
+        params = _field(dicts, "3dmm_params", len(dicts), 1).to(device, torch.float32).contiguous()
+        index = _head_index(dicts, image_index, device)
+        if len(index) != len(dicts):
+            raise ValueError(f"image_index: {len(index)} entries for {len(dicts)} predictions")
+        creator.render_frames(params, textures, target if form != "single" else [target], index, mapping=mapping, mutate=False)
+        return target
     if head_mesh is None:
         from .head_mesh import HeadMesh
         head_mesh = HeadMesh(device=device.index)

@@ -2,7 +2,9 @@
 
 Same surface as the reference (`get_mesh`, `_compute_texture_map`, `__call__`, the `texture_data` dict), plus the batched
 device-resident entry `bake_batch`: ONE fused decode launch (`to_2d=False`, translation z := 0) followed by the float64 vertex
-normals and the texel bake (csrc/uv_texture.hip); vertices, normals, photos and textures never leave HBM.
+normals and the texel bake (csrc/uv_texture.hip); vertices, normals, photos and textures never leave HBM. For heads tracked in
+a video: `bake_frames` (head k read from the frame its `image_index` names, csrc/uv_texture_frames.hip), `TextureAccumulator` (one
+texture per tracker slot, the best view of every texel kept over time) and `render_frames` (the textured heads drawn into their frames).
 
 What the reference computes, per candidate i of the atlas (`_compute_texture_map`, uv_texture.py:21-46), in float64:
     p = v[a] * b0 + v[b] * b1 + v[c] * b2,  the same with the vertex normals,  n_dot_view = -n.z
@@ -32,6 +34,7 @@ from torch import Tensor
 
 from . import _lib
 from .head_mesh import HeadMesh
+from .Sim3DR.frames import DeviceFrames
 from .Sim3DR.mesh import Mesh
 from .synthetic import load_static
 
@@ -152,6 +155,43 @@ class UVMap:
                                               images.data_ptr(), hw.data_ptr() if hw is not None else None, b, h, w, stream))
         return out
 
+    def bake_frames(self, vertices: Tensor, normals: Tensor, frames, image_index, out: Optional[Tensor] = None,
+                    score: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The bake for heads that name their frames (`dad3d_uvmap_bake_frames`): head k reads `frames[image_index[k]]` and owns
+        texture k. vertices `[N,V,3]` float32 in frame coordinates, normals `[N,V,3]` float64. `frames`: a list of uint8 CUDA
+        tensors `[H,W,3]` of any sizes and row strides (views included), one `[B,H,W,3]` tensor, or a `DeviceFrames` (its table is
+        uploaded once: what a graph capture needs). `image_index`: an int32 CUDA tensor `[N]`, used as it is and never read on the
+        host, or a host sequence, uploaded. `score=None`: the plain bake into `out` (allocated when None), every byte written.
+        `score [N,S,S]` float32: `out` (required) and `score` are the running state, a texel is replaced iff its new sample's
+        n_dot_view is greater ("best view wins"). -> (textures uint8 `[N,S,S,3]`, int32 flags `[N]`: 0 or `_lib.BAKE_FLAG_INDEX`, the
+        index names no frame). Async on the current stream, no host wait."""
+        n = vertices.shape[0]
+        dev = torch.device("cuda", self.device)
+        self._check(vertices, "vertices", torch.float32, (n, self.n_verts, 3))
+        self._check(normals, "normals", torch.float64, (n, self.n_verts, 3))
+        fr = frames if isinstance(frames, DeviceFrames) else DeviceFrames(frames, dev)
+        if fr.device.device != dev:
+            raise ValueError(f"frames: on {fr.device.device}, the map on {dev}")
+        if isinstance(image_index, Tensor) and image_index.is_cuda:
+            idx = image_index
+        else:
+            idx = torch.as_tensor(np.asarray(image_index, dtype=np.int32).reshape(-1)).to(dev)
+        self._check(idx, "image_index", torch.int32, (n,))
+        s = self.size
+        if score is not None:
+            if out is None:
+                raise ValueError("score: accumulation needs `out`, the textures the scores belong to")
+            self._check(score, "score", torch.float32, (n, s, s))
+        if out is None:
+            out = torch.empty((n, s, s, 3), dtype=torch.uint8, device=dev)
+        self._check(out, "out", torch.uint8, (n, s, s, 3))
+        flags = torch.empty(n, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.dad3d_uvmap_bake_frames(self._handle, out.data_ptr(), score.data_ptr() if score is not None else None,
+                                                     vertices.data_ptr(), normals.data_ptr(), fr.device.data_ptr(), fr.host.ctypes.data,
+                                                     len(fr), idx.data_ptr(), n, flags.data_ptr(), stream))
+        return out, flags
+
 
 class UVTextureCreator:
     """`UVTextureCreator(texture_data=path | dict | None, head_mesh=None, static=None, **head_mesh_kwargs)`.
@@ -249,6 +289,22 @@ class UVTextureCreator:
         normals = m.vertex_normals(verts, out=self._normals[:b])
         return m.bake(verts, normals, images, hw=hw, out=out)
 
+    def bake_frames(self, params: Tensor, frames, image_index, mutate: bool = True, out: Optional[Tensor] = None,
+                    score: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """`params [N,413]` fp32 on the GPU, in FRAME coordinates (what `predict_boxes` / `HeadTracker.step` return), head k read from
+        `frames[image_index[k]]` -> (textures `[N,S,S,3]` uint8, flags `[N]` int32), both on the GPU.
+
+        Three launches on the current stream, no host sync: the decode of `bake_batch` (`proj=True, to_2d=False`, no flip; `mutate`
+        writes translation z := 0 into `params`), the float64 normals and `UVMap.bake_frames` -- see there for `frames`, `image_index`,
+        `out`, `score` and the flags. A lost slot of the tracker (`image_index == -1`) is flagged and, with `score`, changes nothing.
+        Capturable in a graph after one call of the same N or after `reserve(N)`, with `frames` a `DeviceFrames`."""
+        m = self.uv_map
+        n = params.shape[0]
+        self.reserve(n)
+        verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, mutate=mutate)["proj"]
+        normals = m.vertex_normals(verts, out=self._normals[:n])
+        return m.bake_frames(verts, normals, frames, image_index, out=out, score=score)
+
     # -- textured render: the other half of the bake -------------------------------------------------------
     def set_texcoords(self, tex_coords: np.ndarray, tex_triangles: np.ndarray) -> None:
         """The corner layout `render_batch` samples with: `tex_coords [T,2]` in TEXEL units of the S x S texture (x = column,
@@ -314,3 +370,78 @@ class UVTextureCreator:
             out.copy_(bg)
         verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=mutate)["proj"]
         return mesh.render_texture(verts, textures, out, mapping=mapping)
+
+    def render_frames(self, params: Tensor, textures, frames, image_index, mapping: str = "bilinear", mutate: bool = True) -> Tensor:
+        """`params [N,413]` fp32 on the GPU in frame coordinates and `textures` (`[N,S,S,3]`, one shared `[S,S,3]`, uint8 or float32,
+        or a `TextureAccumulator`) -> head k drawn with its texture into `frames[image_index[k]]`, in place: the decode of
+        `render_batch` (z flipped), then `Mesh.render_texture_frames`. A later head of a frame paints over an earlier one.
+        -> int32 CUDA flags `[N]` (`Mesh.rasterize_frames`). No host sync."""
+        tex = textures.textures if isinstance(textures, TextureAccumulator) else textures
+        if tex.ndim == 4 and tex.shape[0] > params.shape[0]:
+            tex = tex[:params.shape[0]]  # fewer heads than slots: head k still samples texture k
+        verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, flip_z=True, mutate=mutate)["proj"]
+        return self.renderer.render_texture_frames(frames, verts, tex, image_index, mapping=mapping)
+
+
+class TextureAccumulator:
+    """The texture of every tracker slot, accumulated over the frames of a video, on the device: `textures` uint8 `[n,S,S,3]` and
+    `score` float32 `[n,S,S]`, the n_dot_view of the sample each texel holds (-1: none yet).
+
+    A one-frame bake is half empty, because the reference skips every texel whose normal faces away; over a video the head turns and
+    `add` keeps, per texel, the sample seen most frontally ("best view wins": strictly greater n_dot_view replaces, a tie keeps the
+    older sample). Head k of a call always goes to slot k -- the tracker's slots are fixed. Not done: blending of samples, occlusion
+    of a head by another head or an object, temporal filtering."""
+
+    def __init__(self, creator: UVTextureCreator, n_slots: int):
+        if int(n_slots) < 1:
+            raise ValueError(f"n_slots: {n_slots}, at least 1")
+        self.creator = creator
+        self.n_slots = int(n_slots)
+        dev = creator.head_mesh.flame.torch_device
+        s = creator.img_size
+        self.textures = torch.zeros((self.n_slots, s, s, 3), dtype=torch.uint8, device=dev)
+        self.score = torch.full((self.n_slots, s, s), -1.0, dtype=torch.float32, device=dev)
+        creator.reserve(self.n_slots)
+
+    def reserve(self, n: int) -> None:
+        """Size the creator's buffers for `n` heads a call, so that a later `add` can be captured in a graph."""
+        self.creator.reserve(int(n))
+
+    def reset(self, slots=None) -> None:
+        """Zeros and score -1 for all slots (None) or the given ones (a sequence or an int64 CUDA tensor): what a caller does beside
+        `HeadTracker.reseed`. No host read."""
+        if slots is None:
+            self.textures.zero_()
+            self.score.fill_(-1.0)
+            return
+        idx = slots.to(self.textures.device, torch.int64) if isinstance(slots, Tensor) else torch.as_tensor(
+            np.asarray(slots, dtype=np.int64).reshape(-1)).to(self.textures.device)
+        self.textures.index_fill_(0, idx, 0)
+        self.score.index_fill_(0, idx, -1.0)
+
+    def add(self, predictions_or_params, frames, image_index=None) -> Tensor:
+        """One frame set of the video: `predictions_or_params` the list of per-head dicts of `predict_boxes` / `HeadTracker.step`
+        (their `3dmm_params` are stacked and `image_index=None` means their own, as `overlay.draw_heads` does) or a `[N,413]` tensor
+        with `image_index`; N <= n_slots, head k into slot k. -> int32 CUDA flags `[N]` (`_lib.BAKE_FLAG_INDEX`: the slot named no
+        frame and kept its state). Nothing waits for the device; the params are not mutated."""
+        dev = self.textures.device
+        if isinstance(predictions_or_params, Tensor):
+            if image_index is None:
+                raise ValueError("image_index: required with a params tensor")
+            params, index = predictions_or_params, image_index
+        else:
+            from .overlay import _field, _head_index
+            dicts = list(predictions_or_params)
+            params = _field(dicts, "3dmm_params", len(dicts), 1).to(dev, torch.float32).contiguous()
+            index = _head_index(dicts, image_index, dev)
+        n = params.shape[0]
+        if n > self.n_slots:
+            raise ValueError(f"{n} heads for {self.n_slots} slots")
+        if len(index) != n:
+            raise ValueError(f"image_index: {len(index)} entries for {n} heads")
+        _, flags = self.creator.bake_frames(params, frames, index, mutate=False, out=self.textures[:n], score=self.score[:n])
+        return flags
+
+    def filled(self) -> Tensor:
+        """bool `[n,S,S]` on the device: the texels that hold a sample."""
+        return self.score > -1.0

@@ -407,6 +407,27 @@ DAD3D_EXPORT dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, 
                                                     int batch, int h, int w, int c, int tex_h, int tex_w, int tex_c,
                                                     int mapping_type, int indexing, void* stream);
 
+/* Textured heads through the frames chain. Per frame, in ascending head order:
+ *   frame = (unsigned char) _render_texture_core(image = float(frame), vertices[k], .., texture[k], a fresh depth buffer at -1e8)
+ * A later head paints over an earlier one wherever it covers a pixel; an uncovered pixel is not written. Seven launches: the six
+ * list-building launches of dad3d_mesh_rasterize_frames, then a tile kernel with dad3d_mesh_render_texture's coverage, depth test and
+ * texel arithmetic (see there). The two-pixel border band is that of the FRAME (x < 2 || x > w - 3 || y < 2 || y > h - 3) and is kept
+ * on purpose, as the reference has it; it only matters for a head whose triangle boxes reach the frame's outer two pixels.
+ *   frames, frames_host, vertices, image_index, flags   as for dad3d_mesh_rasterize_frames (DAD3D_FRAME_FLAG_INDEX / _CAPACITY; a
+ *                flagged head changes no byte of any frame)
+ *   texture      DEVICE [n_heads,tex_h,tex_w,tex_c] (texture_batched != 0: head k samples texture k) or one [tex_h,tex_w,tex_c] for
+ *                all heads, float32 or uint8 (texture_dtype); tex_c >= 3, the first three channels are used
+ *   mapping_type 0 = nearest, otherwise bilinear; indexing DAD3D_TEX_INDEX_CORNER or _REFERENCE (dad3d_mesh_set_texcoords)
+ * Pixels are written as three single bytes, (unsigned char) of the float result; no byte outside [row, row + 3 * w) of a row is
+ * touched. `reverse` is not offered; alpha == 1; no depth output and no depth buffer shared between heads. A missing texcoord table,
+ * tex_c < 3, an unknown dtype or indexing mode -> DAD3D_E_INVALID. Limits, list pool, scratch ownership (shared with the two entries
+ * above), stream and graph rule: exactly those of dad3d_mesh_rasterize_frames. Every argument check happens before any device work. */
+DAD3D_EXPORT dad3d_status dad3d_mesh_render_texture_frames(dad3d_mesh* m, const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                                           const float* vertices, const void* texture, int texture_dtype,
+                                                           int texture_batched, int tex_h, int tex_w, int tex_c, int mapping_type,
+                                                           int indexing, const int32_t* image_index, int n_heads, int32_t* flags,
+                                                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Matrix projection of meshes (GT annotations): model_training/data/flame_dataset.py:115-141 (`_load_mesh`,
  * `_project_vertices_onto_image`), visualize.py:10-22 (`get_2d_keypoints`). All DEVICE pointers:
@@ -592,6 +613,37 @@ DAD3D_EXPORT dad3d_status dad3d_uvmap_vertex_normals(dad3d_uvmap* m, double* nor
                                         void* stream);
 DAD3D_EXPORT dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* vertices, const double* normals,
                               const uint8_t* images, const int32_t* hw, int batch, int h, int w, void* stream);
+
+/* The bake for heads that name their frames (a tracker's slots over a video): head k reads the frame image_index[k] of the frame
+ * table of dad3d_preprocess_boxes and owns texture k, so frames of any sizes and row strides serve several heads each without
+ * being gathered into a batch, and no two heads ever write one texture. One launch: a lane owns four consecutive texels of a head.
+ *   texture      DEVICE uint8 [n_heads,S,S,3]
+ *   score        DEVICE float32 [n_heads,S,S], or NULL (see below)
+ *   vertices     DEVICE [n_heads,nver,3] float32 (frame pixel x, pixel y, depth); normals DEVICE [n_heads,nver,3] float64 (from
+ *                dad3d_uvmap_vertex_normals)
+ *   frames       DEVICE int64 [n_frames][4] {address of the first byte, h, w, row stride in bytes}: uint8 RGB pixels, HWC, unit pixel
+ *                stride; neither the address nor the stride need be aligned
+ *   frames_host  HOST copy of the same table, checked before any device work: an address, h, w >= 1, stride >= 3 * w, else
+ *                DAD3D_E_INVALID. The tile limits of dad3d_mesh_rasterize_frames do not apply.
+ *   image_index  DEVICE int32 [n_heads], in any order; never read on the host
+ *   flags        DEVICE int32 [n_heads], written: 0, or DAD3D_BAKE_FLAG_INDEX = image_index outside [0, n_frames) -- what a tracker
+ *                reports for a lost slot (-1), so an ordinary outcome
+ * Per texel the candidate is chosen exactly as dad3d_uvmap_bake chooses it: the LAST candidate with !(n_dot_view < 0) whose
+ * interpolated point, rounded half to even, satisfies 0 < x < w, 0 < y < h with the FRAME's own w and h; its pixel is the three
+ * bytes at address + y * stride + 3 * x.
+ *   score == NULL  plain bake: every byte of texture k is written, the pixel where there is a candidate, zeros elsewhere; a flagged
+ *                  head gives zeros. For one head per equal-size frame these are the bytes of dad3d_uvmap_bake.
+ *   score != NULL  accumulate, "best view wins": with s = (float) n_dot_view of the chosen candidate (float64 rounded to the nearest
+ *                  float32), the texel's three bytes and score[k,t] are replaced iff s > score[k,t]. A NaN s never replaces, a tie
+ *                  keeps the older sample, a texel without a candidate keeps its state, and a flagged head changes no byte of its
+ *                  texture or score. Start a texture at zeros with score -1.0f: then any first sample (n_dot_view >= 0) enters.
+ * Not done: blending of samples, occlusion of a head by another head or an object, temporal filtering of the texture.
+ * The entry allocates nothing, is stream-ordered and can be captured into a graph. n_heads == 0: DAD3D_OK, nothing to do; n_frames
+ * == 0: every head is flagged. At most 65535 heads a call. One handle may serve several streams. */
+#define DAD3D_BAKE_FLAG_INDEX 1
+DAD3D_EXPORT dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices,
+                                                  const double* normals, const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                                  const int32_t* image_index, int n_heads, int32_t* flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The vertex block of the demo's `.obj` files (demo_utils.py:130-144 `MeshSaver.__call__`): for every mesh of a batch the bytes of
