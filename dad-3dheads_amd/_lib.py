@@ -44,6 +44,8 @@ PREPROCESS_OUT_F32_NCHW, PREPROCESS_OUT_F16_NHWC, PREPROCESS_OUT_BF16_NHWC = 0, 
 BOX_FLAG_EMPTY, BOX_FLAG_COLLAPSED, BOX_FLAG_RANGE = 0x1, 0x2, 0x4
 TRACK_FLAG_PREVIOUS, TRACK_FLAG_RANGE, TRACK_FLAG_NONFINITE, TRACK_FLAG_SMALL, TRACK_FLAG_OUTSIDE = 0x1, 0x2, 0x4, 0x8, 0x10
 TRACK_FLAG_DUPLICATE, TRACK_MAX_SLOTS = 0x20, 1024
+TRACK_FLAG_RETIRED, TRACK_MAX_DETECTIONS = 0x40, 1024
+ASSIGN_FLAG_PADDING, ASSIGN_FLAG_INVALID, ASSIGN_FLAG_COVERED, ASSIGN_FLAG_SPAWNED, ASSIGN_FLAG_FULL = 0x1, 0x2, 0x4, 0x8, 0x10
 FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0x2, 4096, 65535
 RENDER_REVERSE, RENDER_CLEAR = 1, 2
 BAKE_FLAG_INDEX = 0x1
@@ -154,6 +156,7 @@ SIGNATURES = {
     "dad3d_boxes_from_heads": (_I, [_P, _I, _I, C.c_int64, _I, _P, _I, _P, _I, _P, _P, _I, C.c_double, _P, _P, _I, _P]),
     "dad3d_one_euro_rows": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P, _I, _P]),
     "dad3d_track_suppress_duplicates": (_I, [_P, _P, _P, _I, C.c_double, _I, _P]),
+    "dad3d_track_assign_detections": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, C.c_double, _I, _I, _P, _P, _P, _I, _P]),
     "dad3d_cube_region_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "dad3d_point_loss_terms": (_I, [_I]),
     "dad3d_weighted_point_loss": (_I, [_P, _P, _I, _I, _I, _P, _F, _I, _P, _P, _I, _P]),

@@ -2,10 +2,12 @@
 to every box on the device (csrc/preprocess_boxes.hip), restated with `dataset.extend_bbox` / `ensure_bbox_boundaries` and
 `resize_geometry`, so that a box the kernel would flag is refused before anything is launched; and `next_boxes`, the rule by which
 `dad3d_boxes_from_heads` (csrc/track_boxes.hip) takes the boxes of the next call from the heads of this one; and `suppress_duplicates`,
-the rule by which `dad3d_track_suppress_duplicates` (csrc/track_steady.hip) drops the later of two slots on one head. Pure numpy: no GPU,
-no library."""
+the rule by which `dad3d_track_suppress_duplicates` (csrc/track_steady.hip) drops the later of two slots on one head; and
+`assign_detections`, the rule by which `dad3d_track_assign_detections` (csrc/track_assign.hip) matches a detector's boxes to the slots,
+spawns and retires. Pure numpy: no GPU, no library."""
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -180,6 +182,112 @@ def suppress_duplicates(boxes, flags, image_index, merge_iou: float) -> Tuple[np
         else:
             kept.append((frame, x, y, x1, y1, area))
     return out_boxes, out_flags
+
+
+AssignedDetections = namedtuple("AssignedDetections", "boxes flags image_index misses assign det_flags spawned")
+MISSES_MAX = 2 ** 30
+
+
+def assign_detections(boxes, flags, image_index, misses, det_boxes, det_index, n_frames: int, match_iou: float, count: Optional[int] = None,
+                      frame_searched=None, refresh: bool = False, max_misses: Optional[int] = None) -> AssignedDetections:
+    """Detections into tracks: `dad3d_track_assign_detections` (csrc/track_assign.hip, include/dad3d.h) on the host, rule for rule,
+    in Python's integers. Slot state `boxes` int32 `[N,4]` as (x, y, w, h), `flags [N]`, `image_index [N]`, `misses [N]` (or None:
+    nothing is counted and nothing retires); detections `det_boxes [M,4]`, `det_index [M]`, of which the first `count` are real
+    (None: all; clamped to 0 .. M); `frame_searched [n_frames]` (None: every frame). -> copies of the slot state after the call,
+    `assign [M]` (the slot of a matched or spawned detection, else -1), `det_flags [M]` (`_lib.ASSIGN_FLAG_*`, 0 for a match) and
+    `spawned [N]` (1 where a slot was given to a new head).
+
+    A slot is live if its flags are 0 and both sides positive, as it stands at entry; every other slot is free. A valid detection and
+    a live slot of the same frame pass if `inter > 0` and `float(inter) >= match_iou * float(union)`, the comparison of
+    `suppress_duplicates`. The passing pairs are sorted by the exact ratio inter / union, best first, ties by the lower detection,
+    then the lower slot, and a pair is taken if neither side is taken: best-first, because "the first slot that passes" swaps two
+    neighbouring heads whose boxes overlap. A taken slot has its misses cleared (and with `refresh` takes the detection's box). An
+    unmatched detection that passes with any live slot is COVERED (its head has a track); the others take the slots that were free
+    at entry, in order (SPAWNED), or are FULL. Two unmatched detections that overlap each other both spawn: that is the detector's
+    own NMS to prevent, and `suppress_duplicates` takes what is left. A live slot that was searched for and not matched counts a
+    miss (saturating at 2^30), and with more than `max_misses` (None: never) it is retired: `_lib.TRACK_FLAG_RETIRED`, the zero
+    box, free from the next call on. Any number of slots and detections: the caps are the kernel's (its LDS), not the rule's."""
+    out_boxes = np.array(boxes, dtype=np.int32).reshape(-1, 4)
+    out_flags = np.array(flags, dtype=np.int32).reshape(-1)
+    out_index = np.array(image_index, dtype=np.int32).reshape(-1)
+    out_misses = None if misses is None else np.array(misses, dtype=np.int32).reshape(-1)
+    dets = np.asarray(det_boxes, dtype=np.int32).reshape(-1, 4)
+    det_frames = np.asarray(det_index, dtype=np.int32).reshape(-1)
+    n, m = len(out_boxes), len(dets)
+    if len(out_flags) != n or len(out_index) != n or (out_misses is not None and len(out_misses) != n):
+        raise ValueError(f"flags / image_index / misses: expected {n} entries")
+    if len(det_frames) != m:
+        raise ValueError(f"det_index: expected {m} entries")
+    iou, n_frames = float(match_iou), int(n_frames)
+    if not 0.0 < iou <= 1.0:  # false for a NaN
+        raise ValueError(f"match_iou {match_iou} is outside (0, 1]")
+    if n_frames < 1:
+        raise ValueError(f"n_frames {n_frames} is below 1")
+    limit = -1 if max_misses is None else int(max_misses)
+    if limit >= 0 and out_misses is None:
+        raise ValueError(f"max_misses {max_misses} needs the misses it counts")
+    searched = None if frame_searched is None else np.asarray(frame_searched).reshape(-1)
+    if searched is not None and len(searched) != n_frames:
+        raise ValueError(f"frame_searched: expected {n_frames} entries")
+    real = m if count is None else min(max(int(count), 0), m)
+    assign, det_flags, spawned = np.full(m, -1, np.int32), np.zeros(m, np.int32), np.zeros(n, np.int32)
+
+    # int64 holds every value below: a corner is below 2^32 in magnitude, a side of the intersection below 2^31, an area below 2^62
+    s64, d64 = out_boxes.astype(np.int64), dets.astype(np.int64)
+    live = (out_flags == 0) & (s64[:, 2] > 0) & (s64[:, 3] > 0)
+    valid = (np.arange(m) < real) & (d64[:, 2] > 0) & (d64[:, 3] > 0) & (det_frames >= 0) & (det_frames < n_frames)
+    det_flags[~valid] = _lib.ASSIGN_FLAG_INVALID
+    det_flags[real:] = _lib.ASSIGN_FLAG_PADDING
+    iw = np.minimum((d64[:, 0] + d64[:, 2])[:, None], (s64[:, 0] + s64[:, 2])[None]) - np.maximum(d64[:, 0][:, None], s64[:, 0][None])
+    ih = np.minimum((d64[:, 1] + d64[:, 3])[:, None], (s64[:, 1] + s64[:, 3])[None]) - np.maximum(d64[:, 1][:, None], s64[:, 1][None])
+    both = valid[:, None] & live[None] & (det_frames[:, None] == out_index[None]) & (iw > 0) & (ih > 0)
+    inter = np.where(both, iw, 0) * np.where(both, ih, 0)
+    union = np.where(both, (d64[:, 2] * d64[:, 3])[:, None] + (s64[:, 2] * s64[:, 3])[None] - inter, 1)
+    passing = both & (inter.astype(np.float64) >= iou * union.astype(np.float64))  # int64 -> float64 rounds to nearest even, as the device's
+    covered = passing.any(axis=1)
+    pair_d, pair_s = np.nonzero(passing)  # ascending in (d, s)
+    # the exact ratio as one integer: two different ratios of numbers below 2^63 lie more than 2^-126 apart, so their floors at
+    # 128 fractional bits differ and keep their order, and equal ratios give equal floors. The sort is stable: ties stay in (d, s) order.
+    ratio = [(int(i) << 128) // int(u) for i, u in zip(inter[pair_d, pair_s], union[pair_d, pair_s])]
+    matched = np.zeros(n, bool)
+    for k in sorted(range(len(ratio)), key=lambda k: -ratio[k]):
+        d, s = int(pair_d[k]), int(pair_s[k])
+        if assign[d] < 0 and not matched[s]:
+            assign[d], matched[s] = s, True
+            if out_misses is not None:
+                out_misses[s] = 0
+            if refresh:
+                out_boxes[s] = dets[d]
+    vacant = [s for s in range(n) if not live[s]]  # free at entry, ascending
+    rank = 0
+    for d in range(m):
+        if not valid[d] or assign[d] >= 0:
+            continue
+        if covered[d]:
+            det_flags[d] = _lib.ASSIGN_FLAG_COVERED
+        elif rank < len(vacant):
+            s = vacant[rank]
+            rank += 1
+            out_boxes[s], out_index[s], out_flags[s], spawned[s] = dets[d], det_frames[d], 0, 1
+            if out_misses is not None:
+                out_misses[s] = 0
+            assign[d], det_flags[d] = s, _lib.ASSIGN_FLAG_SPAWNED
+        else:
+            det_flags[d] = _lib.ASSIGN_FLAG_FULL
+    if out_misses is not None:
+        for s in range(n):
+            if not live[s] or matched[s]:
+                continue
+            frame = int(out_index[s])
+            if searched is not None and not (0 <= frame < n_frames and searched[frame] != 0):
+                continue
+            seen = int(out_misses[s])
+            now = MISSES_MAX if seen >= MISSES_MAX else seen + 1
+            out_misses[s] = now
+            if limit >= 0 and now > limit:
+                out_flags[s] = _lib.TRACK_FLAG_RETIRED
+                out_boxes[s] = 0
+    return AssignedDetections(out_boxes, out_flags, out_index, out_misses, assign, det_flags, spawned)
 
 
 def check_boxes(shapes: Sequence[Tuple[int, int]], flat: np.ndarray, index: np.ndarray, factors, img_size: int) -> None:

@@ -1935,6 +1935,27 @@ dad3d_status dad3d_track_suppress_duplicates(int32_t* boxes, int32_t* flags, con
     return launch_suppress_duplicates(a, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_track_assign_detections(int32_t* boxes, int32_t* flags, int32_t* image_index, int32_t* misses, int n, const int32_t* det_boxes,
+                                           const int32_t* det_index, const int32_t* det_count, int m, const int32_t* frame_searched, int n_frames,
+                                           double match_iou, int refresh, int max_misses, int32_t* assign, int32_t* det_flags, int32_t* spawned,
+                                           int device, void* stream) {
+    const char* who = "dad3d_track_assign_detections";
+    DAD3D_REQUIRE(match_iou > 0.0 && match_iou <= 1.0, "%s: match_iou %g is outside (0, 1]", who, match_iou);  // false for a NaN
+    DAD3D_REQUIRE(n >= 0 && n <= DAD3D_TRACK_MAX_SLOTS, "%s: %d slots outside 0 .. %d", who, n, DAD3D_TRACK_MAX_SLOTS);
+    DAD3D_REQUIRE(m >= 0 && m <= DAD3D_TRACK_MAX_DETECTIONS, "%s: %d detections outside 0 .. %d", who, m, DAD3D_TRACK_MAX_DETECTIONS);
+    DAD3D_REQUIRE(n_frames >= 1, "%s: %d frames", who, n_frames);
+    DAD3D_REQUIRE(refresh == 0 || refresh == 1, "%s: refresh %d is neither 0 nor 1", who, refresh);
+    DAD3D_REQUIRE(max_misses < 0 || misses || n == 0, "%s: max_misses %d needs the misses it counts", who, max_misses);
+    DAD3D_REQUIRE(n == 0 || (boxes && flags && image_index && spawned), "%s: null slot argument", who);
+    DAD3D_REQUIRE(m == 0 || (det_boxes && det_index && assign && det_flags), "%s: null detection argument", who);
+    if (n == 0 && m == 0) return DAD3D_OK;
+    DeviceGuard guard(device);
+    DAD3D_REQUIRE(guard.ok, "cannot select HIP device %d", device);
+    AssignDetectionsArgs a{boxes, flags, image_index, misses, n, det_boxes, det_index, det_count, m, frame_searched, n_frames, match_iou,
+                           refresh, max_misses, assign, det_flags, spawned};
+    return launch_assign_detections(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_cube_region_loss(const float* pred, const float* target, int batch, int n_verts,
                                     const int32_t* region_ptr, const int32_t* region_idx, const float* region_weight,
                                     int n_regions, const int32_t* vert_ptr, const int32_t* vert_region,

@@ -771,6 +771,26 @@ struct SuppressDuplicatesArgs {
 };
 dad3d_status launch_suppress_duplicates(const SuppressDuplicatesArgs& a, hipStream_t s);
 
+// detections into tracks (track_assign.hip): match, spawn and retire slots in one launch
+struct AssignDetectionsArgs {
+    int32_t* boxes;        // [N][4] (x, y, w, h), in place
+    int32_t* flags;        // [N], in place
+    int32_t* image_index;  // [N], in place
+    int32_t* misses;       // [N], in place, or null
+    int n;                 // 0 .. DAD3D_TRACK_MAX_SLOTS
+    const int32_t* det_boxes;       // [M][4]
+    const int32_t* det_index;       // [M]
+    const int32_t* det_count;       // one word, or null: all M
+    int m;                          // 0 .. DAD3D_TRACK_MAX_DETECTIONS
+    const int32_t* frame_searched;  // [n_frames] or null: all
+    int n_frames;
+    double match_iou;
+    int refresh, max_misses;
+    int32_t *assign, *det_flags;  // [M]
+    int32_t* spawned;             // [N]
+};
+dad3d_status launch_assign_detections(const AssignDetectionsArgs& a, hipStream_t s);
+
 }  // namespace dad3d
 
 #include "uv_texture.hpp"

@@ -476,6 +476,46 @@ class FaceMeshPredictor:
         _lib.check(self._lib.dad3d_track_suppress_duplicates(boxes.data_ptr(), flags.data_ptr(), image_index.data_ptr(), n, float(merge_iou),
                                                              self.cuda_id, stream))
 
+    def assign_detections(self, boxes: torch.Tensor, flags: torch.Tensor, image_index: torch.Tensor, misses: Optional[torch.Tensor],
+                          det_boxes: torch.Tensor, det_index: torch.Tensor, n_frames: int, match_iou: float,
+                          count: Optional[torch.Tensor] = None, frame_searched: Optional[torch.Tensor] = None, refresh: bool = False,
+                          max_misses: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """A detector's boxes against tracked slots, on the device: `dad3d_track_assign_detections` on the current stream, ONE launch,
+        the rule of `boxes.assign_detections`. In place on the slot state -- `boxes` int32 `[N,4]`, `flags [N]`, `image_index [N]`
+        and `misses [N]` (or None: nothing is counted, nothing retires) -- from `det_boxes` int32 `[M,4]`, `det_index [M]`, `count`
+        (an int32 tensor of one element on the device: how many detections are real; None: all) and `frame_searched [n_frames]` (None:
+        every frame). All contiguous int32 tensors on this device; at most `_lib.TRACK_MAX_SLOTS` slots and
+        `_lib.TRACK_MAX_DETECTIONS` detections (the kernel's limits). -> (assign `[M]`, det_flags `[M]`, spawned `[N]`), new device
+        tensors. Nothing is read on the host. `match_iou` and `max_misses` are the caller's choices; nobody has tuned them."""
+        n, m, n_frames = boxes.shape[0], det_boxes.shape[0], int(n_frames)
+        if not 0.0 < float(match_iou) <= 1.0:  # false for a NaN
+            raise ValueError(f"match_iou {match_iou} is outside (0, 1]")
+        if n > _lib.TRACK_MAX_SLOTS or m > _lib.TRACK_MAX_DETECTIONS:
+            raise ValueError(f"{n} slots and {m} detections: one launch takes {_lib.TRACK_MAX_SLOTS} and {_lib.TRACK_MAX_DETECTIONS}")
+        if n_frames < 1:
+            raise ValueError(f"n_frames {n_frames} is below 1")
+        if max_misses is not None and int(max_misses) >= 0 and misses is None:
+            raise ValueError(f"max_misses {max_misses} needs the misses it counts")
+        for name, t, shape in (("boxes", boxes, (n, 4)), ("flags", flags, (n,)), ("image_index", image_index, (n,)), ("misses", misses, (n,)),
+                               ("det_boxes", det_boxes, (m, 4)), ("det_index", det_index, (m,)), ("count", count, None),
+                               ("frame_searched", frame_searched, (n_frames,))):
+            if t is None and name in ("misses", "count", "frame_searched"):
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() \
+                    or (tuple(t.shape) != shape if shape is not None else t.numel() != 1):
+                raise ValueError(f"{name}: expected a contiguous int32 tensor {list(shape) if shape else '[1]'} on {self.device}, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        assign = torch.empty((m,), dtype=torch.int32, device=self.device)
+        det_flags = torch.empty((m,), dtype=torch.int32, device=self.device)
+        spawned = torch.empty((n,), dtype=torch.int32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.dad3d_track_assign_detections(
+            boxes.data_ptr(), flags.data_ptr(), image_index.data_ptr(), ptr(misses), n, det_boxes.data_ptr(), det_index.data_ptr(), ptr(count), m,
+            ptr(frame_searched), n_frames, float(match_iou), int(bool(refresh)), -1 if max_misses is None else int(max_misses),
+            assign.data_ptr(), det_flags.data_ptr(), spawned.data_ptr(), self.cuda_id, stream))
+        return assign, det_flags, spawned
+
     def _dev_int32(self, values: Any, n: Optional[int], name: str) -> torch.Tensor:
         """Integers as a contiguous int32 tensor `[n]` on this device: a tensor is converted where it lies, host values are uploaded."""
         t = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values).reshape(-1).astype(np.int32))

@@ -130,9 +130,17 @@ class OneEuroFilter:
                                                  self.state_dx.data_ptr(), self.age.data_ptr(), self.device.index, stream))
         return out
 
-    def reset(self, rows: Any = None) -> None:
+    def reset(self, rows: Any = None, mask: Optional[torch.Tensor] = None) -> None:
         """The tracks of `rows` (device or host indices; None: all) restart at their next sample. Device rows are never read on the
-        host: one outside 0 .. n - 1 moves nothing. Nothing waits."""
+        host: one outside 0 .. n - 1 moves nothing. `mask` instead of `rows`: a tensor `[n]` on the device, the rows where it is
+        not 0 (the `spawned` of `dad3d_track_assign_detections`): one masked fill, no index list. Nothing waits."""
+        if mask is not None:
+            if rows is not None:
+                raise ValueError("reset: rows or mask, not both")
+            if not torch.is_tensor(mask) or mask.device != self.device or tuple(mask.shape) != (self.n,) or mask.is_floating_point():
+                raise ValueError(f"mask: expected an integer or bool tensor [{self.n}] on {self.device}")
+            self.age.masked_fill_(mask != 0, 0)
+            return
         if rows is None:
             self.age.zero_()
             return

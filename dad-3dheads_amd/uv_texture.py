@@ -407,9 +407,21 @@ class TextureAccumulator:
         """Size the creator's buffers for `n` heads a call, so that a later `add` can be captured in a graph."""
         self.creator.reserve(int(n))
 
-    def reset(self, slots=None) -> None:
+    def reset(self, slots=None, mask=None) -> None:
         """Zeros and score -1 for all slots (None) or the given ones (a sequence or an int64 CUDA tensor): what a caller does beside
-        `HeadTracker.reseed`. No host read."""
+        `HeadTracker.reseed`. `mask` instead of `slots`: an integer or bool tensor `[k]`, k <= n_slots, on the device; slot i < k is
+        reset where the mask is not 0 (what `HeadTracker.update` does with the slots it spawned): masked fills, no index list. No
+        host read."""
+        if mask is not None:
+            dev = self.textures.device
+            if slots is not None:
+                raise ValueError("reset: slots or mask, not both")
+            if not isinstance(mask, Tensor) or mask.device != dev or mask.ndim != 1 or mask.shape[0] > self.n_slots or mask.is_floating_point():
+                raise ValueError(f"mask: expected an integer or bool tensor [k <= {self.n_slots}] on {dev}")
+            k, on = mask.shape[0], mask != 0
+            self.textures[:k].masked_fill_(on.view(k, 1, 1, 1), 0)
+            self.score[:k].masked_fill_(on.view(k, 1, 1), -1.0)
+            return
         if slots is None:
             self.textures.zero_()
             self.score.fill_(-1.0)

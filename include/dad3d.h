@@ -1263,6 +1263,70 @@ DAD3D_EXPORT dad3d_status dad3d_one_euro_rows(const float* x, int64_t x_stride, 
 DAD3D_EXPORT dad3d_status dad3d_track_suppress_duplicates(int32_t* boxes, int32_t* flags, const int32_t* image_index, int n,
                                  double merge_iou, int device, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detections into tracks (csrc/track_assign.hip): what a caller's detector found, as a padded buffer of boxes and a count on the
+ * device, against the tracker's slots. ONE launch, no value is read on the host: detections are matched to live slots, unmatched
+ * ones get a free slot, live slots the detector has not confirmed for a while are retired, and the assignment is reported. Still no
+ * detector and no appearance. Held word for word to its numpy statement (boxes.assign_detections); built with -ffp-contract=off.
+ *
+ * dad3d_track_assign_detections  DEVICE pointers; all boxes int32 (x, y, w, h); every sum and product of coordinates in int64.
+ *   Slot state, read and written in place:
+ *     boxes           int32 [n][4]
+ *     flags           int32 [n]: DAD3D_TRACK_FLAG_*
+ *     image_index     int32 [n]: the frame of each slot
+ *     misses          int32 [n] or NULL: the consecutive calls in which a slot was searched for and not confirmed
+ *   Detections, read only:
+ *     det_boxes       int32 [m][4]
+ *     det_index       int32 [m]: the frame of each detection
+ *     det_count       one int32 or NULL: count = m if NULL, else *det_count clamped to [0, m]; the rest is padding
+ *     frame_searched  int32 [n_frames] or NULL: non-zero where the detector looked; NULL: everywhere
+ *   Written in full: assign int32 [m], det_flags int32 [m] (DAD3D_ASSIGN_FLAG_*), spawned int32 [n].
+ *   The rule, in this order:
+ *     1. A slot is LIVE if flags == 0 and w > 0 and h > 0, as it stands at entry; every other slot is FREE.
+ *     2. A detection k >= count is padding: assign -1, DAD3D_ASSIGN_FLAG_PADDING. One with w <= 0, h <= 0 or det_index outside
+ *        [0, n_frames) is invalid: assign -1, DAD3D_ASSIGN_FLAG_INVALID.
+ *     3. A pair (valid detection d, live slot s) PASSES if both are in the same frame and
+ *            inter > 0  and  double(inter) >= match_iou * double(union)
+ *        with inter and union as in dad3d_track_suppress_duplicates: one rounded product, no division.
+ *     4. One-to-one, greedy, best IoU first: the passing pairs sorted by the exact ratio inter / union, descending (ratios are
+ *        compared as the 128-bit products inter_a * union_b and inter_b * union_a), ties by the lower detection, then the lower
+ *        slot; walking that list, a pair is taken if neither its detection nor its slot is taken. Best-first, not "the first slot
+ *        that passes", which swaps the identities of two neighbouring heads whose boxes overlap.
+ *     5. A taken pair: assign[d] = s, det_flags[d] = 0, misses[s] = 0; with refresh the slot's box becomes the detection's.
+ *     6. An unmatched valid detection that passes with ANY live slot, matched or not: assign -1, DAD3D_ASSIGN_FLAG_COVERED. It
+ *        spawns nothing: its head has a track.
+ *     7. The other unmatched valid detections are spawn candidates, in detection order; the r-th takes the r-th slot that was free
+ *        at entry, in slot order: the slot gets the detection's box and frame, flags 0, misses 0, spawned 1; the detection
+ *        assign = slot and DAD3D_ASSIGN_FLAG_SPAWNED. Candidates beyond the free slots: assign -1, DAD3D_ASSIGN_FLAG_FULL. Two
+ *        unmatched detections that overlap each other both spawn: that is the detector's own NMS to prevent, and
+ *        dad3d_track_suppress_duplicates takes what is left.
+ *     8. A slot that was live at entry, is unmatched, and whose frame was searched (frame_searched is NULL, or image_index is in
+ *        [0, n_frames) and its word is non-zero) gets misses = min(misses + 1, 2^30). If max_misses >= 0 and the new count exceeds
+ *        it, the slot is retired: flags = DAD3D_TRACK_FLAG_RETIRED, box (0, 0, 0, 0); it is free from the next call on, and until
+ *        then an ordinary lost slot. A live unmatched slot whose frame was not searched is untouched. Without misses (NULL) nothing
+ *        is counted and nothing retires.
+ *     9. spawned[s] = 0 for every slot that did not spawn.
+ *   No other word is written. A matched slot is the same head: nothing else of it changes.
+ *   n <= DAD3D_TRACK_MAX_SLOTS and m <= DAD3D_TRACK_MAX_DETECTIONS: one workgroup holds the pass bits in LDS. The allocation is
+ *   static, 160 072 bytes of the CU's 160 KiB whatever n and m are: 1024^2 / 8 bytes of pass bits, 16 KiB of slot boxes, 4 KiB of
+ *   slot frames, two lists of 1024 ints, 64 words of free masks, 16 of scan scratch and 2 round words. The detections are not staged.
+ *   DAD3D_E_INVALID before any launch: match_iou not finite or outside (0, 1]; n or m negative or beyond its cap; n_frames < 1;
+ *   refresh not 0 or 1; max_misses >= 0 with a null misses and n > 0; a null boxes, flags, image_index or spawned with n > 0; a null
+ *   det_boxes, det_index, assign or det_flags with m > 0. n == 0 is valid (every detection ends padding, invalid or FULL), m == 0
+ *   is valid (only step 8 runs and spawned is zeroed), both 0 launch nothing. */
+#define DAD3D_TRACK_MAX_DETECTIONS 1024
+/* Parenthesised as DAD3D_TRACK_FLAG_DUPLICATE is: set by dad3d_track_assign_detections alone. */
+#define DAD3D_TRACK_FLAG_RETIRED (0x40)
+#define DAD3D_ASSIGN_FLAG_PADDING 0x1
+#define DAD3D_ASSIGN_FLAG_INVALID 0x2
+#define DAD3D_ASSIGN_FLAG_COVERED 0x4
+#define DAD3D_ASSIGN_FLAG_SPAWNED 0x8
+#define DAD3D_ASSIGN_FLAG_FULL 0x10
+DAD3D_EXPORT dad3d_status dad3d_track_assign_detections(int32_t* boxes, int32_t* flags, int32_t* image_index, int32_t* misses /* or NULL */,
+                                 int n, const int32_t* det_boxes, const int32_t* det_index, const int32_t* det_count /* or NULL */, int m,
+                                 const int32_t* frame_searched /* or NULL */, int n_frames, double match_iou, int refresh, int max_misses,
+                                 int32_t* assign, int32_t* det_flags, int32_t* spawned, int device, void* stream);
+
 /* Single-image HOST entry points with the argument lists of Sim3DR/lib/rasterize.h:84-100 (`bool` spelled
  * `int` for C). libdad3d_hip.so additionally exports the C++-linkage symbols `_get_tri_normal`,
  * `_get_ver_normal`, `_get_normal`, `_rasterize_triangles`, `_rasterize` with the reference's exact
