@@ -128,6 +128,15 @@ static int decode_kernel_choice() {
     }();
     return choice;
 }
+// DAD3D_DECODE_KERNEL=halfblocks (read once per process, like the choice above): whole-mesh launches of 33..64 rows stay on the pipelined
+// kernel's two half-blocks instead of flame_decode_head.hip's 48 + 16 (A/B timing; the bits are the same: tests/test_gpu_decode_head.py).
+static bool decode_halfblocks_forced() {
+    static const bool forced = [] {
+        const char* e = getenv("DAD3D_DECODE_KERNEL");
+        return e && std::strcmp(e, "halfblocks") == 0;
+    }();
+    return forced;
+}
 
 // Every fragment of a basis pack in MFMA B-fragment order, [tile][group of 16 k][wave][lane][4 MFMA steps]: MFMA step s of group g has
 // lane (q = lane >> 4, n = lane & 15) of wave w supply basis row k = 16 g + 4 q + s of column 16 w + n (the k order inside a group is
@@ -631,7 +640,9 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
         pa.flags = flags & 0xFFu;
         pa.n_chunks = 1;
         if (!h->d_trace && (!proj || (flags & DAD3D_TO_2D))) pipe_chunking(pa.n_tiles, pa.n_half, &pa.chunk_half, &pa.n_chunks, &pa.wg_per_xcd);
-        st = launch_flame_decode_pipe(pa, s);
+        // 33..64 rows of the whole mesh with a vertex output: 48 rows under the basis stream, 16 behind it (flame_decode_head.hip; same bits)
+        const bool head = pa.chunk_half == 0 && batch > kPipeHalf && batch <= 2 * kPipeHalf && (verts3d || proj) && !decode_halfblocks_forced();
+        st = head ? launch_flame_decode_head(pa, s) : launch_flame_decode_pipe(pa, s);
     } else {
         DAD3D_REQUIRE(!h->d_trace || h->trace_capacity >= trace_entries_two_role(h, batch), "dad3d_flame_decode: the trace buffer holds %llu "
                       "entries, this launch stamps %llu (dad3d_flame_debug_trace_entries)", (unsigned long long)h->trace_capacity,

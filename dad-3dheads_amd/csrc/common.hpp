@@ -175,6 +175,9 @@ constexpr PipeGeom pipe_geom_unpack(unsigned w) {
 }
 dad3d_status launch_flame_decode_pipe(const PipeArgs& a, hipStream_t s);
 size_t flame_decode_pipe_lds_bytes();
+// The same decode for whole-mesh launches of 33..64 rows with a vertex output (flame_decode_head.hip): rows 0..47 multiply while the basis
+// streams in, rows 48..63 behind it. Same arguments (chunk_half = 0), same bits.
+dad3d_status launch_flame_decode_head(const PipeArgs& a, hipStream_t s);
 
 // The exact-product splits of the same decode (flame_decode_split.hip, round 6; gated: DAD3D_KERNEL_SPLIT_BF16 -- three bf16 planes, six
 // products -- and DAD3D_KERNEL_SPLIT_F16 -- two fp16 planes, three products). Two launches:

@@ -150,7 +150,10 @@ __device__ __forceinline__ void gemm_groups(const float* afrag, const float4 (&b
 // TO2D: `proj` is [B,V,2] (head_mesh.py:44-45 `to_2d`), else [B,V,3]. DAD3D_ZERO_ROTATION launches take the two-role kernel.
 // (Measured and dropped, profiles/r04_kernel_log.md: a launch of 33..64 images as ONE pass of four row blocks over both A images,
 // all eight waves finishing both half-blocks -- 13.2 us at B = 64 against 12.8 for the two-phase pipeline: every store of the
-// launch then leaves at the very end. And profiles/r07_kernel_log.md: the LAST half-block as two row blocks of 16 images with a barrier
+// launch then leaves at the very end. Round 4's "48 + 16" -- three row blocks under the basis stream, one behind it -- lost there too, because it
+// kept all 26 basis requests in front of the first MFMA; with the requests as an issue-ahead ring it wins 0.8 us at B = 64 and 2 us at 33..48 and
+// is what whole-mesh launches of 33..64 rows with a vertex output now take: flame_decode_head.hip, profiles/r10_kernel_log.md (capi.cpp sends
+// them there; DAD3D_DECODE_KERNEL=halfblocks keeps them here). And profiles/r07_kernel_log.md: the LAST half-block as two row blocks of 16 images with a barrier
 // between them, rows 0..15 finished inside row block 1's GEMM and only rows 16..31 behind A(H - 1) -- bit-identical, 12.50 against 12.47 us
 // at B = 64 on top of the write-through landmark stores, 12.78 against 12.68 alone: the tail behind the last barrier is ~1.5 k cycles of
 // latency whether a lane finishes one vertex or two, and two chains of 104 dependent MFMAs are slower than one of 208 independent pairs.)

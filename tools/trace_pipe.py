@@ -9,7 +9,11 @@ stager waves: 1 first loads issued | 2 A(0) published (3, 4: constants round 0 b
 First four half-blocks h: 16+4h before the GEMM / phase start, 17+4h accumulators parked / A(h+1) written, 18+4h past the barrier / next loads
 issued, 19+4h (stagers) past the barrier.
 (Builds before profiles/r08_kernel_log.md wrote the round between groups 6 and 7 of the first GEMM, in front of a barrier of its own: there slot 1
-is also "first seven MFMA groups done". Launches of one half-block still do. A slot a build does not stamp prints as n/a.)"""
+is also "first seven MFMA groups done". Launches of one half-block still do. A slot a build does not stamp prints as n/a.)
+Whole-mesh launches of 33..64 rows take flame_decode_head.hip (48 rows under the basis stream, then 16; DAD3D_DECODE_KERNEL=halfblocks: the two
+half-blocks above). Same slots: 16 up-front basis requests issued | 8 first MFMA | 2, 17 pass 1 multiplied, parked | 18 past barrier P1 |
+20, 21 pass 2 start, parked | 22, 3 past barrier P2. Stagers: 16, 17 rows 48..63 requested, written | 18, 19 at / past P1 | 21 rows 32..47
+finished | 23 past P2. The half-block lines below then read: half-block 0 = pass 1, half-block 1 = pass 2."""
 import os
 import sys
 
@@ -56,6 +60,13 @@ for h in range(min(4, (batch + 31) // 32)):
     print(f"  half-block {h}: GEMM start {a[0]:.0f}/{b[0]:.0f}  parked {a[1]:.0f}/{b[1]:.0f} (GEMM incl. the previous half-block's epilogue {a[1] - a[0]:.0f})  "
           f"past barrier {a[2]:.0f}/{b[2]:.0f} (wait {a[2] - a[1]:.0f})")
 print(f"  last half-block finished by all eight waves: {med(0, 5) - med(0, 3):.0f} cycles")
+if t[:, 0, 8].any():  # the 48 + 16 kernel of whole-mesh launches of 33..64 rows (flame_decode_head.hip) stamps its first MFMA
+    print(f"  48 + 16: up-front basis requests issued {med(0, 16):.0f} / {med(3, 16):.0f}; first MFMA {med(0, 8):.0f} / {med(3, 8):.0f}; "
+          f"pass 1 (rows 0..47) multiplied {med(0, 2):.0f} / {med(3, 2):.0f}, parked {med(0, 17):.0f} / {med(3, 17):.0f}; "
+          f"pass 2 (rows 48..63) start {cyc(med(0, 20))} / {cyc(med(3, 20))}, parked {cyc(med(0, 21))} / {cyc(med(3, 21))}; "
+          f"last barrier passed {med(0, 3):.0f} / {med(3, 3):.0f}")
+    print(f"  48 + 16 stagers (wave 4): rows 48..63 requested {cyc(med(4, 16))}, written {cyc(med(4, 17))}; at barrier P1 {med(4, 18):.0f}, past it {med(4, 19):.0f}; "
+          f"rows 32..47 finished {cyc(med(4, 21))}; past barrier P2 {cyc(med(4, 23))}")
 print("stager waves (wave 4 / wave 7):")
 print(f"  first loads issued {med(4, 1):.0f} / {med(7, 1):.0f}; past the first barrier {med(4, 6):.0f}; first part of A(0) published {med(4, 7):.0f}; "
       f"constants round 0 begun {cyc(med(4, 3))} / {cyc(med(7, 3))}, written {cyc(med(4, 4))} / {cyc(med(7, 4))}; A(0) published {med(4, 2):.0f}; end {med(4, 5):.0f}")
