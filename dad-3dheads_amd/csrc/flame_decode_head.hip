@@ -7,9 +7,13 @@
 //   pass 1  rows 0..47 as THREE row blocks of 16 images against each basis group as it lands: 12 MFMAs per group instead of 8 under the
 //           stream. The basis requests are an issue-ahead ring: DAD3D_HEAD_DEPTH of them up front, then one per k-group between the MFMAs,
 //           so the first MFMA waits for group 0 and not for 26 issues, and a stager's request never stands behind the whole slice.
+//           A step's request and its LDS reads of the next A fragments stand BETWEEN the step's MFMAs: a wave issues in order, in one
+//           clump in front of the step they cost ~50 cycles of matrix pipe a step, which is what looked like a wait for the stream.
 //           The stagers ask for slab 0 (k 0..127) of the 48 rows in front of the start-up barrier and for the rest behind it.
 //   pass 2  (B > 48) rows 48..63 as ONE row block, a chain of 104 dependent MFMAs. Rows 0..31 are finished in its hooks by the mma waves
-//           (the pipelined kernel's hook layout and pieces), rows 32..47 by the stagers, which have nothing else to do.
+//           (the pipelined kernel's hook layout and its first two pieces), rows 32..47 and vertices 16..19 of rows 0..31 (the half-empty
+//           third piece) by the stagers, which have nothing else to do. Multiplying part of this chain inside pass 1 was measured and
+//           loses: profiles/r11_kernel_log.md.
 //   tail    all eight waves finish rows 48..63 -- or rows 0..47 when B <= 48: there is no pass 2 then.
 //
 // Every accumulator sums G = 0..25, s = 0..3 from zero and every (vertex, image) goes through finish_vertex (flame_pipe_epilogue.hpp) with
@@ -29,11 +33,28 @@
 #define DAD3D_HEAD_R0_AT 1  // behind the last of them: 0.05-0.2 us slower at every size
 #endif
 
+#ifndef DAD3D_HEAD_SPREAD  // 1: pass 1 issues a step's basis request and LDS reads between its MFMAs; 0: all in front of the step's first MFMA
+#define DAD3D_HEAD_SPREAD 1
+#endif
+#ifndef DAD3D_HEAD_SPREAD_REQ_AT  // the MFMA row (s = 0..3, three MFMAs each) behind which the request goes: 2 never lost, 0 and 1 read 0.05-0.1 us slower
+#define DAD3D_HEAD_SPREAD_REQ_AT 2
+#endif
+#ifndef DAD3D_HEAD_SPREAD_LDS_AT  // ... and the three LDS reads go; 4: one read behind each MFMA of row 0 (0.03-0.1 us better than all behind row 0 at 49..64)
+#define DAD3D_HEAD_SPREAD_LDS_AT 4
+#endif
+#ifndef DAD3D_HEAD_V16_STAGERS  // 1: vertices 16..19 of rows 0..31 (B > 48) are finished by the stagers, which wait at P2, not in the chain's last hook
+#define DAD3D_HEAD_V16_STAGERS 1
+#endif
+
 namespace dad3d {
 
 namespace {
 
 using namespace pipe;
+constexpr bool kSpread = DAD3D_HEAD_SPREAD != 0;
+constexpr int kSpreadReqAt = DAD3D_HEAD_SPREAD_REQ_AT, kSpreadLdsAt = DAD3D_HEAD_SPREAD_LDS_AT;
+constexpr bool kV16Stagers = DAD3D_HEAD_V16_STAGERS != 0;
+static_assert(kSpreadReqAt >= 0 && kSpreadReqAt < 4 && kSpreadLdsAt >= 0 && kSpreadLdsAt <= 4, "rows of a step's MFMAs");
 
 constexpr int KG = kPipeKGroups;       // MFMA groups of 16 k
 constexpr int TV = kPipeTileVerts;     // vertices per tile
@@ -160,6 +181,19 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
                                     live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
         }
     };
+    // fin_v16: vertices 16..19 of rows 8 w .. 8 w + 7, lanes 0..31 = (row of eight, vertex of four): the hooks' third piece
+    auto fin_v16 = [&](int w) {
+        const int fu = (lane >> 3) & 3, j = fu + 16, b = 8 * w + (lane & 7);
+        const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
+        const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3], c4 = cp[4], c5 = cp[5];
+        const float* ot = otile + b * OS;
+        const float jx = ot[kJawCol], jy = ot[kJawCol + 1], jz = ot[kJawCol + 2];
+        const unsigned vrow = (unsigned)b * (unsigned)a.n_verts + (unsigned)(v0 + fu), bnl = (unsigned)b * nl;
+        const float4 t = vt_lds[j];
+        const bool live = lane < 32 && v0 + j < a.n_verts;  // (b < 32 < B)
+        finish_vertex<TO2D, 16>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * j], ot[3 * j + 1], ot[3 * j + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
+                                live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
+    };
     auto fin2 = [&](int row0) {
         const int fi = lane & 1, fu = min(lane >> 1, TV - 1), b = row0 + 2 * wave + fi;
         const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
@@ -254,6 +288,8 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         if (two) {
             fin4(32, fw);  // rows 32..47, while the mma waves multiply rows 48..63 and finish rows 0..31
             stamp(21);
+            if (kV16Stagers) fin_v16(fw);  // ... but for their vertices 16..19
+            stamp(9);
             phase_barrier();  // P2
             stamp(23);
             fin2(kRows1);
@@ -341,13 +377,21 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         for (int m = 0; m < 3; ++m) af[m] = *reinterpret_cast<const float4*>(afrag0 + m * 16 * LD);
 #pragma unroll
         for (int G = 0; G < KG; ++G) {
-            if (G + D < KG) bq[G + D] = bsrc[(size_t)(G + D) * 256];
+            // The step's request and its three LDS reads each stand behind a row of three MFMAs (kSpread), not all in front of the step:
+            // a wave issues in order, and only what is issued while an MFMA still runs costs the matrix pipe nothing.
+            auto request = [&]() {
+                if (G + D < KG) bq[G + D] = bsrc[(size_t)(G + D) * 256];
+            };
+            auto next_a = [&]() {
+                if (G + 1 < KG) {
+#pragma unroll
+                    for (int m = 0; m < 3; ++m) an[m] = *reinterpret_cast<const float4*>(afrag0 + m * 16 * LD + 16 * (G + 1));
+                }
+            };
+            if (!kSpread) request();
             if (G + 1 == 8) wait_ge(parts + 1, 4);
             if (G + 1 == 16) wait_ge2(parts + 2, 6, parts + 3, 4);
-            if (G + 1 < KG) {
-#pragma unroll
-                for (int m = 0; m < 3; ++m) an[m] = *reinterpret_cast<const float4*>(afrag0 + m * 16 * LD + 16 * (G + 1));
-            }
+            if (!kSpread) next_a();
             __builtin_amdgcn_sched_barrier(0);
             if (G == 0) stamp(8);  // first MFMA: basis group 0 and slab 0 are here
 #pragma unroll
@@ -357,6 +401,21 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
                 for (int m = 0; m < 3; ++m) {
                     const float av = s == 0 ? af[m].x : s == 1 ? af[m].y : s == 2 ? af[m].z : af[m].w;
                     acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[m], 0, 0, 0);
+                    if (kSpread && kSpreadLdsAt == 4 && s == 0 && G + 1 < KG) {  // (4: one read behind each MFMA of row 0)
+                        __builtin_amdgcn_sched_barrier(0);
+                        an[m] = *reinterpret_cast<const float4*>(afrag0 + m * 16 * LD + 16 * (G + 1));
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if (kSpread && s == kSpreadReqAt) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    request();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (kSpread && s == kSpreadLdsAt) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    next_a();
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -435,8 +494,11 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
                 epi_fetch(0);
             }
             if (G == 3) epi_finish(0), epi_fetch(1);
-            if (G == 11) epi_finish(1), epi_fetch(2);
-            if (G == 19) epi_finish(2);
+            if (G == 11) {
+                epi_finish(1);
+                if (!kV16Stagers) epi_fetch(2);
+            }
+            if (G == 19 && !kV16Stagers) epi_finish(2);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
