@@ -49,6 +49,7 @@ ASSIGN_FLAG_PADDING, ASSIGN_FLAG_INVALID, ASSIGN_FLAG_COVERED, ASSIGN_FLAG_SPAWN
 FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0x2, 4096, 65535
 RENDER_REVERSE, RENDER_CLEAR = 1, 2
 BAKE_FLAG_INDEX = 0x1
+POSE_FLAG_NONFINITE, POSE_FLAG_DEGENERATE, POSE_FLAG_GIMBAL, POSE_FLAG_INDEX = 0x1, 0x2, 0x4, 0x8
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -208,6 +209,10 @@ SIGNATURES = {
     "dad3d_jpeg_encode_host": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_int64, _P, _P]),
     "dad3d_overlay_segments": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _U, _I, _I, _P]),
     "dad3d_overlay_discs": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _U, _I, _P]),
+    "dad3d_head_pose": (_I, [_P, _I, C.c_int64, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "dad3d_head_pose_host": (_I, [_P, _I, C.c_int64, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "dad3d_procrustes": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "dad3d_procrustes_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "dad3d_sim3dr_get_tri_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_ver_normal": (None, [_P, _P, _P, _I, _I]),
     "dad3d_sim3dr_get_normal": (None, [_P, _P, _P, _I, _I]),

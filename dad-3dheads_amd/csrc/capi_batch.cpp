@@ -371,4 +371,66 @@ dad3d_status dad3d_eval_z5_ranks(const float* gt_head, const float* pred_head, i
     return launch_eval_z5(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- head pose and similarity alignment (head_pose.hip) -----------------------------------------------------------------
+static dad3d_status head_pose_check(const char* who, const float* params, int n, int64_t row_stride, int rot_offset, const int64_t* frames,
+                                    int n_frames, const int32_t* image_index, int h, int w, const double* rpy, const float* points) {
+    DAD3D_REQUIRE(n >= 0 && row_stride >= 0 && rot_offset >= 0, "%s: negative size (n %d, row_stride %lld, rot_offset %d)", who, n,
+                  (long long)row_stride, rot_offset);
+    if (n == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(params, "%s: null params", who);
+    DAD3D_REQUIRE(aligned(params, 4) && aligned(rpy, 8) && aligned(points, 4), "%s: params / rpy / points are not aligned to their elements", who);
+    DAD3D_REQUIRE((frames != nullptr) == (image_index != nullptr), "%s: the frame table and image_index come together", who);
+    DAD3D_REQUIRE(!frames || n_frames >= 0, "%s: n_frames %d is negative", who, n_frames);
+    DAD3D_REQUIRE(!points || frames || (h >= 1 && w >= 1), "%s: points need a frame table or one frame size, got %d x %d", who, h, w);
+    return DAD3D_OK;
+}
+
+dad3d_status dad3d_head_pose(const float* params, int n, int64_t row_stride, int rot_offset, const int64_t* frames, int n_frames,
+                             const int32_t* image_index, int h, int w, float* rotation, double* rpy, float* points, int32_t* flags,
+                             int device, void* stream) {
+    const dad3d_status st = head_pose_check("dad3d_head_pose", params, n, row_stride, rot_offset, frames, n_frames, image_index, h, w, rpy, points);
+    if (st != DAD3D_OK || n == 0) return st;
+    DAD3D_SELECT_DEVICE(device);
+    HeadPoseArgs a{params, (long long)row_stride, rot_offset, n, reinterpret_cast<const long long*>(frames), image_index, n_frames, h, w,
+                   rotation, rpy, points, flags};
+    return launch_head_pose(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_head_pose_host(const float* params, int n, int64_t row_stride, int rot_offset, const int64_t* frames, int n_frames,
+                                  const int32_t* image_index, int h, int w, float* rotation, double* rpy, float* points, int32_t* flags) {
+    const dad3d_status st = head_pose_check("dad3d_head_pose_host", params, n, row_stride, rot_offset, frames, n_frames, image_index, h, w, rpy, points);
+    if (st != DAD3D_OK || n == 0) return st;
+    HeadPoseArgs a{params, (long long)row_stride, rot_offset, n, reinterpret_cast<const long long*>(frames), image_index, n_frames, h, w,
+                   rotation, rpy, points, flags};
+    head_pose_host(a);
+    return DAD3D_OK;
+}
+
+static dad3d_status procrustes_check(const char* who, const double* x, const double* y, int batch, int n_points, const double* b, const double* t,
+                                     const double* c, const int32_t* flags) {
+    DAD3D_REQUIRE(batch >= 0 && n_points >= 1, "%s: bad size (batch %d, n_points %d)", who, batch, n_points);
+    DAD3D_REQUIRE((long long)batch * n_points * 3 <= 0x7fffffffLL, "%s: %d x %d points are beyond 2^31 values", who, batch, n_points);
+    if (batch == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(x && y && b && t && c && flags, "%s: null argument", who);
+    DAD3D_REQUIRE(aligned(x, 8) && aligned(y, 8) && aligned(b, 8) && aligned(t, 8) && aligned(c, 8), "%s: float64 arrays must be 8-byte aligned", who);
+    return DAD3D_OK;
+}
+
+dad3d_status dad3d_procrustes(const double* x, const double* y, int batch, int n_points, double* b, double* t, double* c, int32_t* flags,
+                              int device, void* stream) {
+    const dad3d_status st = procrustes_check("dad3d_procrustes", x, y, batch, n_points, b, t, c, flags);
+    if (st != DAD3D_OK || batch == 0) return st;
+    DAD3D_SELECT_DEVICE(device);
+    ProcrustesArgs a{x, y, batch, n_points, b, t, c, flags};
+    return launch_procrustes(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_procrustes_host(const double* x, const double* y, int batch, int n_points, double* b, double* t, double* c, int32_t* flags) {
+    const dad3d_status st = procrustes_check("dad3d_procrustes_host", x, y, batch, n_points, b, t, c, flags);
+    if (st != DAD3D_OK || batch == 0) return st;
+    ProcrustesArgs a{x, y, batch, n_points, b, t, c, flags};
+    procrustes_host(a);
+    return DAD3D_OK;
+}
+
 }  // extern "C"

@@ -435,6 +435,34 @@ struct OverlayDiscsArgs {
 dad3d_status launch_overlay_segments(const OverlaySegmentsArgs& a, hipStream_t s);
 dad3d_status launch_overlay_discs(const OverlayDiscsArgs& a, hipStream_t s);
 
+// head pose and similarity alignment (head_pose.hip, pose_math.hpp): the same routines on the device and, `_host`, on the CPU
+struct HeadPoseArgs {
+    const float* params;        // row i's six rotation floats at params[i * row_stride + rot_offset ..]
+    long long row_stride;       // in floats
+    int rot_offset;
+    int n;
+    const long long* frames;    // [n_frames][4] {address, h, w, row stride}, or null: `h` x `w` for every row
+    const int* image_index;     // [n] with `frames`
+    int n_frames, h, w;
+    float* rotation;            // [n,3,3] or null
+    double* rpy;                // [n,3] or null
+    float* points;              // [n,10,2] or null
+    int* flags;                 // [n] or null
+};
+struct ProcrustesArgs {
+    const double* x;            // [B,n,3]
+    const double* y;            // [B,n,3]
+    int batch, n_points;
+    double* b;                  // [B]
+    double* t;                  // [B,3,3]
+    double* c;                  // [B,3]
+    int* flags;                 // [B]
+};
+dad3d_status launch_head_pose(const HeadPoseArgs& a, hipStream_t s);
+dad3d_status launch_procrustes(const ProcrustesArgs& a, hipStream_t s);
+void head_pose_host(const HeadPoseArgs& a);
+void procrustes_host(const ProcrustesArgs& a);
+
 // the rest of the reference's training objective (train_objective.hip): heatmap target, heatmap IoU, visibility landmark
 // loss, keypoint metrics
 struct HeatmapEncodeArgs {

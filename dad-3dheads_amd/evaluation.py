@@ -129,18 +129,26 @@ def procrustes(x: Tensor, y: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     return b, t, c
 
 
+_procrustes_host = procrustes  # `evaluate_batch` has an argument of the function's name
+
+
 def evaluate_batch(gt_vertices: Tensor, model_view: Tensor, projection: Tensor, bbox: Tensor, height: Tensor,
                    pred_lmk68_2d: Tensor, pred_vertices: Tensor, pred_counts: Tensor, pred_lmk7: Tensor, pred_rotation: Tensor, *,
-                   landmarks: Landmarks68, head_indices: Tensor, face_indices: Tensor, z5: str = "reference") -> Dict[str, Tensor]:
+                   landmarks: Landmarks68, head_indices: Tensor, face_indices: Tensor, z5: str = "reference",
+                   procrustes: str = "host") -> Dict[str, Tensor]:
     """The four benchmark metrics of a batch of items on one device (module docstring).
 
     GT: gt_vertices [B,5023,3] MODEL-space fp32, model_view / projection [B,4,4], bbox [B,4], height [B].
     Prediction: pred_lmk68_2d [B,68,2], pred_vertices [B,Nmax,3] padded with pred_counts [B] valid rows, pred_lmk7 [B,7,3],
     pred_rotation [B,3,3]. All on the same CUDA device. Returns {"pose_error", "nme", "z5", "chamfer"}: float64 [B] on it.
     An item whose prediction cannot give a metric (short N for Z5, placeholders) gets a meaningless value there: the caller
-    decides which values count (`metrics_reached`)."""
+    decides which values count (`metrics_reached`). `procrustes="device"`: the alignment's 3x3 SVDs run where the landmarks lie
+    (`pose.procrustes_batch`), so the batch makes no copy and no wait; "host" (the default) runs them through torch on the CPU.
+    The two agree to a few float64 roundings, which can move the last bits of `chamfer` (the similarity is rounded to float32)."""
     if z5 not in ("reference", "knn"):
         raise ValueError(f"z5 must be 'reference' or 'knn', not {z5!r}")
+    if procrustes not in ("host", "device"):
+        raise ValueError(f"procrustes must be 'host' or 'device', not {procrustes!r}")
     dev = gt_vertices.device
     bsz = gt_vertices.shape[0]
     f32 = lambda t: t.to(dev, torch.float32).contiguous()  # noqa: E731
@@ -181,7 +189,11 @@ def evaluate_batch(gt_vertices: Tensor, model_view: Tensor, projection: Tensor, 
     scale = INTER_EYE_DIST / (lmk_w[:, 39] - lmk_w[:, 42]).norm(dim=-1)
     gt7 = scale[:, None, None] * lmk_w[:, list(SEVEN_OF_68)]  # = the 7 landmarks of the scaled mesh (linear in the mesh)
     pred7 = pred_lmk7.to(dev, torch.float32).double()
-    b, t, c = (x.to(dev) for x in procrustes(gt7.cpu(), pred7.cpu()))  # 3x3 SVDs on the host: the same bits in any batch
+    if procrustes == "device":  # one wave per item: the same bits in any batch, and nothing leaves the device
+        from .pose import procrustes_batch
+        b, t, c, _ = procrustes_batch(gt7, pred7)
+    else:
+        b, t, c = (x.to(dev) for x in _procrustes_host(gt7.cpu(), pred7.cpu()))  # 3x3 SVDs on the host: the same bits in any batch
     mu_x, mu_y = gt7.mean(1), pred7.mean(1)
     query = (scale[:, None, None] * world64[:, face_indices] - mu_x[:, None]).float()
     points = (pred_vertices.to(dev, torch.float32).double() - mu_y[:, None]).float()
@@ -229,10 +241,15 @@ class DADEvaluator:
     face_indices: the reference's `model_training/model/static/flame_indices/face.npy` (array or path; reference data, not
     shipped with this package). `z5="knn"` selects the README's nearest-neighbour Z5 (different numbers, module docstring).
     Skipped items are logged and listed in `self.warnings` as (id, reason). `reader="device"` reads both documents through
-    `json_reader.load`: the same trees, the arrays of numbers parsed on the GPU and gathered into the batch tensors there."""
+    `json_reader.load`: the same trees, the arrays of numbers parsed on the GPU and gathered into the batch tensors there.
+    `procrustes="device"`: `evaluate_batch`'s alignment on the GPU (no copy, no wait in the batch); the default stays "host"."""
 
     def __init__(self, ground_truth_path: str, submission_path: str, face_indices, z5: str = "reference", batch_size: int = 64,
-                 device: Optional[Union[int, torch.device]] = None, static: Optional[dict] = None, reader: str = "host"):
+                 device: Optional[Union[int, torch.device]] = None, static: Optional[dict] = None, reader: str = "host",
+                 procrustes: str = "host"):
+        if procrustes not in ("host", "device"):
+            raise ValueError(f"procrustes must be 'host' or 'device', not {procrustes!r}")
+        self.procrustes = procrustes
         if z5 not in ("reference", "knn"):
             raise ValueError(f"z5 must be 'reference' or 'knn', not {z5!r}")
         if reader not in ("host", "device"):
@@ -306,7 +323,7 @@ class DADEvaluator:
             pv, t(np.asarray(n_pts, dtype=np.int32), torch.int32),
             stack([field(p, "7_landmarks_3d", (7, 3)) for _, p, _ in items]),
             stack([field(p, "rotation_matrix", (3, 3)) for _, p, _ in items]),
-            landmarks=self.landmarks, head_indices=self._head, face_indices=self._face, z5=self.z5)
+            landmarks=self.landmarks, head_indices=self._head, face_indices=self._face, z5=self.z5, procrustes=self.procrustes)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def __call__(self) -> Tuple[Dict[str, float], Dict[str, Dict[str, Dict[Any, float]]]]:
@@ -366,8 +383,10 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     ap.add_argument("--z5", choices=("reference", "knn"), default="reference")
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--reader", choices=("host", "device"), default="host", help="device: parse the arrays of numbers of both files on the GPU")
+    ap.add_argument("--procrustes", choices=("host", "device"), default="host", help="device: the alignment's 3x3 SVDs on the GPU")
     args = ap.parse_args(argv)
-    ev = DADEvaluator(args.gt, args.submission, face_indices=args.face_indices, z5=args.z5, batch_size=args.batch_size, reader=args.reader)
+    ev = DADEvaluator(args.gt, args.submission, face_indices=args.face_indices, z5=args.z5, batch_size=args.batch_size, reader=args.reader,
+                      procrustes=args.procrustes)
     overall, attribute = ev()
     print(summary_text(overall, attribute))
     if ev.warnings:

@@ -500,16 +500,37 @@ def pose_points(rpy: RPY, h: int, w: int) -> np.ndarray:
     return np.array([centre] + ends + tips, dtype=np.int64)
 
 
-def draw_pose(predictions: Predictions, images: Images, out: Optional[Images] = None, image_index=None):
+def draw_pose(predictions: Predictions, images: Images, out: Optional[Images] = None, image_index=None, angles: str = "host"):
     """demo_utils.py:68-94: the head's three axes as arrows from the image centre, colours (0,0,255), (0,255,0), (255,0,0) in
     that order, thickness `int(h * 0.005)` (ValueError where that is 0). An arrow is three solid segments: the shaft, then the two
     tips from its end point. The angles come from `calculate_rpy`, which synchronises; the segment ends are float64 on the host.
-    `image_index`: as in `draw_landmarks`; every head's arrows start at the centre of its frame, as the reference draws them."""
+    `image_index`: as in `draw_landmarks`; every head's arrows start at the centre of its frame, as the reference draws them.
+    `angles="device"`: the point table comes from `pose.head_pose` (`dad3d_head_pose`: the same route to the angles, in a kernel)
+    and goes straight into the segment launch; no `calculate_rpy`, no wait. A row whose rotation is NaN / Inf or degenerate, on
+    which `calculate_rpy` raises, then draws ten points at the centre instead."""
+    if angles not in ("host", "device"):
+        raise ValueError(f"angles: 'host' or 'device', got {angles!r}")
     if image_index is not None:
-        return _by_frame(draw_pose, predictions, images, image_index, out)
+        return _by_frame(draw_pose, predictions, images, image_index, out, angles=angles)
     items, _ = _image_list(images)
     for t in items:
         pose_thickness(t.shape[0])
+    if angles == "device":
+        from .pose import head_pose
+
+        params = _field(predictions, "3dmm_params", len(items), 1)
+        if params.shape[1] != sum(FLAME_CONSTS.values()):
+            raise ValueError(f"params_3dmm: expected [B,{sum(FLAME_CONSTS.values())}], got shape {tuple(params.shape)}")
+
+        def device_tables_for(idx, h, w, device):
+            rows = params if idx == list(range(params.shape[0])) else params[torch.as_tensor(idx, device=params.device)]
+            return head_pose(rows.to(device), size=(h, w), want=("points",)).points
+
+        def device_launch(src, dst, tab, h, w):
+            _launch_segments(src, dst, tab, torch.from_numpy(_POSE_EDGES).to(src.device), torch.from_numpy(_POSE_SEGMENT_COLORS).to(src.device), 0,
+                             pose_thickness(h))
+
+        return _draw(images, out, device_tables_for, device_launch)
     rpy = calculate_rpy(_field(predictions, "3dmm_params", len(items), 1))
 
     def tables_for(idx, h, w, device):

@@ -154,12 +154,14 @@ class FaceMeshPredictor:
         res = self.predict_batch([x])[0]
         return res
 
-    def predict_tensor(self, images: torch.Tensor, landmarks_px: bool = True) -> Dict[str, torch.Tensor]:
+    def predict_tensor(self, images: torch.Tensor, landmarks_px: bool = True, pose: bool = False) -> Dict[str, torch.Tensor]:
         """Device-resident batch entry: uint8 RGB `[B, H, W, 3]` on this GPU, all images of one size -> device tensors
         `3dmm_params [B,413]`, `3d_vertices [B,5023,3]`, `projected_vertices [B,5023,2]`, `points [B,68,2]` int32
         and, when the head mesh was built with a landmark list, `landmarks [B,n,2]` int32. Nothing is copied to the
         host and nothing synchronises: normalisation, CNN, re-adjustment kernel and the fused decode are queued on
-        the current stream (the reference does `.cpu()` after the CNN, predictor.py:104, then decodes twice on the CPU)."""
+        the current stream (the reference does `.cpu()` after the CNN, predictor.py:104, then decodes twice on the CPU).
+        `pose=True` adds `rotation_matrix [B,3,3]` float32, `rpy [B,3]` float64 (roll, pitch, yaw in degrees) and `pose_flags [B]`
+        int32 (`_lib.POSE_FLAG_*`) from the returned params: one more launch (`pose.head_pose`), still no wait."""
         assert images.ndim == 4 and images.shape[-1] == 3 and images.dtype == torch.uint8 and images.is_cuda
         b, h, w = images.shape[:3]
         pads, scale, (nh, nw) = self._geometry((h, w))
@@ -180,20 +182,33 @@ class FaceMeshPredictor:
         pts = self._landmarks_68(out, (pads[2], pads[0], scale))  # predictor.py:106-112,147-152 on the device
         if pts is not None:
             res["points"] = pts
+        if pose:
+            res.update(self._pose_of(params))
         return res
 
+    @staticmethod
+    def _pose_of(params: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """`rotation_matrix`, `rpy` and `pose_flags` of params rows on the device (`dad3d_head_pose`, one launch, no wait):
+        `rot_mat_from_6dof` as the reference computes it and `calculate_rpy`'s angles."""
+        from .pose import head_pose
+
+        hp = head_pose(params, want=("rotation", "rpy"))
+        return {"rotation_matrix": hp.rotation, "rpy": hp.rpy, "pose_flags": hp.flags}
+
     def predict_batch(self, images: Sequence[np.ndarray], device_outputs: bool = False,
-                      points_on_device: bool = False) -> List[Dict[str, Any]]:
+                      points_on_device: bool = False, pose: bool = False) -> List[Dict[str, Any]]:
         """Batched predictor: list of HxWx3 uint8 RGB arrays (any sizes) -> list of the reference's result dicts. With
         `points_on_device` the `points` are int32 `[68,2]` device tensors; together with `device_outputs` the call makes no
-        host wait after the upload."""
+        host wait after the upload. `pose=True`: every dict gains `rotation_matrix` (float32 `[3,3]`, `rot_mat_from_6dof` of the
+        returned params), `rpy` (float64 `[3]`: roll, pitch, yaw in degrees, `calculate_rpy`'s values) and `pose_flags`
+        (`_lib.POSE_FLAG_*`), computed on the device: device tensors under `device_outputs`, else they come in the params' copy."""
         staged = []
         for im in images:
             if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
                 raise ValueError(f"expected uint8 RGB images [H,W,3], got {im.dtype} {im.shape}")
             staged.append(torch.from_numpy(np.ascontiguousarray(im)).to(self.device))
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.shape[1] * 3) for t in staged])
-        return self._results_of(batch, [im.shape[:2] for im in images], device_outputs, points_on_device)
+        return self._results_of(batch, [im.shape[:2] for im in images], device_outputs, points_on_device, pose)
 
     # -- frames and bounding boxes (model_training/data/flame_dataset.py:96-99; csrc/preprocess_boxes.hip) -------------------------
     def _input_format(self) -> int:
@@ -257,7 +272,7 @@ class FaceMeshPredictor:
         return out, crops, geometry, flags
 
     def predict_boxes(self, frames: Sequence[Any], boxes: Any, image_index: Any = None, offset: Any = 0.1,
-                      device_outputs: bool = False, points_on_device: bool = False) -> List[Dict[str, Any]]:
+                      device_outputs: bool = False, points_on_device: bool = False, pose: bool = False) -> List[Dict[str, Any]]:
         """The heads of frames from bounding boxes, in the frames' coordinates: one result dict per box, in box order, with the
         keys and shapes of `predict_batch` plus `"bbox"` (the crop used, int32 `[4]` as (x, y, w, h)), `"image_index"` and
         `"flags"` (`_lib.BOX_FLAG_*`). No detector is part of this: the boxes are the caller's.
@@ -274,11 +289,12 @@ class FaceMeshPredictor:
 
         A host box that the kernel would flag raises ValueError before anything is launched. Device boxes are never looked at on
         the host: flagged rows come back with their flags and with finite, meaningless values, and with `device_outputs` and
-        `points_on_device` nothing waits for the device (`bbox`, `image_index` and `flags` are then device tensors too)."""
-        return self._predict_boxes_staged(self._stage_frames(frames), boxes, image_index, offset, device_outputs, points_on_device)
+        `points_on_device` nothing waits for the device (`bbox`, `image_index` and `flags` are then device tensors too).
+        `pose=True`: `predict_batch`'s pose keys, from the params moved into the frame (the move does not touch the rotation)."""
+        return self._predict_boxes_staged(self._stage_frames(frames), boxes, image_index, offset, device_outputs, points_on_device, pose)
 
     def _predict_boxes_staged(self, frames: List[torch.Tensor], boxes: Any, image_index: Any, offset: Any, device_outputs: bool,
-                              points_on_device: bool) -> List[Dict[str, Any]]:
+                              points_on_device: bool, pose: bool = False) -> List[Dict[str, Any]]:
         factors = _boxes.offset_factors(offset)
         if torch.is_tensor(boxes):
             if not boxes.is_cuda or boxes.ndim != 2 or boxes.shape[1] != 4 or boxes.dtype == torch.bool or boxes.is_complex():
@@ -297,7 +313,7 @@ class FaceMeshPredictor:
             return []
         batched = self._predict_boxes_batched(frames, dev_boxes, dev_index, factors)
         crops, flags = batched["bbox"], batched["flags"]
-        results = self._rows_of(batched, device_outputs, points_on_device)
+        results = self._rows_of(batched, device_outputs, points_on_device, pose)
         if device_outputs and points_on_device:  # no wait: the side outputs stay where they are
             for i, r in enumerate(results):
                 r.update({"bbox": crops[i], "image_index": dev_index[i], "flags": flags[i]})
@@ -309,7 +325,7 @@ class FaceMeshPredictor:
 
     def predict_files(self, sources: Sequence[Any], device_outputs: bool = False, jpeg_entropy: str = "segments",
                       points_on_device: bool = False, boxes: Any = None, image_index: Any = None,
-                      offset: Any = 0.1) -> List[Dict[str, Any]]:
+                      offset: Any = 0.1, pose: bool = False) -> List[Dict[str, Any]]:
         """`predict_batch` fed with image files (paths or bytes, any sizes): PNG files and baseline JPEG files are decoded to RGB
         on the device (png_reader.PngDecoder, jpeg_reader.JpegDecoder, channels=3) and the decoded images go to the preprocess launch
         where they lie, so no decoded pixel crosses the bus. A source that starts FF D8 goes to the JPEG decoder, every other one
@@ -318,7 +334,7 @@ class FaceMeshPredictor:
         `np.asarray(Image.open(f).convert("RGB"))`, in the order of `sources`; what follows the preprocess launch is
         `predict_batch`'s own code. `jpeg_entropy` is `JpegDecoder`'s `entropy`: "sync" decodes a JPEG file without restart markers
         in pieces, to the same pixels. With `boxes` (and `image_index`, `offset`) the files are frames and the call is `predict_boxes`
-        on them."""
+        on them. `pose`: as in `predict_batch`."""
         from ._packed_files import bytes_of, read_back
         from .jpeg_reader import SOI, JpegDecoder
         from .png_reader import PngDecoder
@@ -337,24 +353,24 @@ class FaceMeshPredictor:
                     for i, t in zip(where, pending.finish(*words).tensors()):
                         decoded[i] = t
         if boxes is not None:  # the decoded frames stay on the device; the crops are read from them in place
-            return self._predict_boxes_staged(self._stage_frames(decoded), boxes, image_index, offset, device_outputs, points_on_device)
+            return self._predict_boxes_staged(self._stage_frames(decoded), boxes, image_index, offset, device_outputs, points_on_device, pose)
         batch = self._preprocess_launch([(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)) for t in decoded])
-        return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs, points_on_device)
+        return self._results_of(batch, [tuple(t.shape[:2]) for t in decoded], device_outputs, points_on_device, pose)
 
     def _results_of(self, batch: torch.Tensor, shapes: Sequence[Tuple[int, int]], device_outputs: bool,
-                    points_on_device: bool = False) -> List[Dict[str, Any]]:
+                    points_on_device: bool = False, pose: bool = False) -> List[Dict[str, Any]]:
         """What `predict_batch` does behind its preprocess launch, for images of the sizes `shapes` = [(h, w)]."""
         geo = [self._geometry(s) for s in shapes]
         # both uploads in front of the CNN. The points need the scale as the float64 it is (predictor.py:151); the params kernel reads float32
         pads_scale = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float32, device=self.device)
         geometry = torch.tensor([[g[0][2], g[0][0], g[1]] for g in geo], dtype=torch.float64).to(self.device)
-        return self._results_from(batch, pads_scale, geometry, device_outputs, points_on_device)
+        return self._results_from(batch, pads_scale, geometry, device_outputs, points_on_device, pose)
 
     def _results_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor, device_outputs: bool,
-                      points_on_device: bool) -> List[Dict[str, Any]]:
+                      points_on_device: bool, pose: bool = False) -> List[Dict[str, Any]]:
         """The CNN and everything behind it. `pads_scale` is what `_readjust` takes and `geometry` what `_landmarks_68` takes: for
         crops both are the float64 `[B,5]` geometry of `dad3d_preprocess_boxes`."""
-        return self._rows_of(self._batched_from(batch, pads_scale, geometry), device_outputs, points_on_device)
+        return self._rows_of(self._batched_from(batch, pads_scale, geometry), device_outputs, points_on_device, pose)
 
     def _batched_from(self, batch: torch.Tensor, pads_scale: torch.Tensor, geometry: torch.Tensor,
                       params_hook: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -381,19 +397,35 @@ class FaceMeshPredictor:
         v3d, proj, params = self._readjust_and_decode(params, pads_scale, True)
         return {"points": pts, "projected_vertices": proj, "3d_vertices": v3d, "3dmm_params": params}
 
-    @staticmethod
-    def _rows_of(batched: Dict[str, torch.Tensor], device_outputs: bool, points_on_device: bool) -> List[Dict[str, Any]]:
-        """One result dict per row of `_batched_from`'s tensors, copied to the host first unless the caller keeps them on the device."""
-        params = batched["3dmm_params"] if device_outputs else batched["3dmm_params"].cpu()
-        n = params.shape[0]
+    @classmethod
+    def _rows_of(cls, batched: Dict[str, torch.Tensor], device_outputs: bool, points_on_device: bool, pose: bool = False) -> List[Dict[str, Any]]:
+        """One result dict per row of `_batched_from`'s tensors, copied to the host first unless the caller keeps them on the device.
+        `pose`: the rows' `rotation_matrix`, `rpy` and `pose_flags` too, computed on the device from `3dmm_params`."""
+        dev_params = batched["3dmm_params"]
+        n = dev_params.shape[0]
+        extra: List[Dict[str, Any]] = [{} for _ in range(n)]
+        if pose:
+            found = cls._pose_of(dev_params)
+            rot, rpy, pflags = found["rotation_matrix"], found["rpy"], found["pose_flags"]
+            if device_outputs:
+                params = dev_params
+            else:  # the params' copy carries the pose: the rows' bytes side by side, cut apart on the host
+                packed = torch.cat([dev_params.view(torch.uint8), rot.reshape(n, 9).view(torch.uint8), rpy.view(torch.uint8),
+                                    pflags[:, None].view(torch.uint8)], dim=1).cpu()
+                parts = [part.contiguous() for part in packed.split([dev_params.shape[1] * 4, 36, 24, 4], dim=1)]
+                params = parts[0].view(torch.float32)
+                rot, rpy, pflags = parts[1].view(torch.float32).reshape(n, 3, 3), parts[2].view(torch.float64), parts[3].view(torch.int32)[:, 0].tolist()
+            extra = [{"rotation_matrix": rot[i], "rpy": rpy[i], "pose_flags": pflags[i]} for i in range(n)]
+        else:
+            params = dev_params if device_outputs else dev_params.cpu()
         if "points" not in batched:
-            return [{"3dmm_params": params[i : i + 1]} for i in range(n)]
+            return [{"3dmm_params": params[i : i + 1], **extra[i]} for i in range(n)]
         pts, proj, v3d = batched["points"], batched["projected_vertices"], batched["3d_vertices"]
         if not device_outputs:
             v3d, proj = v3d.cpu(), proj.cpu()
         if not points_on_device:
             pts = pts.cpu().numpy().astype(int)  # one copy; `astype(int)` is the reference's dtype (predictor.py:152)
-        return [{"points": pts[i], "projected_vertices": proj[i : i + 1], "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1]}
+        return [{"points": pts[i], "projected_vertices": proj[i : i + 1], "3d_vertices": v3d[i], "3dmm_params": params[i : i + 1], **extra[i]}
                 for i in range(n)]
 
     def _predict_boxes_batched(self, frames: List[torch.Tensor], dev_boxes: torch.Tensor, dev_index: torch.Tensor,

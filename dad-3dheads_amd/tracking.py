@@ -37,12 +37,14 @@ Assignment = namedtuple("Assignment", "assign det_flags spawned")  # what `HeadT
 
 class HeadTracker:
     def __init__(self, predictor, offset: Any = 0.1, subset: Any = None, min_side: int = 1, min_visible: float = 0.5,
-                 steady: Optional[SteadyConfig] = None, merge_iou: Optional[float] = None):
+                 steady: Optional[SteadyConfig] = None, merge_iou: Optional[float] = None, pose: bool = False):
         """`predictor`: a `FaceMeshPredictor`. `offset`: what `predict_boxes` widens every box by. `subset`: the vertex indices whose
         bounds are a head's next box (an index list such as the face or head lists of the metrics; None: all vertices, the head box
         the dataset's `bbox` and the training crop are about). `min_side`, `min_visible`: see `boxes.next_boxes`. `steady`: a
         `steady.SteadyConfig` to filter the params with, or None. `merge_iou` in (0, 1]: the IoU from which two slots of one frame
-        are one head, or None. With both None every result is what it is without them. Nothing is launched here."""
+        are one head, or None. With both None every result is what it is without them. `pose`: every result of `step` gains
+        `predict_boxes(.., pose=True)`'s `rotation_matrix`, `rpy` and `pose_flags`, on the device. Nothing is launched here."""
+        self.pose = bool(pose)
         if steady is not None and not isinstance(steady, SteadyConfig):
             raise ValueError(f"steady: expected a steady.SteadyConfig or None, got {type(steady).__name__}")
         if merge_iou is not None and not 0.0 < float(merge_iou) <= 1.0:  # false for a NaN
@@ -129,7 +131,8 @@ class HeadTracker:
         from it, and the new key `"3dmm_params_raw"` is the readjusted row before the filter (its tz as the network gave it). A row
         whose box is flagged passes unfiltered and restarts its track. `"points"` are the network's 2-D head's and are not
         filtered. The filter works in frame coordinates: if the frames change size (another video, another scale), call `reset()`.
-        With `merge_iou`: a duplicate slot has `TRACK_FLAG_DUPLICATE` in `"track_flags"`, so `"image_index"` -1."""
+        With `merge_iou`: a duplicate slot has `TRACK_FLAG_DUPLICATE` in `"track_flags"`, so `"image_index"` -1.
+        With `pose`: the pose keys come from `"3dmm_params"`, so with `steady` from the filtered row."""
         if self._boxes is None:
             raise ValueError("step: call start(frames, boxes) first")
         if len(frames) != self._n_frames:
@@ -153,7 +156,7 @@ class HeadTracker:
             pred._suppress_duplicates_launch(self._boxes, self._track_flags, self._index, self.merge_iou)
         track = self._track_flags.clone()  # the results keep this step's flags when the next step writes its own
         drawn = torch.where((flags | track) != 0, torch.full_like(self._index, -1), self._index)
-        results = pred._rows_of(batched, True, True)
+        results = pred._rows_of(batched, True, True, self.pose)
         for i, r in enumerate(results):
             r.update({"bbox": batched["bbox"][i], "image_index": drawn[i], "flags": flags[i], "track_flags": track[i]})
             if hook is not None:

@@ -777,6 +777,58 @@ DAD3D_EXPORT dad3d_status dad3d_overlay_discs(const uint8_t* src, uint8_t* dst, 
                                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Head pose where the params lie: the rotation matrix, (roll, pitch, yaw) and the arrows of `draw_pose`, one lane per row, and the
+ * similarity alignment of the scorer, one wave per item. Both rest on one float64 3x3 SVD (one-sided cyclic Jacobi, a fixed number
+ * of sweeps; csrc/pose_math.hpp). DESIGN.md 4.29.
+ *
+ * dad3d_head_pose   row i reads its six rotation floats at params[i * row_stride + rot_offset ..] (strides in floats: a [n,413]
+ *   tensor with rot_offset 403, a view of it, or a bare [n,6] with row_stride 6 and rot_offset 0) and writes whichever outputs are
+ *   not NULL:
+ *     rotation [n,3,3] float32  `rot_mat_from_6dof` (model_training/model/utils.py:92-101), columns b1 b2 b3, row-major; float32
+ *                               operation for operation: sqrt of the left-to-right sum of squares, clamped at 1e-12, three
+ *                               divisions, the two crosses
+ *     rpy      [n,3]   float64  roll, pitch, yaw in degrees (model_training/model/flame.py:254-264): the matrix transposed, its
+ *                               orthogonal polar factor, scipy's quaternion and `as_euler("xyz")` route, then limit_angle of
+ *                               (a[2], a[0] - 180, a[1])
+ *     points   [n,10,2] float32 the point table of the three arrows (demo_utils.py:73-92) for dad3d_overlay_segments: the frame's
+ *                               centre, the three ends (truncated), the six tip ends (rounded half to even)
+ *     flags    [n]     int32    0 or DAD3D_POSE_FLAG_*
+ *   The frame of a row's points: `frames` NULL: h x w for every row; else the DEVICE int64 table [n_frames][4] {address, h, w, row
+ *   stride} of dad3d_preprocess_boxes with the DEVICE int32 image_index [n] (only h and w are read; no pixel is).
+ *     NONFINITE   one of the six floats is NaN or +-inf
+ *     DEGENERATE  the polar factor is undefined: the smallest singular value is below 1e-6 or the determinant is <= 0 (a zero first
+ *                 vector, a second one parallel to it): the rows on which scipy raises
+ *     GIMBAL      the second Euler angle is within 1e-7 rad of +-90 degrees: the third angle is 0 by convention
+ *     INDEX       image_index outside [0, n_frames) or a frame without a size: rotation and rpy are written, points are all zero
+ *   A NONFINITE or DEGENERATE row gets NaN angles and all ten points at its frame's centre.
+ *   One launch on `stream`, no allocation, no scratch, no synchronisation: can be captured into a graph.
+ * dad3d_procrustes  utils.py:183-272 `procrustes(X, Y)` with scaling and reflection="best" per item, float64:
+ *     x, y [batch,n_points,3] -> b [batch], t [batch,3,3] row-major, c [batch,3] such that b * y . t + c best fits x; t = V U^T of
+ *     the SVD of the normalised covariance with NO determinant fix (it may be a reflection); flags [batch]: DAD3D_POSE_FLAG_DEGENERATE
+ *     with NaN results where a centred norm is 0 or not finite (one point, identical points, non-finite input; "0" is anything
+ *     within n sqrt(n) eps max|mean|, the rounding error that the mean of n identical points leaves). Where the
+ *     covariance is singular (planar or collinear points) t is one of the orthogonal matrices that fit, a proper rotation.
+ *     An item's bits do not depend on what else is in the batch.
+ * The two `_host` entries run the same routines on the CPU with HOST pointers (the frame table and image_index too) and need no GPU.
+ * Arguments (NULL, negative sizes, alignment, points without a frame size) are validated before any work -> DAD3D_E_INVALID; n == 0 or
+ * batch == 0: DAD3D_OK, nothing to do.
+ * --------------------------------------------------------------------------------------------- */
+#define DAD3D_POSE_FLAG_NONFINITE 0x1
+#define DAD3D_POSE_FLAG_DEGENERATE 0x2
+#define DAD3D_POSE_FLAG_GIMBAL 0x4
+#define DAD3D_POSE_FLAG_INDEX 0x8
+DAD3D_EXPORT dad3d_status dad3d_head_pose(const float* params, int n, int64_t row_stride, int rot_offset, const int64_t* frames /* or NULL */,
+                                          int n_frames, const int32_t* image_index /* with frames */, int h, int w, float* rotation,
+                                          double* rpy, float* points, int32_t* flags, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_head_pose_host(const float* params, int n, int64_t row_stride, int rot_offset, const int64_t* frames,
+                                               int n_frames, const int32_t* image_index, int h, int w, float* rotation, double* rpy,
+                                               float* points, int32_t* flags);
+DAD3D_EXPORT dad3d_status dad3d_procrustes(const double* x, const double* y, int batch, int n_points, double* b, double* t, double* c,
+                                           int32_t* flags, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_procrustes_host(const double* x, const double* y, int batch, int n_points, double* b, double* t, double* c,
+                                                int32_t* flags);
+
+/* ---------------------------------------------------------------------------------------------
  * PNG files and zlib streams read back on the device, bit-equal to `PIL.Image.open` and `zlib.decompress` (RFC 1950, 1951, the PNG
  * specification): 8-bit grey, grey + alpha, RGB and RGBA files without interlace, of any sizes in one call.
  *   files   DEVICE: the bytes of every file, file b at files[desc[b][0] .. + desc[b][1])
