@@ -12,9 +12,13 @@
 //           The stagers ask for slab 0 (k 0..127) of the 48 rows in front of the start-up barrier and for the rest behind it.
 //   pass 2  (B > 48) rows 48..63 as ONE row block, a chain of 104 dependent MFMAs. Rows 0..31 are finished in its hooks by the mma waves
 //           (the pipelined kernel's hook layout and its first two pieces), rows 32..47 and vertices 16..19 of rows 0..31 (the half-empty
-//           third piece) by the stagers, which have nothing else to do. Multiplying part of this chain inside pass 1 was measured and
-//           loses: profiles/r11_kernel_log.md.
-//   tail    all eight waves finish rows 48..63 -- or rows 0..47 when B <= 48: there is no pass 2 then.
+//           third piece) by the stagers, which have nothing else to do -- in two calls: vertices 0..15 of rows 32..47, then vertices
+//           16..19 of rows 0..47 as ONE call of 48 lanes, so that the stagers are not the late party at barrier P2. Multiplying part of
+//           this chain inside pass 1 was measured and loses (profiles/r11_kernel_log.md); so does starting it without barrier P1, on
+//           arrival words, with the park and the hook set-up between its first MFMAs (profiles/r12_kernel_log.md).
+//   tail    all eight waves finish rows 48..63 -- or rows 0..47 when B <= 48: there is no pass 2 then. B > 48: what the tail does not get
+//           from the chain (constants, vertex-table row, masks, offsets) is read in front of barrier P2, by the mma waves inside the
+//           chain's last groups and by the stagers in front of their two calls; behind P2 it reads the jaw and three accumulator values.
 //
 // Every accumulator sums G = 0..25, s = 0..3 from zero and every (vertex, image) goes through finish_vertex (flame_pipe_epilogue.hpp) with
 // the constants of write_round below, which is flame_decode_pipe.hip's: a row's bits do not depend on the kernel, the pass or the wave that
@@ -22,6 +26,8 @@
 // same trace slots as the pipelined kernel; capi.cpp sends a launch here. The small device helpers are copies: the pipelined unit's three
 // kernels are held to their instruction streams (tests/test_decode_pipe_entry.py), so nothing of theirs moved into a header.
 #pragma clang fp contract(off)
+#include <type_traits>
+
 #include "common.hpp"
 #include "flame_math.hpp"
 #include "flame_pipe_epilogue.hpp"
@@ -45,6 +51,15 @@
 #ifndef DAD3D_HEAD_V16_STAGERS  // 1: vertices 16..19 of rows 0..31 (B > 48) are finished by the stagers, which wait at P2, not in the chain's last hook
 #define DAD3D_HEAD_V16_STAGERS 1
 #endif
+#ifndef DAD3D_HEAD_V16_MERGED  // 1: the stagers' two mostly empty calls (vertices 16..19 of rows 32..47 and of rows 0..31) are ONE call of 48 lanes
+#define DAD3D_HEAD_V16_MERGED 1
+#endif
+#ifndef DAD3D_HEAD_TAIL_PRE  // 1 (B > 48): the tail's constants, vertex-table row, masks and offsets are read in front of barrier P2, by both roles
+#define DAD3D_HEAD_TAIL_PRE 1
+#endif
+#ifndef DAD3D_HEAD_TAIL_PRE_AT  // ... by the mma waves behind this group of the chain (in front of barrier P1, where they wait, ties: profiles/r12_kernel_log.md)
+#define DAD3D_HEAD_TAIL_PRE_AT 22
+#endif
 
 namespace dad3d {
 
@@ -55,6 +70,10 @@ constexpr bool kSpread = DAD3D_HEAD_SPREAD != 0;
 constexpr int kSpreadReqAt = DAD3D_HEAD_SPREAD_REQ_AT, kSpreadLdsAt = DAD3D_HEAD_SPREAD_LDS_AT;
 constexpr bool kV16Stagers = DAD3D_HEAD_V16_STAGERS != 0;
 static_assert(kSpreadReqAt >= 0 && kSpreadReqAt < 4 && kSpreadLdsAt >= 0 && kSpreadLdsAt <= 4, "rows of a step's MFMAs");
+constexpr bool kV16Merged = DAD3D_HEAD_V16_STAGERS != 0 && DAD3D_HEAD_V16_MERGED != 0;
+constexpr bool kTailPre = DAD3D_HEAD_TAIL_PRE != 0;
+constexpr int kTailPreAt = DAD3D_HEAD_TAIL_PRE_AT;
+static_assert(kTailPreAt >= 0 && kTailPreAt < 26, "a group of the chain");
 
 constexpr int KG = kPipeKGroups;       // MFMA groups of 16 k
 constexpr int TV = kPipeTileVerts;     // vertices per tile
@@ -160,7 +179,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
     // final_epilogue -- wave w of a set takes rows row0 + 4 w .. + 3, lane = (row fi of four, vertex fu of sixteen) -> vertices fu and, for
     // fu < 4, fu + 16. fin2: all eight waves on sixteen rows -- rows row0 + 2 wave + {0, 1}, lane = (row fi of two, vertex fu of 32), one
     // vertex a lane.
-    auto fin4 = [&](int row0, int w) {
+    auto fin4 = [&](int row0, int w, auto both) {  // both: std::false_type = vertices 0..15 only
         const int fi = lane & 3, fu = lane >> 2, b = row0 + 4 * w + fi;
         const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
         const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3], c4 = cp[4], c5 = cp[5];
@@ -173,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
             finish_vertex<TO2D, 0>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * fu], ot[3 * fu + 1], ot[3 * fu + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
                                    live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
         }
-        if (fu < TV - 16) {
+        if (decltype(both)::value && fu < TV - 16) {
             const int j = fu + 16;
             const float4 t = vt_lds[j];
             const bool live = b < B && v0 + j < a.n_verts;
@@ -194,6 +213,22 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         finish_vertex<TO2D, 16>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * j], ot[3 * j + 1], ot[3 * j + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
                                 live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
     };
+    // fin_v16_both (kV16Merged): that piece and fin4(32, w)'s second one in ONE call of 48 lanes -- lanes 0..31 as in fin_v16, lanes 32..47 =
+    // (row 32 + 4 w + (lane & 3), vertex 16 + ((lane >> 2) & 3)), fin4's lanes 0..15. Constants, jaw and accumulators are per lane: the same
+    // pairs with the same arithmetic, two calls beside the chain instead of three. (Lanes 48..63 compute lanes 32..47's pairs and store nothing.)
+    auto fin_v16_both = [&](int w) {
+        const bool hi = lane >= 32;
+        const int fu = hi ? (lane >> 2) & 3 : (lane >> 3) & 3, j = fu + 16, b = hi ? 32 + 4 * w + (lane & 3) : 8 * w + (lane & 7);
+        const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
+        const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3], c4 = cp[4], c5 = cp[5];
+        const float* ot = otile + b * OS;
+        const float jx = ot[kJawCol], jy = ot[kJawCol + 1], jz = ot[kJawCol + 2];
+        const unsigned vrow = (unsigned)b * (unsigned)a.n_verts + (unsigned)(v0 + fu), bnl = (unsigned)b * nl;
+        const float4 t = vt_lds[j];
+        const bool live = lane < 48 && v0 + j < a.n_verts;  // (b < 48 < B)
+        finish_vertex<TO2D, 16>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * j], ot[3 * j + 1], ot[3 * j + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
+                                live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
+    };
     auto fin2 = [&](int row0) {
         const int fi = lane & 1, fu = min(lane >> 1, TV - 1), b = row0 + 2 * wave + fi;
         const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
@@ -205,6 +240,29 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         const bool live = b < B && (lane >> 1) < TV && v0 + fu < a.n_verts;
         finish_vertex<TO2D, 0>(cx, rs3, rsp, c0, c1, c2, c3, c4, c5, jx, jy, jz, ot[3 * fu], ot[3 * fu + 1], ot[3 * fu + 2], t.x, t.y, __float_as_int(t.z), __float_as_int(t.w),
                                live && (outs & 1u), live && (outs & 2u), live && nl > 0 && __float_as_int(t.z) >= 0, vrow, bnl);
+    };
+
+    // The tail of a launch with a pass 2 in two halves (kTailPre): what does not come out of the chain -- the constants and the vertex-table row
+    // of the lane's pair, masks and offsets -- in front of barrier P2, where each role has time (round 0 and the vertex table are in LDS behind
+    // P1); behind it the jaw and three accumulator values: fin2(kRows1)'s arithmetic on fin2's operands.
+    float4 t0, t1, t2, t3, t4, t5, tvt;
+    unsigned t_vrow = 0, t_bnl = 0;
+    bool t_live3 = false, t_livep = false, t_livel = false;
+    auto tail_pre = [&]() {
+        const int fu = min(lane >> 1, TV - 1), b = kRows1 + 2 * wave + (lane & 1);
+        const float4* cp = reinterpret_cast<const float4*>(cst + b * CS);
+        t0 = cp[0], t1 = cp[1], t2 = cp[2], t3 = cp[3], t4 = cp[4], t5 = cp[5];
+        tvt = vt_lds[fu];
+        t_vrow = (unsigned)b * (unsigned)a.n_verts + (unsigned)(v0 + fu), t_bnl = (unsigned)b * nl;
+        const bool live = b < B && (lane >> 1) < TV && v0 + fu < a.n_verts;
+        t_live3 = live && (outs & 1u), t_livep = live && (outs & 2u), t_livel = live && nl > 0 && __float_as_int(tvt.z) >= 0;
+    };
+    auto tail_post = [&]() {
+        const int fu = min(lane >> 1, TV - 1), b = kRows1 + 2 * wave + (lane & 1);
+        const float* ot = otile + b * OS;
+        const float jx = ot[kJawCol], jy = ot[kJawCol + 1], jz = ot[kJawCol + 2];
+        finish_vertex<TO2D, 0>(cx, rs3, rsp, t0, t1, t2, t3, t4, t5, jx, jy, jz, ot[3 * fu], ot[3 * fu + 1], ot[3 * fu + 2], tvt.x, tvt.y, __float_as_int(tvt.z), __float_as_int(tvt.w),
+                               t_live3, t_livep, t_livel, t_vrow, t_bnl);
     };
 
     if (wave >= 4) {
@@ -286,15 +344,18 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         phase_barrier();  // P1
         stamp(19);
         if (two) {
-            fin4(32, fw);  // rows 32..47, while the mma waves multiply rows 48..63 and finish rows 0..31
+            if (kTailPre) tail_pre();
+            fin4(32, fw, std::bool_constant<!kV16Merged>{});  // rows 32..47, while the mma waves multiply rows 48..63 and finish rows 0..31
             stamp(21);
-            if (kV16Stagers) fin_v16(fw);  // ... but for their vertices 16..19
+            if (kV16Merged) fin_v16_both(fw);  // vertices 16..19 of rows 0..31 (not in the chain's last hook) and of rows 32..47
+            else if (kV16Stagers) fin_v16(fw);
             stamp(9);
             phase_barrier();  // P2
             stamp(23);
-            fin2(kRows1);
+            if (kTailPre) tail_post();
+            else fin2(kRows1);
         } else {
-            fin4(0, wave);
+            fin4(0, wave, std::true_type{});
             fin2(32);
         }
         stamp(5);
@@ -434,7 +495,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
         phase_barrier();  // P1
         stamp(18);
         stamp(3);
-        fin4(0, wave);
+        fin4(0, wave, std::true_type{});
         fin2(32);
         stamp(5);
         if (trace && lane == 0) trace[13] = wall_clock64();
@@ -499,6 +560,7 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
                 if (!kV16Stagers) epi_fetch(2);
             }
             if (G == 19 && !kV16Stagers) epi_finish(2);
+            if (kTailPre && G == kTailPreAt) tail_pre();  // (the basis registers of the groups behind are free, and the reads land under the groups in front)
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -508,7 +570,8 @@ __global__ __launch_bounds__(512, 2) void flame_decode_head_kernel(float* params
     phase_barrier();  // P2
     stamp(22);
     stamp(3);
-    fin2(kRows1);
+    if (kTailPre) tail_post();
+    else fin2(kRows1);
     stamp(5);
     if (trace && lane == 0) trace[13] = wall_clock64();
 }

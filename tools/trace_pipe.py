@@ -14,6 +14,9 @@ Whole-mesh launches of 33..64 rows take flame_decode_head.hip (48 rows under the
 half-blocks above). Same slots: 16 up-front basis requests issued | 8 first MFMA | 2, 17 pass 1 multiplied, parked | 18 past barrier P1 |
 20, 21 pass 2 start, parked | 22, 3 past barrier P2. Stagers: 16, 17 rows 48..63 requested, written | 18, 19 at / past P1 | 21 rows 32..47
 finished | 23 past P2. The half-block lines below then read: half-block 0 = pass 1, half-block 1 = pass 2.
+The seam experiment (profiles/r12_seam_experiment.patch, no barrier P1 at B > 48) keeps the slots usable: mma waves 20 = behind the chain's
+first MFMA | 17 = pass 1 parked and announced (behind the chain's fourth MFMA) | 18 = `parked` seen full, in front of the hooks' first fetch;
+stagers 17 = rows 48..63 written and announced | 18, 19 = in front of / behind the wait for `parked`.
 Stagers, B > 48: 9 = vertices 16..19 of rows 0..31 finished (behind slot 21). The ride experiment (profiles/r11_ride_experiment.patch) uses
 9, 10 differently: mma waves 9 = k 0..127 of rows 48..63 seen in LDS; stagers 9, 10 = k 0..127, k 128..255 of rows 48..63 published."""
 import os
@@ -70,6 +73,9 @@ if t[:, 0, 8].any():  # the 48 + 16 kernel of whole-mesh launches of 33..64 rows
     print(f"  48 + 16 stagers (wave 4): rows 48..63 requested {cyc(med(4, 16))}, written {cyc(med(4, 17))}; at barrier P1 {med(4, 18):.0f}, past it {med(4, 19):.0f}; "
           f"rows 32..47 finished {cyc(med(4, 21))}; past barrier P2 {cyc(med(4, 23))}")
     print(f"  48 + 16 stagers (wave 4 / 7): vertices 16..19 of rows 0..31 finished {cyc(med(4, 9))} / {cyc(med(7, 9))}")
+    if batch > 48:  # the two seams (profiles/r12_kernel_log.md)
+        print(f"  48 + 16 seams (mma wave 0): pass 1 multiplied -> chain start {cyc(med(0, 20) - med(0, 2))}; pass 1 parked (and announced) {cyc(med(0, 17))}, "
+              f"`parked` seen / past P1 {cyc(med(0, 18))}; chain parked -> last barrier passed {cyc(med(0, 3) - med(0, 21))}; end {med(0, 5):.0f}")
 print("stager waves (wave 4 / wave 7):")
 print(f"  first loads issued {med(4, 1):.0f} / {med(7, 1):.0f}; past the first barrier {med(4, 6):.0f}; first part of A(0) published {med(4, 7):.0f}; "
       f"constants round 0 begun {cyc(med(4, 3))} / {cyc(med(7, 3))}, written {cyc(med(4, 4))} / {cyc(med(7, 4))}; A(0) published {med(4, 2):.0f}; end {med(4, 5):.0f}")
