@@ -13,6 +13,7 @@ from dad_3dheads_amd import coder, loss_module, losses, metrics
 from oracle import reference_runner
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_objective_golden.npz")
+EDGES_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_objective_edges_golden.npz")
 
 
 @pytest.fixture(scope="module")
@@ -21,20 +22,30 @@ def golden():
         return {k: z[k] for k in z.files}
 
 
+@pytest.fixture(scope="module")
+def edges_golden():
+    with np.load(EDGES_GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
 def _cases(g, key):
     return [c.split(":") for c in g[key]]
 
 
-def test_restated_encode_is_the_reference_coder_byte_for_byte(golden):
-    for name, img, stride, radius in _cases(golden, "coder_cases"):
-        radius = radius if radius == "pointwise" else int(radius)
-        size = int(img) // int(stride)
-        kp, pr = golden[f"coder_{name}_keypoints"], golden[f"coder_{name}_presence"]
-        for form in ("raw", "uint8", "float"):
-            ref = golden[f"coder_{name}_{form}"]
-            got = rs.encode(kp, pr, size, int(stride), radius, form)
-            assert got.dtype == ref.dtype and got.tobytes() == ref.tobytes(), (name, form)
-        assert np.count_nonzero(golden[f"coder_{name}_raw"]) > 0
+def test_restated_encode_is_the_reference_coder_byte_for_byte(golden, edges_golden):
+    sizes = set()
+    for g in (golden, edges_golden):  # the second file: planes that are no multiple of a 16-byte chunk (S = 3, 5, 9, 25)
+        for name, img, stride, radius in _cases(g, "coder_cases"):
+            radius = radius if radius == "pointwise" else int(radius)
+            size = int(img) // int(stride)
+            sizes.add(size)
+            kp, pr = g[f"coder_{name}_keypoints"], g[f"coder_{name}_presence"]
+            for form in ("raw", "uint8", "float"):
+                ref = g[f"coder_{name}_{form}"]
+                got = rs.encode(kp, pr, size, int(stride), radius, form)
+                assert got.dtype == ref.dtype and got.tobytes() == ref.tobytes(), (name, form)
+            assert np.count_nonzero(g[f"coder_{name}_raw"]) > 0
+    assert {3, 5, 9, 25} <= sizes
 
 
 @pytest.mark.parametrize("radius", [0, 1, 2, 3, 5, 8, "pointwise"])
@@ -243,3 +254,21 @@ def test_committed_golden_is_what_the_reference_produces_here(tmp_path):
         assert sorted(fresh.files) == sorted(committed.files)
         for k in fresh.files:
             assert np.array_equal(fresh[k], committed[k], equal_nan=fresh[k].dtype.kind == "f"), k
+
+
+@pytest.mark.skipif(not reference_runner.reference_available(), reason="reference tree not present on this machine")
+def test_committed_edges_golden_is_what_the_reference_produces_here(tmp_path):
+    """Authoring container only: re-run the odd-size generator (the reference's own coder) and compare every array."""
+    import subprocess
+    import sys
+
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    out = tmp_path / "train_objective_edges_golden.npz"
+    subprocess.run([sys.executable, os.path.join(here, "make_train_objective_edges_golden.py"), str(out)], check=True,
+                   capture_output=True, timeout=600)
+    with np.load(out) as fresh, np.load(EDGES_GOLDEN) as committed:
+        assert sorted(fresh.files) == sorted(committed.files)
+        for k in fresh.files:
+            assert fresh[k].dtype == committed[k].dtype, k
+            assert np.array_equal(fresh[k], committed[k], equal_nan=fresh[k].dtype.kind == "f"), k  # the absent NaN keypoints
+    assert os.path.getsize(EDGES_GOLDEN) < os.path.getsize(GOLDEN) and os.path.getsize(EDGES_GOLDEN) < 100_000
