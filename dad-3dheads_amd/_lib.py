@@ -48,7 +48,7 @@ TRACK_FLAG_RETIRED, TRACK_MAX_DETECTIONS = 0x40, 1024
 ASSIGN_FLAG_PADDING, ASSIGN_FLAG_INVALID, ASSIGN_FLAG_COVERED, ASSIGN_FLAG_SPAWNED, ASSIGN_FLAG_FULL = 0x1, 0x2, 0x4, 0x8, 0x10
 FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0x2, 4096, 65535
 RENDER_REVERSE, RENDER_CLEAR = 1, 2
-BAKE_FLAG_INDEX = 0x1
+BAKE_FLAG_INDEX, BAKE_FLAG_DEPTH_WINDOW, BAKE_FLAG_NONFINITE, BAKE_MAX_DEPTH_SIDE = 0x1, 0x2, 0x4, 4096
 POSE_FLAG_NONFINITE, POSE_FLAG_DEGENERATE, POSE_FLAG_GIMBAL, POSE_FLAG_INDEX = 0x1, 0x2, 0x4, 0x8
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
@@ -174,6 +174,8 @@ SIGNATURES = {
     "dad3d_uvmap_vertex_normals": (_I, [_P, _P, _P, _I, _P]),
     "dad3d_uvmap_bake": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dad3d_uvmap_bake_frames": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "dad3d_uvmap_depth_frames": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "dad3d_uvmap_bake_frames_occluded": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _P, _P]),
     "dad3d_obj_format_scratch_bytes": (C.c_size_t, [_I, _I]),
     "dad3d_obj_format_vertices": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _I, _P]),
     "dad3d_json_format_scratch_bytes": (C.c_size_t, [_I, _I]),

@@ -1,5 +1,6 @@
 // C ABI, render side: the Sim3DR mesh handle, the UV-map handle and the overlays (sim3dr_*.hip, uv_texture*.hip, overlay.hip).
 #include <algorithm>
+#include <cmath>
 #include <memory>
 
 #include "capi_checks.hpp"
@@ -79,6 +80,8 @@ struct dad3d_uvmap {
     int* d_texel_ptr = nullptr;  // texel -> candidates, descending (UvBakeArgs)
     int* d_cand_verts = nullptr;
     double* d_cand_bary = nullptr;
+    int* d_faces = nullptr;  // [ntri,3]: the depth maps' triangles (UvDepthFramesArgs)
+    int ntri = 0;
 };
 
 extern "C" {
@@ -515,9 +518,9 @@ dad3d_status dad3d_uvmap_create(const int32_t* faces, int ntri, int nver, const 
         for (int c = 0; c < 3; ++c) verts[3 * (size_t)j + c] = cand_verts[3 * (size_t)i + c], bary[3 * (size_t)j + c] = cand_bary[3 * (size_t)i + c];
     }
     std::unique_ptr<dad3d_uvmap> m(new dad3d_uvmap);
-    m->device = device, m->nver = nver, m->size = img_size, m->n_cand = n;
+    m->device = device, m->nver = nver, m->size = img_size, m->n_cand = n, m->ntri = ntri;
     dad3d_status st;
-    if ((st = upload(&m->d_adj_ptr, ptr)) || (st = upload(&m->d_adj, adj)) || (st = upload(&m->d_texel_ptr, tptr)) ||
+    if ((st = upload(&m->d_faces, std::vector<int>(faces, faces + 3 * (size_t)ntri))) || (st = upload(&m->d_adj_ptr, ptr)) || (st = upload(&m->d_adj, adj)) || (st = upload(&m->d_texel_ptr, tptr)) ||
         (st = upload(&m->d_cand_verts, verts)) || (st = upload(&m->d_cand_bary, bary))) {
         dad3d_uvmap_destroy(m.release());
         return st;
@@ -529,7 +532,7 @@ dad3d_status dad3d_uvmap_create(const int32_t* faces, int ntri, int nver, const 
 void dad3d_uvmap_destroy(dad3d_uvmap* m) {
     if (!m) return;
     DeviceGuard guard(m->device);
-    for (void* p : {(void*)m->d_adj_ptr, (void*)m->d_adj, (void*)m->d_texel_ptr, (void*)m->d_cand_verts, (void*)m->d_cand_bary})
+    for (void* p : {(void*)m->d_adj_ptr, (void*)m->d_adj, (void*)m->d_texel_ptr, (void*)m->d_cand_verts, (void*)m->d_cand_bary, (void*)m->d_faces})
         if (p) (void)hipFree(p);
     delete m;
 }
@@ -558,11 +561,8 @@ dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* ver
     return launch_uv_bake(a, static_cast<hipStream_t>(stream));
 }
 
-dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices, const double* normals,
-                                     const int64_t* frames, const int64_t* frames_host, int n_frames, const int32_t* image_index, int n_heads,
-                                     int32_t* flags, void* stream) {
-    const char* who = "dad3d_uvmap_bake_frames";
-    // the scalars and the host table first: a bad one is refused before the handle is looked at or any device work starts
+// the scalars and the host frame table of the bakes from frames: a bad one is refused before the handle is looked at or any device work starts
+static dad3d_status uv_frames_checked(const char* who, const int64_t* frames_host, int n_frames, int n_heads) {
     DAD3D_REQUIRE(n_frames >= 0 && n_heads >= 0, "%s: negative count (%d frames, %d heads)", who, n_frames, n_heads);
     DAD3D_REQUIRE(n_heads <= 65535, "%s: %d heads, beyond the launch grid of 65535", who, n_heads);
     DAD3D_REQUIRE(n_frames == 0 || frames_host, "%s: null host frame table", who);
@@ -575,6 +575,14 @@ dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* sc
         DAD3D_REQUIRE(stride >= 3 * w, "%s: frame %d has a row stride of %lld bytes for %lld pixels of 3 bytes", who, f, (long long)stride,
                       (long long)w);
     }
+    return DAD3D_OK;
+}
+
+dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices, const double* normals,
+                                     const int64_t* frames, const int64_t* frames_host, int n_frames, const int32_t* image_index, int n_heads,
+                                     int32_t* flags, void* stream) {
+    const char* who = "dad3d_uvmap_bake_frames";
+    if (dad3d_status st = uv_frames_checked(who, frames_host, n_frames, n_heads)) return st;
     DAD3D_REQUIRE(m, "%s: null handle", who);
     if (n_heads == 0) return DAD3D_OK;
     DAD3D_REQUIRE(texture && image_index && flags && ((vertices && normals) || m->n_cand == 0), "%s: null buffer", who);
@@ -583,6 +591,46 @@ dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* sc
     UvBakeFramesArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, reinterpret_cast<const long long*>(frames), image_index,
                        texture, score, flags, n_heads, n_frames, m->nver, m->size};
     return launch_uv_bake_frames(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_uvmap_depth_frames(dad3d_uvmap* m, float* depth, int32_t* window, const float* vertices, const int64_t* frames,
+                                      const int64_t* frames_host, int n_frames, const int32_t* image_index, int n_heads, int depth_side,
+                                      int32_t* flags, void* stream) {
+    const char* who = "dad3d_uvmap_depth_frames";
+    if (dad3d_status st = uv_frames_checked(who, frames_host, n_frames, n_heads)) return st;
+    DAD3D_REQUIRE(depth_side >= 1 && depth_side <= DAD3D_BAKE_MAX_DEPTH_SIDE, "%s: depth_side %d outside 1..%d", who, depth_side,
+                  DAD3D_BAKE_MAX_DEPTH_SIDE);
+    DAD3D_REQUIRE(n_heads == 0 || (depth && window && image_index && flags), "%s: null buffer", who);
+    DAD3D_REQUIRE(n_heads == 0 || n_frames == 0 || frames, "%s: null device frame table", who);
+    DAD3D_REQUIRE(m, "%s: null handle", who);
+    if (n_heads == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(vertices || m->nver == 0, "%s: null vertices", who);
+    DAD3D_SELECT_DEVICE(m->device);
+    UvDepthFramesArgs a{m->d_faces, vertices, reinterpret_cast<const long long*>(frames), image_index, depth, window, flags,
+                        n_heads, n_frames, m->nver, m->ntri, depth_side};
+    return launch_uv_depth_frames(a, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_uvmap_bake_frames_occluded(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices, const double* normals,
+                                              const int64_t* frames, const int64_t* frames_host, int n_frames, const int32_t* image_index,
+                                              int n_heads, const float* depth, const int32_t* window, const int32_t* depth_flags, int depth_side,
+                                              double depth_bias, double slope_bias, int32_t* flags, void* stream) {
+    const char* who = "dad3d_uvmap_bake_frames_occluded";
+    if (dad3d_status st = uv_frames_checked(who, frames_host, n_frames, n_heads)) return st;
+    DAD3D_REQUIRE(depth_side >= 1 && depth_side <= DAD3D_BAKE_MAX_DEPTH_SIDE, "%s: depth_side %d outside 1..%d", who, depth_side,
+                  DAD3D_BAKE_MAX_DEPTH_SIDE);
+    DAD3D_REQUIRE(std::isfinite(depth_bias) && depth_bias >= 0.0 && std::isfinite(slope_bias) && slope_bias >= 0.0,
+                  "%s: depth_bias %g and slope_bias %g must be finite and not negative", who, depth_bias, slope_bias);
+    DAD3D_REQUIRE(n_heads == 0 || (texture && image_index && flags && depth && window && depth_flags), "%s: null buffer", who);
+    DAD3D_REQUIRE(n_heads == 0 || n_frames == 0 || frames, "%s: null device frame table", who);
+    DAD3D_REQUIRE(m, "%s: null handle", who);
+    if (n_heads == 0) return DAD3D_OK;
+    DAD3D_REQUIRE((vertices && normals) || m->n_cand == 0, "%s: null vertices or normals", who);
+    DAD3D_SELECT_DEVICE(m->device);
+    UvBakeOccludedArgs a{{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, reinterpret_cast<const long long*>(frames),
+                          image_index, texture, score, flags, n_heads, n_frames, m->nver, m->size},
+                         depth, window, depth_flags, depth_side, depth_bias, slope_bias};
+    return launch_uv_bake_frames_occluded(a, static_cast<hipStream_t>(stream));
 }
 
 static dad3d_status overlay_checked(const char* who, const uint8_t* src, uint8_t* dst, int batch, int h, int w, const float* points,

@@ -1,7 +1,8 @@
-// What the two UV-texture units (uv_texture.hip, uv_texture_frames.hip) share: the argument structs of their kernels, the launchers'
-// declarations and the per-candidate routine of the bake -- the source pixel of a candidate, or -1 where the reference skips it.
+// What the UV-texture units (uv_texture.hip, uv_texture_frames.hip, uv_texture_occlusion.hip) share: the argument structs of their
+// kernels, the launchers' declarations and the per-candidate routines of the bake -- the source pixel of a candidate, or -1 where the
+// reference skips it, and the depth test of the occluded bake.
 //
-// A UNIT THAT CALLS uv_sample IS COMPILED WITH -ffp-contract=off: every product and sum rounds on its own, as NumPy's does.
+// A UNIT THAT CALLS uv_sample OR uv_hidden IS COMPILED WITH -ffp-contract=off: every product and sum rounds on its own, as NumPy's does.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +47,26 @@ struct UvBakeFramesArgs {
     int* flags;                  // [N]
     int n_heads, n_frames, n_verts, size;
 };
+// the depth maps of heads in frames (uv_texture_occlusion.hip): head k's nearest z per pixel of its window in the frame it names
+struct UvDepthFramesArgs {
+    const int* faces;         // [n_tri,3]
+    const float* vertices;    // [N,V,3] frame pixel x, pixel y, z with the viewer at -z
+    const long long* frames;  // [M][4]: only h and w are read
+    const int* image_index;   // [N]
+    float* depth;             // [N,D,D]
+    int* window;              // [N,4] {x0, y0, ww, wh}
+    int* flags;               // [N]
+    int n_heads, n_frames, n_verts, n_tri, depth_side;
+};
+// the bake from frames with the depth test (uv_texture_occlusion.hip)
+struct UvBakeOccludedArgs {
+    UvBakeFramesArgs bake;
+    const float* depth;      // [N,D,D] of UvDepthFramesArgs, read only
+    const int* window;       // [N,4]
+    const int* depth_flags;  // [N]
+    int depth_side;
+    double depth_bias, slope_bias;
+};
 constexpr int kUvBakeChunk = 8;  // images per bake workgroup: the table is read once per chunk
 constexpr int kUvBakeThreads = 256;
 constexpr int kUvBakeTexels = 4;  // texels per lane: 12 output bytes, three dword stores
@@ -53,6 +74,8 @@ int uv_bake_grid_y(int batch, int chunk);
 dad3d_status launch_uv_vertex_normals(const UvNormalArgs& a, hipStream_t s);
 dad3d_status launch_uv_bake(const UvBakeArgs& a, hipStream_t s);
 dad3d_status launch_uv_bake_frames(const UvBakeFramesArgs& a, hipStream_t s);
+dad3d_status launch_uv_depth_frames(const UvDepthFramesArgs& a, hipStream_t s);
+dad3d_status launch_uv_bake_frames_occluded(const UvBakeOccludedArgs& a, hipStream_t s);
 
 namespace {
 
@@ -83,6 +106,18 @@ __device__ __forceinline__ int uv_sample(const UvCand& c, const float* vb, const
     if (!(rx > 0.0 && rx < (double)w && ry > 0.0 && ry < (double)h)) return -1;
     const uint8_t* p = pixel_at((int)ry, (int)rx);
     return p[0] | (p[1] << 8) | (p[2] << 16);
+}
+
+// The third test of the occluded bake, for a candidate that passed uv_sample's two with n_dot_view ndv: is its point behind the head's
+// own surface at its pixel? d: the head's depth there (+inf where the map has none). The candidate's z and the normal's x and y are
+// float64 sums of products in uv_sample's order; the comparison is false on NaN, so an uncovered pixel, ndv == +0 (a slope of inf, or
+// NaN where slope_bias == 0 or nx == ny == 0) and a NaN anywhere leave the candidate visible.
+__device__ __forceinline__ bool uv_hidden(const UvCand& c, const float* vb, const double* nb, double ndv, float d, double depth_bias,
+                                          double slope_bias) {
+    const double pz = ((double)vb[c.v0 * 3 + 2] * c.w0 + (double)vb[c.v1 * 3 + 2] * c.w1) + (double)vb[c.v2 * 3 + 2] * c.w2;
+    const double nx = (nb[c.v0 * 3] * c.w0 + nb[c.v1 * 3] * c.w1) + nb[c.v2 * 3] * c.w2;
+    const double ny = (nb[c.v0 * 3 + 1] * c.w0 + nb[c.v1 * 3 + 1] * c.w1) + nb[c.v2 * 3 + 1] * c.w2;
+    return pz > (double)d + (depth_bias + slope_bias * ((fabs(nx) + fabs(ny)) / ndv));
 }
 
 }  // namespace

@@ -5,6 +5,8 @@ device-resident entry `bake_batch`: ONE fused decode launch (`to_2d=False`, tran
 normals and the texel bake (csrc/uv_texture.hip); vertices, normals, photos and textures never leave HBM. For heads tracked in
 a video: `bake_frames` (head k read from the frame its `image_index` names, csrc/uv_texture_frames.hip), `TextureAccumulator` (one
 texture per tracker slot, the best view of every texel kept over time) and `render_frames` (the textured heads drawn into their frames).
+`occlusion="self"` on the two former adds what the reference's rule lacks, a depth test of every sample against the head's own depth
+map (`UVMap.depth_frames`, csrc/uv_texture_occlusion.hip); it is off by default.
 
 What the reference computes, per candidate i of the atlas (`_compute_texture_map`, uv_texture.py:21-46), in float64:
     p = v[a] * b0 + v[b] * b1 + v[c] * b2,  the same with the vertex normals,  n_dot_view = -n.z
@@ -155,20 +157,8 @@ class UVMap:
                                               images.data_ptr(), hw.data_ptr() if hw is not None else None, b, h, w, stream))
         return out
 
-    def bake_frames(self, vertices: Tensor, normals: Tensor, frames, image_index, out: Optional[Tensor] = None,
-                    score: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        """The bake for heads that name their frames (`dad3d_uvmap_bake_frames`): head k reads `frames[image_index[k]]` and owns
-        texture k. vertices `[N,V,3]` float32 in frame coordinates, normals `[N,V,3]` float64. `frames`: a list of uint8 CUDA
-        tensors `[H,W,3]` of any sizes and row strides (views included), one `[B,H,W,3]` tensor, or a `DeviceFrames` (its table is
-        uploaded once: what a graph capture needs). `image_index`: an int32 CUDA tensor `[N]`, used as it is and never read on the
-        host, or a host sequence, uploaded. `score=None`: the plain bake into `out` (allocated when None), every byte written.
-        `score [N,S,S]` float32: `out` (required) and `score` are the running state, a texel is replaced iff its new sample's
-        n_dot_view is greater ("best view wins"). -> (textures uint8 `[N,S,S,3]`, int32 flags `[N]`: 0 or `_lib.BAKE_FLAG_INDEX`, the
-        index names no frame). Async on the current stream, no host wait."""
-        n = vertices.shape[0]
+    def _frames_and_index(self, frames, image_index, n: int):
         dev = torch.device("cuda", self.device)
-        self._check(vertices, "vertices", torch.float32, (n, self.n_verts, 3))
-        self._check(normals, "normals", torch.float64, (n, self.n_verts, 3))
         fr = frames if isinstance(frames, DeviceFrames) else DeviceFrames(frames, dev)
         if fr.device.device != dev:
             raise ValueError(f"frames: on {fr.device.device}, the map on {dev}")
@@ -177,6 +167,68 @@ class UVMap:
         else:
             idx = torch.as_tensor(np.asarray(image_index, dtype=np.int32).reshape(-1)).to(dev)
         self._check(idx, "image_index", torch.int32, (n,))
+        return fr, idx
+
+    def depth_frames(self, vertices: Tensor, frames, image_index, depth_side: int = 512, out=None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Depth maps of heads in frames (`dad3d_uvmap_depth_frames`): for head k the nearest z of its own surface at every pixel of
+        its box in `frames[image_index[k]]`. vertices `[N,V,3]` float32 in the bake's coordinates (frame pixel x, pixel y, z with the
+        viewer at -z: the nearer surface has the SMALLER z); `frames` and `image_index` as in `bake_frames` (no pixel is read).
+        -> (depth float32 `[N,D,D]`, window int32 `[N,4]` = {x0, y0, ww, wh}, flags int32 `[N]`), D = `depth_side` in 1..4096:
+        `depth[k, j, i]` for `j < wh, i < ww` belongs to pixel `(x0 + i, y0 + j)`, `+inf` where no triangle covers it; entries outside
+        the window are not written. Flags: `_lib.BAKE_FLAG_INDEX`, `BAKE_FLAG_NONFINITE` (a NaN or inf vertex), `BAKE_FLAG_DEPTH_WINDOW`
+        (the box is larger than D); a flagged head has the window {0,0,0,0} and an untouched map. A head outside its frame has an
+        empty window and no flag. `out`: a depth tensor, or the tuple (depth, window, flags), to write into. Three launches on the
+        current stream, no host wait."""
+        n = vertices.shape[0]
+        d = int(depth_side)
+        dev = torch.device("cuda", self.device)
+        if not 1 <= d <= _lib.BAKE_MAX_DEPTH_SIDE:
+            raise ValueError(f"depth_side: {depth_side} outside 1..{_lib.BAKE_MAX_DEPTH_SIDE}")
+        self._check(vertices, "vertices", torch.float32, (n, self.n_verts, 3))
+        fr, idx = self._frames_and_index(frames, image_index, n)
+        depth, window, flags = out if isinstance(out, (tuple, list)) else (out, None, None)
+        if depth is None:
+            depth = torch.empty((n, d, d), dtype=torch.float32, device=dev)
+        if window is None:
+            window = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        if flags is None:
+            flags = torch.empty(n, dtype=torch.int32, device=dev)
+        self._check(depth, "depth", torch.float32, (n, d, d))
+        self._check(window, "window", torch.int32, (n, 4))
+        self._check(flags, "depth flags", torch.int32, (n,))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.dad3d_uvmap_depth_frames(self._handle, depth.data_ptr(), window.data_ptr(), vertices.data_ptr(),
+                                                      fr.device.data_ptr(), fr.host.ctypes.data, len(fr), idx.data_ptr(), n, d,
+                                                      flags.data_ptr(), stream))
+        return depth, window, flags
+
+    def bake_frames(self, vertices: Tensor, normals: Tensor, frames, image_index, out: Optional[Tensor] = None,
+                    score: Optional[Tensor] = None, occlusion: Optional[str] = None, depth_side: int = 512, depth_bias: float = 1.0,
+                    slope_bias: float = 1.0, depth=None) -> Tuple[Tensor, Tensor]:
+        """The bake for heads that name their frames (`dad3d_uvmap_bake_frames`): head k reads `frames[image_index[k]]` and owns
+        texture k. vertices `[N,V,3]` float32 in frame coordinates, normals `[N,V,3]` float64. `frames`: a list of uint8 CUDA
+        tensors `[H,W,3]` of any sizes and row strides (views included), one `[B,H,W,3]` tensor, or a `DeviceFrames` (its table is
+        uploaded once: what a graph capture needs). `image_index`: an int32 CUDA tensor `[N]`, used as it is and never read on the
+        host, or a host sequence, uploaded. `score=None`: the plain bake into `out` (allocated when None), every byte written.
+        `score [N,S,S]` float32: `out` (required) and `score` are the running state, a texel is replaced iff its new sample's
+        n_dot_view is greater ("best view wins"). -> (textures uint8 `[N,S,S,3]`, int32 flags `[N]`: 0 or `_lib.BAKE_FLAG_INDEX`, the
+        index names no frame). Async on the current stream, no host wait.
+
+        `occlusion="self"`: `depth_frames` (into `depth` -- what its `out` takes -- or tensors allocated here) and then
+        `dad3d_uvmap_bake_frames_occluded`: a candidate whose point lies behind the head's own surface at its pixel by more than
+        `depth_bias + slope_bias * (|nx| + |ny|) / n_dot_view` pixels of depth is skipped and the texel's next candidate tried. The
+        defaults 1.0 and 1.0 are untuned design choices. The flags then also carry `BAKE_FLAG_NONFINITE` and `BAKE_FLAG_DEPTH_WINDOW`
+        (the head's box exceeds `depth_side`); a head with any flag gives zeros, or with `score` keeps its state. `occlusion=None`
+        (the default) is the call without the depth test, untouched; the other keywords are then ignored."""
+        if occlusion not in (None, "self"):
+            raise ValueError(f"occlusion: {occlusion!r}, expected None or 'self'")
+        if occlusion is not None and not (np.isfinite(depth_bias) and depth_bias >= 0 and np.isfinite(slope_bias) and slope_bias >= 0):
+            raise ValueError(f"depth_bias {depth_bias} and slope_bias {slope_bias} must be finite and not negative")
+        n = vertices.shape[0]
+        dev = torch.device("cuda", self.device)
+        self._check(vertices, "vertices", torch.float32, (n, self.n_verts, 3))
+        self._check(normals, "normals", torch.float64, (n, self.n_verts, 3))
+        fr, idx = self._frames_and_index(frames, image_index, n)
         s = self.size
         if score is not None:
             if out is None:
@@ -187,9 +239,16 @@ class UVMap:
         self._check(out, "out", torch.uint8, (n, s, s, 3))
         flags = torch.empty(n, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(self._lib.dad3d_uvmap_bake_frames(self._handle, out.data_ptr(), score.data_ptr() if score is not None else None,
-                                                     vertices.data_ptr(), normals.data_ptr(), fr.device.data_ptr(), fr.host.ctypes.data,
-                                                     len(fr), idx.data_ptr(), n, flags.data_ptr(), stream))
+        if occlusion is None:
+            _lib.check(self._lib.dad3d_uvmap_bake_frames(self._handle, out.data_ptr(), score.data_ptr() if score is not None else None,
+                                                         vertices.data_ptr(), normals.data_ptr(), fr.device.data_ptr(), fr.host.ctypes.data,
+                                                         len(fr), idx.data_ptr(), n, flags.data_ptr(), stream))
+            return out, flags
+        d_map, window, d_flags = self.depth_frames(vertices, fr, idx, depth_side=depth_side, out=depth)
+        _lib.check(self._lib.dad3d_uvmap_bake_frames_occluded(
+            self._handle, out.data_ptr(), score.data_ptr() if score is not None else None, vertices.data_ptr(), normals.data_ptr(),
+            fr.device.data_ptr(), fr.host.ctypes.data, len(fr), idx.data_ptr(), n, d_map.data_ptr(), window.data_ptr(), d_flags.data_ptr(),
+            int(depth_side), float(depth_bias), float(slope_bias), flags.data_ptr(), stream))
         return out, flags
 
 
@@ -290,20 +349,23 @@ class UVTextureCreator:
         return m.bake(verts, normals, images, hw=hw, out=out)
 
     def bake_frames(self, params: Tensor, frames, image_index, mutate: bool = True, out: Optional[Tensor] = None,
-                    score: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                    score: Optional[Tensor] = None, occlusion: Optional[str] = None, depth_side: int = 512, depth_bias: float = 1.0,
+                    slope_bias: float = 1.0, depth=None) -> Tuple[Tensor, Tensor]:
         """`params [N,413]` fp32 on the GPU, in FRAME coordinates (what `predict_boxes` / `HeadTracker.step` return), head k read from
         `frames[image_index[k]]` -> (textures `[N,S,S,3]` uint8, flags `[N]` int32), both on the GPU.
 
         Three launches on the current stream, no host sync: the decode of `bake_batch` (`proj=True, to_2d=False`, no flip; `mutate`
         writes translation z := 0 into `params`), the float64 normals and `UVMap.bake_frames` -- see there for `frames`, `image_index`,
-        `out`, `score` and the flags. A lost slot of the tracker (`image_index == -1`) is flagged and, with `score`, changes nothing.
+        `out`, `score`, the flags and `occlusion="self"` with its keywords (three more launches: the head's own depth map, then the bake
+        with the depth test). A lost slot of the tracker (`image_index == -1`) is flagged and, with `score`, changes nothing.
         Capturable in a graph after one call of the same N or after `reserve(N)`, with `frames` a `DeviceFrames`."""
         m = self.uv_map
         n = params.shape[0]
         self.reserve(n)
         verts = self.head_mesh.flame.decode(params, proj=True, to_2d=False, mutate=mutate)["proj"]
         normals = m.vertex_normals(verts, out=self._normals[:n])
-        return m.bake_frames(verts, normals, frames, image_index, out=out, score=score)
+        return m.bake_frames(verts, normals, frames, image_index, out=out, score=score, occlusion=occlusion, depth_side=depth_side,
+                             depth_bias=depth_bias, slope_bias=slope_bias, depth=depth)
 
     # -- textured render: the other half of the bake -------------------------------------------------------
     def set_texcoords(self, tex_coords: np.ndarray, tex_triangles: np.ndarray) -> None:
@@ -389,23 +451,41 @@ class TextureAccumulator:
 
     A one-frame bake is half empty, because the reference skips every texel whose normal faces away; over a video the head turns and
     `add` keeps, per texel, the sample seen most frontally ("best view wins": strictly greater n_dot_view replaces, a tie keeps the
-    older sample). Head k of a call always goes to slot k -- the tracker's slots are fixed. Not done: blending of samples, occlusion
-    of a head by another head or an object, temporal filtering."""
+    older sample). Head k of a call always goes to slot k -- the tracker's slots are fixed.
 
-    def __init__(self, creator: UVTextureCreator, n_slots: int):
+    `occlusion="self"`: every `add` first draws each head's own depth map (`UVMap.depth_frames`, `depth_side` pixels square, owned
+    here) and skips the samples that lie behind it (`UVMap.bake_frames`: `depth_bias`, `slope_bias`, untuned defaults) -- without it
+    a sample taken through the nose stays until a better-scored view arrives, which for a texel only ever seen at a grazing angle is
+    never. Off by default. Not done: blending of samples, occlusion of a head by another head or an object (depths of different heads
+    do not compare), temporal filtering."""
+
+    def __init__(self, creator: UVTextureCreator, n_slots: int, occlusion: Optional[str] = None, depth_side: int = 512,
+                 depth_bias: float = 1.0, slope_bias: float = 1.0):
         if int(n_slots) < 1:
             raise ValueError(f"n_slots: {n_slots}, at least 1")
+        if occlusion not in (None, "self"):
+            raise ValueError(f"occlusion: {occlusion!r}, expected None or 'self'")
+        if not 1 <= int(depth_side) <= _lib.BAKE_MAX_DEPTH_SIDE:
+            raise ValueError(f"depth_side: {depth_side} outside 1..{_lib.BAKE_MAX_DEPTH_SIDE}")
+        self.occlusion, self.depth_side, self.depth_bias, self.slope_bias = occlusion, int(depth_side), float(depth_bias), float(slope_bias)
+        self._depth = None  # (depth [n,D,D], window [n,4], flags [n]) with occlusion="self"
         self.creator = creator
         self.n_slots = int(n_slots)
         dev = creator.head_mesh.flame.torch_device
         s = creator.img_size
         self.textures = torch.zeros((self.n_slots, s, s, 3), dtype=torch.uint8, device=dev)
         self.score = torch.full((self.n_slots, s, s), -1.0, dtype=torch.float32, device=dev)
-        creator.reserve(self.n_slots)
+        self.reserve(self.n_slots)
 
     def reserve(self, n: int) -> None:
-        """Size the creator's buffers for `n` heads a call, so that a later `add` can be captured in a graph."""
-        self.creator.reserve(int(n))
+        """Size the creator's buffers, and with `occlusion="self"` the depth maps, windows and depth flags, for `n` heads a call, so
+        that a later `add` can be captured in a graph."""
+        n = int(n)
+        self.creator.reserve(n)
+        if self.occlusion is not None and (self._depth is None or self._depth[0].shape[0] < n):
+            dev, d = self.textures.device, self.depth_side
+            self._depth = (torch.empty((n, d, d), dtype=torch.float32, device=dev), torch.zeros((n, 4), dtype=torch.int32, device=dev),
+                           torch.zeros(n, dtype=torch.int32, device=dev))
 
     def reset(self, slots=None, mask=None) -> None:
         """Zeros and score -1 for all slots (None) or the given ones (a sequence or an int64 CUDA tensor): what a caller does beside
@@ -435,7 +515,7 @@ class TextureAccumulator:
         """One frame set of the video: `predictions_or_params` the list of per-head dicts of `predict_boxes` / `HeadTracker.step`
         (their `3dmm_params` are stacked and `image_index=None` means their own, as `overlay.draw_heads` does) or a `[N,413]` tensor
         with `image_index`; N <= n_slots, head k into slot k. -> int32 CUDA flags `[N]` (`_lib.BAKE_FLAG_INDEX`: the slot named no
-        frame and kept its state). Nothing waits for the device; the params are not mutated."""
+        frame and kept its state; with `occlusion="self"` also `BAKE_FLAG_NONFINITE` and `BAKE_FLAG_DEPTH_WINDOW`, likewise kept). Nothing waits for the device; the params are not mutated."""
         dev = self.textures.device
         if isinstance(predictions_or_params, Tensor):
             if image_index is None:
@@ -451,7 +531,13 @@ class TextureAccumulator:
             raise ValueError(f"{n} heads for {self.n_slots} slots")
         if len(index) != n:
             raise ValueError(f"image_index: {len(index)} entries for {n} heads")
-        _, flags = self.creator.bake_frames(params, frames, index, mutate=False, out=self.textures[:n], score=self.score[:n])
+        if self.occlusion is None:
+            _, flags = self.creator.bake_frames(params, frames, index, mutate=False, out=self.textures[:n], score=self.score[:n])
+            return flags
+        self.reserve(n)
+        _, flags = self.creator.bake_frames(params, frames, index, mutate=False, out=self.textures[:n], score=self.score[:n],
+                                            occlusion=self.occlusion, depth_side=self.depth_side, depth_bias=self.depth_bias,
+                                            slope_bias=self.slope_bias, depth=tuple(t[:n] for t in self._depth))
         return flags
 
     def filled(self) -> Tensor:

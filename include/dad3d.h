@@ -637,13 +637,65 @@ DAD3D_EXPORT dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, con
  *                  float32), the texel's three bytes and score[k,t] are replaced iff s > score[k,t]. A NaN s never replaces, a tie
  *                  keeps the older sample, a texel without a candidate keeps its state, and a flagged head changes no byte of its
  *                  texture or score. Start a texture at zeros with score -1.0f: then any first sample (n_dot_view >= 0) enters.
- * Not done: blending of samples, occlusion of a head by another head or an object, temporal filtering of the texture.
+ * Not done: blending of samples, occlusion of a head by another head or an object (a head's occlusion of itself:
+ * dad3d_uvmap_bake_frames_occluded below), temporal filtering of the texture.
  * The entry allocates nothing, is stream-ordered and can be captured into a graph. n_heads == 0: DAD3D_OK, nothing to do; n_frames
  * == 0: every head is flagged. At most 65535 heads a call. One handle may serve several streams. */
 #define DAD3D_BAKE_FLAG_INDEX 1
+#define DAD3D_BAKE_FLAG_DEPTH_WINDOW 2 /* the head's box in its frame is wider or higher than depth_side */
+#define DAD3D_BAKE_FLAG_NONFINITE 4    /* a coordinate of one of the head's vertices is NaN or +-inf */
+#define DAD3D_BAKE_MAX_DEPTH_SIDE 4096
 DAD3D_EXPORT dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices,
                                                   const double* normals, const int64_t* frames, const int64_t* frames_host, int n_frames,
                                                   const int32_t* image_index, int n_heads, int32_t* flags, void* stream);
+
+/* Depth maps of heads in frames: for every head the nearest z of its own surface at every pixel of its box in the frame it names --
+ * what a depth test against the head itself needs, and a depth output in its own right. Coordinates are the bake's: frame pixel x,
+ * pixel y, and z with the viewer at -z (n_dot_view = -n_z), so the nearer surface has the SMALLER z. Depths of different heads do not
+ * compare (every head is decoded with translation z := 0).
+ *   depth        DEVICE float32 [n_heads, D, D], D = depth_side in 1 .. DAD3D_BAKE_MAX_DEPTH_SIDE
+ *   window       DEVICE int32 [n_heads,4] = {x0, y0, ww, wh}, written
+ *   vertices     DEVICE [n_heads,nver,3] float32; frames / frames_host / image_index as in dad3d_uvmap_bake_frames, with the same host
+ *                checks; only h and w of a frame entry are used, no pixel is read
+ *   flags        DEVICE int32 [n_heads], written: DAD3D_BAKE_FLAG_INDEX (the bake's rule) | DAD3D_BAKE_FLAG_NONFINITE (any x, y or z of the
+ *                head's vertices is NaN or +-inf) | DAD3D_BAKE_FLAG_DEPTH_WINDOW (ww > D or wh > D). A flagged head gets the window
+ *                {0,0,0,0} and no byte of its map is written.
+ * Window, in float: x0 = max(floorf(min x), 0), x1 = min(ceilf(max x), w - 1), likewise y; ww = x1 - x0 + 1. x0 > x1 or y0 > y1: the head
+ * lies outside its frame, the window is {0,0,0,0} and NO flag is set. For 0 <= j < wh, 0 <= i < ww, depth[k, j, i] (row pitch D) belongs
+ * to pixel (x0 + i, y0 + j): the minimum interpolated z over the head's triangles that cover the pixel centre, in exactly the
+ * arithmetic of the reference's _rasterize_triangles (rasterize_kernel.cpp:295-353) called on the head with z negated on an h x w canvas
+ * initialised to -1e8 and negated back -- the box of lines 321-325, is_point_in_tri, w0 * z0 + w1 * z1 + w2 * z2 with
+ * get_point_weight's float32 weights. +inf where no triangle covers the pixel, or only fragments with z >= 1e8 do; NaN never enters;
+ * -0 is stored as +0. Entries outside ww x wh are not written.
+ * Three launches (window, clear, one lane per head and triangle with a 32-bit atomic minimum); nothing is allocated; stream-ordered
+ * and capturable. Every store is bounded by the head's own ww, wh <= D, whatever the device frame table says. */
+DAD3D_EXPORT dad3d_status dad3d_uvmap_depth_frames(dad3d_uvmap* m, float* depth, int32_t* window, const float* vertices,
+                                                   const int64_t* frames, const int64_t* frames_host, int n_frames,
+                                                   const int32_t* image_index, int n_heads, int depth_side, int32_t* flags, void* stream);
+
+/* dad3d_uvmap_bake_frames with a depth test against the head itself: a texel on the far cheek that faces the camera from behind the
+ * nose no longer takes the nose's pixel. depth / window / depth_flags / depth_side: what dad3d_uvmap_depth_frames wrote for the SAME
+ * vertices, frames and image_index (read only). Everything is dad3d_uvmap_bake_frames except:
+ *   third test   a candidate that passes the two tests, with rounded pixel (rx, ry), is HIDDEN iff
+ *                    pz > (double) d + (depth_bias + slope_bias * ((fabs(nx) + fabs(ny)) / n_dot_view))
+ *                d = the head's depth at (rx, ry), +inf for a pixel outside the window; pz, nx, ny = the float64 sums of products of the
+ *                candidate's z and its normal's x and y, in the order of the point's x and the normal's z; every operation rounds on its
+ *                own. The comparison is false on NaN: an uncovered pixel, n_dot_view == +0 (a slope of inf or NaN) and a NaN leave the
+ *                candidate visible (n_dot_view == -0 divides to -inf where the normal has an x or y, and hides it). A hidden candidate is skipped like a back-facing one: the texel's next candidate is tried.
+ *   flags        flags[k] = depth_flags[k] | DAD3D_BAKE_FLAG_INDEX where the index names no frame. A head with any flag changes no
+ *                byte of texture or score (score != NULL) or gives zeros (score == NULL).
+ *   biases       in pixels of depth, both finite and >= 0, else DAD3D_E_INVALID before any device work. depth_bias covers the rounding of
+ *                the map against the point; the slope term covers the up to half a pixel in x and in y between the point and the pixel
+ *                centre, 0.5 * (|nx| + |ny|) / |nz| of depth on a plane with normal n, at slope_bias = 0.5; 1.0 and 1.0 are what the
+ *                Python layer passes by default -- UNTUNED design choices: with both at 0 a quarter to a half of the accepted samples
+ *                are "hidden" by their own surface (shadow acne).
+ * Not done: occlusion of a head by another head or by an object -- depths of different heads do not compare.
+ * One launch; nothing is allocated; stream-ordered and capturable. */
+DAD3D_EXPORT dad3d_status dad3d_uvmap_bake_frames_occluded(dad3d_uvmap* m, uint8_t* texture, float* score, const float* vertices,
+                                                           const double* normals, const int64_t* frames, const int64_t* frames_host,
+                                                           int n_frames, const int32_t* image_index, int n_heads, const float* depth,
+                                                           const int32_t* window, const int32_t* depth_flags, int depth_side,
+                                                           double depth_bias, double slope_bias, int32_t* flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The vertex block of the demo's `.obj` files (demo_utils.py:130-144 `MeshSaver.__call__`): for every mesh of a batch the bytes of
