@@ -50,6 +50,7 @@ FRAME_FLAG_INDEX, FRAME_FLAG_CAPACITY, FRAME_MAX_TILES, FRAME_MAX_COUNT = 0x1, 0
 RENDER_REVERSE, RENDER_CLEAR = 1, 2
 BAKE_FLAG_INDEX, BAKE_FLAG_DEPTH_WINDOW, BAKE_FLAG_NONFINITE, BAKE_MAX_DEPTH_SIDE = 0x1, 0x2, 0x4, 4096
 POSE_FLAG_NONFINITE, POSE_FLAG_DEGENERATE, POSE_FLAG_GIMBAL, POSE_FLAG_INDEX = 0x1, 0x2, 0x4, 0x8
+HEADS_MAX, HEAD_ACT_NONE, HEAD_ACT_RELU, HEAD_ACT_TANH = 4, 0, 1, 2
 KERNEL_AUTO, KERNEL_TWO_ROLE, KERNEL_PIPELINED, KERNEL_SPLIT_BF16, KERNEL_SPLIT_F16 = 0, 1, 2, 3, 4
 
 
@@ -91,6 +92,22 @@ class LightC(C.Structure):
         ("color_directional", C.c_float * 3),
         ("light_pos", C.c_float * 3),
         ("view_pos", C.c_float * 3),
+    ]
+
+
+class HeadDescC(C.Structure):
+    _fields_ = [
+        ("w1", C.c_void_p),
+        ("b1", C.c_void_p),
+        ("w2", C.c_void_p),
+        ("b2", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("dst_row_stride", C.c_int64),
+        ("dst_col_offset", C.c_int64),
+        ("hidden", C.c_int32),
+        ("out_dim", C.c_int32),
+        ("act", C.c_int32),
+        ("limit", C.c_float),
     ]
 
 
@@ -148,6 +165,9 @@ SIGNATURES = {
     "dad3d_preprocess_images": (_I, [_P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _I, _P]),
     "dad3d_nhwc_bias_act": (_I, [_P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
     "dad3d_nhwc_resize_sum": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_float), _I, _P]),
+    "dad3d_nhwc_fusion_concat": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dad3d_nhwc_bias_mul": (_I, [_P, _P, _P, C.c_int64, _I, _I, _I, _P]),
+    "dad3d_regression_heads": (_I, [_P, _I, _I, _I, _I, C.POINTER(HeadDescC), _I, _P, _P, _P, _I, _P]),
     "dad3d_heatmap_argmax": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "dad3d_points_readjust": (_I, [_P, _I, _I, _I, _F, _F, _P, _I, _I, C.c_double, _P, _I, _P]),
     "dad3d_preprocess_boxes": (_I, [_P, _I, _P, _I, _P, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, _P,

@@ -79,6 +79,64 @@ dad3d_status dad3d_nhwc_resize_sum(void* out, int n, int oh, int ow, int channel
     return launch_nhwc_resize_sum(out, n, oh, ow, channels, dtype, n_inputs, xs, hs, ws, weights, static_cast<hipStream_t>(stream));
 }
 
+dad3d_status dad3d_nhwc_fusion_concat(void* out, const void* x, const void* heat, const void* level, int n, int oh, int ow, int hh, int hw,
+                                      int cx, int ch, int cl, int dtype, int device, void* stream) {
+    DAD3D_REQUIRE(n >= 0 && oh >= 0 && ow >= 0 && hh > 0 && hw > 0 && cx > 0 && ch > 0 && cl > 0 && dtype_vec(dtype),
+                  "dad3d_nhwc_fusion_concat: bad argument");
+    const int per_piece = dtype_vec(dtype) / 2;  // elements of 8 bytes
+    DAD3D_REQUIRE(cx % per_piece == 0 && ch % per_piece == 0 && cl % per_piece == 0,
+                  "dad3d_nhwc_fusion_concat: %d / %d / %d channels are not multiples of %d (8 bytes)", cx, ch, cl, per_piece);
+    DAD3D_REQUIRE((int64_t)cx + ch + cl <= 0x7fffffff && (int64_t)n * hh * hw <= 0x7fffffff && (int64_t)n * oh * ow <= 0x7fffffff,
+                  "dad3d_nhwc_fusion_concat: sizes beyond 2^31 - 1");
+    if (n == 0 || oh == 0 || ow == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(out && x && heat && level, "dad3d_nhwc_fusion_concat: null tensor");
+    DAD3D_REQUIRE(aligned(out, 16) && aligned(x, 16) && aligned(heat, 16) && aligned(level, 16),
+                  "dad3d_nhwc_fusion_concat: tensors must be 16-byte aligned");
+    DAD3D_SELECT_DEVICE(device);
+    return launch_nhwc_fusion_concat(out, x, heat, level, n, oh, ow, hh, hw, cx, ch, cl, dtype, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_nhwc_bias_mul(void* y, const void* bias, const void* x, int64_t n_pixels, int channels, int dtype, int device, void* stream) {
+    DAD3D_REQUIRE(n_pixels >= 0 && channels > 0 && dtype_vec(dtype), "dad3d_nhwc_bias_mul: bad argument");
+    if (n_pixels == 0) return DAD3D_OK;
+    DAD3D_REQUIRE(y && bias && x, "dad3d_nhwc_bias_mul: null tensor");
+    DAD3D_REQUIRE(channels % dtype_vec(dtype) == 0, "dad3d_nhwc_bias_mul: %d channels are not a multiple of %d (16 bytes)", channels, dtype_vec(dtype));
+    DAD3D_REQUIRE(aligned(y, 16) && aligned(bias, 16) && aligned(x, 16), "dad3d_nhwc_bias_mul: tensors must be 16-byte aligned");
+    DAD3D_SELECT_DEVICE(device);
+    return launch_nhwc_bias_mul(y, bias, x, (size_t)n_pixels, channels, dtype, static_cast<hipStream_t>(stream));
+}
+
+dad3d_status dad3d_regression_heads(const void* top, int batch, int channels, int hw, int dtype, const dad3d_head_desc* heads, int n_heads,
+                                    float* workspace, float* pooled_out, float* hidden_out, int device, void* stream) {
+    const int vec = dtype_vec(dtype);
+    DAD3D_REQUIRE(vec, "dad3d_regression_heads: unknown dtype %d", dtype);
+    DAD3D_REQUIRE(batch > 0 && batch <= 65535 && channels > 0 && hw > 0 && n_heads >= 1 && n_heads <= DAD3D_HEADS_MAX,
+                  "dad3d_regression_heads: bad size (batch %d, channels %d, hw %d, heads %d)", batch, channels, hw, n_heads);
+    DAD3D_REQUIRE(channels % vec == 0, "dad3d_regression_heads: %d channels are not a multiple of %d (16 bytes)", channels, vec);
+    DAD3D_REQUIRE((int64_t)hw * (channels / vec) <= 0x7fffffff, "dad3d_regression_heads: an image of %d x %d is beyond 2^31 - 1 vectors", hw, channels);
+    DAD3D_REQUIRE(top && heads && workspace, "dad3d_regression_heads: null argument");
+    DAD3D_REQUIRE(aligned(top, 16) && aligned(workspace, 16) && aligned(pooled_out, 16) && aligned(hidden_out, 16),
+                  "dad3d_regression_heads: tensors must be 16-byte aligned");
+    RegressionHeadsArgs a{top, batch, channels, hw, dtype, n_heads, {}, nullptr, nullptr};
+    for (int j = 0; j < n_heads; ++j) {
+        const dad3d_head_desc& d = heads[j];
+        DAD3D_REQUIRE(d.hidden > 0 && d.out_dim > 0 && d.hidden % vec == 0, "dad3d_regression_heads: head %d: hidden %d (a multiple of %d), out_dim %d", j,
+                      d.hidden, vec, d.out_dim);
+        DAD3D_REQUIRE(d.act >= DAD3D_HEAD_ACT_NONE && d.act <= DAD3D_HEAD_ACT_TANH, "dad3d_regression_heads: head %d: unknown activation %d", j, d.act);
+        DAD3D_REQUIRE(d.w1 && d.b1 && d.w2 && d.b2 && d.dst, "dad3d_regression_heads: head %d: null tensor", j);
+        DAD3D_REQUIRE(aligned(d.w1, 16) && aligned(d.w2, 16) && aligned(d.b1, vec == 4 ? 4 : 2) && aligned(d.b2, vec == 4 ? 4 : 2) && aligned(d.dst, 4),
+                      "dad3d_regression_heads: head %d: misaligned tensor", j);
+        DAD3D_REQUIRE(d.dst_col_offset >= 0 && d.dst_row_stride >= d.dst_col_offset + d.out_dim,
+                      "dad3d_regression_heads: head %d: a destination row of %lld floats does not hold columns %lld .. +%d", j,
+                      (long long)d.dst_row_stride, (long long)d.dst_col_offset, d.out_dim);
+        a.head[j] = d;
+    }
+    a.pooled = pooled_out ? pooled_out : workspace;
+    a.hidden = hidden_out ? hidden_out : workspace + (size_t)batch * channels;
+    DAD3D_SELECT_DEVICE(device);
+    return launch_regression_heads(a, static_cast<hipStream_t>(stream));
+}
+
 dad3d_status dad3d_heatmap_argmax(const void* heatmap, int dtype, int batch, int channels, int h, int w, int layout, int sigmoid,
                                   int32_t* yx_out, float* peak_out, int device, void* stream) {
     const int es = dtype == DAD3D_DTYPE_F32 ? 4 : (dtype == DAD3D_DTYPE_F16 || dtype == DAD3D_DTYPE_BF16) ? 2 : dtype == DAD3D_HEATMAP_DTYPE_U8 ? 1 : 0;

@@ -718,6 +718,18 @@ dad3d_status launch_nhwc_bias_act(void* y, const void* bias, const void* z, size
 dad3d_status launch_nhwc_resize_sum(void* out, int n, int oh, int ow, int channels, int dtype, int n_inputs, const void* const* xs,
                                     const int* hs, const int* ws, const float* weights, hipStream_t s);
 
+// the forward's tail (net_tail.hip): the fusion layer's input and output, the regression heads
+dad3d_status launch_nhwc_fusion_concat(void* out, const void* x, const void* heat, const void* level, int n, int oh, int ow, int hh, int hw,
+                                       int cx, int ch, int cl, int dtype, hipStream_t s);
+dad3d_status launch_nhwc_bias_mul(void* y, const void* bias, const void* x, size_t n_pixels, int channels, int dtype, hipStream_t s);
+struct RegressionHeadsArgs {
+    const void* top;  // [batch, hw, channels]
+    int batch, channels, hw, dtype, n_heads;
+    dad3d_head_desc head[DAD3D_HEADS_MAX];
+    float *pooled, *hidden;  // float32 [batch, channels] and [batch, sum of hidden]: the stages between the three launches
+};
+dad3d_status launch_regression_heads(const RegressionHeadsArgs& a, hipStream_t s);
+
 // heatmap peaks and the landmark readjustment (heatmap_points.hip): dtype = DAD3D_DTYPE_* or DAD3D_HEATMAP_DTYPE_U8, layout = DAD3D_LAYOUT_*
 struct HeatmapArgmaxArgs {
     const void* heatmap;

@@ -40,6 +40,10 @@ OUTPUT_3DMM_PARAMS = "OUTPUT_3DMM_PARAMS"
 OUTPUT_2D_LANDMARKS = "OUTPUT_2D_LANDMARKS"
 OUTPUT_LANDMARKS_HEATMAP = "OUTPUT_LANDMARKS_HEATMAP"
 
+# What InferenceNet(tail="hip") takes from csrc/net_tail.hip: the pieces that tests/perf/bench_net_tail.py measured faster than the
+# framework chain they replace by more than both spreads at batch 1 or batch 64 (profiles/net_tail_bench.json).
+HIP_TAIL_PIECES = frozenset({"fusion_in", "fusion_out", "heads"})
+
 
 def _conv_bn(cin: int, cout: int, k: int, stride: int = 1, relu: bool = True) -> nn.Sequential:
     layers: List[nn.Module] = [nn.Conv2d(cin, cout, k, stride, k // 2, bias=False), nn.BatchNorm2d(cout)]
@@ -219,9 +223,21 @@ class DAD3DNet(nn.Module):
             feats.append(x)
         levels = self.bifpn(feats[1:])
         heatmap = self.heatmap(levels[0])
-        hm = F.interpolate(heatmap, size=x.shape[2:], mode="bilinear", align_corners=True).sigmoid()
-        fused = self.fusion(torch.cat([x, hm, levels[2]], dim=1)) * x
+        tail = self.__dict__.get("tail") or ()  # the pieces of the tail served by csrc/net_tail.hip (InferenceNet(tail="hip"))
+        if "fusion_in" in tail and _glue.supported_fusion(x, heatmap, levels[2]):
+            fusion_in = _glue.fusion_concat(x, heatmap, levels[2])
+        else:
+            hm = F.interpolate(heatmap, size=x.shape[2:], mode="bilinear", align_corners=True).sigmoid()
+            fusion_in = torch.cat([x, hm, levels[2]], dim=1)
+        if "fusion_out" in tail and x.is_cuda and self.fusion.bias.dtype == x.dtype:
+            y = F.conv2d(fusion_in, self.fusion.weight)  # without its bias: the bias and the product are one pass behind it
+            fused = _glue.bias_mul_(y, self.fusion.bias, x) if _glue.supported(y, x) else (y + self.fusion.bias.view(1, -1, 1, 1)) * x
+        else:
+            fused = self.fusion(fusion_in) * x
         top = stages[4](fused)
+        if "heads" in tail and self.__dict__["tail_heads"].supported(top):
+            params, lmk = self.__dict__["tail_heads"](top)
+            return {OUTPUT_LANDMARKS_HEATMAP: heatmap, OUTPUT_3DMM_PARAMS: params, OUTPUT_2D_LANDMARKS: lmk}
         shape = torch.tanh(self.shape(top)) * self.limit_value
         lmk = F.relu(self.landmarks(top)).reshape(x.shape[0], -1, 2)
         return {OUTPUT_LANDMARKS_HEATMAP: heatmap, OUTPUT_3DMM_PARAMS: torch.cat([shape, self.pose(top)], dim=1),
@@ -380,12 +396,22 @@ def fuse_glue(module: nn.Module) -> nn.Module:
 class InferenceNet(nn.Module):
     """`DAD3DNet` frozen for serving: eval mode, BatchNorm folded into the convolutions, channels-last, reduced-precision
     autocast; fp32 parameters out. `tune=True` lets MIOpen time its kernels per layer shape on the first call (+36 % at
-    batch 64, first call ~17 s)."""
+    batch 64, first call ~17 s). `tail="hip"` serves the stretch between the BiFPN and the params rows -- the fusion layer's input and
+    output, the three regression heads -- through csrc/net_tail.hip (`HIP_TAIL_PIECES`); the heads then return float32 computed in
+    fp32 from the last stage's map, not rounded through the serving dtype. The default, "framework", is the plain ops."""
 
     def __init__(self, net: nn.Module, dtype: torch.dtype = torch.bfloat16, fold_bn: bool = True, tune: bool = False,
-                 glue: bool = True):
+                 glue: bool = True, tail: str = "framework"):
         super().__init__()
+        if tail not in ("framework", "hip"):
+            raise ValueError(f"InferenceNet: tail must be 'framework' or 'hip', not {tail!r}")
         net = net.eval()
+        if tail == "hip":
+            if not isinstance(net, DAD3DNet):
+                raise ValueError("InferenceNet: tail='hip' serves the tail of a DAD3DNet")
+            # flags in __dict__, not attributes: no module, parameter or state-dict entry is added (as BiFPNBlock's "glue")
+            net.__dict__["tail"] = HIP_TAIL_PIECES
+            net.__dict__["tail_heads"] = _glue.RegressionHeads((net.shape, net.pose, net.landmarks), net.limit_value)
         if fold_bn:
             fold_batchnorm(net)
             if glue:

@@ -67,19 +67,25 @@ class FaceMeshPredictor:
         self._lib = _lib.load()
 
     @classmethod
-    def dad_3dnet(cls, **kwargs):
+    def dad_3dnet(cls, tail: str = "framework", **kwargs):
+        """`tail` reaches a `model` that is an `InferenceNet` built for it; the TorchScript checkpoint has no such choice."""
         from .config import load_default_config
 
+        if tail not in ("framework", "hip"):
+            raise ValueError(f"dad_3dnet: tail must be 'framework' or 'hip', not {tail!r}")
+        if tail == "hip" and kwargs.get("model") is None:
+            raise ValueError("dad_3dnet: tail='hip' needs model=InferenceNet(DAD3DNet, tail='hip'): a TorchScript file runs the framework's ops")
         return cls(config=load_default_config(), **kwargs)
 
     @classmethod
-    def random_init(cls, dtype: torch.dtype = torch.bfloat16, seed: int = 0, tune: bool = False, graph: bool = False, **kwargs):
+    def random_init(cls, dtype: torch.dtype = torch.bfloat16, seed: int = 0, tune: bool = False, graph: bool = False,
+                    tail: str = "framework", **kwargs):
         """DAD-3DNet architecture declared in `network.py` with seeded random weights (no checkpoint offline):
-        the real compute and memory footprint of the front half for throughput and plumbing tests."""
+        the real compute and memory footprint of the front half for throughput and plumbing tests. `tail`: InferenceNet's."""
         from .config import load_default_config
         from .network import DAD3DNet, GraphedNet, InferenceNet
 
-        net = InferenceNet(DAD3DNet(seed=seed), dtype, tune=tune)
+        net = InferenceNet(DAD3DNet(seed=seed), dtype, tune=tune, tail=tail)
         device = torch.device("cuda", kwargs.get("cuda_id", 0))
         model = GraphedNet(net.to(device)) if graph else net  # graph=True: one hipGraph per input shape
         return cls(config=load_default_config(), model=model, **kwargs)

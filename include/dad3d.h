@@ -1168,6 +1168,58 @@ DAD3D_EXPORT dad3d_status dad3d_nhwc_resize_sum(void* out, int n, int oh, int ow
                                    const int* hs, const int* ws, const float* weights, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The tail of the DAD-3DNet forward (csrc/net_tail.hip): the fusion layer's glue and the three regression heads
+ * (model_training/model/flame_regression.py:28-43, 45-59, 96-100). Channels-last (NHWC, dense) DEVICE tensors of dtype
+ * DAD3D_DTYPE_*, base pointers 16-byte aligned. Each entry runs on `stream`, allocates nothing, waits for nothing and uses no
+ * floating-point atomics: two calls, and a graph replay, give the same bits.
+ *
+ * dad3d_nhwc_fusion_concat  out[n,y,x,:] = [ x[n,y,x,0:cx] | sigmoid(bilinear(heat)[n,y,x,0:ch]) | level[n,y,x,0:cl] ]
+ *   x [n,oh,ow,cx] and level [n,oh,ow,cl] at out's extent, heat [n,hh,hw,ch] at its own; every segment's byte width a multiple of 8
+ *   (the 68 heat-map channels of a 2-byte type are 136 bytes). The copied segments are byte copies. The middle one is
+ *   F.interpolate(mode="bilinear", align_corners=True) and the sigmoid in fp32, every operation rounded on its own (no fused
+ *   multiply-add), ONE rounding to nearest even at the store; per axis
+ *     scale = (n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.0f
+ *     src = scale * (float)dst;  i0 = (int)src;  i1 = i0 + (i0 < n_in - 1);  l1 = src - (float)i0;  l0 = 1.0f - l1
+ *     v   = lh0 * (lw0 * a + lw1 * b) + lh1 * (lw0 * c + lw1 * d)              (a, b from row i0; c, d from row i1)
+ *     out = round_to_dtype(1.0f / (1.0f + expf(-v)))
+ *   Non-finite values follow the formula (0 * inf = NaN).
+ *
+ * dad3d_nhwc_bias_mul  y[p][c] = round_to_dtype((y[p][c] + bias[c]) * x[p][c]), in place: the fusion convolution's bias and the
+ *   product with its first input in one pass; fp32, two rounded operations (no fused form); `channels` a multiple of 16 bytes' worth.
+ *
+ * dad3d_regression_heads  top [batch, hw positions, channels] -> for each of n_heads <= DAD3D_HEADS_MAX heads
+ *     pooled = (fp32 sum of top over the hw positions) / (float)hw                       (once for all heads)
+ *     hidden = relu(pooled . w1^T + b1);  dst[b][col_offset + j] = act(hidden . w2^T + b2)[j]
+ *   fp32 accumulation throughout; pooled and hidden are never rounded to the tensors' dtype. w1 [hidden, channels], b1 [hidden],
+ *   w2 [out_dim, hidden], b2 [out_dim] row-major in top's dtype (nn.Linear's layout), 16-byte aligned; `channels` and every `hidden`
+ *   a multiple of 16 bytes' worth. act: DAD3D_HEAD_ACT_NONE, _RELU (a NaN stays a NaN, as in F.relu) or _TANH (limit * tanhf(v),
+ *   one rounded product). dst is float32 with dst_row_stride floats between images, so several heads can share one buffer.
+ *     workspace   float32 [batch * (channels + sum of hidden)], 16-byte aligned: pooled, then hidden
+ *     pooled_out  float32 [batch, channels] or NULL;  hidden_out  float32 [batch, sum of hidden] or NULL (heads in order): when given,
+ *                 the stage is written there instead of into the workspace (for tests; 16-byte aligned)
+ *   Three launches: the pool, the first layer of all heads, the second layer of all heads.
+ *   DAD3D_E_INVALID before any device work: a null or misaligned tensor, a size <= 0, batch > 65535, an unknown dtype or activation,
+ *   a channel or hidden count that is no multiple of 16 bytes' worth, a destination row shorter than its columns. */
+#define DAD3D_HEADS_MAX 4
+#define DAD3D_HEAD_ACT_NONE 0
+#define DAD3D_HEAD_ACT_RELU 1
+#define DAD3D_HEAD_ACT_TANH 2
+typedef struct dad3d_head_desc {
+    const void *w1, *b1, *w2, *b2;
+    float* dst;
+    int64_t dst_row_stride, dst_col_offset; /* in floats */
+    int32_t hidden, out_dim, act;
+    float limit; /* DAD3D_HEAD_ACT_TANH only */
+} dad3d_head_desc;
+DAD3D_EXPORT dad3d_status dad3d_nhwc_fusion_concat(void* out, const void* x, const void* heat, const void* level, int n, int oh, int ow, int hh,
+                                      int hw, int cx, int ch, int cl, int dtype, int device, void* stream);
+DAD3D_EXPORT dad3d_status dad3d_nhwc_bias_mul(void* y, const void* bias, const void* x, int64_t n_pixels, int channels, int dtype, int device,
+                                 void* stream);
+DAD3D_EXPORT dad3d_status dad3d_regression_heads(const void* top, int batch, int channels, int hw, int dtype, const dad3d_head_desc* heads,
+                                    int n_heads, float* workspace, float* pooled_out /* or NULL */, float* hidden_out /* or NULL */,
+                                    int device, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * From the network's 2-D outputs to landmark points (csrc/heatmap_points.hip). All tensors are DEVICE pointers.
  *
  * dad3d_heatmap_argmax   `unravel_index` (model_training/model/utils.py:44-52) of a dense [B,C,H,W] heatmap: the argmax of
