@@ -74,7 +74,7 @@ def test_head_mesh_and_a_batch_blend_bit_exact(static, decode_golden, sim3dr_ora
 
 @pytest.mark.parametrize("profile", ["pixel_centres", "slivers", "tie_planes", "tile_straddle", "mixed_sizes", "split_tile", "wild", "layers"])
 def test_adversarial_profiles_blend_bit_exact(sim3dr_oracle, profile):
-    from test_gpu_raster_fuzz import build_case
+    from raster_cases import build_case
 
     for k, alpha in enumerate(ALPHAS):
         for seed in (11 + 100 * k, 12 + 100 * k):
