@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "capi_checks.hpp"
+#include "flame_plan.hpp"
 
 namespace dad3d {
 
@@ -25,35 +26,35 @@ void set_error(const char* fmt, ...) {
 
 using namespace dad3d;
 
+static_assert(plan::kJoints == kNumJoints && plan::kTileVerts == kTileVerts && plan::kTileCols == kTileCols &&
+                  plan::kPipeTileVerts == kPipeTileVerts && plan::kPipeKGroups == kPipeKGroups,
+              "flame_plan.hpp: not the tile geometry of common.hpp");
+
 // Read-only model constants on the device, shared by a handle and its forks (dad3d_flame_fork). A landmark sub-model keeps its pipelined
 // pack in one of these too (d_bpack_pipe, n_tiles_pipe, split_b_scale and the fp16 planes only).
 struct FlameConsts {
-    int device = 0;
-    float *d_bpack = nullptr, *d_jdirs = nullptr, *d_j0 = nullptr, *d_w8 = nullptr;
-    float* d_bpack_pipe = nullptr;  // basis of the 20-vertex tiles + jaw-joint columns (flame_decode_pipe.hip); null: model not covered
-    float split_b_scale = 1.0f;     // DAD3D_KERNEL_SPLIT_F16: the power of two its entries are multiplied by in front of their fp16 split
-    float* d_bpack_f16 = nullptr;   // ... and the pack split into its two fp16 planes, built by the first decode in that form (ensure_basis_f16)
+    DeviceArray<float> d_bpack, d_jdirs, d_j0, d_w8;
+    DeviceArray<float> d_bpack_pipe;  // basis of the 20-vertex tiles + jaw-joint columns (flame_decode_pipe.hip); empty: model not covered
+    float split_b_scale = 1.0f;       // DAD3D_KERNEL_SPLIT_F16: the power of two its entries are multiplied by in front of their fp16 split
+    DeviceArray<float> d_bpack_f16;   // ... and the pack split into its two fp16 planes, built by the first decode in that form (ensure_basis_f16)
     std::mutex f16_mu;
     int n_tiles_pipe = 0;
-    float* d_gpack = nullptr;  // basis^T in MFMA fragment order for dad3d_flame_grad_inputs: built by the first training forward
+    DeviceArray<float> d_gpack;  // basis^T in MFMA fragment order for dad3d_flame_grad_inputs: built by the first training forward
     std::mutex gpack_mutex;
-    ~FlameConsts() { free_device(device, {d_bpack, d_jdirs, d_j0, d_w8, d_gpack, d_bpack_pipe, d_bpack_f16}); }
 };
 
 // A landmark list on the device. Immutable once built -- dad3d_flame_set_landmarks builds a new one -- except for the sub-model's fp16
 // planes (built under their mutex), so a handle and its forks share it until one of them installs another list.
 struct LandmarkList {
-    int device = 0;
     int n = 0;
-    int *d_head = nullptr, *d_next = nullptr;  // [V][2] {first slot of the vertex, the slot after it}, [n] the slot after each slot
-    float4* d_vtab = nullptr;  // [V] {W, w_jaw, first landmark slot, slot chained after it}: the pipelined kernel's; null when it does not cover the model
+    DeviceArray<int> d_head, d_next;  // [V][2] {first slot of the vertex, the slot after it}, [n] the slot after each slot
+    DeviceArray<float4> d_vtab;  // [V] {W, w_jaw, first landmark slot, slot chained after it}: the pipelined kernel's; empty when it does not cover the model
     // Landmark-only launches on the pipelined and split kernels (SURVEY 7.1 "landmark-only fast path"; BASELINE configs[3]'s per-GPU work):
     // the SUB-MODEL of the distinct vertices the list names (445 of 5023: 23 tiles instead of 252). Same per-vertex arithmetic, ~11x less
     // of it. Its slot chains are the list's own (d_next): renumbering the vertices does not change which slot follows which.
-    std::unique_ptr<FlameConsts> sub;  // its pipelined pack (build_landmark_sub); null: no sub-model
+    std::unique_ptr<FlameConsts> sub;  // its pipelined pack (plan::landmark_sub); null: no sub-model
     int sub_verts = 0;
-    float4* d_sub_vtab = nullptr;  // [sub_verts] the rows of d_vtab of its vertices
-    ~LandmarkList() { free_device(device, {d_head, d_next, d_vtab, d_sub_vtab}); }
+    DeviceArray<float4> d_sub_vtab;  // [sub_verts] the rows of d_vtab of its vertices
 };
 
 // What a fork copies from its parent: the model's dimensions and parameter layout
@@ -73,27 +74,21 @@ struct dad3d_flame : FlameShape {
     std::shared_ptr<FlameConsts> c;     // shared with forks
     std::shared_ptr<LandmarkList> lmk;  // shared with forks until either calls dad3d_flame_set_landmarks; never null
     int kernel_choice = -1;    // dad3d_flame_select_kernel; -1 = the process default (DAD3D_DECODE_KERNEL)
-    // ---- per handle, freed by the destructor
-    float* d_bwd_partials = nullptr;  // [cap][kBackwardMaxSplit][72] scratch of dad3d_flame_decode_backward
-    int bwd_cap = 0;
-    float* d_grad_partials = nullptr;  // [slices][padded batch][kGradRows] scratch of dad3d_flame_grad_inputs
-    size_t grad_cap = 0;               // its capacity in rows of kGradRows floats
-    float* d_imgc = nullptr;
-    unsigned* d_sync = nullptr;   // [0] arrival counter, [1] time-out counter; [4], [5], [last]: device-epoch launches
-    unsigned arrive_total = 0;    // host mirror of sync[0] after the last launch
-    int cap_nbb = 0;
+    // ---- per handle
+    DeviceScratch d_bwd_partials;   // [batch][kBackwardMaxSplit][72] scratch of dad3d_flame_decode_backward
+    DeviceScratch d_grad_partials;  // [slices][padded batch][kGradRows] scratch of dad3d_flame_grad_inputs
+    DeviceScratch d_imgc;           // [blocks of kBlockImages images][kImgConsts]
+    DeviceArray<unsigned> d_sync;   // [0] arrival counter, [1] time-out counter; [4], [5], [last]: device-epoch launches
+    unsigned arrive_total = 0;      // host mirror of sync[0] after the last launch
     bool profiling = false;
-    unsigned long long* d_trace = nullptr;  // diagnostics (dad3d_flame_debug_trace)
+    unsigned long long* d_trace = nullptr;  // diagnostics (dad3d_flame_debug_trace): the caller's buffer, borrowed
     uint64_t trace_capacity = 0;
-    char* d_split_a = nullptr;    // scratch of the split kernels (flame_decode_split.hip): params rows as planes + per-image
-    int split_cap = 0;            // constants; split_cap phases of 16 images
-    std::vector<char*> split_retired;  // smaller scratches it outgrew: kept until destroy -- a graph captured at a smaller batch still points there
+    DeviceScratch d_split_a;  // scratch of the split kernels (flame_decode_split.hip): params rows as planes + per-image constants
+    std::vector<DeviceArray<char>> split_retired;  // smaller scratches it outgrew: kept until destroy -- a graph captured at a smaller batch still points there
     hipEvent_t ev_first = nullptr, ev_last = nullptr;  // bracket a run of back-to-back launches
     int prof_launches = 0;
     ~dad3d_flame() {
         DeviceGuard guard(device);
-        for (void* p : {(void*)d_sync, (void*)d_imgc, (void*)d_bwd_partials, (void*)d_grad_partials, (void*)d_split_a}) (void)hipFree(p);
-        for (char* p : split_retired) (void)hipFree(p);
         if (ev_first) (void)hipEventDestroy(ev_first);
         if (ev_last) (void)hipEventDestroy(ev_last);
     }
@@ -121,20 +116,6 @@ static bool decode_halfblocks_forced() {
     return forced;
 }
 
-// Every fragment of a basis pack in MFMA B-fragment order, [tile][group of 16 k][wave][lane][4 MFMA steps]: MFMA step s of group g has
-// lane (q = lane >> 4, n = lane & 15) of wave w supply basis row k = 16 g + 4 q + s of column 16 w + n (the k order inside a group is
-// permuted so the A operand can be read row-major with one 16-byte LDS load). frag_offset places the four floats of (tile, g, col, q).
-static size_t frag_offset(int tile, int kgroups, int g, int col, int q) {
-    return ((((size_t)tile * kgroups + g) * 4 + col / 16) * 64 + (col % 16) + 16 * q) * 4;
-}
-template <typename F>
-static void for_each_fragment(std::vector<float>& pack, int n_tiles, int kgroups, F&& f) {  // f(tile, g, col, q, float* four)
-    for (int t = 0; t < n_tiles; ++t)
-        for (int g = 0; g < kgroups; ++g)
-            for (int col = 0; col < kTileCols; ++col)
-                for (int q = 0; q < 4; ++q) f(t, g, col, q, &pack[frag_offset(t, kgroups, g, col, q)]);
-}
-
 static int grad_chunks(const dad3d_flame* h) { return (h->n_verts * 3 + kGradChunk - 1) / kGradChunk; }
 
 // basis^T pack (once per model, shared by forks) and the split-K scratch for `batch` images (per handle)
@@ -145,9 +126,10 @@ static dad3d_status grad_inputs_prepare(dad3d_flame* h, int batch, hipStream_t s
     bool need_pack;
     {   // forks share the pack: the pointer is only ever looked at under its mutex
         std::lock_guard<std::mutex> lock(h->c->gpack_mutex);
-        need_pack = h->c->d_gpack == nullptr;
+        need_pack = !h->c->d_gpack;
     }
-    const bool need_scratch = rows > h->grad_cap;
+    const size_t scratch_bytes = rows * kGradRows * sizeof(float);
+    const bool need_scratch = scratch_bytes > h->d_grad_partials.capacity();
     if (!need_pack && !need_scratch) return DAD3D_OK;
     DAD3D_REQUIRE(!stream_is_capturing(s),
                   "the first training step of a handle (and the first at a larger batch) allocates: run it once before capturing a graph");
@@ -155,40 +137,23 @@ static dad3d_status grad_inputs_prepare(dad3d_flame* h, int batch, hipStream_t s
     if (need_pack) {
         std::lock_guard<std::mutex> lock(h->c->gpack_mutex);
         if (!h->c->d_gpack) {
-            float* pack = nullptr;
-            DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&pack), grad_pack_floats(grad_chunks(h)) * sizeof(float)));
-            GradPackArgs pa{h->c->d_bpack, pack, h->kgroups, h->n_betas, h->n_pose_feats, h->pose_feat_first, h->n_betas + 36,
+            DeviceArray<float> pack;
+            if (dad3d_status st = pack.allocate(grad_pack_floats(grad_chunks(h)))) return st;
+            GradPackArgs pa{h->c->d_bpack.get(), pack.get(), h->kgroups, h->n_betas, h->n_pose_feats, h->pose_feat_first, h->n_betas + 36,
                             h->n_verts * 3, grad_chunks(h)};
             dad3d_status st = launch_grad_pack(pa, nullptr);
             if (st == DAD3D_OK && hipDeviceSynchronize() != hipSuccess) st = DAD3D_E_HIP;
             if (st) {
-                (void)hipFree(pack);
                 set_error("building the basis^T pack failed");
                 return st;
             }
-            h->c->d_gpack = pack;
+            h->c->d_gpack = std::move(pack);
         }
     }
-    if (need_scratch) {
-        DAD3D_HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->d_grad_partials);
-        h->d_grad_partials = nullptr;
-        h->grad_cap = 0;
-        DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_grad_partials), rows * kGradRows * sizeof(float)));
-        h->grad_cap = rows;
-    }
-    return DAD3D_OK;
+    return h->d_grad_partials.grow(scratch_bytes);
 }
 
-static dad3d_status flame_reserve(dad3d_flame* h, int nbb) {
-    if (nbb <= h->cap_nbb) return DAD3D_OK;
-    if (h->d_imgc) (void)hipFree(h->d_imgc);
-    h->d_imgc = nullptr;
-    h->cap_nbb = 0;
-    DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_imgc), (size_t)nbb * kBlockImages * kImgConsts * sizeof(float)));
-    h->cap_nbb = nbb;
-    return DAD3D_OK;
-}
+static size_t imgc_bytes(int nbb) { return (size_t)nbb * kBlockImages * kImgConsts * sizeof(float); }
 
 static bool landmark_subset_enabled() {
     static const bool on = [] {
@@ -198,69 +163,33 @@ static bool landmark_subset_enabled() {
     return on;
 }
 
-// The sub-model of list L (idx[0..n)): the model's pipelined pack restricted to the distinct vertices the list names, in ascending vertex
-// order, copied out fragment by fragment. A column's 416 values do not depend on which tile holds it (the jaw-joint columns are the same in
-// every tile), so the sub-model multiplies the same numbers in the same order: a landmark-only launch returns the bits a full-output launch
-// of the same handle returns for those vertices (tests/test_gpu_landmark_subset.py). None when the list names more than a third of the mesh.
-static dad3d_status build_landmark_sub(const dad3d_flame* h, const int64_t* idx, int n, const std::vector<float4>& vtab, LandmarkList* L) {
-    std::vector<char> named(h->n_verts, 0);
-    for (int s = 0; s < n; ++s) named[idx[s]] = 1;
-    std::vector<int> uniq;
-    for (int v = 0; v < h->n_verts; ++v)
-        if (named[v]) uniq.push_back(v);
-    const int nu = (int)uniq.size(), nt = (nu + kPipeTileVerts - 1) / kPipeTileVerts;
-    if ((size_t)nu * 3 > (size_t)h->n_verts) return DAD3D_OK;
-    std::vector<float> full((size_t)h->c->n_tiles_pipe * kPipeKGroups * 4 * 64 * 4), pack((size_t)nt * kPipeKGroups * 4 * 64 * 4, 0.0f);
-    DAD3D_HIP_TRY(hipMemcpy(full.data(), h->c->d_bpack_pipe, full.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for_each_fragment(pack, nt, kPipeKGroups, [&](int t, int g, int col, int q, float* dst) {
-        int src_tile = 0, src_col = col;  // the jaw-joint columns (and the zero pad) are the same in every tile
-        if (col < 3 * kPipeTileVerts) {
-            const int u = t * kPipeTileVerts + col / 3;
-            if (u >= nu) return;
-            src_tile = uniq[u] / kPipeTileVerts, src_col = (uniq[u] % kPipeTileVerts) * 3 + col % 3;
-        }
-        std::copy_n(&full[frag_offset(src_tile, kPipeKGroups, g, src_col, q)], 4, dst);
-    });
-    std::vector<float4> sub_vtab(nu);
-    for (int u = 0; u < nu; ++u) sub_vtab[u] = vtab[uniq[u]];
-    L->sub.reset(new FlameConsts);
-    L->sub->device = h->device;
-    L->sub->n_tiles_pipe = nt;
-    L->sub->split_b_scale = h->c->split_b_scale;  // a subset of the model's entries: its scale holds
-    L->sub_verts = nu;
-    const dad3d_status st = upload(&L->sub->d_bpack_pipe, pack);
-    return st ? st : upload(&L->d_sub_vtab, sub_vtab);
-}
-
 // A new landmark list for h's model: the per-vertex slot chains, the pipelined kernel's per-vertex table (skinning weights from the model,
-// landmark slots from the list) and the sub-model, the last two for models the pipelined kernel covers only.
+// landmark slots from the list) and the sub-model of the vertices the list names (flame_plan.hpp), the last two for models the pipelined
+// kernel covers only. The model's tables are read back from the device: the handle keeps no host copy of 27 MB.
 static dad3d_status build_landmarks(const dad3d_flame* h, const int64_t* idx, int n, std::shared_ptr<LandmarkList>* out) {
     const int V = h->n_verts;
-    std::vector<int> head(V, -1), next(n, -1);
-    for (int s = n - 1; s >= 0; --s) {  // reverse walk: each vertex's chain comes out in ascending slot order
-        next[s] = head[idx[s]];
-        head[idx[s]] = s;
-    }
-    std::vector<int> head2((size_t)V * 2, -1);  // what the kernels stage per tile: {head, next[head]}
-    for (int v = 0; v < V; ++v)
-        if (head[v] >= 0) head2[(size_t)v * 2] = head[v], head2[(size_t)v * 2 + 1] = next[head[v]];
+    std::vector<int> head2, next;
+    plan::landmark_chains(idx, n, V, &head2, &next);
     auto L = std::make_shared<LandmarkList>();
-    L->device = h->device;
     L->n = n;
     dad3d_status st;
-    if ((st = upload(&L->d_head, head2)) || (st = upload(&L->d_next, next))) return st;
+    if ((st = L->d_head.upload(head2)) || (st = L->d_next.upload(next))) return st;
     if (h->c->d_bpack_pipe) {
         std::vector<float> w8((size_t)V * 8);
-        DAD3D_HIP_TRY(hipMemcpy(w8.data(), h->c->d_w8, w8.size() * sizeof(float), hipMemcpyDeviceToHost));
-        std::vector<float4> vtab(V);
-        for (int v = 0; v < V; ++v) {
-            const float* w = &w8[(size_t)v * 8];
-            float fh, fn;
-            memcpy(&fh, &head2[(size_t)v * 2], 4), memcpy(&fn, &head2[(size_t)v * 2 + 1], 4);
-            vtab[v] = float4{w[5] + w[2], w[2], fh, fn};  // W = (w0 + w1 + w3 + w4) + w_jaw
+        DAD3D_HIP_TRY(hipMemcpy(w8.data(), h->c->d_w8.get(), w8.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const std::vector<plan::Float4> vtab = plan::vertex_table(w8, head2, V);
+        if ((st = L->d_vtab.upload(vtab))) return st;
+        const std::vector<int> uniq = landmark_subset_enabled() ? plan::landmark_sub_vertices(idx, n, V) : std::vector<int>();
+        if (!uniq.empty()) {
+            std::vector<float> full(plan::pack_floats(h->c->n_tiles_pipe, kPipeKGroups));
+            DAD3D_HIP_TRY(hipMemcpy(full.data(), h->c->d_bpack_pipe.get(), full.size() * sizeof(float), hipMemcpyDeviceToHost));
+            const plan::LandmarkSub sub = plan::landmark_sub(uniq, full, vtab);
+            L->sub.reset(new FlameConsts);
+            L->sub->n_tiles_pipe = sub.n_tiles;
+            L->sub->split_b_scale = h->c->split_b_scale;  // a subset of the model's entries: its scale holds
+            L->sub_verts = (int)uniq.size();
+            if ((st = L->sub->d_bpack_pipe.upload(sub.pack)) || (st = L->d_sub_vtab.upload(sub.vtab))) return st;
         }
-        if ((st = upload(&L->d_vtab, vtab))) return st;
-        if (landmark_subset_enabled() && n > 0 && (st = build_landmark_sub(h, idx, n, vtab, L.get()))) return st;
     }
     *out = std::move(L);
     return DAD3D_OK;
@@ -310,123 +239,35 @@ dad3d_status dad3d_flame_create(const dad3d_flame_model* m, const dad3d_flame_co
                       m->parents[j]);
     DAD3D_SELECT_DEVICE(device);
 
+    const plan::FlameDims<ParamLayout> d = plan::flame_dims<ParamLayout>(*m, *c);
+    DAD3D_REQUIRE(d.kgroups == 26 || d.kgroups == 28, "unexpected basis depth %d", d.k_used);
     std::unique_ptr<dad3d_flame> h(new dad3d_flame);
     h->device = device;
     h->n_verts = m->n_verts;
     h->n_betas = m->n_betas;
     h->image_size = image_size;
-    ParamLayout& L = h->lay;
-    int cur = 0;
-    L.shape_off = cur, L.shape_n = c->shape, cur += c->shape;
-    L.expr_off = cur, L.expr_n = c->expression, cur += c->expression;
-    L.jaw_off = cur, L.jaw_n = c->jaw, cur += c->jaw;
-    L.rot_off = cur, cur += c->rotation;
-    L.eye_off = cur, L.eye_n = c->eyeballs, cur += c->eyeballs;
-    L.neck_off = cur, L.neck_n = c->neck, cur += c->neck;
-    L.trans_off = cur, cur += c->translation;
-    L.scale_off = cur, cur += c->scale;
-    L.n_params = cur;
+    h->lay = d.lay;
     for (int j = 0; j < kNumJoints; ++j) h->parents[j] = (j == 0) ? -1 : m->parents[j];
+    h->n_pose_feats = d.n_pose_feats;
+    h->pose_feat_first = d.pose_feat_first;
+    h->kgroups = d.kgroups;
+    h->ksteps = d.kgroups * 4;
+    h->n_tiles = d.n_tiles;
+    h->n_tiles_pad8 = (d.n_tiles + 7) / 8 * 8;
 
-    // Only the jaw can rotate when neck and eyeballs are size-0 inputs: their Rodrigues matrix is exactly
-    // I, so 27 of the 36 pose features are exactly 0 and their basis rows can be skipped (same result).
-    // ... and the jaw-only epilogue (S = w0+w1+w3+w4 for "the joints that cannot rotate") also needs no joint to hang
-    // off the jaw: a kinematic tree with a child of joint 2 takes the generic 36-feature path.
-    bool jaw_is_leaf = true;
-    for (int j = 1; j < kNumJoints; ++j) jaw_is_leaf = jaw_is_leaf && m->parents[j] != 2;
-    const bool jaw_only = (c->neck == 0 && c->eyeballs == 0 && jaw_is_leaf);
-    h->n_pose_feats = jaw_only ? 9 : 36;
-    h->pose_feat_first = jaw_only ? 9 : 0;
-    const int k_used = h->n_betas + h->n_pose_feats + 1;  // [betas | pose feature | template]
-    h->kgroups = (k_used + 15) / 16;
-    h->ksteps = h->kgroups * 4;
-    DAD3D_REQUIRE(h->kgroups == 26 || h->kgroups == 28, "unexpected basis depth %d", k_used);
-    const int V = m->n_verts, NB = m->n_betas;
-    h->n_tiles = (V + kTileVerts - 1) / kTileVerts;
-    h->n_tiles_pad8 = (h->n_tiles + 7) / 8 * 8;
-
-    // ---- pack the basis in MFMA B-fragment order (for_each_fragment), 21 vertices = 63 columns per tile -------
-    auto basis = [&](int k, int v, int comp) -> float {
-        if (k < NB) return m->shapedirs[((size_t)v * 3 + comp) * NB + k];
-        if (k < NB + h->n_pose_feats) {
-            const int f = h->pose_feat_first + (k - NB);
-            return m->posedirs[(size_t)f * 3 * V + (size_t)v * 3 + comp];
-        }
-        return m->v_template[(size_t)v * 3 + comp];  // k == NB + n_pose_feats: the row multiplied by 1
-    };
-    std::vector<float> bpack((size_t)h->n_tiles * h->kgroups * 4 * 64 * 4, 0.0f);
-    for_each_fragment(bpack, h->n_tiles, h->kgroups, [&](int t, int g, int col, int q, float* dst) {
-        const int v = t * kTileVerts + col / 3;
-        if (col >= kTileVerts * 3 || v >= V) return;
-        for (int i = 0; i < 4; ++i) {
-            const int k = 16 * g + 4 * q + i;
-            if (k < k_used) dst[i] = basis(k, v, col % 3);
-        }
-    });
-
-    // ---- joints are linear in betas: J = J_regressor.v_template + (J_regressor.shapedirs).betas ----
-    std::vector<float> j0(3 * kNumJoints), jdirs((size_t)3 * kNumJoints * NB);
-    {
-        std::vector<double> acc((size_t)3 * kNumJoints * (NB + 1), 0.0);
-        for (int j = 0; j < kNumJoints; ++j)
-            for (int v = 0; v < V; ++v) {
-                const double r = m->j_regressor[(size_t)j * V + v];
-                if (r == 0.0) continue;
-                for (int comp = 0; comp < 3; ++comp) {
-                    double* a = &acc[((size_t)j * 3 + comp) * (NB + 1)];
-                    a[NB] += r * m->v_template[(size_t)v * 3 + comp];
-                    const float* sd = &m->shapedirs[((size_t)v * 3 + comp) * NB];
-                    for (int l = 0; l < NB; ++l) a[l] += r * sd[l];
-                }
-            }
-        for (int o = 0; o < 3 * kNumJoints; ++o) {
-            j0[o] = (float)acc[(size_t)o * (NB + 1) + NB];
-            for (int l = 0; l < NB; ++l) jdirs[(size_t)o * NB + l] = (float)acc[(size_t)o * (NB + 1) + l];
-        }
-    }
-    std::vector<float> w8((size_t)V * 8, 0.0f);
-    for (int v = 0; v < V; ++v) {
-        const float* w = &m->lbs_weights[(size_t)v * kNumJoints];
-        for (int j = 0; j < kNumJoints; ++j) w8[(size_t)v * 8 + j] = w[j];
-        w8[(size_t)v * 8 + 5] = ((w[0] + w[1]) + w[3]) + w[4];  // weight of the joints that cannot rotate (jaw-only mode)
-    }
-    // ---- the pipelined single-role kernel (flame_decode_pipe.hip): jaw-only models with the dad_3dnet.yaml params layout.
-    // Tiles of 20 vertices; columns 60..62 of every tile carry the jaw joint J_jaw = J0_jaw + Jdirs_jaw . betas (rows of the pose
-    // feature contribute nothing to a joint: smplx regresses the joints from v_shaped), column 63 is zero.
-    const bool pipe_ok = jaw_only && c->jaw == 3 && c->shape == 300 && c->expression == 100 && L.jaw_off == 400 && L.rot_off == 403 &&
-                         L.trans_off == 409 && L.scale_off == 412 && L.n_params == 413 && h->kgroups == kPipeKGroups;
-    std::vector<float> bpack_pipe;
-    const int n_tiles_pipe = (V + kPipeTileVerts - 1) / kPipeTileVerts;
-    if (pipe_ok) {
-        bpack_pipe.assign((size_t)n_tiles_pipe * kPipeKGroups * 4 * 64 * 4, 0.0f);
-        for_each_fragment(bpack_pipe, n_tiles_pipe, kPipeKGroups, [&](int t, int g, int col, int q, float* dst) {
-            for (int i = 0; i < 4; ++i) {
-                const int k = 16 * g + 4 * q + i;
-                if (k >= k_used) continue;
-                if (col < 3 * kPipeTileVerts) {
-                    const int v = t * kPipeTileVerts + col / 3;
-                    if (v < V) dst[i] = basis(k, v, col % 3);
-                } else if (col < 3 * kPipeTileVerts + 3) {
-                    const int o = 2 * 3 + (col - 3 * kPipeTileVerts);  // joint 2 = jaw
-                    dst[i] = k < NB ? jdirs[(size_t)o * NB + k] : (k == NB + h->n_pose_feats ? j0[o] : 0.0f);
-                }
-            }
-        });
-    }
-
+    std::vector<float> j0, jdirs;
+    plan::joint_regressors(*m, &j0, &jdirs);
     h->c = std::make_shared<FlameConsts>();
-    h->c->device = device;
-    h->c->n_tiles_pipe = n_tiles_pipe;
-    if (pipe_ok) {
-        float max_abs = 0.0f;
-        for (float v : bpack_pipe) max_abs = std::max(max_abs, std::fabs(v));
-        h->c->split_b_scale = split_basis_scale(max_abs);
-    }
+    h->c->n_tiles_pipe = d.n_tiles_pipe;
     dad3d_status st;
-    if ((pipe_ok && (st = upload(&h->c->d_bpack_pipe, bpack_pipe))) || (st = upload(&h->c->d_bpack, bpack)) ||
-        (st = upload(&h->c->d_jdirs, jdirs)) || (st = upload(&h->c->d_j0, j0)) || (st = upload(&h->c->d_w8, w8)) ||
-        (st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) || (st = flame_reserve(h.get(), 1)) ||
-        (st = build_landmarks(h.get(), nullptr, 0, &h->lmk)))
+    if (d.pipe_ok) {
+        const std::vector<float> bpack_pipe = plan::basis_pack_pipe(*m, d, j0, jdirs);
+        h->c->split_b_scale = split_basis_scale(plan::max_abs(bpack_pipe));
+        if ((st = h->c->d_bpack_pipe.upload(bpack_pipe))) return st;
+    }
+    if ((st = h->c->d_bpack.upload(plan::basis_pack(*m, d))) || (st = h->c->d_jdirs.upload(jdirs)) || (st = h->c->d_j0.upload(j0)) ||
+        (st = h->c->d_w8.upload(plan::weights8(*m))) || (st = h->d_sync.upload(std::vector<unsigned>(kSyncWords, 0u))) ||
+        (st = h->d_imgc.allocate(imgc_bytes(1))) || (st = build_landmarks(h.get(), nullptr, 0, &h->lmk)))
         return st;
     *out = h.release();
     return DAD3D_OK;
@@ -444,7 +285,7 @@ dad3d_status dad3d_flame_fork(dad3d_flame* parent, dad3d_flame** out) {
     h->lmk = parent->lmk;
     h->kernel_choice = parent->kernel_choice;
     dad3d_status st;
-    if ((st = upload(&h->d_sync, std::vector<unsigned>(kSyncWords, 0u))) || (st = flame_reserve(h.get(), 1))) return st;
+    if ((st = h->d_sync.upload(std::vector<unsigned>(kSyncWords, 0u))) || (st = h->d_imgc.allocate(imgc_bytes(1)))) return st;
     *out = h.release();
     return DAD3D_OK;
 }
@@ -481,34 +322,30 @@ static dad3d_status ensure_basis_f16(FlameConsts* c, hipStream_t s) {
     std::lock_guard<std::mutex> lock(c->f16_mu);
     if (c->d_bpack_f16) return DAD3D_OK;
     DAD3D_REQUIRE(!stream_is_capturing(s), "the first fp16-split decode of a model builds its basis planes: run it once before capturing a graph");
-    const size_t bytes = (size_t)c->n_tiles_pipe * kPipeKGroups * 4 * 64 * 4 * sizeof(float);
-    float* d = nullptr;
-    DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    dad3d_status st = launch_split_basis_f16(c->d_bpack_pipe, d, c->n_tiles_pipe, c->split_b_scale, s);
+    const size_t floats = plan::pack_floats(c->n_tiles_pipe, kPipeKGroups);
+    DeviceArray<float> d;
+    if (dad3d_status st = d.allocate(floats)) return st;
+    dad3d_status st = launch_split_basis_f16(c->d_bpack_pipe.get(), d.get(), c->n_tiles_pipe, c->split_b_scale, s);
     if (st == DAD3D_OK && hipStreamSynchronize(s) != hipSuccess) {
         set_error("ensure_basis_f16: hipStreamSynchronize failed");
         st = DAD3D_E_HIP;
     }
-    if (st) {
-        (void)hipFree(d);
-        return st;
-    }
-    c->d_bpack_f16 = d;
+    if (st) return st;
+    c->d_bpack_f16 = std::move(d);
     return DAD3D_OK;
 }
 
 // Scratch of the split kernels (pre-pass -> tile kernel): n_phase blocks of kSplitBlockBytes, grown on demand -- never inside a capture.
 static dad3d_status ensure_split_scratch(dad3d_flame* h, int n_phase, hipStream_t s) {
-    if (n_phase <= h->split_cap) return DAD3D_OK;
+    const size_t bytes = (size_t)n_phase * kSplitBlockBytes;
+    if (bytes <= h->d_split_a.capacity()) return DAD3D_OK;
     DAD3D_REQUIRE(!stream_is_capturing(s),
                   "the first split-kernel decode of a handle (and the first at a larger batch) allocates: run it once before capturing a graph");
-    if (h->d_split_a) h->split_retired.push_back(h->d_split_a);  // (2.6 KB per image: never worth a dangling pointer in somebody's graph)
-    h->d_split_a = nullptr, h->split_cap = 0;
-    DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_split_a), (size_t)n_phase * kSplitBlockBytes));
+    if (h->d_split_a.get()) h->split_retired.push_back(h->d_split_a.retire());  // (2.6 KB per image: never worth a dangling pointer in somebody's graph)
+    if (dad3d_status st = h->d_split_a.allocate(bytes)) return st;
     // (the padding is copied into LDS, never read.) On the LAUNCH's stream: hipMemset is ordered on the null stream only, and a
     // non-blocking stream's pre-pass overtook it -- zero planes under the first launch of a fork (found by the two-streams test)
-    DAD3D_HIP_TRY(hipMemsetAsync(h->d_split_a, 0, (size_t)n_phase * kSplitBlockBytes, s));
-    h->split_cap = n_phase;
+    DAD3D_HIP_TRY(hipMemsetAsync(h->d_split_a.get(), 0, bytes, s));
     return DAD3D_OK;
 }
 
@@ -554,7 +391,7 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
     // output and no DAD3D_COMPAT_CROSS_B3 here: resolve_kernel sent those to the two-role kernel, which always decodes the whole mesh.
     const bool on_sub = L.sub && !verts3d && !proj && n_lmk && !h->d_trace && pinned != DAD3D_KERNEL_PIPELINED;
     FlameConsts* c = on_sub ? L.sub.get() : h->c.get();
-    const float4* vtab = on_sub ? L.d_sub_vtab : L.d_vtab;
+    const float4* vtab = on_sub ? L.d_sub_vtab.get() : L.d_vtab.get();
     const int n_verts = on_sub ? L.sub_verts : h->n_verts;
 
     dad3d_status st;
@@ -571,15 +408,15 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
         if (st) return st;
         SplitArgs sa{};
         sa.params = params;
-        sa.bpack = c->d_bpack_pipe;
-        sa.bpack_f16 = c->d_bpack_f16;
+        sa.bpack = c->d_bpack_pipe.get();
+        sa.bpack_f16 = c->d_bpack_f16.get();
         sa.vtab = vtab;
-        sa.lmk_next = L.d_next;
+        sa.lmk_next = L.d_next.get();
         sa.verts3d = verts3d;
         sa.proj = proj;
         sa.lmk_xy = lmk_xy;
         sa.lmk_px = lmk_px;
-        sa.aplanes = h->d_split_a;
+        sa.aplanes = static_cast<char*>(h->d_split_a.get());
         sa.b_scale = c->split_b_scale;
         sa.n_params = h->lay.n_params;
         sa.batch = batch;
@@ -597,9 +434,9 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
                       (unsigned long long)trace_entries_pipe(h));
         PipeArgs pa{};
         pa.params = params;
-        pa.bpack = c->d_bpack_pipe;
+        pa.bpack = c->d_bpack_pipe.get();
         pa.vtab = vtab;
-        pa.lmk_next = L.d_next;
+        pa.lmk_next = L.d_next.get();
         pa.verts3d = verts3d;
         pa.proj = proj;
         pa.lmk_xy = lmk_xy;
@@ -628,20 +465,17 @@ static dad3d_status decode_impl(dad3d_flame* h, float* params, int batch, unsign
         // forward must not fail for a backward path that will not be taken: dad3d_flame_grad_inputs reports it when called).
         if (posed && batch <= DAD3D_GRAD_INPUTS_MAX_BATCH && h->n_betas + 36 <= kGradRows && (st = grad_inputs_prepare(h, batch, s))) return st;
         const int nbb = (batch + kBlockImages - 1) / kBlockImages;
-        if (nbb > h->cap_nbb) {
-            DAD3D_HIP_TRY(hipDeviceSynchronize());
-            if ((st = flame_reserve(h, nbb))) return st;
-        }
+        if ((st = h->d_imgc.grow(imgc_bytes(nbb)))) return st;
         DecodeArgs da{};
         da.params = params;
-        da.bpack = h->c->d_bpack;
-        da.jdirs = h->c->d_jdirs;
-        da.j0 = h->c->d_j0;
-        da.weights8 = h->c->d_w8;
-        da.lmk_head = L.d_head;
-        da.lmk_next = L.d_next;
-        da.imgc = h->d_imgc;
-        da.sync = h->d_sync;
+        da.bpack = h->c->d_bpack.get();
+        da.jdirs = h->c->d_jdirs.get();
+        da.j0 = h->c->d_j0.get();
+        da.weights8 = h->c->d_w8.get();
+        da.lmk_head = L.d_head.get();
+        da.lmk_next = L.d_next.get();
+        da.imgc = static_cast<float*>(h->d_imgc.get());
+        da.sync = h->d_sync.get();
         da.verts3d = verts3d;
         da.proj = proj;
         da.lmk_xy = lmk_xy;
@@ -699,9 +533,9 @@ dad3d_status dad3d_flame_decode_host(dad3d_flame* h, float* params, int batch, u
     const size_t pc = (flags & DAD3D_TO_2D) ? 2 : 3;
     const size_t n_par = B * P, n_v = verts3d ? B * V * 3 : 0, n_p = proj ? B * V * pc : 0;
     const size_t n_lx = lmk_xy ? B * NL * 2 : 0, n_lp = lmk_px ? B * NL * 2 : 0;
-    float* d = nullptr;
-    DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (n_par + n_v + n_p + n_lx + n_lp + 4) * sizeof(float)));
-    float* d_par = d;
+    DeviceArray<float> d;
+    if (dad3d_status st = d.allocate(n_par + n_v + n_p + n_lx + n_lp + 4)) return st;
+    float* d_par = d.get();
     float* d_v = n_v ? d_par + n_par : nullptr;
     float* d_p = n_p ? d_par + n_par + n_v : nullptr;
     float* d_lx = n_lx ? d_par + n_par + n_v + n_p : nullptr;
@@ -721,7 +555,6 @@ dad3d_status dad3d_flame_decode_host(dad3d_flame* h, float* params, int batch, u
     if (!st && n_p) fail(hipMemcpy(proj, d_p, n_p * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
     if (!st && n_lx) fail(hipMemcpy(lmk_xy, d_lx, n_lx * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
     if (!st && n_lp) fail(hipMemcpy(lmk_px, d_lp, n_lp * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy");
-    (void)hipFree(d);
     return st;
 }
 
@@ -753,7 +586,7 @@ dad3d_status dad3d_flame_handoff_timeouts(dad3d_flame* h, unsigned* count) {
     DAD3D_REQUIRE(h && count, "null argument");
     DeviceGuard guard(h->device);
     DAD3D_HIP_TRY(hipDeviceSynchronize());
-    DAD3D_HIP_TRY(hipMemcpy(count, h->d_sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+    DAD3D_HIP_TRY(hipMemcpy(count, h->d_sync.get() + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
     return DAD3D_OK;
 }
 
@@ -783,7 +616,7 @@ dad3d_status dad3d_flame_decode_backward(dad3d_flame* h, int batch, unsigned fla
     DAD3D_REQUIRE(!(posed && (flags & DAD3D_COMPAT_CROSS_B3)), "DAD3D_COMPAT_CROSS_B3 is inference-only (dad3d_flame_decode_posed refuses it)");
     DeviceGuard guard(h->device);
     BackwardArgs ba{};
-    ba.weights8 = h->c->d_w8;
+    ba.weights8 = h->c->d_w8.get();
     ba.consts = consts;
     ba.posed = posed;
     ba.g_verts3d = grad_verts3d;
@@ -797,16 +630,8 @@ dad3d_status dad3d_flame_decode_backward(dad3d_flame* h, int batch, unsigned fla
     // small batches: split every image over several workgroups (about one per CU), partial sums added in fixed order
     ba.nsplit = std::max(1, std::min(kBackwardMaxSplit, 256 / batch));
     if (ba.nsplit > 1) {
-        if (batch > h->bwd_cap) {
-            DAD3D_HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(h->d_bwd_partials);
-            h->d_bwd_partials = nullptr;
-            h->bwd_cap = 0;
-            DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_bwd_partials),
-                                    (size_t)batch * kBackwardMaxSplit * kBackwardConsts * sizeof(float)));
-            h->bwd_cap = batch;
-        }
-        ba.partials = h->d_bwd_partials;
+        if (dad3d_status st = h->d_bwd_partials.grow((size_t)batch * kBackwardMaxSplit * kBackwardConsts * sizeof(float))) return st;
+        ba.partials = static_cast<float*>(h->d_bwd_partials.get());
     }
     return launch_flame_backward(ba, static_cast<hipStream_t>(stream));
 }
@@ -822,7 +647,7 @@ dad3d_status dad3d_flame_grad_inputs(dad3d_flame* h, const float* grad_posed, in
     if (st) return st;
     const int pad = (batch + kBlockImages - 1) / kBlockImages * kBlockImages;
     const int per_slice = grad_chunks_per_slice(pad);
-    GradInputsArgs ga{grad_posed, h->c->d_gpack, h->d_grad_partials, grad_inputs, batch, pad, h->n_verts * 3, grad_chunks(h),
+    GradInputsArgs ga{grad_posed, h->c->d_gpack.get(), static_cast<float*>(h->d_grad_partials.get()), grad_inputs, batch, pad, h->n_verts * 3, grad_chunks(h),
                       h->n_betas + 36, per_slice, (grad_chunks(h) + per_slice - 1) / per_slice};
     return launch_grad_inputs(ga, s);
 }
@@ -830,8 +655,8 @@ dad3d_status dad3d_flame_grad_inputs(dad3d_flame* h, const float* grad_posed, in
 static ChainArgs chain_args(const dad3d_flame* h, const float* params, int batch) {
     ChainArgs ca{};
     ca.params = params;
-    ca.jdirs = h->c->d_jdirs;
-    ca.j0 = h->c->d_j0;
+    ca.jdirs = h->c->d_jdirs.get();
+    ca.j0 = h->c->d_j0.get();
     ca.lay = h->lay;
     std::copy(h->parents, h->parents + kNumJoints, ca.parents);
     ca.batch = batch;

@@ -1,25 +1,20 @@
-// What the host units of the C ABI (capi*.cpp) write out over and over. Host code only: no kernel unit and no other header includes this.
+// What the host units of the C ABI (capi*.cpp) write out over and over: the owners of device memory (device_memory.hpp), the device and
+// batch checks, the capture test. Host code only: no kernel unit and no other header includes this.
 #pragma once
 #include <algorithm>
-#include <initializer_list>
+#include <cstddef>
 
-#include "common.hpp"
+#include "device_memory.hpp"
+#include "plan_pods.hpp"
 
 namespace dad3d {
 
-template <typename T>
-static dad3d_status upload(T** dst, const std::vector<T>& src) {
-    *dst = nullptr;
-    const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    DAD3D_HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), bytes));
-    if (!src.empty()) DAD3D_HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return DAD3D_OK;
-}
-
-inline void free_device(int device, std::initializer_list<void*> ptrs) {
-    DeviceGuard guard(device);
-    for (void* p : ptrs) (void)hipFree(p);
-}
+// the host planners' vectors are uploaded as arrays of HIP's vector types (DeviceArray::upload)
+static_assert(sizeof(plan::Int4) == sizeof(int4) && sizeof(plan::UInt2) == sizeof(uint2) && sizeof(plan::UInt4) == sizeof(uint4) &&
+                  sizeof(plan::Float4) == sizeof(float4) && offsetof(plan::Float4, w) == offsetof(float4, w) &&
+                  offsetof(plan::Int4, w) == offsetof(int4, w) && offsetof(plan::UInt2, y) == offsetof(uint2, y) &&
+                  offsetof(plan::UInt4, w) == offsetof(uint4, w),
+              "plan_pods.hpp: not the layout of HIP's vector types");
 
 // `device` current until the end of the caller's scope, or the caller returns DAD3D_E_INVALID (a macro: DAD3D_REQUIRE returns from the caller)
 #define DAD3D_SELECT_DEVICE(device) \

@@ -4,55 +4,40 @@
 #include <memory>
 
 #include "capi_checks.hpp"
+#include "mesh_plan.hpp"
 
 using namespace dad3d;
 
 struct dad3d_mesh {
     int device = 0;
     int ntri = 0, nver = 0;
-    int *d_tri = nullptr, *d_adj_ptr = nullptr, *d_adj_face = nullptr;
-    int4* d_adj_tri = nullptr;
+    DeviceArray<int> d_tri, d_adj_ptr, d_adj_face;
+    DeviceArray<int4> d_adj_tri;
     std::vector<int> h_tri;  // the triangle list on the host (dad3d_mesh_set_texcoords reads it)
-    uint2* d_nc_faces[kNormalChunkings] = {};  // chunk face lists of the normals kernels (NormalChunksDev)
-    unsigned short* d_nc_slot[kNormalChunkings] = {};
-    uint4* d_nc_row8[kNormalChunkings] = {};
+    DeviceArray<uint2> d_nc_faces[kNormalChunkings];  // chunk face lists of the normals kernels (NormalChunksDev)
+    DeviceArray<unsigned short> d_nc_slot[kNormalChunkings];
+    DeviceArray<uint4> d_nc_row8[kNormalChunkings];
     NormalChunksDev nc[kNormalChunkings] = {};
-    unsigned long long* d_trace = nullptr;  // diagnostics (dad3d_mesh_debug_trace)
-    float4* d_tex_tri[2] = {};  // texel coordinates per triangle corner, [ntri][2] (dad3d_mesh_set_texcoords): corner / reference indexing
-    void* d_raster = nullptr;  // per-image triangle boxes + corner planes, grown on demand (one stream at a time)
-    size_t raster_bytes = 0;
+    unsigned long long* d_trace = nullptr;  // diagnostics (dad3d_mesh_debug_trace): the caller's buffer, borrowed
+    DeviceArray<float4> d_tex_tri[2];  // texel coordinates per triangle corner, [ntri][2] (dad3d_mesh_set_texcoords): corner / reference indexing
+    DeviceScratch d_raster;  // per-image triangle boxes + corner planes, grown on demand (one stream at a time)
     int raster_batch = 0, raster_h = 0, raster_w = 0;
     // The scratch layout depends on (batch, h, w): a change of shape re-zeroes the tile counters in stream order.
     dad3d_status raster_scratch(int batch, int h, int w, hipStream_t s) {
         if (batch == raster_batch && h == raster_h && w == raster_w) return DAD3D_OK;
-        const size_t need = raster_scratch_bytes(dev(), batch, h, w);
-        if (need > raster_bytes) {
-            DAD3D_HIP_TRY(hipDeviceSynchronize());
-            if (d_raster) (void)hipFree(d_raster);
-            d_raster = nullptr;
-            raster_bytes = 0;
-            raster_batch = 0;
-            DAD3D_HIP_TRY(hipMalloc(&d_raster, need));
-            raster_bytes = need;
-        }
-        if (dad3d_status st = raster_scratch_init(dev(), d_raster, batch, h, w, s)) return st;
+        const size_t had = d_raster.capacity();
+        const dad3d_status grown = d_raster.grow(raster_scratch_bytes(dev(), batch, h, w));
+        if (d_raster.capacity() != had) raster_batch = 0;  // a new buffer holds no shape
+        if (grown) return grown;
+        if (dad3d_status st = raster_scratch_init(dev(), d_raster.get(), batch, h, w, s)) return st;
         raster_batch = batch, raster_h = h, raster_w = w;
         return DAD3D_OK;
     }
-    void* d_frames = nullptr;  // scratch of the frames chain (sim3dr_frames.hip), grown on demand like d_raster; needs no initialisation
-    size_t frames_bytes = 0;
+    DeviceScratch d_frames;  // scratch of the frames chain (sim3dr_frames.hip), grown on demand like d_raster; needs no initialisation
     dad3d_status frames_scratch(int n_frames, int n_heads, int total_tiles) {
-        const size_t need = frames_scratch_bytes(ntri, n_frames, n_heads, total_tiles);
-        if (need <= frames_bytes) return DAD3D_OK;
-        DAD3D_HIP_TRY(hipDeviceSynchronize());
-        if (d_frames) (void)hipFree(d_frames);
-        d_frames = nullptr;
-        frames_bytes = 0;
-        DAD3D_HIP_TRY(hipMalloc(&d_frames, need));
-        frames_bytes = need;
-        return DAD3D_OK;
+        return d_frames.grow(frames_scratch_bytes(ntri, n_frames, n_heads, total_tiles));
     }
-    MeshDev dev() const { return MeshDev{d_tri, d_adj_ptr, d_adj_face, d_adj_tri, ntri, nver}; }
+    MeshDev dev() const { return MeshDev{d_tri.get(), d_adj_ptr.get(), d_adj_face.get(), d_adj_tri.get(), ntri, nver}; }
 };
 
 // the checks the two frames entries share, all on the host; *total_tiles = 0: nothing to do
@@ -75,12 +60,12 @@ static dad3d_status frames_arguments(const char* who, dad3d_mesh* m, const int64
 struct dad3d_uvmap {
     int device = 0;
     int nver = 0, size = 0, n_cand = 0;
-    int* d_adj_ptr = nullptr;  // vertex -> faces (UvNormalArgs)
-    int4* d_adj = nullptr;
-    int* d_texel_ptr = nullptr;  // texel -> candidates, descending (UvBakeArgs)
-    int* d_cand_verts = nullptr;
-    double* d_cand_bary = nullptr;
-    int* d_faces = nullptr;  // [ntri,3]: the depth maps' triangles (UvDepthFramesArgs)
+    DeviceArray<int> d_adj_ptr;  // vertex -> faces (UvNormalArgs)
+    DeviceArray<int4> d_adj;
+    DeviceArray<int> d_texel_ptr;  // texel -> candidates, descending (UvBakeArgs)
+    DeviceArray<int> d_cand_verts;
+    DeviceArray<double> d_cand_bary;
+    DeviceArray<int> d_faces;  // [ntri,3]: the depth maps' triangles (UvDepthFramesArgs)
     int ntri = 0;
 };
 
@@ -92,143 +77,29 @@ dad3d_status dad3d_mesh_create(const int32_t* tri, int ntri, int nver, int devic
     for (int i = 0; i < 3 * ntri; ++i)
         DAD3D_REQUIRE(tri[i] >= 0 && tri[i] < nver, "triangle index %d out of range [0,%d)", tri[i], nver);
     DAD3D_SELECT_DEVICE(device);
-    // vertex -> incident (face, corner) list; faces ascending, so a gather reproduces the serial
-    // scatter-add order of rasterize_kernel.cpp:188-198
-    std::vector<int> ptr(nver + 1, 0), face(3 * (size_t)ntri);
-    for (int i = 0; i < 3 * ntri; ++i) ++ptr[tri[i] + 1];
-    for (int v = 0; v < nver; ++v) ptr[v + 1] += ptr[v];
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    for (int f = 0; f < ntri; ++f)
-        for (int c = 0; c < 3; ++c) face[fill[tri[3 * f + c]]++] = f;
+    const plan::MeshAdjacency adj = plan::mesh_adjacency(tri, ntri, nver);
     std::unique_ptr<dad3d_mesh> m(new dad3d_mesh);
     m->device = device;
     m->ntri = ntri;
     m->nver = nver;
-    std::vector<int> tri_v(tri, tri + 3 * (size_t)ntri);
-    m->h_tri = tri_v;
-    std::vector<int4> adj_tri(face.size());
-    for (size_t e = 0; e < face.size(); ++e) {
-        const int f = face[e];
-        adj_tri[e] = make_int4(tri[3 * f], tri[3 * f + 1], tri[3 * f + 2], f);
-    }
+    m->h_tri.assign(tri, tri + 3 * (size_t)ntri);
     dad3d_status st;
-    if ((st = upload(&m->d_tri, tri_v)) || (st = upload(&m->d_adj_ptr, ptr)) || (st = upload(&m->d_adj_face, face)) ||
-        (st = upload(&m->d_adj_tri, adj_tri))) {
-        dad3d_mesh_destroy(m.release());
+    if ((st = m->d_tri.upload(m->h_tri)) || (st = m->d_adj_ptr.upload(adj.ptr)) || (st = m->d_adj_face.upload(adj.face)) ||
+        (st = m->d_adj_tri.upload(adj.adj_tri)))
         return st;
-    }
     // chunk face lists for 1, 2, 4 and 8 vertex chunks per image (only where table + staged vertices fit the LDS)
-    for (int k = 0; k < kNormalChunkings && nver > 0 && ntri > 0 && nver <= 65535; ++k) {
-        const int chunks = 1 << k, vpb = (nver + chunks - 1) / chunks;
-        std::vector<int> fptr(chunks + 1, 0), slot(face.size(), 0);
-        std::vector<std::vector<int4>> lists(chunks);
-        std::vector<int> pos_of(3 * (size_t)ntri);  // (face, corner) -> position of the face in the list of the corner's chunk
-        for (int f = 0; f < ntri; ++f) {
-            int seen_chunk[3], seen_pos[3], n_seen = 0;
-            for (int c = 0; c < 3; ++c) {
-                const int ch = tri[3 * f + c] / vpb;
-                int p = -1;
-                for (int j = 0; j < n_seen; ++j)
-                    if (seen_chunk[j] == ch) p = seen_pos[j];
-                if (p < 0) {
-                    p = (int)lists[ch].size();
-                    lists[ch].push_back(make_int4(tri[3 * f], tri[3 * f + 1], tri[3 * f + 2], f));
-                    seen_chunk[n_seen] = ch, seen_pos[n_seen] = p, ++n_seen;
-                }
-                pos_of[3 * (size_t)f + c] = p;
-            }
-        }
-        {   // slot[e] for the CSR entries, filled in the same (face-ascending) order as `face`
-            std::vector<int> cursor(ptr.begin(), ptr.end() - 1);
-            for (int f = 0; f < ntri; ++f)
-                for (int c = 0; c < 3; ++c) slot[cursor[tri[3 * f + c]]++] = pos_of[3 * (size_t)f + c];
-        }
-        // The table position of a face is free (a vertex's summation order is the order of its slot row, not of the table):
-        // order every chunk list so that the 32 faces a half-wave crosses together read 32 different LDS banks for each of
-        // their three corners (bank = 3 * index + component mod 32, 3 is invertible mod 32: corner indices distinct mod 32).
-        // First fit over the open groups; what does not fit anywhere goes to the end with its conflicts.
-        for (int ch = 0; ch < chunks; ++ch) {
-            std::vector<int4>& L = lists[ch];
-            const int n = (int)L.size(), ngroups = (n + 31) / 32;
-            std::vector<unsigned> used(3 * (size_t)ngroups, 0u);
-            std::vector<int> fill(ngroups, 0), where(n, -1), spill;
-            int first_open = 0;
-            for (int i = 0; i < n; ++i) {
-                const unsigned b0 = 1u << (L[i].x & 31), b1 = 1u << (L[i].y & 31), b2 = 1u << (L[i].z & 31);
-                int g = first_open, tried = 0;
-                for (; g < ngroups && tried < 64; ++g) {
-                    if (fill[g] >= 32) continue;
-                    ++tried;
-                    if (!(used[3 * g] & b0) && !(used[3 * g + 1] & b1) && !(used[3 * g + 2] & b2)) break;
-                }
-                if (g >= ngroups || tried >= 64) {
-                    spill.push_back(i);
-                    continue;
-                }
-                used[3 * g] |= b0, used[3 * g + 1] |= b1, used[3 * g + 2] |= b2;
-                where[i] = g * 32 + fill[g]++;
-                while (first_open < ngroups && fill[first_open] >= 32) ++first_open;
-            }
-            // full groups first (each lands on a half-wave boundary), then the members of the unfilled groups and the spill
-            std::vector<int> order;  // new position -> old position
-            order.reserve(n);
-            std::vector<std::vector<int>> members(ngroups);
-            for (int i = 0; i < n; ++i)
-                if (where[i] >= 0) members[where[i] / 32].push_back(i);
-            for (int g = 0; g < ngroups; ++g)
-                if (members[g].size() == 32) order.insert(order.end(), members[g].begin(), members[g].end());
-            for (int g = 0; g < ngroups; ++g)
-                if (members[g].size() != 32) order.insert(order.end(), members[g].begin(), members[g].end());
-            order.insert(order.end(), spill.begin(), spill.end());
-            std::vector<int> new_of(n);
-            std::vector<int4> R(n);
-            for (int np = 0; np < n; ++np) new_of[order[np]] = np, R[np] = L[order[np]];
-            L.swap(R);
-            const int lo = ch * vpb, hi = std::min(nver, lo + vpb);
-            for (int v = lo; v < hi; ++v)
-                for (int e = ptr[v]; e < ptr[v + 1]; ++e) slot[e] = new_of[slot[e]];
-        }
-        int max_faces = 0;
-        std::vector<uint2> flat;
-        for (int ch = 0; ch < chunks; ++ch) {
-            fptr[ch] = (int)flat.size();
-            for (const int4& f : lists[ch]) flat.push_back(make_uint2((unsigned)f.x | ((unsigned)f.y << 16), (unsigned)f.z));
-            max_faces = std::max(max_faces, (int)lists[ch].size());
-        }
-        fptr[chunks] = (int)flat.size();
-        if (max_faces > 65535 || normal_table_lds_bytes(nver, max_faces) > 160 * 1024 - 1024) continue;
-        std::vector<unsigned short> slot16(slot.begin(), slot.end());
-        std::vector<uint4> row8(nver);
-        for (int v = 0; v < nver; ++v) {
-            unsigned short r[8];
-            const int deg = ptr[v + 1] - ptr[v];
-            for (int j = 0; j < 8; ++j) r[j] = j < deg ? slot16[ptr[v] + j] : (unsigned short)0xFFFF;
-            if (deg > 8) r[7] = 0xFFFE;
-            row8[v] = make_uint4(r[0] | ((unsigned)r[1] << 16), r[2] | ((unsigned)r[3] << 16), r[4] | ((unsigned)r[5] << 16), r[6] | ((unsigned)r[7] << 16));
-        }
-        if (max_faces >= 0xFFFE) continue;
-        if ((st = upload(&m->d_nc_faces[k], flat)) || (st = upload(&m->d_nc_slot[k], slot16)) || (st = upload(&m->d_nc_row8[k], row8))) {
-            dad3d_mesh_destroy(m.release());
-            return st;
-        }
-        m->nc[k] = NormalChunksDev{m->d_nc_faces[k], {}, m->d_nc_slot[k], m->d_nc_row8[k], chunks, vpb, max_faces};
-        for (int ch = 0; ch <= chunks; ++ch) m->nc[k].face_ptr[ch] = fptr[ch];
+    for (int k = 0; k < kNormalChunkings; ++k) {
+        const plan::NormalChunkPlan p = plan::plan_normal_chunks(tri, ntri, nver, adj, 1 << k, normal_table_lds_bytes);
+        if (!p.built) continue;
+        if ((st = m->d_nc_faces[k].upload(p.faces)) || (st = m->d_nc_slot[k].upload(p.slot)) || (st = m->d_nc_row8[k].upload(p.row8))) return st;
+        m->nc[k] = NormalChunksDev{m->d_nc_faces[k].get(), {}, m->d_nc_slot[k].get(), m->d_nc_row8[k].get(), p.chunks, p.vpb, p.max_faces};
+        std::copy(p.face_ptr.begin(), p.face_ptr.end(), m->nc[k].face_ptr);
     }
     *out = m.release();
     return DAD3D_OK;
 }
 
-void dad3d_mesh_destroy(dad3d_mesh* m) {
-    if (!m) return;
-    DeviceGuard guard(m->device);
-    for (void* p : {(void*)m->d_tri, (void*)m->d_adj_ptr, (void*)m->d_adj_face, (void*)m->d_adj_tri, m->d_raster, m->d_frames, (void*)m->d_tex_tri[0],
-                    (void*)m->d_tex_tri[1]})
-        if (p) (void)hipFree(p);
-    for (int k = 0; k < kNormalChunkings; ++k)
-        for (void* p : {(void*)m->d_nc_faces[k], (void*)m->d_nc_slot[k], (void*)m->d_nc_row8[k]})
-            if (p) (void)hipFree(p);
-    delete m;
-}
+void dad3d_mesh_destroy(dad3d_mesh* m) { delete m; }
 
 dad3d_status dad3d_mesh_get_normal(dad3d_mesh* m, float* ver_normal, const float* vertices, int batch, unsigned flags,
                                    void* stream) {
@@ -268,7 +139,7 @@ dad3d_status dad3d_mesh_rasterize(dad3d_mesh* m, uint8_t* image, const float* ve
     DeviceGuard guard(m->device);
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
     // alpha != 1: the blends of rasterize_kernel.cpp:268-284 replayed in triangle order (mode 2)
-    return launch_rasterize(m->dev(), m->nc, m->d_raster, m->d_trace, image, vertices, colors, depth, nullptr, nullptr, batch, h, w, c, reverse,
+    return launch_rasterize(m->dev(), m->nc, m->d_raster.get(), m->d_trace, image, vertices, colors, depth, nullptr, nullptr, batch, h, w, c, reverse,
                             alpha == 1.0f ? 0 : 2, nullptr, static_cast<hipStream_t>(stream), alpha);
 }
 
@@ -284,7 +155,7 @@ dad3d_status dad3d_mesh_render(dad3d_mesh* m, uint8_t* image, const float* verti
     }
     DAD3D_REQUIRE(vertices && light, "dad3d_mesh_render: null buffer");
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
-    return launch_rasterize(m->dev(), m->nc, m->d_raster, m->d_trace, image, vertices, light, depth, nullptr, nullptr, batch, h, w, 3,
+    return launch_rasterize(m->dev(), m->nc, m->d_raster.get(), m->d_trace, image, vertices, light, depth, nullptr, nullptr, batch, h, w, 3,
                             flags, 0, cfg, static_cast<hipStream_t>(stream));
 }
 
@@ -297,7 +168,7 @@ dad3d_status dad3d_mesh_rasterize_frames(dad3d_mesh* m, const int64_t* frames, c
     if (total_tiles == 0) return DAD3D_OK;  // no frames or no heads
     DeviceGuard guard(m->device);
     if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
-    return launch_rasterize_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, colors, image_index, n_heads, reverse ? 1 : 0,
+    return launch_rasterize_frames(m->dev(), m->d_frames.get(), frames, n_frames, total_tiles, vertices, colors, image_index, n_heads, reverse ? 1 : 0,
                                    flags, static_cast<hipStream_t>(stream));
 }
 
@@ -316,7 +187,7 @@ dad3d_status dad3d_mesh_render_frames(dad3d_mesh* m, const int64_t* frames, cons
     if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
     // the light of every head, flagged or not, as dad3d_mesh_normal_phong_light computes it; then it is the colours
     if (dad3d_status st = launch_phong(m->dev(), m->nc, light, vertices, nullptr, nullptr, n_heads, *cfg, static_cast<hipStream_t>(stream))) return st;
-    return launch_rasterize_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, light, image_index, n_heads,
+    return launch_rasterize_frames(m->dev(), m->d_frames.get(), frames, n_frames, total_tiles, vertices, light, image_index, n_heads,
                                    render_flags & DAD3D_RENDER_REVERSE, flags, static_cast<hipStream_t>(stream));
 }
 
@@ -345,14 +216,14 @@ dad3d_status dad3d_mesh_render_texture_frames(dad3d_mesh* m, const int64_t* fram
     }
     DeviceGuard guard(m->device);
     if (dad3d_status st = m->frames_scratch(n_frames, n_heads, total_tiles)) return st;
-    return launch_render_texture_frames(m->dev(), m->d_frames, frames, n_frames, total_tiles, vertices, m->d_tex_tri[indexing], texture,
+    return launch_render_texture_frames(m->dev(), m->d_frames.get(), frames, n_frames, total_tiles, vertices, m->d_tex_tri[indexing].get(), texture,
                                         texture_dtype == DAD3D_DTYPE_U8, texture_batched ? (size_t)tex_h * tex_w * tex_c : 0, tex_h, tex_w, tex_c,
                                         mapping_type == 0, image_index, n_heads, flags, static_cast<hipStream_t>(stream));
 }
 
 dad3d_status dad3d_mesh_frames_scratch_bytes(dad3d_mesh* m, size_t* bytes) {
     DAD3D_REQUIRE(m && bytes, "dad3d_mesh_frames_scratch_bytes: bad argument");
-    *bytes = m->frames_bytes;
+    *bytes = m->d_frames.capacity();
     return DAD3D_OK;
 }
 
@@ -363,7 +234,7 @@ dad3d_status dad3d_mesh_rasterize_triangles(dad3d_mesh* m, const float* vertices
     DAD3D_REQUIRE(depth && tri_buf && bary && (vertices || m->ntri == 0), "dad3d_mesh_rasterize_triangles: null buffer");
     DeviceGuard guard(m->device);
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
-    return launch_rasterize(m->dev(), m->nc, m->d_raster, m->d_trace, nullptr, vertices, nullptr, depth, tri_buf, bary, batch, h, w, 3, 0, 1,
+    return launch_rasterize(m->dev(), m->nc, m->d_raster.get(), m->d_trace, nullptr, vertices, nullptr, depth, tri_buf, bary, batch, h, w, 3, 0, 1,
                             nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -374,33 +245,13 @@ dad3d_status dad3d_mesh_set_texcoords(dad3d_mesh* m, const float* tex_coords, in
     const size_t nt = (size_t)m->ntri;
     for (size_t i = 0; i < 3 * nt; ++i)
         DAD3D_REQUIRE(tex_triangles[i] >= 0 && tex_triangles[i] < n_tex, "texture triangle index %d out of range [0,%d)", tex_triangles[i], n_tex);
-    // reference indexing (rasterize_kernel.cpp:398-403) reads row tri[i] of tex_coords for y: possible when every mesh index is a row
-    bool ref_ok = stride == 3;
-    for (size_t i = 0; i < 3 * nt && ref_ok; ++i) ref_ok = m->h_tri[i] < n_tex;
-    std::vector<float4> corner(2 * nt), ref(ref_ok ? 2 * nt : 0);
-    for (size_t f = 0; f < nt; ++f) {
-        float cx[3], cy[3], ry[3];
-        for (int k = 0; k < 3; ++k) {
-            const size_t t = (size_t)tex_triangles[3 * f + k];
-            cx[k] = tex_coords[stride * t], cy[k] = tex_coords[stride * t + 1];
-            ry[k] = ref_ok ? tex_coords[stride * (size_t)m->h_tri[3 * f + k] + 1] : 0.0f;
-        }
-        corner[2 * f] = make_float4(cx[0], cy[0], cx[1], cy[1]);
-        corner[2 * f + 1] = make_float4(cx[2], cy[2], 0.0f, 0.0f);
-        if (ref_ok) {
-            ref[2 * f] = make_float4(cx[0], ry[0], cx[1], ry[1]);
-            ref[2 * f + 1] = make_float4(cx[2], ry[2], 0.0f, 0.0f);
-        }
-    }
+    const plan::TexcoordTables T = plan::plan_texcoords(m->h_tri, tex_coords, n_tex, stride, tex_triangles);
     DeviceGuard guard(m->device);
     DAD3D_HIP_TRY(hipDeviceSynchronize());  // a launch in flight may still read the tables being replaced
-    for (float4*& p : m->d_tex_tri) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
+    for (DeviceArray<float4>& t : m->d_tex_tri) t.reset();
     if (nt == 0) return DAD3D_OK;
-    if (dad3d_status st = upload(&m->d_tex_tri[DAD3D_TEX_INDEX_CORNER], corner)) return st;
-    return ref_ok ? upload(&m->d_tex_tri[DAD3D_TEX_INDEX_REFERENCE], ref) : DAD3D_OK;
+    if (dad3d_status st = m->d_tex_tri[DAD3D_TEX_INDEX_CORNER].upload(T.corner)) return st;
+    return T.ref_ok ? m->d_tex_tri[DAD3D_TEX_INDEX_REFERENCE].upload(T.ref) : DAD3D_OK;
 }
 
 dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, int image_dtype, const float* vertices, const void* texture,
@@ -420,7 +271,7 @@ dad3d_status dad3d_mesh_render_texture(dad3d_mesh* m, void* image, int image_dty
     DAD3D_REQUIRE(m->d_tex_tri[indexing], "dad3d_mesh_render_texture: reference indexing needs tex_coords rows of 3 floats, one for every vertex a triangle names");
     DeviceGuard guard(m->device);
     if (dad3d_status st = m->raster_scratch(batch, h, w, static_cast<hipStream_t>(stream))) return st;
-    return launch_render_texture(m->dev(), m->d_raster, image, image_dtype == DAD3D_DTYPE_U8, vertices, m->d_tex_tri[indexing], texture,
+    return launch_render_texture(m->dev(), m->d_raster.get(), image, image_dtype == DAD3D_DTYPE_U8, vertices, m->d_tex_tri[indexing].get(), texture,
                                  texture_dtype == DAD3D_DTYPE_U8, texture_batched ? (size_t)tex_h * tex_w * tex_c : 0, depth, batch, h, w, c, tex_h,
                                  tex_w, tex_c, mapping_type == 0, static_cast<hipStream_t>(stream));
 }
@@ -486,56 +337,20 @@ dad3d_status dad3d_uvmap_create(const int32_t* faces, int ntri, int nver, const 
                           "dad3d_uvmap_create: candidate %d names vertex %d outside [0,%d)", i, cand_verts[3 * (size_t)i + c], nver);
     }
     DAD3D_SELECT_DEVICE(device);
-    // vertex -> faces in ascending face order, each face once with its multiplicity: the rows of psbody's faces_by_vertex
-    // CSR after scipy summed the duplicate (vertex, face) entries
-    std::vector<int> ptr(nver + 1, 0);
-    std::vector<int4> adj;
-    {
-        std::vector<std::vector<int4>> rows(nver);
-        for (int f = 0; f < ntri; ++f) {
-            const int* t = faces + 3 * (size_t)f;
-            for (int c = 0; c < 3; ++c) {
-                std::vector<int4>& r = rows[t[c]];
-                if ((c > 0 && t[c] == t[0]) || (c == 2 && t[c] == t[1])) {
-                    ++r.back().w;  // the same face names this vertex again
-                    continue;
-                }
-                r.push_back(make_int4(t[0], t[1], t[2], 1));
-            }
-        }
-        for (int v = 0; v < nver; ++v) ptr[v + 1] = ptr[v] + (int)rows[v].size();
-        adj.reserve(ptr[nver]);
-        for (int v = 0; v < nver; ++v) adj.insert(adj.end(), rows[v].begin(), rows[v].end());
-    }
-    // texel -> candidates, descending candidate index: the first that passes is the reference's last writer
-    std::vector<int> tptr(n_tex + 1, 0);
-    for (int i = 0; i < n; ++i) ++tptr[cand_texel[i] + 1];
-    for (int t = 0; t < n_tex; ++t) tptr[t + 1] += tptr[t];
-    std::vector<int> fill(tptr.begin(), tptr.end() - 1), verts(3 * (size_t)n);
-    std::vector<double> bary(3 * (size_t)n);
-    for (int i = n - 1; i >= 0; --i) {
-        const int j = fill[cand_texel[i]]++;
-        for (int c = 0; c < 3; ++c) verts[3 * (size_t)j + c] = cand_verts[3 * (size_t)i + c], bary[3 * (size_t)j + c] = cand_bary[3 * (size_t)i + c];
-    }
+    const plan::UvAdjacency adj = plan::uv_adjacency(faces, ntri, nver);
+    const plan::UvTexelTables tex = plan::uv_texel_tables(cand_texel, cand_verts, cand_bary, n, n_tex);
     std::unique_ptr<dad3d_uvmap> m(new dad3d_uvmap);
     m->device = device, m->nver = nver, m->size = img_size, m->n_cand = n, m->ntri = ntri;
     dad3d_status st;
-    if ((st = upload(&m->d_faces, std::vector<int>(faces, faces + 3 * (size_t)ntri))) || (st = upload(&m->d_adj_ptr, ptr)) || (st = upload(&m->d_adj, adj)) || (st = upload(&m->d_texel_ptr, tptr)) ||
-        (st = upload(&m->d_cand_verts, verts)) || (st = upload(&m->d_cand_bary, bary))) {
-        dad3d_uvmap_destroy(m.release());
+    if ((st = m->d_faces.upload(std::vector<int>(faces, faces + 3 * (size_t)ntri))) || (st = m->d_adj_ptr.upload(adj.ptr)) ||
+        (st = m->d_adj.upload(adj.adj)) || (st = m->d_texel_ptr.upload(tex.tptr)) || (st = m->d_cand_verts.upload(tex.verts)) ||
+        (st = m->d_cand_bary.upload(tex.bary)))
         return st;
-    }
     *out = m.release();
     return DAD3D_OK;
 }
 
-void dad3d_uvmap_destroy(dad3d_uvmap* m) {
-    if (!m) return;
-    DeviceGuard guard(m->device);
-    for (void* p : {(void*)m->d_adj_ptr, (void*)m->d_adj, (void*)m->d_texel_ptr, (void*)m->d_cand_verts, (void*)m->d_cand_bary, (void*)m->d_faces})
-        if (p) (void)hipFree(p);
-    delete m;
-}
+void dad3d_uvmap_destroy(dad3d_uvmap* m) { delete m; }
 
 int dad3d_uvmap_size(const dad3d_uvmap* m) { return m ? m->size : 0; }
 
@@ -545,7 +360,7 @@ dad3d_status dad3d_uvmap_vertex_normals(dad3d_uvmap* m, double* normals, const f
     if (batch == 0 || m->nver == 0) return DAD3D_OK;
     DAD3D_REQUIRE(normals && vertices, "dad3d_uvmap_vertex_normals: null argument");
     DAD3D_SELECT_DEVICE(m->device);
-    UvNormalArgs a{m->d_adj_ptr, m->d_adj, vertices, normals, batch, m->nver};
+    UvNormalArgs a{m->d_adj_ptr.get(), m->d_adj.get(), vertices, normals, batch, m->nver};
     return launch_uv_vertex_normals(a, static_cast<hipStream_t>(stream));
 }
 
@@ -556,7 +371,7 @@ dad3d_status dad3d_uvmap_bake(dad3d_uvmap* m, uint8_t* texture, const float* ver
     if (batch == 0) return DAD3D_OK;
     DAD3D_REQUIRE(texture && images && ((vertices && normals) || m->n_cand == 0), "dad3d_uvmap_bake: null argument");
     DAD3D_SELECT_DEVICE(m->device);
-    UvBakeArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, images, hw, texture,
+    UvBakeArgs a{m->d_texel_ptr.get(), m->d_cand_verts.get(), m->d_cand_bary.get(), vertices, normals, images, hw, texture,
                  batch, m->nver, m->size, h, w, kUvBakeChunk};
     return launch_uv_bake(a, static_cast<hipStream_t>(stream));
 }
@@ -588,7 +403,7 @@ dad3d_status dad3d_uvmap_bake_frames(dad3d_uvmap* m, uint8_t* texture, float* sc
     DAD3D_REQUIRE(texture && image_index && flags && ((vertices && normals) || m->n_cand == 0), "%s: null buffer", who);
     DAD3D_REQUIRE(n_frames == 0 || frames, "%s: null device frame table", who);
     DAD3D_SELECT_DEVICE(m->device);
-    UvBakeFramesArgs a{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, reinterpret_cast<const long long*>(frames), image_index,
+    UvBakeFramesArgs a{m->d_texel_ptr.get(), m->d_cand_verts.get(), m->d_cand_bary.get(), vertices, normals, reinterpret_cast<const long long*>(frames), image_index,
                        texture, score, flags, n_heads, n_frames, m->nver, m->size};
     return launch_uv_bake_frames(a, static_cast<hipStream_t>(stream));
 }
@@ -606,7 +421,7 @@ dad3d_status dad3d_uvmap_depth_frames(dad3d_uvmap* m, float* depth, int32_t* win
     if (n_heads == 0) return DAD3D_OK;
     DAD3D_REQUIRE(vertices || m->nver == 0, "%s: null vertices", who);
     DAD3D_SELECT_DEVICE(m->device);
-    UvDepthFramesArgs a{m->d_faces, vertices, reinterpret_cast<const long long*>(frames), image_index, depth, window, flags,
+    UvDepthFramesArgs a{m->d_faces.get(), vertices, reinterpret_cast<const long long*>(frames), image_index, depth, window, flags,
                         n_heads, n_frames, m->nver, m->ntri, depth_side};
     return launch_uv_depth_frames(a, static_cast<hipStream_t>(stream));
 }
@@ -627,7 +442,7 @@ dad3d_status dad3d_uvmap_bake_frames_occluded(dad3d_uvmap* m, uint8_t* texture, 
     if (n_heads == 0) return DAD3D_OK;
     DAD3D_REQUIRE((vertices && normals) || m->n_cand == 0, "%s: null vertices or normals", who);
     DAD3D_SELECT_DEVICE(m->device);
-    UvBakeOccludedArgs a{{m->d_texel_ptr, m->d_cand_verts, m->d_cand_bary, vertices, normals, reinterpret_cast<const long long*>(frames),
+    UvBakeOccludedArgs a{{m->d_texel_ptr.get(), m->d_cand_verts.get(), m->d_cand_bary.get(), vertices, normals, reinterpret_cast<const long long*>(frames),
                           image_index, texture, score, flags, n_heads, n_frames, m->nver, m->size},
                          depth, window, depth_flags, depth_side, depth_bias, slope_bias};
     return launch_uv_bake_frames_occluded(a, static_cast<hipStream_t>(stream));

@@ -68,7 +68,8 @@ dad3d_mesh* cached_mesh(const int* tri, int ntri, int nver) {
 
 // Staging buffers of the single-image host entry points: a few grow-only device buffers kept for the life of the process
 // (a hipMalloc + hipFree per call cost more than the kernels; calls are serialised by g_cache.mu). A DevBuf takes the next
-// free slot of the arena; the arena is rewound when the call returns.
+// free slot of the arena; the arena is rewound when the call returns. Not DeviceScratch (device_memory.hpp): a slot is replaced without
+// waiting for the device -- every call here ends synchronised -- and is never freed, and DeviceScratch would do both.
 struct StagingArena {
     static constexpr int kSlots = 4;
     void* buf[kSlots] = {};
